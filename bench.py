@@ -17,6 +17,10 @@ batch (which the 256 MiB L3 can keep) is reported beside it as `resident_input`,
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).  The GPU legs never touch oracle/; only the
 `cpu_baseline` leg (rank 0, N=1) times the scalar-C oracle on a bounded sample of the same workload.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, ...).  `--full` adds the legs that take
+runs of their own: `roofline`, `consumer_loop`, `bit_exact_kernel`, `resident_input` and `cpu_baseline`.  `--dump-outputs DIR` writes what
+the last timed step computed (the audio, or the PCM of --pcm-call runs) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import glob
@@ -41,6 +45,7 @@ if "WORLD_SIZE" in os.environ or "TORCHELASTIC_RUN_ID" in os.environ:   # (a ran
 HBM_PEAK_GBPS = 8000.0          # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 REST_S = float(os.environ.get("BENCH_REST_S", "0.05"))   # idle time before every secondary timed region (see timed())
 L3_BYTES = 256 << 20            # Infinity Cache (same guide): the rotated inputs must exceed it
+DUMP_BYTES = 64 << 20           # --dump-outputs: all files of one run together, over all ranks
 
 
 def parse():
@@ -85,6 +90,13 @@ def parse():
     ap.add_argument("--end-to-end", action="store_true",
                     help="fm workload: every step also scatters the IQ batch from rank 0 to all ranks and gathers the audio back "
                          "over RCCL (SURVEY 8e C1/C2); reported separately from the compute-only default")
+    ap.add_argument("--full", action="store_true",
+                    help="fm workload: also run the legs beside the headline — `roofline` (calls one after the other, per-launch events, the sustained and steady "
+                         "series, the measured read ceiling), `consumer_loop`, `bit_exact_kernel`, `resident_input` and `cpu_baseline`.  Without it the run sets up, "
+                         "warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller as DIR/<name>.npy (float32; %d MB at most, a fixed "
+                         "seeded sample of the streams beyond that); the inputs are the same from run to run for the same arguments" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
     if not (args.iq_class in ("fm", "random") or (args.iq_class.startswith("mixed:") and args.iq_class[6:].isdigit() and 0 < int(args.iq_class[6:]) < 100)):
         ap.error("--iq-class: fm, random or mixed:P (P per cent, 1..99)")
@@ -390,6 +402,24 @@ def per_launch_events(torch, stream, step, n):
     return [a.elapsed_time(b) for a, b in evs]
 
 
+def dump_outputs(outdir, arrays, rank, world):
+    """--dump-outputs: write {name: device tensor, rows = streams} as outdir/<name>.npy (outdir/<name>_rank<r>.npy at N > 1) in float32.  A rank's files
+    share DUMP_BYTES / N; past that a fixed, seeded sample of the streams is kept (the same rows in every array and every run).  Returns the names written."""
+    import numpy as np
+    host = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    rows = host[next(iter(host))].shape[0]
+    per_row = sum(a.nbytes // max(a.shape[0], 1) for a in host.values())
+    keep = min(rows, (DUMP_BYTES // world) // max(per_row, 1))
+    sel = np.sort(np.random.default_rng(1234).choice(rows, keep, replace=False)) if keep < rows else None
+    os.makedirs(outdir, exist_ok=True)
+    names = []
+    for k, a in host.items():
+        name = k if world == 1 else "%s_rank%d" % (k, rank)
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a if sel is None else a[sel], dtype=np.float32))
+        names.append(name)
+    return names
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -526,44 +556,57 @@ def main():
         routed_timed, routed_kernel = dm.route(), served_by      # (the assignment the timed region ran with: a stream is tried on design Q again every 1024 calls)
         if "overlapped" not in served_by:                        # a handle the matrix-pipe kernel does not serve (--bit-exact, other taps): the
             overlap = False                                      # library makes the calls one after the other; time them as such (below)
-    if overlap:
-        # the roofline figure: the same K calls made one after the other (what rocprofv3 --kernel-trace reports as the kernel's duration),
-        # from a rested GPU and behind the same warm-up as the timed region
-        # — taken five times when K is short: the clock state a short region meets varies from region to region on one box (26.4 - 31.3 us per
-        # call over 20 steps in seven consecutive regions of one process, whatever the rest between them; the overlapped regions do not show
-        # this); `frac` is the MEDIAN region, all five are listed and the best one is given beside it
-        serial_regions = []
-        for _ in range(5 if args.steps < 100 else 1):
-            time.sleep(REST_S)
-            for i in range(args.warmup):
-                step_rot(i)
-            serial_regions.append(timed(torch, dist, use_dist, stream, step_rot, args.steps)[1])
-        kernel_ms_avg = sorted(serial_regions)[len(serial_regions) // 2]
-    else:
+    if not overlap:
         elapsed, kernel_ms_avg = timed(torch, dist, use_dist, stream, step_rot, args.steps)
         elapsed_with_barrier = TIMED_WITH_BARRIER["s"]
         routed_timed, routed_kernel = dm.route(), dm.kernel_name
     n_audio = last["n"]
-    kernel_ms = per_launch_events(torch, stream, step_rot, min(args.steps, 20))
-    # sustained figure: at least 300 back-to-back steps (a short timed region runs at the boost clock)
-    if args.steps >= 300 or e2e is not None:
-        kernel_ms_sus, sus_steps = kernel_ms_avg, args.steps
-    else:
-        sus_steps = 300
-        _, kernel_ms_sus = timed(torch, dist, use_dist, stream, step_rot, sus_steps, rest=REST_S)
-    if overlap:
-        _, kernel_ms_ovl_sus = (None, kernel_ms_ovl) if args.steps >= 300 else timed(torch, dist, use_dist, stream, step_ovl, 300, finish=dm.flush, rest=REST_S)
-    # steady state: ten regions of 300 calls back to back; the median of the last five (single-GPU runs: a scaling run's ranks are not held together here)
-    steady_ser = steady_ovl = None
-    if e2e is None and not use_dist and not args.no_steady:
-        time.sleep(REST_S)
-        steady_ser = steady_regions(torch, stream, step_rot)
+    if args.dump_outputs:
+        # what the last timed step handed its caller: the buffers it wrote (the overlapped calls take two audio buffers in turn, the PCM calls three),
+        # n_audio samples per stream (the PCM: L = R pairs)
+        dm.synchronize()
+        if pcm_sink is not None:
+            k = (pcm_calls["n"] - 1) % 3
+            outs = {"pcm": pcm_bufs[k][:, :2 * n_audio]}
+            if args.pcm_call == "both":
+                outs["audio"] = audio3[k][:, :n_audio]
+        else:
+            outs = {"audio": (audio_pair[(ovl_calls["n"] - 1) & 1] if overlap else audio)[:, :n_audio]}
+        dump_outputs(args.dump_outputs, outs, rank, world)
+    kernel_ms = kernel_ms_sus = sus_steps = None
+    steady_ser = steady_ovl = consumer = bit_exact_leg = elapsed_res = peak_measured = per_rank = None
+    if args.full:
         if overlap:
+            # the roofline figure: the same K calls made one after the other (what rocprofv3 --kernel-trace reports as the kernel's duration),
+            # from a rested GPU and behind the same warm-up as the timed region
+            # — taken five times when K is short: the clock state a short region meets varies from region to region on one box (26.4 - 31.3 us per
+            # call over 20 steps in seven consecutive regions of one process, whatever the rest between them; the overlapped regions do not show
+            # this); `frac` is the MEDIAN region, all five are listed and the best one is given beside it
+            serial_regions = []
+            for _ in range(5 if args.steps < 100 else 1):
+                time.sleep(REST_S)
+                for i in range(args.warmup):
+                    step_rot(i)
+                serial_regions.append(timed(torch, dist, use_dist, stream, step_rot, args.steps)[1])
+            kernel_ms_avg = sorted(serial_regions)[len(serial_regions) // 2]
+        kernel_ms = per_launch_events(torch, stream, step_rot, min(args.steps, 20))
+        # sustained figure: at least 300 back-to-back steps (a short timed region runs at the boost clock)
+        if args.steps >= 300 or e2e is not None:
+            kernel_ms_sus, sus_steps = kernel_ms_avg, args.steps
+        else:
+            sus_steps = 300
+            _, kernel_ms_sus = timed(torch, dist, use_dist, stream, step_rot, sus_steps, rest=REST_S)
+        if overlap:
+            _, kernel_ms_ovl_sus = (None, kernel_ms_ovl) if args.steps >= 300 else timed(torch, dist, use_dist, stream, step_ovl, 300, finish=dm.flush, rest=REST_S)
+        # steady state: ten regions of 300 calls back to back; the median of the last five (single-GPU runs: a scaling run's ranks are not held together here)
+        if e2e is None and not use_dist and not args.no_steady:
             time.sleep(REST_S)
-            steady_ovl = steady_regions(torch, stream, step_ovl, finish=dm.flush)
+            steady_ser = steady_regions(torch, stream, step_rot)
+            if overlap:
+                time.sleep(REST_S)
+                steady_ovl = steady_regions(torch, stream, step_ovl, finish=dm.flush)
     # what a consumer of the audio gets: the same overlapped calls made through sdrfm_process_batch_pcm — the board's sink format
     # (de-emphasis, int16 L = R) out of the demodulator's own launch —, steady state, with and without the float audio stored beside the PCM
-    consumer = None
     if steady_ovl and overlap and not args.dev_library and not args.no_consumer_leg and pcm_sink is None:
         alpha, gain = float(pkg.load_library().sdrfm_pcm_alpha(48000.0, 75e-6)), float(32767.0 / (2 * np.pi * 75e3 / (fs / D)))
         with torch.cuda.stream(stream):
@@ -595,8 +638,7 @@ def main():
     # the north-star's literal design beside the default one: a SDRFM_CFG_BIT_EXACT handle — fp32 fmaf chains on the vector pipe, no matrix
     # instruction, bit-identical to the definition's chains — over the same rotated batches: K serial calls from rest (median of five regions when K is short) and
     # the steady series.  A second handle; nothing of the default handle's figures depends on it.
-    bit_exact_leg = None
-    if e2e is None and not use_dist and not args.bit_exact and not args.dev_library and not args.no_bit_exact_leg and args.iq_class == "fm":
+    if args.full and e2e is None and not use_dist and not args.bit_exact and not args.dev_library and not args.no_bit_exact_leg and args.iq_class == "fm":
         time.sleep(REST_S)
         dx = pkg.FmDemod(pkg.FmConfig(fir_coeffs=h, audio_coeffs=g, fir_decim=D, audio_decim=Da, n_streams=ns, device=local_rank, bit_exact=True))
         dx.set_stream(stream.cuda_stream)
@@ -620,16 +662,18 @@ def main():
         dx.close()
     # second, labelled figure: ONE resident input batch (fits the 256 MiB Infinity Cache) — what round 1 reported as `value`
     res_steps = min(args.steps, 100)
-    for i in range(min(args.warmup, 10)):
-        step_res(i)
-    elapsed_res, kernel_ms_res = timed(torch, dist, use_dist, stream, step_res, res_steps) if e2e is None else (None, None)
+    if args.full:
+        for i in range(min(args.warmup, 10)):
+            step_res(i)
+        elapsed_res, kernel_ms_res = timed(torch, dist, use_dist, stream, step_res, res_steps) if e2e is None else (None, None)
 
     # measured read ceiling (a read-only stream with the kernel's own access pattern over the same rotated batches), and how much of the
     # timed work went through the matrix-pipe kernel's repair path
-    time.sleep(REST_S)
-    peak_measured = read_ceiling(pkg, batches, local_rank) if e2e is None else None
+    if args.full:
+        time.sleep(REST_S)
+        peak_measured = read_ceiling(pkg, batches, local_rank) if e2e is None else None
+        per_rank = gather_per_rank(torch, dist, world, kernel_ms_avg) if use_dist else None
     guard = dm.q_guard()
-    per_rank = gather_per_rank(torch, dist, world, kernel_ms_avg) if use_dist else None
 
     ok = None
     if args.check and rank == 0:
@@ -651,8 +695,6 @@ def main():
         alg_bytes = samples_per_launch * 2.0 + ns * n_audio * 4.0        # 2 B in + 4/(D*Da) B out per IQ sample
         if args.pcm_call == "both":
             alg_bytes += ns * n_audio * 4.0                             # (--pcm-call both: the int16 pair beside the float; 'pcm': instead of it — the same 4 B)
-        achieved = alg_bytes / (kernel_ms_avg * 1e-3) / 1e9
-        traffic = latest_traffic(dm.kernel_name, alg_bytes)
         res = {
             "metric": "IQ MSamples/s through FIR+FM-demod+resample",
             **{k: sf[k] for k in ("value", "unit", "n_gpus", "rccl_world")}, "steps": args.steps, "warmup": args.warmup,
@@ -675,48 +717,53 @@ def main():
                        "input_batches_rotated": nb, "input_bytes_rotated_per_gpu": nb * ns * nbytes,
                        "bytes_per_sample_algorithmic": round(alg_bytes / samples_per_launch, 4),
                        "GB_per_s_input": round(value * 2e6 / 1e9, 1)},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4),
-                         "frac_sustained": round(alg_bytes / (kernel_ms_sus * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                         "sustained_steps": sus_steps, "kernel_ms_sustained": round(kernel_ms_sus, 4),
-                         "peak_measured": round(peak_measured, 1) if peak_measured else None,
-                         "frac_of_measured": round(achieved / peak_measured, 4) if peak_measured else None,
-                         "frac_sustained_of_measured": round(alg_bytes / (kernel_ms_sus * 1e-3) / 1e9 / peak_measured, 4) if peak_measured else None,
-                         "peak_measured_note": "read-only LDS-DMA stream with this kernel's access pattern (12 one-wave workgroups per CU, 5 KiB in flight each, nt) over the same rotated batches, 60 passes in this run (sdrfm_debug_read_ceiling)",
-                         "traffic": traffic["hbm_bytes_per_launch"] if traffic else None,
-                         "traffic_source": ("profiles/%s (rocprofv3 --pmc TCC_EA0 read/write request passes at commit %s; same kernel, same workload size)" % (traffic["file"], traffic.get("commit", "?"))) if traffic else None,
-                         "kernel": dm.kernel_name, "kernel_ms_avg": round(kernel_ms_avg, 4),
-                         "kernel_ms_isolated_avg": round(float(np.mean(kernel_ms)), 4),
-                         "kernel_ms_min": round(float(np.min(kernel_ms)), 4),
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         **({"frac_steady": round(alg_bytes / (float(np.median(steady_ser[5:])) * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                             "kernel_ms_regions_300": [round(x, 4) for x in steady_ser],
-                             "steady_note": "ten regions of 300 calls back to back from a rested GPU; frac_steady = the median of the last five (the state a consumer "
-                                            "that runs for seconds sees); frac_sustained = ONE 300-call region from rest, which sits inside the power management's dip "
-                                            "between ~1 and ~30 ms after a load starts (profiles/r05_clock_transient.txt)"} if steady_ser else {}),
-                         **({"kernel_ms_avg_regions": [round(x, 4) for x in serial_regions],
-                             "frac_best_region": round(alg_bytes / (min(serial_regions) * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
-                            if serial_regions and len(serial_regions) > 1 else {})},
             "gen_seconds": round(t_gen, 2),
         }
-        # The >= 70 % target of BASELINE.md section 2 is defined on the HBM-READ basis (2 B per IQ sample; the audio writes are not counted): every
-        # fraction above again on that basis, and whether the target is met — judged on the steady overlapped calls (what a consumer that runs for
-        # seconds gets through the API's fastest way), or on the timed region's overlapped calls when the steady series was not taken.
-        rl = res["roofline"]
-        rb = {"bytes_per_launch": samples_per_launch * 2.0, "frac": read_basis(samples_per_launch, kernel_ms_avg),
-              "frac_sustained": read_basis(samples_per_launch, kernel_ms_sus),
-              "frac_steady": read_basis(samples_per_launch, float(np.median(steady_ser[5:]))) if steady_ser else None,
-              "note": "samples x 2 B / time / 8 TB/s — the basis the >= 70 % target is defined on; `frac` etc. above count the audio writes too (2.08 B per sample)"}
-        if overlap:
-            rb["overlapped_calls"] = {"frac": read_basis(samples_per_launch, kernel_ms_ovl), "frac_sustained": read_basis(samples_per_launch, kernel_ms_ovl_sus),
-                                      "frac_steady": read_basis(samples_per_launch, float(np.median(steady_ovl[5:]))) if steady_ovl else None}
-        rl["read_basis"] = rb
-        rl["frac_read_basis"] = rb["frac"]
-        judged = (rb.get("overlapped_calls", {}).get("frac_steady") or rb.get("overlapped_calls", {}).get("frac") or rb["frac_steady"] or rb["frac"])
-        rl["target_70pct_read_roofline_met"] = bool(judged is not None and judged >= 0.70) if (D == 10 and args.iq_class == "fm" and not args.bit_exact) else None
-        rl["target_judged_on"] = {"frac_read_basis": judged, "which": ("overlapped calls, steady state" if rb.get("overlapped_calls", {}).get("frac_steady") else
-                                                                      "overlapped calls, the timed region" if rb.get("overlapped_calls", {}).get("frac") else
-                                                                      "serial calls, steady state" if rb["frac_steady"] else "serial calls, the timed region")}
+        if args.full:
+            achieved = alg_bytes / (kernel_ms_avg * 1e-3) / 1e9
+            traffic = latest_traffic(dm.kernel_name, alg_bytes)
+            res["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBPS, 4),
+                               "frac_sustained": round(alg_bytes / (kernel_ms_sus * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                               "sustained_steps": sus_steps, "kernel_ms_sustained": round(kernel_ms_sus, 4),
+                               "peak_measured": round(peak_measured, 1) if peak_measured else None,
+                               "frac_of_measured": round(achieved / peak_measured, 4) if peak_measured else None,
+                               "frac_sustained_of_measured": round(alg_bytes / (kernel_ms_sus * 1e-3) / 1e9 / peak_measured, 4) if peak_measured else None,
+                               "peak_measured_note": "read-only LDS-DMA stream with this kernel's access pattern (12 one-wave workgroups per CU, 5 KiB in flight each, nt) over the same rotated batches, 60 passes in this run (sdrfm_debug_read_ceiling)",
+                               "traffic": traffic["hbm_bytes_per_launch"] if traffic else None,
+                               "traffic_source": ("profiles/%s (rocprofv3 --pmc TCC_EA0 read/write request passes at commit %s; same kernel, same workload size)" % (traffic["file"], traffic.get("commit", "?"))) if traffic else None,
+                               "kernel": dm.kernel_name, "kernel_ms_avg": round(kernel_ms_avg, 4),
+                               "kernel_ms_isolated_avg": round(float(np.mean(kernel_ms)), 4),
+                               "kernel_ms_min": round(float(np.min(kernel_ms)), 4),
+                               "algorithmic_bytes_per_launch": alg_bytes,
+                               **({"frac_steady": round(alg_bytes / (float(np.median(steady_ser[5:])) * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                                   "kernel_ms_regions_300": [round(x, 4) for x in steady_ser],
+                                   "steady_note": "ten regions of 300 calls back to back from a rested GPU; frac_steady = the median of the last five (the state a consumer "
+                                                  "that runs for seconds sees); frac_sustained = ONE 300-call region from rest, which sits inside the power management's dip "
+                                                  "between ~1 and ~30 ms after a load starts (profiles/r05_clock_transient.txt)"} if steady_ser else {}),
+                               **({"kernel_ms_avg_regions": [round(x, 4) for x in serial_regions],
+                                   "frac_best_region": round(alg_bytes / (min(serial_regions) * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
+                                  if serial_regions and len(serial_regions) > 1 else {})}
+            # The >= 70 % target of BASELINE.md section 2 is defined on the HBM-READ basis (2 B per IQ sample; the audio writes are not counted): every
+            # fraction above again on that basis, and whether the target is met — judged on the steady overlapped calls (what a consumer that runs for
+            # seconds gets through the API's fastest way), or on the timed region's overlapped calls when the steady series was not taken.
+            rl = res["roofline"]
+            rb = {"bytes_per_launch": samples_per_launch * 2.0, "frac": read_basis(samples_per_launch, kernel_ms_avg),
+                  "frac_sustained": read_basis(samples_per_launch, kernel_ms_sus),
+                  "frac_steady": read_basis(samples_per_launch, float(np.median(steady_ser[5:]))) if steady_ser else None,
+                  "note": "samples x 2 B / time / 8 TB/s — the basis the >= 70 % target is defined on; `frac` etc. above count the audio writes too (2.08 B per sample)"}
+            if overlap:
+                rb["overlapped_calls"] = {"frac": read_basis(samples_per_launch, kernel_ms_ovl), "frac_sustained": read_basis(samples_per_launch, kernel_ms_ovl_sus),
+                                          "frac_steady": read_basis(samples_per_launch, float(np.median(steady_ovl[5:]))) if steady_ovl else None}
+            rl["read_basis"] = rb
+            rl["frac_read_basis"] = rb["frac"]
+            judged = (rb.get("overlapped_calls", {}).get("frac_steady") or rb.get("overlapped_calls", {}).get("frac") or rb["frac_steady"] or rb["frac"])
+            rl["target_70pct_read_roofline_met"] = bool(judged is not None and judged >= 0.70) if (D == 10 and args.iq_class == "fm" and not args.bit_exact) else None
+            rl["target_judged_on"] = {"frac_read_basis": judged, "which": ("overlapped calls, steady state" if rb.get("overlapped_calls", {}).get("frac_steady") else
+                                                                          "overlapped calls, the timed region" if rb.get("overlapped_calls", {}).get("frac") else
+                                                                          "serial calls, steady state" if rb["frac_steady"] else "serial calls, the timed region")}
+        else:
+            res["legs"] = "the headline only: bench.py --full adds roofline, consumer_loop, bit_exact_kernel, resident_input and cpu_baseline"
         if consumer:
             res["consumer_loop"] = consumer
         if bit_exact_leg:
@@ -741,7 +788,7 @@ def main():
                             "note": "design Q's conditioning guard (DESIGN.md 4.Q): lanes (pairs of discriminator outputs) recomputed with the definition's fmaf chain, over every call this handle served in this run"}
         if per_rank:
             res["roofline"]["per_rank_kernel_ms"] = {"min": min(per_rank), "max": max(per_rank), "all": per_rank}
-        if overlap:
+        if overlap and args.full:
             # `roofline` above: calls one after the other = the kernel's own duration.  This: the timed region itself (overlapped calls);
             # event span / K is then shorter than a kernel's duration, because consecutive kernels run side by side.
             res["roofline"]["overlapped_calls"] = {
@@ -765,7 +812,7 @@ def main():
                                      "note": "same kernel re-reading ONE %.0f MB batch, which the 256 MiB Infinity Cache can hold; not the headline" % (ns * nbytes / 1e6)}
         if ok is not None:
             res["parity_ok"] = ok
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(pkg, h, g, iq_host, args.cpu_seconds, os.cpu_count() or 1)
         print(json.dumps(res), flush=True)
     dm.set_stream(None)
@@ -802,6 +849,9 @@ def main_wbfm(args, pkg, world, rank, local_rank, use_dist, rccl_world):
         step(i)
     elapsed, ms = timed(torch, dist, use_dist, stream, step, args.steps)   # ms = launch duration incl. inter-launch gap (see main())
     n_audio = last["n"]
+    if args.dump_outputs:
+        dm.synchronize()
+        dump_outputs(args.dump_outputs, {"audio": audio[:, :, :n_audio]}, rank, world)     # [stream, band, sample]
     if rank == 0:
         alg = ns * nsamp * 2.0 + ns * 16 * n_audio * 4.0
         tr = latest_traffic(kname, alg)
@@ -846,6 +896,9 @@ def main_spectrum(args, pkg, world, rank, local_rank, use_dist, rccl_world):
         step(i)
     elapsed, ms = timed(torch, dist, use_dist, stream, step, args.steps)
     frames = last["n"]
+    if args.dump_outputs:
+        sv.synchronize()
+        dump_outputs(args.dump_outputs, {"power": power}, rank, world)
     if rank == 0:
         alg = ns * frames * nfft * 2.0 + ns * nfft * 4.0
         kname = sv.kernel_name

@@ -74,3 +74,38 @@ def test_mixed_input_class_spreads_the_noisy_streams_evenly():
         assert abs(len(rows) - ns * pct / 100.0) <= 1.0, (ns, pct, len(rows))
         gaps = [y - x for x, y in zip(rows, rows[1:])]
         assert max(gaps) - min(gaps) <= 1, (ns, pct)
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    """`bench.py --gpus 1 --steps K --warmup W` times the headline only; the other legs run with --full, and nothing is dumped unless asked."""
+    b = _bench()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = b.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_float32_capped_and_seeded(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 .npy per output, the valid part only; past the size cap a seeded sample of the streams, the same rows in every array."""
+    import numpy as np
+    import torch
+    b = _bench()
+    audio = torch.arange(6 * 5, dtype=torch.float32).reshape(6, 5)
+    pcm = torch.arange(6 * 10, dtype=torch.int16).reshape(6, 10)
+    assert b.dump_outputs(str(tmp_path / "a"), {"audio": audio, "pcm": pcm}, 0, 1) == ["audio", "pcm"]
+    got = np.load(tmp_path / "a" / "audio.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, audio.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "pcm.npy"), pcm.numpy().astype(np.float32))
+    # a cap of 3 rows' worth of both arrays: 3 of the 6 streams, chosen by the seed, in order, and in the files of every rank
+    monkeypatch.setattr(b, "DUMP_BYTES", 2 * 3 * (5 * 4 + 10 * 4))
+    for r in range(2):
+        assert b.dump_outputs(str(tmp_path / "b"), {"audio": audio, "pcm": pcm}, r, 2) == ["audio_rank%d" % r, "pcm_rank%d" % r]
+    a0, p0 = np.load(tmp_path / "b" / "audio_rank0.npy"), np.load(tmp_path / "b" / "pcm_rank0.npy")
+    assert a0.shape == (3, 5) and p0.shape == (3, 10)
+    rows = (a0[:, 0] / 5).astype(int)
+    assert list(rows) == sorted(set(rows)) and np.array_equal(p0, pcm.numpy()[rows].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "b" / "audio_rank1.npy"), a0)
+    b.dump_outputs(str(tmp_path / "c"), {"audio": audio, "pcm": pcm}, 0, 2)
+    assert np.array_equal(np.load(tmp_path / "c" / "audio_rank0.npy"), a0)

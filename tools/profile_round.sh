@@ -14,13 +14,13 @@ set -u
 TAG=${1:-r06}; COMMIT=${2:-unknown}
 # PLAIN_ONLY=1: only the un-profiled comparison lines (no rocprofv3 passes)
 OUT=$PWD/gpurun_out/profiles_$TAG; mkdir -p "$OUT"; export TMPDIR=/tmp
-PROF_ARGS="--steps 100 --warmup 10 --no-cpu-baseline --no-steady --no-bit-exact-leg"
+PROF_ARGS="--full --steps 100 --warmup 10 --no-cpu-baseline --no-steady --no-bit-exact-leg"
 run_wl() {   # name, kernel filter, bench args...
   local WL=$1 KF=$2; shift 2
   local W=$OUT/work_$WL; mkdir -p "$W"
   local ARGS="$PROF_ARGS $*"
   if [ -n "${PLAIN_ONLY:-}" ]; then
-    python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-bit-exact-leg ${*//--no-overlap/} > "$OUT/${TAG}_${WL}_bench.json" 2> "$W/bench_plain.err"
+    python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-bit-exact-leg ${*//--no-overlap/} > "$OUT/${TAG}_${WL}_bench.json" 2> "$W/bench_plain.err"
     return
   fi
   rocprofv3 --output-format csv --kernel-trace --stats -d "$W/trace" -o trace -- python3 bench.py $ARGS > "$W/bench_trace.log" 2>&1
@@ -36,7 +36,7 @@ run_wl() {   # name, kernel filter, bench args...
   done
   python3 tools/profile_pmc_summarize.py "$W" "$OUT" "$TAG" "$WL" "$KF" "$COMMIT"
   # the un-profiled comparison line of the same workload (its own steady series, no CPU baseline)
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-bit-exact-leg ${*//--no-overlap/} > "$OUT/${TAG}_${WL}_bench.json" 2> "$W/bench_plain.err"   # (overlapped calls too: the API's fastest way)
+  python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-bit-exact-leg ${*//--no-overlap/} > "$OUT/${TAG}_${WL}_bench.json" 2> "$W/bench_plain.err"   # (overlapped calls too: the API's fastest way)
 }
 WLS=${WLS:-"fm256 fm512 fm256_T16 fm256_bitexact mixed10 mixed25 wbfm spectrum fm256_overlap fm512_overlap driver"}
 for wl in $WLS; do case $wl in
@@ -59,7 +59,7 @@ for wl in $WLS; do case $wl in
     python3 tools/overlap_trace_summarize.py "$(find "$W/trace" -name "*kernel_trace.csv" | head -1)" "$OUT/${TAG}_${wl}_trace.json" "$COMMIT" ;;
   driver)    # the driver's exact command under the kernel tracer, its design-Q dispatches grouped by burst (roofline.frac must be recomputable from profiles/)
     W=$OUT/work_driver; mkdir -p "$W"
-    ( cd /tmp && rocprofv3 --output-format csv --kernel-trace --stats -d "$W/trace" -o trace -- python3 $OLDPWD/bench.py --gpus 1 --steps 20 --warmup 5 > "$W/bench.log" 2>&1 )
+    ( cd "$W" && rocprofv3 --output-format csv --kernel-trace --stats -d "$W/trace" -o trace -- python3 $OLDPWD/bench.py --full --gpus 1 --steps 20 --warmup 5 > "$W/bench.log" 2>&1 )   # (--full: roofline.frac for trace_bursts.py)
     grep "^{\"metric\"" "$W/bench.log" | tail -1 > "$OUT/${TAG}_driver_command_bench_under_rocprof.json"
     find "$W/trace" -name "*kernel_stats.csv" -exec cp {} "$OUT/${TAG}_driver_command_kernel_stats.csv" \;
     python3 tools/trace_bursts.py "$(find "$W/trace" -name "*kernel_trace.csv" | head -1)" "$OUT/${TAG}_driver_command_trace.json" "$OUT/${TAG}_driver_command_bench_under_rocprof.json" ;;
