@@ -1028,6 +1028,7 @@ struct sdrfm {
   const int16_t* prev_ovl_pcm; size_t prev_ovl_pcm_stride;       // the PCM rows the previous overlapped call may still be writing
   int16_t* d_pcm_stage;                                          // sdrfm_process_batch_pcm with host buffers: the PCM rows before they are copied back
   unsigned long long* d_runstate; uint32_t runstate_cap;        // the runs' hand-off words (sdrfm_sink_chain.h), allocated at the first such call
+  uint32_t chain_calls;                                          // launches that held a sink's chain so far: their set and tag of d_runstate (never rewound)
   bool ovl_pending[2], ovl_bound[2], ovl_join_style;   // (bound: the latest kernel of stream k carries ovl_done[k] as its stop event; join_style: the caller joins after every call)
   uint32_t ovl_next;
   // the previous call's device buffer (valid after a SDRFM_F_DEVICE_PTRS call): what an overlapped call warms its streams up from
@@ -1514,7 +1515,7 @@ int sdrfm_reset(sdrfm_t* h) {
   { const int rrc = route_reset(h); if (rrc != SDRFM_OK) return rrc; }   // (behind the synchronisation: no kernel is left that could add to the statistics)
   h->cur = 0;
   h->phase_x = h->phase_d = 0;
-  h->n_seen = 0;
+  h->n_seen = 0;                                                  // (chain_calls goes on: d_runstate keeps the words its launches left)
   return SDRFM_OK;
 }
 
@@ -1975,7 +1976,8 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
       // launch's design-B workgroups'); the call's completion event rides on that last kernel
       chain.pcm = h->pcm_out; chain.pcm_stride = h->pcm_out_stride;
       if (h->pcm_no_audio) q.audio = nullptr;                      // (the clean streams store no audio; the routed ones' goes to the library's own rows)
-      chain.runstate = h->d_runstate + (size_t)(chain.call % SDRFM_CHAIN_SETS) * h->runstate_cap;
+      chain.run_call = h->chain_calls++;
+      chain.runstate = h->d_runstate + (size_t)(chain.run_call % SDRFM_CHAIN_SETS) * h->runstate_cap;
       HIP_TRY(sdrfm_q_launch_mix_pcm(q, chain, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, pb, pb_blocks, pb_R, qs, nullptr), SDRFM_FAIL);
       { const int lrc = sdrfm_sink_launch_list_on(h->pcm_sink, chain, list_dev + n_clean, n_noisy, d_audio, audio_stride, A, h->pcm_out, h->pcm_out_stride, qs, done);
         if (lrc != SDRFM_OK) return lrc; }
@@ -1986,7 +1988,8 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     else if (with_chain) {
       chain.pcm = h->pcm_out; chain.pcm_stride = h->pcm_out_stride;
       if (h->pcm_no_audio) q.audio = nullptr;
-      chain.runstate = h->d_runstate + (size_t)(chain.call % SDRFM_CHAIN_SETS) * h->runstate_cap;
+      chain.run_call = h->chain_calls++;
+      chain.runstate = h->d_runstate + (size_t)(chain.run_call % SDRFM_CHAIN_SETS) * h->runstate_cap;
       HIP_TRY(sdrfm_q_launch_pcm(q, chain, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, qs, done), SDRFM_FAIL);
       sdrfm_sink_chain_issued(h->pcm_sink);
       h->pcm_fused = true;

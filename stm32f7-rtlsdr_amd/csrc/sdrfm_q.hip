@@ -607,7 +607,8 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
           asm volatile("" : "+s"(bid2));
           if (ln_ == 0) {
             const uint32_t call = tp->call, nst = tp->n_streams;
-            const unsigned long long w = ((unsigned long long)(call + 1u) << 32) | __builtin_bit_cast(unsigned, ypub);
+            // (tags: the sink's call number in sg, the handle's launch number in runstate — sdrfm_sink_chain.h, "Order between runs")
+            const unsigned long long w = ((unsigned long long)((last_run ? call : tp->run_call) + 1u) << 32) | __builtin_bit_cast(unsigned, ypub);
             __hip_atomic_store(last_run ? tp->sg + (size_t)((call + 1u) % SDRFM_CHAIN_SG_SLOTS) * nst + st_ : tp->runstate + bid2, w, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
             unsigned long long zero = 0ull;
@@ -1045,11 +1046,11 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
     unsigned long long pv = pv_early;
     if (ln_ == 0) {
       if (!published) {                                          // (a last flush with nothing in it: the state as the earlier flushes left it)
-        const unsigned long long w = ((unsigned long long)(call + 1u) << 32) | __builtin_bit_cast(unsigned, yrun);
+        const unsigned long long w = ((unsigned long long)((last_run ? call : tp->run_call) + 1u) << 32) | __builtin_bit_cast(unsigned, yrun);
         __hip_atomic_store(last_run ? sg + (size_t)((call + 1u) % SDRFM_CHAIN_SG_SLOTS) * nst + st_ : rs + bid_, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
       unsigned long long* const src = run == 0 ? sg + (size_t)(call % SDRFM_CHAIN_SG_SLOTS) * nst + st_ : rs + (bid_ - 1u);
-      const uint32_t want = run == 0 ? call : call + 1u;
+      const uint32_t want = run == 0 ? call : tp->run_call + 1u;
       unsigned long long zero = 0ull;
       asm volatile("" : "+v"(zero));                             // (opaque: "add 0" is a read-modify-write the compiler would turn back into a load, and a load may hit a stale line)
       // (the predecessor ends when this run does: a few polls at most.  The wait is BOUNDED — 2^19 polls, about a second —: a protocol error must not hang the

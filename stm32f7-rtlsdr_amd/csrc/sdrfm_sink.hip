@@ -237,7 +237,7 @@ static void sink_free(sdrfm_pcm_sink* k) {
 // ---- the sink inside a demodulator launch (sdrfm_sink_chain.h) ---------------------------------------------------------------------------------------
 int sdrfm_sink_chain_params(sdrfm_pcm_sink* k, int device, uint32_t n_streams, SdrfmSinkChain* out) {
   if (!k || !out || k->device != device || k->n_streams != n_streams) return 0;
-  out->pcm = nullptr; out->pcm_stride = 0; out->runstate = nullptr;
+  out->pcm = nullptr; out->pcm_stride = 0; out->runstate = nullptr; out->run_call = 0;
   out->sg = k->d_sg; out->n_streams = n_streams; out->dpow = k->d_dpow; out->err = reinterpret_cast<uint32_t*>(k->d_dpow + SDRFM_CHAIN_FIX);
   out->call = k->calls;
   out->alpha = k->alpha; out->gain = k->gain;

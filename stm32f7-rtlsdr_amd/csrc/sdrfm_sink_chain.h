@@ -28,6 +28,11 @@
  * Order between calls: the word {calls applied to stream s, state} is published by the stream's last run of call c with tag c + 1 (in slot tag % 8 of sg: a
  * word is never overwritten while a call that may still read it is incomplete); run 0 of call c + 1 waits (an s_sleep loop of one lane) for that tag.  Call c was launched before call c + 1 and none of its waves waits on anything but its own lower-numbered
  * neighbour, so it always gets there.  The stand-alone sink kernels keep sg up to date too (stream order), so the two styles can follow one another.
+ * Order between runs: the per-run words belong to the HANDLE (sdrfm.hip), not to the sink, and are counted by the handle: its launch number l (run_call, one per
+ * launch that holds a chain, never rewound — not by sdrfm_reset, not by a sink's reset or replacement, whichever sink the launch serves) picks the set l % 4 and tags
+ * the words l + 1.  A word left in that set by an earlier launch carries an older tag, so a run never takes it for its predecessor's.  (Tagged by the sink's call
+ * number, as first written, a sink reset or a second sink on the same handle met the words of an earlier session under the same tag: a run that polled before its
+ * predecessor published took that stale state for its carry.)
  */
 #ifndef SDRFM_SINK_CHAIN_H
 #define SDRFM_SINK_CHAIN_H
@@ -39,7 +44,7 @@ struct sdrfm_pcm_sink;
 
 #define SDRFM_CHAIN_FIX 64u        /* outputs of a run its predecessor's state still reaches */
 #define SDRFM_CHAIN_CH 8u          /* samples per lane of a run's scan: 512 = the most design Q parks before it stores */
-#define SDRFM_CHAIN_SETS 4u        /* sets of per-run words: calls c and c + 1 may be in flight together, c + 2 is ordered behind c */
+#define SDRFM_CHAIN_SETS 4u        /* sets of per-run words, by the handle's launch number: launches l and l + 1 may be in flight together, l + 2 is ordered behind l */
 #define SDRFM_CHAIN_SG_SLOTS 8u    /* slots of the per-stream word: tag t lives in slot t % 8.  Call t reads tag t; while call t is incomplete only calls t, t + 1 and
                                      t + 3 can publish (t + 2 waits for t on its queue, t + 5 for t + 3, which needs t + 2's state): tags t + 1, t + 2, t + 4 — never t + 8 */
 #define SDRFM_CHAIN_MIN_ALPHA 0.231f   /* (1 - alpha)^64 <= 5e-8: below it a run's end state would still depend on its predecessor's */
@@ -49,17 +54,18 @@ struct SdrfmSinkChain {
   size_t pcm_stride;              // int16 elements, even
   unsigned long long* sg;         // [SDRFM_CHAIN_SG_SLOTS][n_streams] {tag << 32 | bits of y[n-1]}: the stream's state behind `tag` calls, in slot tag % 8
   uint32_t n_streams;             // of the handle (the slots' row length)
-  unsigned long long* runstate;   // [grid] this call's set of per-run words {call + 1 << 32 | bits of the run's end state} (sdrfm.hip owns it)
+  unsigned long long* runstate;   // [grid] this launch's set of per-run words {run_call + 1 << 32 | bits of the run's end state} (sdrfm.hip owns it)
   const float* dpow;              // [SDRFM_CHAIN_FIX] (1 - alpha)^(k + 1)
   uint32_t* err;                  // one word: set when a run gave up waiting for its predecessor's word (a protocol error: the sink reports it)
-  uint32_t call;                  // this call's number (mod 2^32)
+  uint32_t call;                  // this call's number OF THE SINK (mod 2^32): the slot and tag of sg
+  uint32_t run_call;              // this launch's number OF THE HANDLE (mod 2^32): the set and tag of runstate
   float alpha, gain, pc;          // pc = (1 - alpha)^SDRFM_CHAIN_CH
   float w[SDRFM_CHAIN_CH];         // w[q] = alpha (1 - alpha)^(SDRFM_CHAIN_CH - 1 - q): what sample q of a chunk adds to the chunk's last output
   float dinv[SDRFM_CHAIN_CH];      // dinv[k] = (1 - alpha)^-k: undoes the decay over the k zeros behind a flush's last output in its lane's chunk
 };
 
 // ---- host side (sdrfm_sink.hip) ---------------------------------------------------------------------------------------------------------------------------
-// The parameters for the sink's NEXT call (pcm / pcm_stride / runstate left for the caller to fill).  0: the sink does not fit the handle (other device, other
+// The parameters for the sink's NEXT call (pcm / pcm_stride / runstate / run_call left for the caller to fill).  0: the sink does not fit the handle (other device, other
 // stream count); 1: it fits, but its time constant is too long for runs to be sunk independently (alpha < SDRFM_CHAIN_MIN_ALPHA): stand-alone kernel only; 2: fits.
 int sdrfm_sink_chain_params(sdrfm_pcm_sink* k, int device, uint32_t n_streams, SdrfmSinkChain* out);
 // The launch that carried `out` is in the queue: the sink's call counter moves on.
