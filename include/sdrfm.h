@@ -246,6 +246,66 @@ int  sdrfm_wbfm_synchronize(sdrfm_wbfm_t* h);
 const char* sdrfm_wbfm_kernel_name(const sdrfm_wbfm_t* h);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Broadcast FM stereo: the same hand-off contract as sdrfm_process_batch (buffer format, status codes,
+ * threading), two audio channels L and R per stream.  K1-K3 (x, y, d, with the state carried across calls) are the definition
+ * at the top of this file, unchanged; behind d, at fs/D, every FIR is an fp32 fmaf chain, oldest sample first, d[m < 0] = 0:
+ *   pilot filter  q[m]  = sum_k b[k] * d[m-k]          P odd, 1 <= P <= 255, Δ = (P-1)/2; b[k] = (br[k], bi[k]) complex taps
+ *                                                      given by the caller: two real chains qr, qi
+ *   pilot power   pw    = fmaf(qr, qr, qi*qi)          pmin2 = pilot_min * pilot_min (fp32, once on the host; may be +inf)
+ *   38 kHz        c[m]  = pw >= pmin2 ? (-2.0f*(qr*qi)) / pw : 0.0f
+ *   difference    s[m]  = (c[m] * diff_gain) * d[m-Δ]
+ *   sum channel   am[j] = sum_k g[k] * d[(j+1)*Da - 1 - k - Δ]
+ *   diff. channel as[j] = sum_k g[k] * s[(j+1)*Da - 1 - k]
+ *   output        L[j]  = am[j] + as[j],  R[j] = am[j] - as[j]          (radians, like the mono audio)
+ * The audio indexes and the per-call output count are the mono path's for the same (D, Da).  With taps from
+ * taps.stereo_pilot_taps (b[k] = 2 w[k] exp(+j 2 pi f_pilot/fs_d (k - Δ)), w a unity-DC-gain low-pass) |q| is the pilot's
+ * amplitude in radians, so pilot_min is in the unit of the audio.  d is the phase step over D inputs: a D-sample boxcar of the
+ * instantaneous frequency, gain H_D(f) = sin(pi f D/fs) / (D sin(pi f/fs)); the L-R subcarrier at 38 kHz arrives H_D(38 kHz)
+ * weaker than L+R (0.9597 at D = 10, 2.4 MS/s), so diff_gain = 2 / H_D(38 kHz) (taps.stereo_diff_gain) separates the channels by
+ * 43-47 dB where the textbook 2 leaves about 32 dB.
+ * Mono identity: where c = 0 and P - 1 = 2 K Da, L == R == a[j - K] bit for bit, a the mono audio of the same (h, g) (a[j < 0] = 0).
+ * Parity unpinned like the rest: every kernel that serves it is bit-identical to this definition.
+ * pilot_count (n_streams words, or NULL): per stream, how many of the call's new d's had pw >= pmin2 (a "stereo" indicator).
+ * Host buffers: synchronous staged call.  SDRFM_F_DEVICE_PTRS: iq, left, right and pilot_count are device memory on cfg.device,
+ * the call is only enqueued on the handle's stream.  SDRFM_F_OVERLAP is rejected (SDRFM_EINVAL).  Any even nbytes up to
+ * max_bytes_per_call (else SDRFM_ECAPACITY).  Invalid configurations answer SDRFM_EINVAL before any device is looked for.
+ * kernel name: "stereo-fast ..." (T = 64, D = 10, P = 101) or "stereo-generic ..." (every other shape); same bits either way.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define SDRFM_STEREO_MAX_PILOT_TAPS 255u
+#define SDRFM_STEREO_CFG_FORCE_GENERIC 1u   /* never the fast kernel (tests) */
+
+typedef struct sdrfm_stereo_config {
+  uint32_t struct_size;           /* = sizeof(sdrfm_stereo_config) */
+  uint32_t n_streams;
+  uint32_t fir_taps;              /* T, as sdrfm_config */
+  uint32_t fir_decim;             /* D, as sdrfm_config */
+  const float* fir_coeffs;        /* h[0..T), copied at create */
+  uint32_t pilot_taps;            /* P: odd, 1 .. SDRFM_STEREO_MAX_PILOT_TAPS */
+  const float* pilot_coeffs;      /* 2P floats: (br[k], bi[k]) pairs, copied at create */
+  float    pilot_min;             /* finite, > 0 (radians, the unit of |q|) */
+  float    diff_gain;             /* finite; 2 = textbook, 2 / H_D(38 kHz) compensates the discriminator */
+  uint32_t audio_taps;            /* Ta, as sdrfm_config */
+  uint32_t audio_decim;           /* Da, as sdrfm_config */
+  const float* audio_coeffs;      /* g[0..Ta), copied at create */
+  uint32_t max_bytes_per_call;    /* per stream; 0 = 1 MiB */
+  int32_t  device;
+  uint32_t flags;                 /* 0 or SDRFM_STEREO_CFG_FORCE_GENERIC */
+} sdrfm_stereo_config;
+
+typedef struct sdrfm_stereo sdrfm_stereo_t;
+
+int  sdrfm_stereo_create(const sdrfm_stereo_config* cfg, sdrfm_stereo_t** out);
+void sdrfm_stereo_destroy(sdrfm_stereo_t* h);
+int  sdrfm_stereo_reset(sdrfm_stereo_t* h);
+int  sdrfm_stereo_audio_count(const sdrfm_stereo_t* h, uint32_t nbytes, uint32_t* n_audio);
+/* left / right for stream s at left + s*audio_stride, right + s*audio_stride (floats) */
+int  sdrfm_stereo_process_batch(sdrfm_stereo_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left, float* right,
+                                size_t audio_stride, uint32_t* pilot_count, uint32_t* n_audio, uint32_t flags);
+int  sdrfm_stereo_set_stream(sdrfm_stereo_t* h, void* hip_stream);
+int  sdrfm_stereo_synchronize(sdrfm_stereo_t* h);
+const char* sdrfm_stereo_kernel_name(const sdrfm_stereo_t* h);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Spectrum view of the IQ buffer — the reference's own next task ("Perform some FFT on the samples to check what we are
  * receiving", README.md:29) on the same buffer contract (RTLSDR_CommItfTypedef.buff, usbh_rtlsdr.h:165-173): per stream
  * the windowed nfft-point power spectrum averaged over the consecutive, non-overlapping frames of the buffer, DC in the
@@ -310,6 +370,10 @@ int sdrfm_e4k_pll_params(uint32_t fosc_hz, uint32_t intended_flo_hz, sdrfm_e4k_p
  * (Utilities/STM32746G-Discovery/stm32746g_discovery_audio.c:224).  pcm_stereo receives 2*n samples. */
 int   sdrfm_pcm_deemph_s16(const float* audio, uint32_t n, float alpha, float gain, float* state, int16_t* pcm_stereo);
 float sdrfm_pcm_alpha(float fs_hz, float tau_s);   /* 1 - exp(-1/(fs*tau)); tau = 75e-6 (US) / 50e-6 (EU) */
+/* The stereo form: each channel de-emphasised on its own (state[0] for L, state[1] for R) with the operations of
+ * sdrfm_pcm_deemph_s16; pcm_stereo[2i] = L, pcm_stereo[2i+1] = R. */
+int   sdrfm_pcm_deemph_stereo_s16(const float* left, const float* right, uint32_t n, float alpha, float gain, float* state,
+                                  int16_t* pcm_stereo);
 
 /* The same sink ON THE DEVICE for the batched path: audio[stream * audio_stride + i] (f32, as sdrfm_process_batch leaves it) ->
  * pcm[stream * pcm_stride + 2*i + {0,1}] (int16, L = R), de-emphasis state carried per stream in the handle.  pcm_stride is in int16

@@ -13,15 +13,16 @@ The directory name contains a hyphen (it is fixed by the build contract), so imp
 from .lib import SdrfmError, load_library, library_path, STATUS, ABI_SYMBOLS
 from .demod import FmDemod, FmConfig
 from .wbfm import WbfmDemod, WbfmConfig
+from .stereo import StereoDemod, StereoConfig
 from .spectrum import SpectrumView, SpectrumConfig, power_db
-from .sink import PcmSink, pcm_deemph_s16_host
-from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config
-from .siggen import make_iq, MODES
+from .sink import PcmSink, pcm_deemph_s16_host, pcm_deemph_stereo_s16_host
+from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain
+from .siggen import make_iq, make_iq_stereo, MODES
 from .frontend import ReplayFrontEnd, XferState
 from . import fanout
 from . import lib
 
 __all__ = [
-    "SdrfmError", "load_library", "library_path", "STATUS", "ABI_SYMBOLS", "FmDemod", "FmConfig", "WbfmDemod", "WbfmConfig", "SpectrumView", "SpectrumConfig", "power_db", "PcmSink", "pcm_deemph_s16_host", "RTLSDR_FIR",
-    "rtlsdr_fir16", "lowpass_taps", "default_config", "make_iq", "MODES", "ReplayFrontEnd", "XferState", "fanout",
+    "SdrfmError", "load_library", "library_path", "STATUS", "ABI_SYMBOLS", "FmDemod", "FmConfig", "WbfmDemod", "WbfmConfig", "StereoDemod", "StereoConfig", "SpectrumView", "SpectrumConfig", "power_db", "PcmSink", "pcm_deemph_s16_host", "pcm_deemph_stereo_s16_host", "RTLSDR_FIR",
+    "rtlsdr_fir16", "lowpass_taps", "default_config", "stereo_pilot_taps", "stereo_diff_gain", "make_iq", "make_iq_stereo", "MODES", "ReplayFrontEnd", "XferState", "fanout",
 ]

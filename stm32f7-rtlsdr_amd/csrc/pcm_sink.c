@@ -29,4 +29,25 @@ int sdrfm_pcm_deemph_s16(const float* audio, uint32_t n, float alpha, float gain
   return SDRFM_OK;
 }
 
+/* one channel of the stereo form: the operations of sdrfm_pcm_deemph_s16, every second PCM slot */
+static void deemph_channel(const float* x, uint32_t n, float alpha, float gain, float* state, int16_t* pcm) {
+  float y = *state;
+  for (uint32_t i = 0; i < n; ++i) {
+    y = fmaf(alpha, x[i] - y, y);
+    float v = y * gain;
+    if (v > 32767.0f) v = 32767.0f;
+    if (v < -32768.0f) v = -32768.0f;
+    pcm[2 * i] = (int16_t)lrintf(v);
+  }
+  *state = y;
+}
+
+int sdrfm_pcm_deemph_stereo_s16(const float* left, const float* right, uint32_t n, float alpha, float gain, float* state,
+                                int16_t* pcm_stereo) {
+  if ((n && (!left || !right || !pcm_stereo)) || !state || !(alpha > 0.0f) || alpha > 1.0f) return SDRFM_EINVAL;
+  deemph_channel(left, n, alpha, gain, &state[0], pcm_stereo);
+  deemph_channel(right, n, alpha, gain, &state[1], pcm_stereo + 1);
+  return SDRFM_OK;
+}
+
 float sdrfm_pcm_alpha(float fs_hz, float tau_s) { return 1.0f - expf(-1.0f / (fs_hz * tau_s)); }

@@ -25,6 +25,8 @@ ABI_SYMBOLS = [
     "sdrfm_pcm_sink_create", "sdrfm_pcm_sink_destroy", "sdrfm_pcm_sink_reset", "sdrfm_pcm_sink_process_batch",
     "sdrfm_pcm_sink_set_stream", "sdrfm_pcm_sink_synchronize", "sdrfm_pcm_sink_get_state",
     "sdrfm_ring_create", "sdrfm_ring_destroy", "sdrfm_ring_submit", "sdrfm_ring_collect",
+    "sdrfm_stereo_create", "sdrfm_stereo_destroy", "sdrfm_stereo_reset", "sdrfm_stereo_audio_count", "sdrfm_stereo_process_batch",
+    "sdrfm_stereo_set_stream", "sdrfm_stereo_synchronize", "sdrfm_stereo_kernel_name", "sdrfm_pcm_deemph_stereo_s16",
 ]
 
 
@@ -67,6 +69,16 @@ class SpectrumConfig(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("n_streams", C.c_uint32), ("nfft", C.c_uint32), ("window", C.POINTER(C.c_float)),
         ("max_bytes_per_call", C.c_uint32), ("device", C.c_int32), ("flags", C.c_uint32),
+    ]
+
+
+class StereoConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_streams", C.c_uint32), ("fir_taps", C.c_uint32), ("fir_decim", C.c_uint32),
+        ("fir_coeffs", C.POINTER(C.c_float)), ("pilot_taps", C.c_uint32), ("pilot_coeffs", C.POINTER(C.c_float)),
+        ("pilot_min", C.c_float), ("diff_gain", C.c_float), ("audio_taps", C.c_uint32), ("audio_decim", C.c_uint32),
+        ("audio_coeffs", C.POINTER(C.c_float)), ("max_bytes_per_call", C.c_uint32), ("device", C.c_int32),
+        ("flags", C.c_uint32),
     ]
 
 
@@ -181,6 +193,24 @@ def load_library(dev=False):
     lib.sdrfm_shard_range.restype = C.c_int
     lib.sdrfm_pcm_deemph_s16.argtypes = [vp, u32, C.c_float, C.c_float, C.POINTER(C.c_float), vp]
     lib.sdrfm_pcm_deemph_s16.restype = C.c_int
+    lib.sdrfm_pcm_deemph_stereo_s16.argtypes = [vp, vp, u32, C.c_float, C.c_float, C.POINTER(C.c_float), vp]
+    lib.sdrfm_pcm_deemph_stereo_s16.restype = C.c_int
+    lib.sdrfm_stereo_create.argtypes = [C.POINTER(StereoConfig), C.POINTER(vp)]
+    lib.sdrfm_stereo_create.restype = C.c_int
+    lib.sdrfm_stereo_destroy.argtypes = [vp]
+    lib.sdrfm_stereo_destroy.restype = None
+    lib.sdrfm_stereo_reset.argtypes = [vp]
+    lib.sdrfm_stereo_reset.restype = C.c_int
+    lib.sdrfm_stereo_audio_count.argtypes = [vp, u32, u32p]
+    lib.sdrfm_stereo_audio_count.restype = C.c_int
+    lib.sdrfm_stereo_process_batch.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, C.c_size_t, vp, u32p, u32]
+    lib.sdrfm_stereo_process_batch.restype = C.c_int
+    lib.sdrfm_stereo_set_stream.argtypes = [vp, vp]
+    lib.sdrfm_stereo_set_stream.restype = C.c_int
+    lib.sdrfm_stereo_synchronize.argtypes = [vp]
+    lib.sdrfm_stereo_synchronize.restype = C.c_int
+    lib.sdrfm_stereo_kernel_name.argtypes = [vp]
+    lib.sdrfm_stereo_kernel_name.restype = C.c_char_p
     lib.sdrfm_pcm_alpha.argtypes = [C.c_float, C.c_float]
     lib.sdrfm_pcm_alpha.restype = C.c_float
     lib.sdrfm_ring_create.argtypes = [vp, u32, u32, C.POINTER(vp)]

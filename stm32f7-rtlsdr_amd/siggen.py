@@ -44,3 +44,31 @@ def make_iq(n_streams, n_samples, mode="fm", fs=2.4e6, first_id=0, threads=None,
         with ThreadPoolExecutor(threads) as ex:
             list(ex.map(one, range(n_streams)))
     return out
+
+
+def make_iq_stereo(n_streams, n_samples, left_hz, right_hz, deviation_hz, pilot=True, fs=2.4e6, first_id=0):
+    """uint8 [n_streams, 2*n_samples] of a broadcast-FM stereo signal, in numpy: composite
+    m = 0.9 [(L+R)/2 + (L-R)/2 sin 2φ] + 0.1 sin φ (φ the 19 kHz pilot's phase; without `pilot` the 0.1 sin φ term is left out and
+    L-R is not transmitted: m = 0.9 (L+R)/2), L = sin(2 pi left_hz t), R = sin(2 pi right_hz t); frequency fc + deviation_hz * m with a
+    per-stream carrier offset fc uniform in +-20 kHz, integrated by a float64 phase accumulator; I/Q = 127.5 + 100 (cos, sin) + N(0, 4)
+    noise, rounded and clipped to u8 (the C generator's amplitude and noise).  left_hz / right_hz: scalars or one per stream.  Stream s
+    draws from numpy's generator seeded with first_id + s."""
+    lh = np.broadcast_to(np.asarray(left_hz, dtype=np.float64), (n_streams,))
+    rh = np.broadcast_to(np.asarray(right_hz, dtype=np.float64), (n_streams,))
+    out = np.empty((n_streams, 2 * n_samples), dtype=np.uint8)
+    t = np.arange(n_samples, dtype=np.float64) / fs
+    ph = 2.0 * np.pi * 19e3 * t
+    for s in range(n_streams):
+        rng = np.random.default_rng(first_id + s)
+        fc = (rng.random() * 2.0 - 1.0) * 20000.0
+        phi0 = rng.random() * 2.0 * np.pi
+        L, R = np.sin(2.0 * np.pi * lh[s] * t), np.sin(2.0 * np.pi * rh[s] * t)
+        if pilot:
+            m = 0.9 * ((L + R) / 2 + (L - R) / 2 * np.sin(2.0 * ph)) + 0.1 * np.sin(ph)
+        else:
+            m = 0.9 * (L + R) / 2
+        phase = phi0 + np.cumsum(2.0 * np.pi * (fc + deviation_hz * m) / fs)
+        noise = rng.normal(0.0, 2.0, size=(2, n_samples))
+        out[s, 0::2] = np.clip(np.rint(127.5 + 100.0 * np.cos(phase) + noise[0]), 0, 255)
+        out[s, 1::2] = np.clip(np.rint(127.5 + 100.0 * np.sin(phase) + noise[1]), 0, 255)
+    return out

@@ -94,3 +94,17 @@ class PcmSink:
         self._ck(self._lib.sdrfm_pcm_sink_process_batch(self._h, C.c_void_p(audio.data_ptr()), audio.stride(0), n,
                                                         C.c_void_p(pcm.data_ptr()), pcm.stride(0), _l.F_DEVICE_PTRS | self._xf),
                  "sdrfm_pcm_sink_process_batch(device)")
+
+
+def pcm_deemph_stereo_s16_host(left, right, alpha, gain, state=(0.0, 0.0)):
+    """sdrfm_pcm_deemph_stereo_s16 (host-side C) on one stream: returns (pcm int16 [2n]: L, R interleaved, new (state_L, state_R))."""
+    lib = _l.load_library()
+    xl = np.ascontiguousarray(left, dtype=np.float32)
+    xr = np.ascontiguousarray(right, dtype=np.float32)
+    assert xl.shape == xr.shape and xl.ndim == 1
+    st = (C.c_float * 2)(*state)
+    pcm = np.zeros(2 * xl.size, np.int16)
+    rc = lib.sdrfm_pcm_deemph_stereo_s16(xl.ctypes.data, xr.ctypes.data, xl.size, alpha, gain, st, pcm.ctypes.data)
+    if rc != _l.OK:
+        raise _l.SdrfmError(rc, "sdrfm_pcm_deemph_stereo_s16")
+    return pcm, (st[0], st[1])

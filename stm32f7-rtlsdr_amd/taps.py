@@ -30,3 +30,20 @@ def default_config(fir_taps=64, fs=2.4e6, fir_decim=10, audio_taps=32, audio_dec
     h = rtlsdr_fir16() if fir_taps == 16 else lowpass_taps(fir_taps, 100e3 / fs)
     g = lowpass_taps(audio_taps, 15e3 / (fs / fir_decim))
     return h, g
+
+
+def stereo_pilot_taps(P, fs_d, f_pilot=19e3, cutoff_hz=1.5e3):
+    """Complex pilot-filter taps b[k] = 2 w[k] exp(+j 2 pi f_pilot/fs_d (k - Δ)), Δ = (P-1)/2, w the unity-DC-gain Hamming low-pass
+    of lowpass_taps: |q| = |b * d| is then the pilot's amplitude in radians.  Returns complex64 [P] (StereoConfig.pilot_coeffs)."""
+    P = int(P)
+    assert P % 2 == 1 and 1 <= P <= 255
+    w = lowpass_taps(P, cutoff_hz / fs_d).astype(np.float64)
+    k = np.arange(P, dtype=np.float64)
+    return (2.0 * w * np.exp(1j * 2.0 * np.pi * f_pilot / fs_d * (k - (P - 1) / 2))).astype(np.complex64)
+
+
+def stereo_diff_gain(D, fs, f_sub=38e3):
+    """2 / H_D(f_sub): H_D(f) = sin(pi f D/fs) / (D sin(pi f/fs)) is the gain of the discriminator's D-sample boxcar (d is the phase
+    step over D inputs), which leaves the L-R subcarrier weaker than L+R; this diff_gain restores the channel separation."""
+    x = np.pi * f_sub / fs
+    return float(2.0 / (np.sin(x * D) / (D * np.sin(x))))
