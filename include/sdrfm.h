@@ -251,7 +251,8 @@ const char* sdrfm_wbfm_kernel_name(const sdrfm_wbfm_t* h);
  * at the top of this file, unchanged; behind d, at fs/D, every FIR is an fp32 fmaf chain, oldest sample first, d[m < 0] = 0:
  *   pilot filter  q[m]  = sum_k b[k] * d[m-k]          P odd, 1 <= P <= 255, Δ = (P-1)/2; b[k] = (br[k], bi[k]) complex taps
  *                                                      given by the caller: two real chains qr, qi
- *   pilot power   pw    = fmaf(qr, qr, qi*qi)          pmin2 = pilot_min * pilot_min (fp32, once on the host; may be +inf)
+ *   pilot power   pw    = fmaf(qr, qr, qi*qi)          pmin2 = pilot_min * pilot_min (fp32, once on the host; may be +inf;
+ *                                                      a pilot_min whose pmin2 rounds to 0 is refused: SDRFM_EINVAL)
  *   38 kHz        c[m]  = pw >= pmin2 ? (-2.0f*(qr*qi)) / pw : 0.0f
  *   difference    s[m]  = (c[m] * diff_gain) * d[m-Δ]
  *   sum channel   am[j] = sum_k g[k] * d[(j+1)*Da - 1 - k - Δ]
@@ -282,7 +283,7 @@ typedef struct sdrfm_stereo_config {
   const float* fir_coeffs;        /* h[0..T), copied at create */
   uint32_t pilot_taps;            /* P: odd, 1 .. SDRFM_STEREO_MAX_PILOT_TAPS */
   const float* pilot_coeffs;      /* 2P floats: (br[k], bi[k]) pairs, copied at create */
-  float    pilot_min;             /* finite, > 0 (radians, the unit of |q|) */
+  float    pilot_min;             /* finite, > 0, pilot_min * pilot_min > 0 in fp32 (radians, the unit of |q|) */
   float    diff_gain;             /* finite; 2 = textbook, 2 / H_D(38 kHz) compensates the discriminator */
   uint32_t audio_taps;            /* Ta, as sdrfm_config */
   uint32_t audio_decim;           /* Da, as sdrfm_config */

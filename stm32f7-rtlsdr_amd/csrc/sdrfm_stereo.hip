@@ -368,6 +368,8 @@ int sdrfm_stereo_create(const sdrfm_stereo_config* cfg, sdrfm_stereo_t** out) {
   if (!cfg->fir_decim || cfg->fir_decim > SDRFM_MAX_DECIM || !cfg->audio_decim || cfg->audio_decim > SDRFM_MAX_DECIM) return SDRFM_EINVAL;
   if (!cfg->pilot_taps || cfg->pilot_taps > SDRFM_STEREO_MAX_PILOT_TAPS || !(cfg->pilot_taps & 1u)) return SDRFM_EINVAL;
   if (!std::isfinite(cfg->pilot_min) || !(cfg->pilot_min > 0.0f) || !std::isfinite(cfg->diff_gain)) return SDRFM_EINVAL;
+  // pmin2 rounding to 0 (pilot_min below ~2.6e-23) would open the gate for pw = 0: c = 0/0 = NaN on silent input
+  if (!(cfg->pilot_min * cfg->pilot_min > 0.0f)) return SDRFM_EINVAL;
   if (!finite_all(cfg->fir_coeffs, cfg->fir_taps) || !finite_all(cfg->audio_coeffs, cfg->audio_taps) ||
       !finite_all(cfg->pilot_coeffs, 2 * cfg->pilot_taps))
     return SDRFM_EINVAL;

@@ -1140,7 +1140,8 @@ int sdrfm_wbfm_create(const sdrfm_wbfm_config* cfg, sdrfm_wbfm_t** out) {
     return SDRFM_NOT_SUPPORTED;
   }
   h->fused_ok = (cfg->proto_taps == 128 && h->HD <= 10 && cfg->resamp_up * 10u <= 512u && !(cfg->flags & SDRFM_WBFM_CFG_FORCE_GENERIC));
-  h->steps_ok = h->fused_ok && cfg->resamp_up >= 2 && !(cfg->flags & SDRFM_WBFM_CFG_BRANCH_LANES);
+  // 4 L <= M is a gate of the step kernel: decided here, so that the name before any call is the kernel the calls will take
+  h->steps_ok = h->fused_ok && cfg->resamp_up >= 2 && 4u * cfg->resamp_up <= cfg->resamp_down && !(cfg->flags & SDRFM_WBFM_CFG_BRANCH_LANES);
   h->n_cu = (uint32_t)prop.multiProcessorCount;
   h->force_nt = (cfg->flags >> SDRFM_WBFM_CFG_RUN_STEPS_SHIFT) & ~1u;   // test hook: fixed run length of the fused kernel (0 = chosen per call)
   if (h->force_nt && (h->force_nt < 64u || h->force_nt > 8192u)) { wfree(h); return SDRFM_EINVAL; }   // the range the kernels' own choice stays in
@@ -1236,7 +1237,7 @@ static int wenqueue(sdrfm_wbfm* h, const uint8_t* d_iq, size_t iq_stride, uint32
   w.res_r0 = (uint32_t)((h->n_a * c.resamp_down) % c.resamp_up);
   const uint64_t span = (uint64_t)(c.n_streams - 1) * iq_stride + nbytes;
   w.iq_span = (uint32_t)span;
-  if (h->steps_ok && Tn >= 64 && 4u * c.resamp_up <= c.resamp_down && ((uint64_t)A + 16) * c.resamp_down + c.resamp_up < (1ull << 26) && ((uint64_t)Tn + 64) * c.resamp_up < (1ull << 31)) {
+  if (h->steps_ok && Tn >= 64 && ((uint64_t)A + 16) * c.resamp_down + c.resamp_up < (1ull << 26) && ((uint64_t)Tn + 64) * c.resamp_up < (1ull << 31)) {
     // step kernel: one wave per run of NT steps of one stream; a run that does not start the call re-computes HD + 1 steps.
     // One round of two waves per SIMD (8 waves per CU) when the streams allow it, runs of at least 128 steps.
     uint64_t runs = (8ull * h->n_cu + c.n_streams - 1) / c.n_streams;

@@ -55,7 +55,8 @@ def _create(pkg, **kw):
 BAD = {
     "P_even": dict(pilot_taps=100), "P_zero": dict(pilot_taps=0), "P_over_255": dict(pilot_taps=257, b=np.zeros(2 * 257, np.float32)),
     "pilot_min_zero": dict(pilot_min=0.0), "pilot_min_negative": dict(pilot_min=-0.05), "pilot_min_nan": dict(pilot_min=float("nan")),
-    "pilot_min_inf": dict(pilot_min=float("inf")), "diff_gain_nan": dict(diff_gain=float("nan")), "diff_gain_inf": dict(diff_gain=float("inf")),
+    "pilot_min_inf": dict(pilot_min=float("inf")), "pilot_min_square_underflows": dict(pilot_min=2e-23),
+    "pilot_min_smallest_denormal": dict(pilot_min=float(np.nextafter(np.float32(0), np.float32(1)))),"diff_gain_nan": dict(diff_gain=float("nan")), "diff_gain_inf": dict(diff_gain=float("inf")),
     "T_zero": dict(fir_taps=0), "T_over": dict(fir_taps=257, h=np.zeros(257, np.float32)), "D_zero": dict(fir_decim=0), "D_over": dict(fir_decim=65),
     "Ta_zero": dict(audio_taps=0), "Ta_over": dict(audio_taps=257, g=np.zeros(257, np.float32)), "Da_zero": dict(audio_decim=0),
     "Da_over": dict(audio_decim=65), "null_h": dict(h=None), "null_g": dict(g=None), "null_b": dict(b=None), "streams_zero": dict(n_streams=0),
