@@ -307,6 +307,98 @@ int  sdrfm_stereo_synchronize(sdrfm_stereo_t* h);
 const char* sdrfm_stereo_kernel_name(const sdrfm_stereo_t* h);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Radio Data System, layer 1: IQ bytes in, the complex RDS baseband out.  The same hand-off contract as
+ * sdrfm_stereo_process_batch (buffer format, status codes, threading).  K1-K3 (x, y, d, state carried across calls) and the pilot
+ * filter are the stereo definition's, unchanged: q[m] = sum_k b[k] * d[m-k] as two real fp32 fmaf chains, oldest sample first,
+ * P odd, Δ = (P-1)/2, pw = fmaf(qr, qr, qi*qi), pmin2 = pilot_min * pilot_min (a pmin2 that rounds to 0 is refused).  Behind it,
+ * all fp32, every product and quotient rounded once, no contraction other than the fmafs written:
+ *   pilot's 2nd harmonic, unit size   on = pw >= pmin2; u2r = fmaf(qr, qr, -(qi*qi)) / pw, u2i = (2.0f*(qr*qi)) / pw
+ *   57 kHz carrier, size |q|          kr = fmaf(u2r, qr, -(u2i*qi)), ki = fmaf(u2r, qi, u2i*qr); kr = ki = 0.0f where !on
+ *   mixed down                        zr[m] = (kr*rds_gain) * d[m-Δ], zi[m] = (ki*rds_gain) * d[m-Δ]; z[m<0] = 0, d[m<0] = 0
+ *   decimating low-pass               wr[j] = sum_k g[k] * zr[(j+1)*Dr - 1 - k], wi[j] likewise: fmaf chains, oldest first
+ *   output                            bb[stream*bb_stride + 2j] = wr[j], bb[... + 2j + 1] = wi[j] (floats), at fs/(D*Dr)
+ * The carrier is |q| e^{j3φ} and not e^{j3φ}: the odd harmonic of a unit phasor needs a square root, and only fmaf, products and /
+ * are known to match the fp32 reference bit for bit.  BPSK decoding is scale-free and the pilot's size is constant for a station,
+ * so nothing is lost.  The standard lets the RDS subcarrier sit in phase or in quadrature with the pilot's third harmonic: the data
+ * may arrive on any fixed axis of w, which is why the output is complex and why the decoder below finds the axis.
+ * rds_gain = 2 / H_D(57 kHz) (taps.rds_gain) undoes the discriminator's boxcar at the subcarrier.
+ * The per-call output count is the mono path's for (D, Dr).  pilot_count (n_streams words, or NULL): per stream, how many of the
+ * call's new d's had pw >= pmin2.  Parity unpinned like the rest: every kernel that serves it is bit-identical to this definition.
+ * Host buffers: synchronous staged call.  SDRFM_F_DEVICE_PTRS: iq, bb and pilot_count are device memory on cfg.device, the call is
+ * only enqueued on the handle's stream.  SDRFM_F_OVERLAP is rejected (SDRFM_EINVAL).  Any even nbytes up to max_bytes_per_call
+ * (else SDRFM_ECAPACITY).  Invalid configurations answer SDRFM_EINVAL before any device is looked for.
+ * kernel name: "rds-fast ..." (T = 64, D = 10, P = 101, any Tr, Dr) or "rds-generic ..." (every other shape); same bits either way.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define SDRFM_RDS_CFG_FORCE_GENERIC 1u      /* never the fast kernel (tests) */
+
+typedef struct sdrfm_rds_config {
+  uint32_t struct_size;           /* = sizeof(sdrfm_rds_config) */
+  uint32_t n_streams;
+  uint32_t fir_taps;              /* T, as sdrfm_config */
+  uint32_t fir_decim;             /* D, as sdrfm_config */
+  const float* fir_coeffs;        /* h[0..T), copied at create */
+  uint32_t pilot_taps;            /* P: odd, 1 .. SDRFM_STEREO_MAX_PILOT_TAPS */
+  const float* pilot_coeffs;      /* 2P floats: (br[k], bi[k]) pairs, copied at create */
+  float    pilot_min;             /* finite, > 0, pilot_min * pilot_min > 0 in fp32 (radians, the unit of |q|) */
+  float    rds_gain;              /* finite; 2 / H_D(57 kHz) compensates the discriminator */
+  uint32_t rds_taps;              /* Tr: 1 .. SDRFM_MAX_TAPS */
+  uint32_t rds_decim;             /* Dr: 1 .. SDRFM_MAX_DECIM */
+  const float* rds_coeffs;        /* g[0..Tr), copied at create */
+  uint32_t max_bytes_per_call;    /* per stream; 0 = 1 MiB */
+  int32_t  device;
+  uint32_t flags;                 /* 0 or SDRFM_RDS_CFG_FORCE_GENERIC */
+} sdrfm_rds_config;
+
+typedef struct sdrfm_rds sdrfm_rds_t;
+
+int  sdrfm_rds_create(const sdrfm_rds_config* cfg, sdrfm_rds_t** out);
+void sdrfm_rds_destroy(sdrfm_rds_t* h);
+int  sdrfm_rds_reset(sdrfm_rds_t* h);
+/* complex outputs of the NEXT call of nbytes */
+int  sdrfm_rds_count(const sdrfm_rds_t* h, uint32_t nbytes, uint32_t* n_out);
+/* bb for stream s at bb + s*bb_stride (floats; 2 per output: bb_stride >= 2 * n_out) */
+int  sdrfm_rds_process_batch(sdrfm_rds_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* bb, size_t bb_stride,
+                             uint32_t* pilot_count, uint32_t* n_out, uint32_t flags);
+int  sdrfm_rds_set_stream(sdrfm_rds_t* h, void* hip_stream);
+int  sdrfm_rds_synchronize(sdrfm_rds_t* h);
+const char* sdrfm_rds_kernel_name(const sdrfm_rds_t* h);
+
+/* Layer 2 (plain C, host only, no GPU): the 1187.5 bit/s part.
+ *   sdrfm_rds_checkword(info, offset) = (info * x^10 mod g(x)) XOR offset word, g(x) = x^10+x^8+x^7+x^5+x^4+x^3+1 (0x5B9);
+ *                                       offset 0..4 = A 0x0FC, B 0x198, C 0x168, C' 0x350, D 0x1B4 (any other: 0xFFFF)
+ *   sdrfm_rds_syndrome(block26)       = block26 mod g(x): syndrome((info << 10) | checkword(info, o)) is offset word o itself.
+ * sdrfm_rds_sync_t is one stream's decoder: it finds the data axis of w, recovers the 1187.5 Hz bit clock and tracks it (a dongle
+ * crystal is off by up to +-100 ppm), undoes the biphase symbol and the differential coding, acquires block synchronisation only
+ * on two consecutive blocks whose syndromes are offset words in sequence 26 bits apart, drops it after a run of failed blocks, and
+ * emits one sdrfm_rds_group per group: block[i] the 16 information bits of block i + 1, ok_mask bit i set where that block's
+ * syndrome was its offset word (error detection only: no correction), version_b 1 where block 3 carried C'.
+ * State persists across pushes: any cut of a baseband into pushes gives the same groups.  bb holds n (re, im) pairs; at most cap
+ * groups are written (further ones of that push are dropped: give cap >= n / (104 * samples per bit) + 1). */
+typedef struct sdrfm_rds_group {
+  uint16_t block[4];
+  uint8_t  ok_mask;
+  uint8_t  version_b;
+} sdrfm_rds_group;
+
+typedef struct sdrfm_rds_sync_info {
+  uint64_t bits;                  /* bits decided */
+  uint64_t blocks_ok;             /* blocks with the expected syndrome, while in sync */
+  uint64_t blocks_failed;
+  uint32_t in_sync;
+  uint32_t groups;                /* groups emitted */
+} sdrfm_rds_sync_info;
+
+typedef struct sdrfm_rds_sync sdrfm_rds_sync_t;
+
+uint16_t sdrfm_rds_checkword(uint16_t info, int offset);
+uint16_t sdrfm_rds_syndrome(uint32_t block26);
+int  sdrfm_rds_sync_create(double sample_rate_hz, sdrfm_rds_sync_t** out);   /* 4 .. 64 samples per bit, else SDRFM_EINVAL */
+void sdrfm_rds_sync_destroy(sdrfm_rds_sync_t* s);
+int  sdrfm_rds_sync_reset(sdrfm_rds_sync_t* s);
+int  sdrfm_rds_sync_push(sdrfm_rds_sync_t* s, const float* bb, uint32_t n, sdrfm_rds_group* out, uint32_t cap, uint32_t* n_out);
+int  sdrfm_rds_sync_stats(const sdrfm_rds_sync_t* s, sdrfm_rds_sync_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Spectrum view of the IQ buffer — the reference's own next task ("Perform some FFT on the samples to check what we are
  * receiving", README.md:29) on the same buffer contract (RTLSDR_CommItfTypedef.buff, usbh_rtlsdr.h:165-173): per stream
  * the windowed nfft-point power spectrum averaged over the consecutive, non-overlapping frames of the buffer, DC in the

@@ -27,6 +27,9 @@ ABI_SYMBOLS = [
     "sdrfm_ring_create", "sdrfm_ring_destroy", "sdrfm_ring_submit", "sdrfm_ring_collect",
     "sdrfm_stereo_create", "sdrfm_stereo_destroy", "sdrfm_stereo_reset", "sdrfm_stereo_audio_count", "sdrfm_stereo_process_batch",
     "sdrfm_stereo_set_stream", "sdrfm_stereo_synchronize", "sdrfm_stereo_kernel_name", "sdrfm_pcm_deemph_stereo_s16",
+    "sdrfm_rds_create", "sdrfm_rds_destroy", "sdrfm_rds_reset", "sdrfm_rds_count", "sdrfm_rds_process_batch", "sdrfm_rds_set_stream",
+    "sdrfm_rds_synchronize", "sdrfm_rds_kernel_name", "sdrfm_rds_checkword", "sdrfm_rds_syndrome", "sdrfm_rds_sync_create",
+    "sdrfm_rds_sync_destroy", "sdrfm_rds_sync_reset", "sdrfm_rds_sync_push", "sdrfm_rds_sync_stats",
 ]
 
 
@@ -80,6 +83,25 @@ class StereoConfig(C.Structure):
         ("audio_coeffs", C.POINTER(C.c_float)), ("max_bytes_per_call", C.c_uint32), ("device", C.c_int32),
         ("flags", C.c_uint32),
     ]
+
+
+class RdsConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_streams", C.c_uint32), ("fir_taps", C.c_uint32), ("fir_decim", C.c_uint32),
+        ("fir_coeffs", C.POINTER(C.c_float)), ("pilot_taps", C.c_uint32), ("pilot_coeffs", C.POINTER(C.c_float)),
+        ("pilot_min", C.c_float), ("rds_gain", C.c_float), ("rds_taps", C.c_uint32), ("rds_decim", C.c_uint32),
+        ("rds_coeffs", C.POINTER(C.c_float)), ("max_bytes_per_call", C.c_uint32), ("device", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
+class RdsGroup(C.Structure):
+    _fields_ = [("block", C.c_uint16 * 4), ("ok_mask", C.c_uint8), ("version_b", C.c_uint8)]
+
+
+class RdsSyncInfo(C.Structure):
+    _fields_ = [("bits", C.c_uint64), ("blocks_ok", C.c_uint64), ("blocks_failed", C.c_uint64), ("in_sync", C.c_uint32),
+                ("groups", C.c_uint32)]
 
 
 def library_path(dev=False):
@@ -211,6 +233,36 @@ def load_library(dev=False):
     lib.sdrfm_stereo_synchronize.restype = C.c_int
     lib.sdrfm_stereo_kernel_name.argtypes = [vp]
     lib.sdrfm_stereo_kernel_name.restype = C.c_char_p
+    lib.sdrfm_rds_create.argtypes = [C.POINTER(RdsConfig), C.POINTER(vp)]
+    lib.sdrfm_rds_create.restype = C.c_int
+    lib.sdrfm_rds_destroy.argtypes = [vp]
+    lib.sdrfm_rds_destroy.restype = None
+    lib.sdrfm_rds_reset.argtypes = [vp]
+    lib.sdrfm_rds_reset.restype = C.c_int
+    lib.sdrfm_rds_count.argtypes = [vp, u32, u32p]
+    lib.sdrfm_rds_count.restype = C.c_int
+    lib.sdrfm_rds_process_batch.argtypes = [vp, vp, C.c_size_t, u32, vp, C.c_size_t, vp, u32p, u32]
+    lib.sdrfm_rds_process_batch.restype = C.c_int
+    lib.sdrfm_rds_set_stream.argtypes = [vp, vp]
+    lib.sdrfm_rds_set_stream.restype = C.c_int
+    lib.sdrfm_rds_synchronize.argtypes = [vp]
+    lib.sdrfm_rds_synchronize.restype = C.c_int
+    lib.sdrfm_rds_kernel_name.argtypes = [vp]
+    lib.sdrfm_rds_kernel_name.restype = C.c_char_p
+    lib.sdrfm_rds_checkword.argtypes = [C.c_uint16, C.c_int]
+    lib.sdrfm_rds_checkword.restype = C.c_uint16
+    lib.sdrfm_rds_syndrome.argtypes = [u32]
+    lib.sdrfm_rds_syndrome.restype = C.c_uint16
+    lib.sdrfm_rds_sync_create.argtypes = [C.c_double, C.POINTER(vp)]
+    lib.sdrfm_rds_sync_create.restype = C.c_int
+    lib.sdrfm_rds_sync_destroy.argtypes = [vp]
+    lib.sdrfm_rds_sync_destroy.restype = None
+    lib.sdrfm_rds_sync_reset.argtypes = [vp]
+    lib.sdrfm_rds_sync_reset.restype = C.c_int
+    lib.sdrfm_rds_sync_push.argtypes = [vp, vp, u32, C.POINTER(RdsGroup), u32, u32p]
+    lib.sdrfm_rds_sync_push.restype = C.c_int
+    lib.sdrfm_rds_sync_stats.argtypes = [vp, C.POINTER(RdsSyncInfo)]
+    lib.sdrfm_rds_sync_stats.restype = C.c_int
     lib.sdrfm_pcm_alpha.argtypes = [C.c_float, C.c_float]
     lib.sdrfm_pcm_alpha.restype = C.c_float
     lib.sdrfm_ring_create.argtypes = [vp, u32, u32, C.POINTER(vp)]

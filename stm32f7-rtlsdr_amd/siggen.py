@@ -72,3 +72,58 @@ def make_iq_stereo(n_streams, n_samples, left_hz, right_hz, deviation_hz, pilot=
         out[s, 0::2] = np.clip(np.rint(127.5 + 100.0 * np.cos(phase) + noise[0]), 0, 255)
         out[s, 1::2] = np.clip(np.rint(127.5 + 100.0 * np.sin(phase) + noise[1]), 0, 255)
     return out
+
+
+def rds_waveform(bits, oversample=128):
+    """The RDS data signal of `bits` (the standard's coder: differential coding e[n] = b[n] xor e[n-1], then per bit a pair of impulses
+    +-(2e - 1) half a bit apart — the biphase symbol —, shaped by H(f) = cos(pi f Tb / 4), |f| <= 2 / Tb = 2375 Hz) on a grid of
+    `oversample` points per bit, periodic over the bits given, peak 1.  Returns float64 [len(bits) * oversample]."""
+    bits = np.asarray(bits, dtype=np.int64) & 1
+    e = np.bitwise_xor.accumulate(bits)
+    n = bits.size * oversample
+    imp = np.zeros(n)
+    imp[0::oversample] = 2.0 * e - 1.0
+    imp[oversample // 2::oversample] = -(2.0 * e - 1.0)
+    f = np.fft.rfftfreq(n, d=1.0 / oversample)                    # in units of 1 / Tb
+    shape = np.where(f <= 2.0, np.cos(np.pi * f / 4.0), 0.0)
+    w = np.fft.irfft(np.fft.rfft(imp) * shape, n)
+    return w / np.abs(w).max()
+
+
+def make_iq_rds(n_streams, n_samples, groups, rds_deviation_hz=3e3, rds_phase=0.0, clock_ppm=0.0, pilot=True, left_hz=1e3, right_hz=3.1e3,
+                deviation_hz=75e3, fs=2.4e6, first_id=0):
+    """uint8 [n_streams, 2*n_samples] of a broadcast-FM station with RDS, in numpy: make_iq_stereo's multiplex with the pilot at 9 % and
+    the RDS term added,
+    m = 0.87 [(L+R)/2 + (L-R)/2 sin 2φ] + 0.09 sin φ + (rds_deviation_hz / deviation_hz) r(t) sin(3φ + rds_phase),
+    r the data signal of `groups` (4-tuples of 16-bit blocks, repeated as long as the samples last; rds_waveform), its bit clock the
+    pilot's frequency / 16, bit 0 starting at t = 0.  clock_ppm scales the pilot (and with it the subcarriers and the bit clock) as a
+    transmitter-against-dongle crystal offset does.  Without `pilot` the station is mono: m = 0.87 (L+R)/2, no subcarriers at all.
+    Carrier offset, start phase and noise per stream as in make_iq_stereo (generator seeded with first_id + s)."""
+    from .rds import rds_group_bits
+    out = np.empty((n_streams, 2 * n_samples), dtype=np.uint8)
+    t = np.arange(n_samples, dtype=np.float64) / fs
+    f_pilot = 19e3 * (1.0 + clock_ppm * 1e-6)
+    ph = 2.0 * np.pi * f_pilot * t
+    L, R = np.sin(2.0 * np.pi * left_hz * t), np.sin(2.0 * np.pi * right_hz * t)
+    if pilot:
+        n_bits = int(np.ceil(n_samples / fs * f_pilot / 16.0)) + 2
+        cyc = [b for g in groups for b in rds_group_bits(g)]
+        bits = (cyc * (n_bits // len(cyc) + 1))[:((n_bits + 103) // 104) * 104]
+        ov = 128
+        w = rds_waveform(bits, ov)
+        pos = (f_pilot * t / 16.0) * ov                            # position on the waveform's grid
+        i0 = np.floor(pos).astype(np.int64)
+        fr = pos - i0
+        r = w[i0 % w.size] * (1.0 - fr) + w[(i0 + 1) % w.size] * fr
+        m = 0.87 * ((L + R) / 2 + (L - R) / 2 * np.sin(2.0 * ph)) + 0.09 * np.sin(ph) + (rds_deviation_hz / deviation_hz) * r * np.sin(3.0 * ph + rds_phase)
+    else:
+        m = 0.87 * (L + R) / 2
+    for s in range(n_streams):
+        rng = np.random.default_rng(first_id + s)
+        fc = (rng.random() * 2.0 - 1.0) * 20000.0
+        phi0 = rng.random() * 2.0 * np.pi
+        phase = phi0 + np.cumsum(2.0 * np.pi * (fc + deviation_hz * m) / fs)
+        noise = rng.normal(0.0, 2.0, size=(2, n_samples))
+        out[s, 0::2] = np.clip(np.rint(127.5 + 100.0 * np.cos(phase) + noise[0]), 0, 255)
+        out[s, 1::2] = np.clip(np.rint(127.5 + 100.0 * np.sin(phase) + noise[1]), 0, 255)
+    return out

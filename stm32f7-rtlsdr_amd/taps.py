@@ -47,3 +47,13 @@ def stereo_diff_gain(D, fs, f_sub=38e3):
     step over D inputs), which leaves the L-R subcarrier weaker than L+R; this diff_gain restores the channel separation."""
     x = np.pi * f_sub / fs
     return float(2.0 / (np.sin(x * D) / (D * np.sin(x))))
+
+
+def rds_gain(D, fs, f_sub=57e3):
+    """2 / H_D(f_sub) at the RDS subcarrier: the same boxcar argument as stereo_diff_gain (H_D = 0.91061 -> 2.1963 at D = 10, 2.4 MS/s)."""
+    return stereo_diff_gain(D, fs, f_sub)
+
+
+def rds_lowpass_taps(Tr, fs_d, cutoff_hz=3.0e3):
+    """The decimating low-pass behind the 57 kHz mixer: lowpass_taps at cutoff_hz / fs_d (the RDS spectrum ends at +-2.4 kHz)."""
+    return lowpass_taps(Tr, cutoff_hz / fs_d)
