@@ -620,9 +620,9 @@ struct sdrfm_spectrum {
   float* d_win;
   uint8_t* d_iq; size_t d_iq_stride;
   float* d_power;
-  spec_kernel_t kernel;     // k_spectrum<log2 N>: every N; for N = 512 / 1024 only when iq or iq_stride is odd
+  spec_kernel_t kernel;     // k_spectrum<log2 N>: every N; for N = 64 .. 1024 only when iq or iq_stride is odd
   size_t lds_bytes;
-  spec_kernel_t chain;      // k_spectrum_chain (N = 512 / 1024, iq and iq_stride even) or null
+  spec_kernel_t chain;      // k_spectrum_chain (N = 64 .. 1024, iq and iq_stride even) or null
   size_t chain_lds_bytes;
   int chain_nwf;            // its waves per workgroup
   char name[2][48];         // kernel names as the profiler prints them: [0] k_spectrum<..>, [1] k_spectrum_chain<..>
