@@ -399,6 +399,62 @@ int  sdrfm_rds_sync_push(sdrfm_rds_sync_t* s, const float* bb, uint32_t n, sdrfm
 int  sdrfm_rds_sync_stats(const sdrfm_rds_sync_t* s, sdrfm_rds_sync_info* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Broadcast receiver: the stereo audio and the RDS baseband of the same streams from one kernel launch, for the
+ * user who tunes a station and wants both.  There is no new arithmetic: L and R are the stereo definition's above, bb is the RDS
+ * definition's, both evaluated on the same d and the same pilot filter output q, and pilot_count is the one number the two handles
+ * agree on.  Every output bit equals what sdrfm_stereo_process_batch and sdrfm_rds_process_batch give for the same taps, pilot_min,
+ * gains and sequence of calls; the launch walks K1-K3 and the pilot filter once where the two handles walk them twice.
+ * The configuration is the union of the two; its limits and refusals are theirs (SDRFM_EINVAL before any device is looked for).
+ * The two decimators' phases are carried separately: n_audio is the mono path's count for (D, Da), n_rds the one for (D, Dr).
+ * The hand-off contract is sdrfm_stereo_process_batch's: host buffers make a synchronous staged call; with SDRFM_F_DEVICE_PTRS iq,
+ * left, right, bb and pilot_count are device memory on cfg.device and the call is only enqueued on the handle's stream.
+ * SDRFM_F_OVERLAP is rejected (SDRFM_EINVAL); odd nbytes: SDRFM_EODD; nbytes above max_bytes_per_call, or (with more than one
+ * stream) iq_stride < nbytes, audio_stride < n_audio, bb_stride < 2 * n_rds: SDRFM_ECAPACITY.  left / right (bb) may be NULL only
+ * when this call's n_audio (n_rds) is 0; pilot_count may be NULL.  nbytes == 0 is a no-op that zeroes pilot_count.  A refused call
+ * leaves the state alone.
+ * kernel name: "bcast-fast T64 D10 P101 Ta.. Da.. Tr.. Dr.." (T = 64, D = 10, P = 101, any Ta, Da, Tr, Dr whose step fits the
+ * workgroup's memory) or "bcast-generic ..." (every other shape); same bits either way.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define SDRFM_BCAST_CFG_FORCE_GENERIC 1u    /* never the fast kernel (tests) */
+
+typedef struct sdrfm_bcast_config {
+  uint32_t struct_size;           /* = sizeof(sdrfm_bcast_config) */
+  uint32_t n_streams;
+  uint32_t fir_taps;              /* T, as sdrfm_config */
+  uint32_t fir_decim;             /* D, as sdrfm_config */
+  const float* fir_coeffs;        /* h[0..T), copied at create */
+  uint32_t pilot_taps;            /* P: odd, 1 .. SDRFM_STEREO_MAX_PILOT_TAPS */
+  const float* pilot_coeffs;      /* 2P floats: (br[k], bi[k]) pairs, copied at create */
+  float    pilot_min;             /* finite, > 0, pilot_min * pilot_min > 0 in fp32 (radians, the unit of |q|) */
+  float    diff_gain;             /* finite; as sdrfm_stereo_config */
+  uint32_t audio_taps;            /* Ta: 1 .. SDRFM_MAX_TAPS */
+  uint32_t audio_decim;           /* Da: 1 .. SDRFM_MAX_DECIM */
+  const float* audio_coeffs;      /* g[0..Ta) of the stereo definition, copied at create */
+  float    rds_gain;              /* finite; as sdrfm_rds_config */
+  uint32_t rds_taps;              /* Tr: 1 .. SDRFM_MAX_TAPS */
+  uint32_t rds_decim;             /* Dr: 1 .. SDRFM_MAX_DECIM */
+  const float* rds_coeffs;        /* g[0..Tr) of the RDS definition, copied at create */
+  uint32_t max_bytes_per_call;    /* per stream; 0 = 1 MiB */
+  int32_t  device;
+  uint32_t flags;                 /* 0 or SDRFM_BCAST_CFG_FORCE_GENERIC */
+} sdrfm_bcast_config;
+
+typedef struct sdrfm_bcast sdrfm_bcast_t;
+
+int  sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out);
+void sdrfm_bcast_destroy(sdrfm_bcast_t* h);
+int  sdrfm_bcast_reset(sdrfm_bcast_t* h);
+/* audio outputs (per channel) and complex RDS outputs of the NEXT call of nbytes */
+int  sdrfm_bcast_counts(const sdrfm_bcast_t* h, uint32_t nbytes, uint32_t* n_audio, uint32_t* n_rds);
+/* left / right for stream s at left + s*audio_stride, right + s*audio_stride (floats); bb at bb + s*bb_stride (floats; 2 per output) */
+int  sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left, float* right,
+                               size_t audio_stride, float* bb, size_t bb_stride, uint32_t* pilot_count, uint32_t* n_audio,
+                               uint32_t* n_rds, uint32_t flags);
+int  sdrfm_bcast_set_stream(sdrfm_bcast_t* h, void* hip_stream);
+int  sdrfm_bcast_synchronize(sdrfm_bcast_t* h);
+const char* sdrfm_bcast_kernel_name(const sdrfm_bcast_t* h);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Spectrum view of the IQ buffer — the reference's own next task ("Perform some FFT on the samples to check what we are
  * receiving", README.md:29) on the same buffer contract (RTLSDR_CommItfTypedef.buff, usbh_rtlsdr.h:165-173): per stream
  * the windowed nfft-point power spectrum averaged over the consecutive, non-overlapping frames of the buffer, DC in the

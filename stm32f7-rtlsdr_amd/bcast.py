@@ -1,0 +1,127 @@
+"""BroadcastDemod — Python mirror of the sdrfm_bcast_* C entry points (the broadcast receiver): the stereo handle's L
+and R and the RDS handle's complex baseband of the same streams from one kernel launch, bit for bit what StereoDemod and RdsDemod give."""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import lib as _l
+from .stereo import _pilot_floats
+
+CFG_FORCE_GENERIC = 1   # SDRFM_BCAST_CFG_FORCE_GENERIC (include/sdrfm.h)
+
+
+@dataclass
+class BroadcastConfig:
+    fir_coeffs: np.ndarray            # h[0..T): channel low-pass at fs
+    audio_coeffs: np.ndarray          # g[0..Ta): audio low-pass at fs/D (StereoConfig.audio_coeffs)
+    rds_coeffs: np.ndarray            # g[0..Tr): low-pass at fs/D behind the 57 kHz mixer (RdsConfig.rds_coeffs)
+    pilot_coeffs: np.ndarray          # b[0..P): complex taps (complex array, or 2P floats re, im), P odd (taps.stereo_pilot_taps)
+    pilot_min: float = 0.05           # |q| below this (radians) is "no pilot": L = R, bb = 0
+    diff_gain: float = 2.0            # taps.stereo_diff_gain(D, fs) compensates the discriminator's boxcar at 38 kHz
+    rds_gain: float = 2.0             # taps.rds_gain(D, fs) does at 57 kHz
+    fir_decim: int = 10
+    audio_decim: int = 5
+    rds_decim: int = 25
+    n_streams: int = 1
+    max_bytes_per_call: int = 1 << 20
+    device: int = 0
+    force_generic: bool = False       # SDRFM_BCAST_CFG_FORCE_GENERIC (tests): never the fast kernel
+
+
+class BroadcastDemod:
+    def __init__(self, cfg: BroadcastConfig):
+        self._lib = _l.load_library()
+        self.cfg = cfg
+        self._hc = np.ascontiguousarray(cfg.fir_coeffs, dtype=np.float32)
+        self._gac = np.ascontiguousarray(cfg.audio_coeffs, dtype=np.float32)
+        self._grc = np.ascontiguousarray(cfg.rds_coeffs, dtype=np.float32)
+        self._bc = _pilot_floats(cfg.pilot_coeffs)
+        fp = C.POINTER(C.c_float)
+        c = _l.BcastConfig()
+        c.struct_size = C.sizeof(_l.BcastConfig)
+        c.n_streams = cfg.n_streams
+        c.fir_taps, c.fir_decim, c.fir_coeffs = self._hc.size, cfg.fir_decim, self._hc.ctypes.data_as(fp)
+        c.pilot_taps, c.pilot_coeffs = self._bc.size // 2, self._bc.ctypes.data_as(fp)
+        c.pilot_min, c.diff_gain, c.rds_gain = float(cfg.pilot_min), float(cfg.diff_gain), float(cfg.rds_gain)
+        c.audio_taps, c.audio_decim, c.audio_coeffs = self._gac.size, cfg.audio_decim, self._gac.ctypes.data_as(fp)
+        c.rds_taps, c.rds_decim, c.rds_coeffs = self._grc.size, cfg.rds_decim, self._grc.ctypes.data_as(fp)
+        c.max_bytes_per_call, c.device = cfg.max_bytes_per_call, cfg.device
+        c.flags = CFG_FORCE_GENERIC if cfg.force_generic else 0
+        self._h = C.c_void_p()
+        st = self._lib.sdrfm_bcast_create(C.byref(c), C.byref(self._h))
+        if st != _l.OK:
+            self._h = None
+            raise _l.SdrfmError(st, "sdrfm_bcast_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sdrfm_bcast_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _ck(self, st, where):
+        if st != _l.OK:
+            raise _l.SdrfmError(st, where)
+
+    def reset(self):
+        self._ck(self._lib.sdrfm_bcast_reset(self._h), "sdrfm_bcast_reset")
+
+    def counts(self, nbytes):
+        """(audio outputs per channel, complex RDS outputs) per stream of the NEXT call of nbytes"""
+        na, nr = C.c_uint32(), C.c_uint32()
+        self._ck(self._lib.sdrfm_bcast_counts(self._h, int(nbytes), C.byref(na), C.byref(nr)), "sdrfm_bcast_counts")
+        return na.value, nr.value
+
+    def set_stream(self, ptr):
+        self._ck(self._lib.sdrfm_bcast_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_bcast_set_stream")
+
+    @property
+    def kernel_name(self):
+        return self._lib.sdrfm_bcast_kernel_name(self._h).decode()
+
+    def synchronize(self):
+        self._ck(self._lib.sdrfm_bcast_synchronize(self._h), "sdrfm_bcast_synchronize")
+
+    def process_batch(self, iq: np.ndarray):
+        """host memory: iq [n_streams, nbytes] uint8 -> (L, R [n_streams, n_audio] float32, bb [n_streams, n_rds] complex64,
+        pilot_count [n_streams] uint32)"""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        if iq.ndim == 1:
+            iq = iq[None, :]
+        assert iq.shape[0] == self.cfg.n_streams
+        nbytes = iq.shape[1]
+        ca, cr = (max(v, 1) for v in self.counts(nbytes & ~1))
+        left = np.zeros((iq.shape[0], ca), dtype=np.float32)
+        right = np.zeros_like(left)
+        bb = np.zeros((iq.shape[0], 2 * cr), dtype=np.float32)
+        pc = np.zeros(iq.shape[0], dtype=np.uint32)
+        na, nr = C.c_uint32(), C.c_uint32()
+        self._ck(self._lib.sdrfm_bcast_process_batch(self._h, iq.ctypes.data, nbytes, nbytes, left.ctypes.data, right.ctypes.data, ca,
+                                                     bb.ctypes.data, 2 * cr, pc.ctypes.data, C.byref(na), C.byref(nr), 0),
+                 "sdrfm_bcast_process_batch")
+        return left[:, : na.value], right[:, : na.value], np.ascontiguousarray(bb[:, : 2 * nr.value]).view(np.complex64), pc
+
+    def process_batch_device(self, iq, left, right, bb, pilot_count=None, nbytes=None):
+        """device tensors: iq uint8 [n_streams, >=nbytes], left / right float32 [n_streams, >= n_audio] (same strides), bb float32
+        [n_streams, >= 2 n_rds] ((re, im) pairs), pilot_count int32 / uint32 [n_streams] or None; enqueue only.  Returns (n_audio, n_rds)."""
+        assert iq.is_cuda and left.is_cuda and right.is_cuda and bb.is_cuda
+        assert left.stride() == right.stride() and left.stride(1) == 1 and bb.stride(1) == 1
+        nbytes = iq.shape[1] if nbytes is None else int(nbytes)
+        pc = C.c_void_p(pilot_count.data_ptr()) if pilot_count is not None else None
+        na, nr = C.c_uint32(), C.c_uint32()
+        self._ck(self._lib.sdrfm_bcast_process_batch(self._h, C.c_void_p(iq.data_ptr()), iq.stride(0), nbytes, C.c_void_p(left.data_ptr()),
+                                                     C.c_void_p(right.data_ptr()), left.stride(0), C.c_void_p(bb.data_ptr()), bb.stride(0),
+                                                     pc, C.byref(na), C.byref(nr), _l.F_DEVICE_PTRS), "sdrfm_bcast_process_batch(device)")
+        return na.value, nr.value

@@ -2,7 +2,7 @@
  * sdrfm_rds.hip — the Radio Data System's complex baseband behind the sdrfm_rds_* C-ABI (include/sdrfm.h).
  *
  * The walk from the input bytes to the pilot filter's q = b * d is sdrfm_pilot_front.h's, shared with the stereo kernel.  What this file
- * adds behind q, at the discriminator rate: the 57 kHz carrier k = u2 q, u2 = q^2 / |q|^2 (gated by |q|^2 >= pilot_min^2), the mixed-down
+ * adds behind q, at the discriminator rate: the 57 kHz carrier k = u2 q, u2 = q^2 / |q|^2 (gated by |q|^2 >= pilot_min^2; sdrfm_carrier.h), the mixed-down
  * z = (k * rds_gain) d[m - Δ], and the decimating low-pass w = g * z, two real chains.  H = P - 1 + Tr - 1.  A step's last two stages here:
  *   pilot   q, carrier, z of the step's new d's -> LDS behind the Tr - 1 z's carried from the previous step (the span's first step
  *           computes those Tr - 1 too: that is what the halo's d's are for); the pilot count of the new d's
@@ -15,6 +15,7 @@
  */
 #include <new>
 
+#include "sdrfm_carrier.h"
 #include "sdrfm_pilot_front.h"
 
 namespace {
@@ -29,22 +30,6 @@ struct RdsParams : FrontParams {
   int32_t f0;
   uint32_t zplane;             // words of one z plane: Tr - 1 + NDT, made odd
 };
-
-// q -> z of one discriminator sample (the 57 kHz carrier of size |q| times rds_gain times the delayed d); returns whether the pilot is on
-__device__ __forceinline__ bool carrier(const RdsParams& p, f2_t q, float dd, float& zr, float& zi) {
-  const float qq = q.y * q.y;
-  const float pw = __builtin_fmaf(q.x, q.x, qq);
-  const bool on = pw >= p.pmin2;
-  const float u2r = __builtin_fmaf(q.x, q.x, -qq) / pw;
-  const float u2i = (2.0f * (q.x * q.y)) / pw;
-  float kr = __builtin_fmaf(u2r, q.x, -(u2i * q.y));
-  float ki = __builtin_fmaf(u2r, q.y, u2i * q.x);
-  kr = on ? kr : 0.0f;
-  ki = on ? ki : 0.0f;
-  zr = (kr * p.rds_gain) * dd;
-  zi = (ki * p.rds_gain) * dd;
-  return on;
-}
 
 template <int FT, int FD, int FP>
 __global__ void __launch_bounds__(PF_THREADS) k_rds(RdsParams p) {
@@ -85,7 +70,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_rds(RdsParams p) {
         }
       front_pilot(w, O0, C, [&](int o, f2_t q) __attribute__((always_inline)) {
         float zr, zi;
-        const bool on = carrier(p, q, ds[o + Dl], zr, zi);
+        const bool on = carrier_rds(p.pmin2, p.rds_gain, q, ds[o + Dl], zr, zi);
         zs[o] = zr;
         zs[ZP + o] = zi;
         cnt += (on && o >= (int)Tr - 1) ? 1u : 0u;

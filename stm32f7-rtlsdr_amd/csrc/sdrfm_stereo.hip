@@ -2,7 +2,7 @@
  * sdrfm_stereo.hip — broadcast FM stereo decoding behind the sdrfm_stereo_* C-ABI (include/sdrfm.h).
  *
  * The walk from the input bytes to the pilot filter's q = b * d is sdrfm_pilot_front.h's, shared with the RDS kernel.  What this file
- * adds behind q, at the discriminator rate: the 38 kHz carrier c = -2 qr qi / |q|^2 (gated by |q|^2 >= pilot_min^2), the difference
+ * adds behind q, at the discriminator rate: the 38 kHz carrier c = -2 qr qi / |q|^2 (gated by |q|^2 >= pilot_min^2; sdrfm_carrier.h), the difference
  * signal s = (c * diff_gain) d[m - Δ] over the step's audio windows -> LDS, and the two audio chains am (on d delayed by Δ) and as
  * (on s), L = am + as, R = am - as -> HBM.  H = P - 1 + Ta - 1.
  *
@@ -10,6 +10,7 @@
  */
 #include <new>
 
+#include "sdrfm_carrier.h"
 #include "sdrfm_pilot_front.h"
 
 namespace {
@@ -24,15 +25,6 @@ struct StereoParams : FrontParams {
   uint32_t A;
   int32_t f0;
 };
-
-// q -> (carrier, s) of one discriminator sample; returns whether the pilot is on
-__device__ __forceinline__ bool carrier(const StereoParams& p, f2_t q, float dd, float& s_out) {
-  const float pw = __builtin_fmaf(q.x, q.x, q.y * q.y);
-  const bool on = pw >= p.pmin2;
-  const float c = on ? (-2.0f * (q.x * q.y)) / pw : 0.0f;
-  s_out = (c * p.diff_gain) * dd;
-  return on;
-}
 
 template <int FT, int FD, int FP>
 __global__ void __launch_bounds__(PF_THREADS) k_stereo(StereoParams p) {
@@ -62,7 +54,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_stereo(StereoParams p) {
       // ---- pilot filter, carrier, s for m in [a - (Ta - 1), b)
       front_pilot(w, 0, b - a + (int)Ta - 1, [&](int o, f2_t q) __attribute__((always_inline)) {
         float sv;
-        const bool on = carrier(p, q, ds[o + Dl], sv);
+        const bool on = carrier_stereo(p.pmin2, p.diff_gain, q, ds[o + Dl], sv);
         ss[o] = sv;
         cnt += (on && o >= (int)Ta - 1) ? 1u : 0u;
       });

@@ -30,6 +30,8 @@ ABI_SYMBOLS = [
     "sdrfm_rds_create", "sdrfm_rds_destroy", "sdrfm_rds_reset", "sdrfm_rds_count", "sdrfm_rds_process_batch", "sdrfm_rds_set_stream",
     "sdrfm_rds_synchronize", "sdrfm_rds_kernel_name", "sdrfm_rds_checkword", "sdrfm_rds_syndrome", "sdrfm_rds_sync_create",
     "sdrfm_rds_sync_destroy", "sdrfm_rds_sync_reset", "sdrfm_rds_sync_push", "sdrfm_rds_sync_stats",
+    "sdrfm_bcast_create", "sdrfm_bcast_destroy", "sdrfm_bcast_reset", "sdrfm_bcast_counts", "sdrfm_bcast_process_batch",
+    "sdrfm_bcast_set_stream", "sdrfm_bcast_synchronize", "sdrfm_bcast_kernel_name",
 ]
 
 
@@ -90,6 +92,17 @@ class RdsConfig(C.Structure):
         ("struct_size", C.c_uint32), ("n_streams", C.c_uint32), ("fir_taps", C.c_uint32), ("fir_decim", C.c_uint32),
         ("fir_coeffs", C.POINTER(C.c_float)), ("pilot_taps", C.c_uint32), ("pilot_coeffs", C.POINTER(C.c_float)),
         ("pilot_min", C.c_float), ("rds_gain", C.c_float), ("rds_taps", C.c_uint32), ("rds_decim", C.c_uint32),
+        ("rds_coeffs", C.POINTER(C.c_float)), ("max_bytes_per_call", C.c_uint32), ("device", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
+class BcastConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_streams", C.c_uint32), ("fir_taps", C.c_uint32), ("fir_decim", C.c_uint32),
+        ("fir_coeffs", C.POINTER(C.c_float)), ("pilot_taps", C.c_uint32), ("pilot_coeffs", C.POINTER(C.c_float)),
+        ("pilot_min", C.c_float), ("diff_gain", C.c_float), ("audio_taps", C.c_uint32), ("audio_decim", C.c_uint32),
+        ("audio_coeffs", C.POINTER(C.c_float)), ("rds_gain", C.c_float), ("rds_taps", C.c_uint32), ("rds_decim", C.c_uint32),
         ("rds_coeffs", C.POINTER(C.c_float)), ("max_bytes_per_call", C.c_uint32), ("device", C.c_int32),
         ("flags", C.c_uint32),
     ]
@@ -249,6 +262,22 @@ def load_library(dev=False):
     lib.sdrfm_rds_synchronize.restype = C.c_int
     lib.sdrfm_rds_kernel_name.argtypes = [vp]
     lib.sdrfm_rds_kernel_name.restype = C.c_char_p
+    lib.sdrfm_bcast_create.argtypes = [C.POINTER(BcastConfig), C.POINTER(vp)]
+    lib.sdrfm_bcast_create.restype = C.c_int
+    lib.sdrfm_bcast_destroy.argtypes = [vp]
+    lib.sdrfm_bcast_destroy.restype = None
+    lib.sdrfm_bcast_reset.argtypes = [vp]
+    lib.sdrfm_bcast_reset.restype = C.c_int
+    lib.sdrfm_bcast_counts.argtypes = [vp, u32, u32p, u32p]
+    lib.sdrfm_bcast_counts.restype = C.c_int
+    lib.sdrfm_bcast_process_batch.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, C.c_size_t, vp, C.c_size_t, vp, u32p, u32p, u32]
+    lib.sdrfm_bcast_process_batch.restype = C.c_int
+    lib.sdrfm_bcast_set_stream.argtypes = [vp, vp]
+    lib.sdrfm_bcast_set_stream.restype = C.c_int
+    lib.sdrfm_bcast_synchronize.argtypes = [vp]
+    lib.sdrfm_bcast_synchronize.restype = C.c_int
+    lib.sdrfm_bcast_kernel_name.argtypes = [vp]
+    lib.sdrfm_bcast_kernel_name.restype = C.c_char_p
     lib.sdrfm_rds_checkword.argtypes = [C.c_uint16, C.c_int]
     lib.sdrfm_rds_checkword.restype = C.c_uint16
     lib.sdrfm_rds_syndrome.argtypes = [u32]
