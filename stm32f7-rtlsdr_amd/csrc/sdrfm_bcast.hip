@@ -5,7 +5,8 @@
  * The walk from the input bytes to the pilot filter's q = b * d is sdrfm_pilot_front.h's and runs once per d.  Behind q both carriers of
  * sdrfm_carrier.h are taken from the same q: s (the stereo difference signal) and zr, zi (the RDS subcarrier mixed down) -> LDS, the gate
  * counted once.  Behind one barrier the audio chains of k_stereo (am on d delayed by Δ, as on s; L = am + as, R = am - as) and the
- * output chains of k_rds (wr, wi: z in two odd-length planes, taps oldest first, 16 z's and taps read ahead of their 16 fmaf's).
+ * output chains of k_rds (wr, wi: z in two odd-length planes, taps oldest first, 16 z's and taps read ahead of their 16 fmaf's): the
+ * functions of sdrfm_out_stages.h, which those two kernels call as well.
  * H = P - 1 + max(Ta, Tr) - 1.  Both tails are carried from step to step in LDS — the last Ta - 1 s's and the last Tr - 1 z's of both
  * planes — so the pilot filter runs once per d and a step takes NY - 1 new d's whatever Ta and Tr are; the span's first step computes
  * the tails before it (that is what the halo's d's are for).  s and z are pure functions of d and q, so carrying them changes no bit.
@@ -17,6 +18,7 @@
 #include <new>
 
 #include "sdrfm_carrier.h"
+#include "sdrfm_out_stages.h"
 #include "sdrfm_pilot_front.h"
 
 namespace {
@@ -35,8 +37,6 @@ struct BcastParams : FrontParams {
   int32_t f0a, f0r;            // the newest d of output 0 of either decimator
   uint32_t zplane;             // words of one z plane: Tr - 1 + NDT, made odd
 };
-
-__device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // how many of a workgroup's nw waves take a step's nc RDS chains (of Tr links), the others taking its na audio outputs (of 2 Ta links):
 // the count with the shortest longer side; nw = every wave takes its share of both, one after the other, where no split beats that
@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   const int tid = w.tid, nthr = w.nthr, lo = (int)(w.blk * p.span);
   const uint32_t s = w.s;
   const float* ds = w.ds;
-  for (int k = tid; k < (int)Tr; k += nthr) grs[k] = p.gr[Tr - 1 - k];
+  rds_taps_to_lds(grs, p.gr, Tr, tid, nthr);
   for (int k = tid; k < (int)Ta; k += nthr) gas[k] = p.ga[k];
   uint32_t cnt = 0;
 
@@ -89,10 +89,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
       //      and computes the new d's only
       const int C = n + Tm - 1, O0 = first ? 0 : Tm - 1;
       if (!first) {
-        for (int k = tid; k < 2 * ((int)Tr - 1); k += nthr) {
-          const int pl = k >= (int)Tr - 1 ? 1 : 0;
-          zs[pl * (int)ZP + (k - pl * ((int)Tr - 1))] = zb[k];
-        }
+        rds_tail_restore(zs, zb, Tr, ZP, tid, nthr);
         for (int k = tid; k < (int)Ta - 1; k += nthr) ss[k] = sb[k];
       }
       front_pilot(w, O0, C, [&](int o, f2_t q) __attribute__((always_inline)) {
@@ -108,65 +105,17 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
         cnt += (on && o >= Tm - 1) ? 1u : 0u;
       });
       __syncthreads();
-      // ---- the outputs whose newest d lies in [a, b): audio ja in [jla, jha), RDS jr in [jlr, jhr) as 2 njr chains (the re ones first)
-      int jla = a - p.f0a > 0 ? (a - p.f0a + (int)Da - 1) / (int)Da : 0;
-      int jha = b - p.f0a > 0 ? (b - p.f0a + (int)Da - 1) / (int)Da : 0;
-      if (jha > (int)p.Aa) jha = (int)p.Aa;
-      int jlr = a - p.f0r > 0 ? (a - p.f0r + (int)Dr - 1) / (int)Dr : 0;
-      int jhr = b - p.f0r > 0 ? (b - p.f0r + (int)Dr - 1) / (int)Dr : 0;
-      if (jhr > (int)p.Ar) jhr = (int)p.Ar;
-      const int nja = jha > jla ? jha - jla : 0, njr = jhr > jlr ? jhr - jlr : 0;
+      // ---- the outputs whose newest d lies in [a, b): nja audio outputs from ja.x, njr RDS outputs from jr.x as 2 njr chains (the re ones first)
+      const int2 ja = step_outputs(a, b, p.f0a, (int)Da, (int)p.Aa), jr = step_outputs(a, b, p.f0r, (int)Dr, (int)p.Ar);
+      const int nja = ja.y > ja.x ? ja.y - ja.x : 0, njr = jr.y > jr.x ? jr.y - jr.x : 0;
       const int nw = nthr / 64, wv = tid >> 6, ln = tid & 63;
       const int wr = bcast_rds_waves(nw, 2 * njr, (int)Tr, nja, (int)Ta);
       const int wa0 = wr < nw ? wr : 0, wa = nw - wa0;            // the audio waves: [wa0, nw)
-      if (wv < wr) {
-        // ---- RDS: a contiguous share of the chains for every wave that takes them; chain i < njr is wr of output jlr + i, chain njr + i its wi
-        const int per_wave = cdiv(2 * njr, wr);
-        const int i_end = (wv + 1) * per_wave < 2 * njr ? (wv + 1) * per_wave : 2 * njr;
-        for (int i = wv * per_wave + ln; i < i_end; i += 64) {
-          const int pl = i >= njr ? 1 : 0, j = jlr + i - pl * njr;
-          const float* wz = zs + pl * (int)ZP + (p.f0r + j * (int)Dr - a);   // the window's oldest z
-          float acc = 0.0f;
-          uint32_t k = 0;
-          for (; k + 16 <= Tr; k += 16) {                             // 16 z's and taps in flight, then their fmaf's in order
-            float zv[16];
-            float4 gv[4];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) zv[u] = wz[k + u];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) gv[u] = *reinterpret_cast<const float4*>(grs + k + 4 * u);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              acc = __builtin_fmaf(gv[u].x, zv[4 * u], acc);
-              acc = __builtin_fmaf(gv[u].y, zv[4 * u + 1], acc);
-              acc = __builtin_fmaf(gv[u].z, zv[4 * u + 2], acc);
-              acc = __builtin_fmaf(gv[u].w, zv[4 * u + 3], acc);
-            }
-          }
-          for (; k < Tr; ++k) acc = __builtin_fmaf(grs[k], wz[k], acc);
-          p.bb[(size_t)s * p.bb_stride + 2 * (size_t)j + pl] = acc;
-        }
-      }
-      if (wv >= wa0) {
-        // ---- audio: one output per lane of the waves that take them
-        for (int j = jla + (wv - wa0) * 64 + ln; j < jha; j += 64 * wa) {
-          const int nj = p.f0a + j * (int)Da - a;                  // step-relative index of the newest d of output j
-          const float* wd = ds + (int)H + nj - (int)Dl - (int)(Ta - 1);
-          const float* wsv = ss + nj;
-          float am = 0.0f, as = 0.0f;
-          for (uint32_t k = 0; k < Ta; ++k) {
-            const float c = gas[Ta - 1 - k];
-            am = __builtin_fmaf(c, wd[k], am);
-            as = __builtin_fmaf(c, wsv[k], as);
-          }
-          p.left[(size_t)s * p.audio_stride + j] = am + as;
-          p.right[(size_t)s * p.audio_stride + j] = am - as;
-        }
-      }
-      for (int k = tid; k < 2 * ((int)Tr - 1); k += nthr) {       // the tails, for the next step
-        const int pl = k >= (int)Tr - 1 ? 1 : 0;
-        zb[k] = zs[pl * (int)ZP + n + (k - pl * ((int)Tr - 1))];
-      }
+      if (wv < wr) rds_chains(zs, grs, Tr, Dr, ZP, p.f0r, a, jr.x, njr, wr, wv, ln, p.bb + (size_t)s * p.bb_stride);
+      if (wv >= wa0)                                              // one output per lane of the waves that take them
+        audio_outputs(ds, ss, gas, Ta, Da, p.f0a, a, H, Dl, ja.x + (wv - wa0) * 64 + ln, 64 * wa, ja.y, p.left + (size_t)s * p.audio_stride,
+                      p.right + (size_t)s * p.audio_stride);
+      rds_tail_save(zb, zs, n, Tr, ZP, tid, nthr);                // the tails, for the next step
       for (int k = tid; k < (int)Ta - 1; k += nthr) sb[k] = ss[n + k];
     }
     __syncthreads();
@@ -184,18 +133,12 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
 struct sdrfm_bcast {
   sdrfm_bcast_config cfg;                      // taps pointers point at the copies in f and below
   PilotFront f;
-  float* gac = nullptr;                        // Ta
-  float* grc = nullptr;                        // Tr
-  uint32_t max_audio = 0, max_rds = 0;
-  float* d_ga = nullptr;
-  float* d_gr = nullptr;
+  Decim au, rd;                                // the audio and the RDS decimator, their phases carried separately
   float* d_left = nullptr;
   float* d_right = nullptr;
   size_t d_audio_stride = 0;
   float* d_bb = nullptr;
   size_t d_bb_stride = 0;
-  uint32_t* d_pc = nullptr;
-  uint32_t phase_da = 0, phase_dr = 0;         // the two decimators' phases
   bool fast = false;
   FrontStep step;                              // of the kernel this handle launches
   uint32_t slots = 1;                          // workgroups the device runs at a time (compute units x workgroups per unit)
@@ -204,14 +147,12 @@ struct sdrfm_bcast {
 
 namespace {
 
-uint32_t bcast_zplane(uint32_t Tr, uint32_t NDT) { return (Tr - 1 + NDT) | 1u; }
-
 // LDS bytes of a step geometry (see the layout in k_bcast); the header's Tg carries both lengths: Ta in the upper half, Tr in the lower
 uint32_t bcast_tg(uint32_t Ta, uint32_t Tr) { return (Ta << 16) | Tr; }
 
 size_t bcast_lds(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t H, uint32_t NY, uint32_t NDT, uint32_t* region_words) {
   const uint32_t Ta = Tg >> 16, Tr = Tg & 0xffffu;
-  const size_t nx = (size_t)(NY - 1) * D + T + 4, nds = (size_t)H + NDT + (Ta - 1 + NDT) + 2 * (size_t)bcast_zplane(Tr, NDT);
+  const size_t nx = (size_t)(NY - 1) * D + T + 4, nds = (size_t)H + NDT + (Ta - 1 + NDT) + 2 * (size_t)rds_zplane(Tr, NDT);
   size_t rw = nx > nds ? nx : nds;
   rw = (rw + 3) & ~(size_t)3;
   if (region_words) *region_words = (uint32_t)rw;
@@ -222,8 +163,8 @@ size_t bcast_lds(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t H, ui
 void bcast_free(sdrfm_bcast* h) {
   if (!h) return;
   front_free(h->f);
-  (void)hipFree(h->d_ga); (void)hipFree(h->d_gr); (void)hipFree(h->d_left); (void)hipFree(h->d_right); (void)hipFree(h->d_bb); (void)hipFree(h->d_pc);
-  free(h->gac); free(h->grc);
+  decim_free(h->au); decim_free(h->rd);
+  (void)hipFree(h->d_left); (void)hipFree(h->d_right); (void)hipFree(h->d_bb);
   delete h;
 }
 
@@ -237,11 +178,9 @@ int sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out) {
   if (!cfg || cfg->struct_size != sizeof(sdrfm_bcast_config)) return SDRFM_EINVAL;
   if (!front_config_ok(cfg->n_streams, cfg->fir_taps, cfg->fir_decim, cfg->fir_coeffs, cfg->pilot_taps, cfg->pilot_coeffs, cfg->pilot_min))
     return SDRFM_EINVAL;
-  if (!cfg->audio_coeffs || !cfg->rds_coeffs || (cfg->flags & ~SDRFM_BCAST_CFG_FORCE_GENERIC)) return SDRFM_EINVAL;
-  if (!cfg->audio_taps || cfg->audio_taps > SDRFM_MAX_TAPS || !cfg->audio_decim || cfg->audio_decim > SDRFM_MAX_DECIM) return SDRFM_EINVAL;
-  if (!cfg->rds_taps || cfg->rds_taps > SDRFM_MAX_TAPS || !cfg->rds_decim || cfg->rds_decim > SDRFM_MAX_DECIM) return SDRFM_EINVAL;
-  if (!std::isfinite(cfg->diff_gain) || !finite_all(cfg->audio_coeffs, cfg->audio_taps)) return SDRFM_EINVAL;
-  if (!std::isfinite(cfg->rds_gain) || !finite_all(cfg->rds_coeffs, cfg->rds_taps)) return SDRFM_EINVAL;
+  if (cfg->flags & ~SDRFM_BCAST_CFG_FORCE_GENERIC) return SDRFM_EINVAL;
+  if (!decim_config_ok(cfg->audio_taps, cfg->audio_decim, cfg->audio_coeffs, cfg->diff_gain)) return SDRFM_EINVAL;
+  if (!decim_config_ok(cfg->rds_taps, cfg->rds_decim, cfg->rds_coeffs, cfg->rds_gain)) return SDRFM_EINVAL;
   hipDeviceProp_t prop;
   int rc = front_open_device(cfg->device, &prop);
   if (rc != SDRFM_OK) return rc;
@@ -254,45 +193,27 @@ int sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out) {
   const size_t ns = cfg->n_streams;
   rc = front_alloc(h->f, cfg->n_streams, T, D, cfg->fir_coeffs, P, cfg->pilot_coeffs, cfg->pilot_min, H, cfg->max_bytes_per_call, cfg->device);
   if (rc != SDRFM_OK) { bcast_free(h); return rc; }
-  {
-    const uint64_t m = (uint64_t)(h->f.max_bytes / 2 + D - 1) / D + 1;
-    h->max_audio = (uint32_t)((m + Da - 1) / Da + 1);
-    h->max_rds = (uint32_t)((m + Dr - 1) / Dr + 1);
-  }
-  h->gac = (float*)malloc(sizeof(float) * Ta);
-  h->grc = (float*)malloc(sizeof(float) * Tr);
-  if (!h->gac || !h->grc) { bcast_free(h); return SDRFM_ENOMEM; }
-  memcpy(h->gac, cfg->audio_coeffs, sizeof(float) * Ta);
-  memcpy(h->grc, cfg->rds_coeffs, sizeof(float) * Tr);
+  rc = decim_alloc(h->au, h->f, Ta, Da, cfg->audio_coeffs);
+  if (rc == SDRFM_OK) rc = decim_alloc(h->rd, h->f, Tr, Dr, cfg->rds_coeffs);
+  if (rc != SDRFM_OK) { bcast_free(h); return rc; }
   h->cfg.fir_coeffs = h->f.hc;
   h->cfg.pilot_coeffs = h->f.bc;
-  h->cfg.audio_coeffs = h->gac;
-  h->cfg.rds_coeffs = h->grc;
-  h->d_audio_stride = ((size_t)h->max_audio + 63) & ~(size_t)63;
-  h->d_bb_stride = (2 * (size_t)h->max_rds + 63) & ~(size_t)63;
-#define CR(expr) do { if ((expr) != hipSuccess) { bcast_free(h); return SDRFM_ENOMEM; } } while (0)
-  CR(hipMalloc(&h->d_ga, sizeof(float) * Ta));
-  CR(hipMalloc(&h->d_gr, sizeof(float) * Tr));
-  CR(hipMalloc(&h->d_left, sizeof(float) * h->d_audio_stride * ns));
-  CR(hipMalloc(&h->d_right, sizeof(float) * h->d_audio_stride * ns));
-  CR(hipMalloc(&h->d_bb, sizeof(float) * h->d_bb_stride * ns));
-  CR(hipMalloc(&h->d_pc, sizeof(uint32_t) * ns));
-  CR(hipMemcpy(h->d_ga, h->gac, sizeof(float) * Ta, hipMemcpyHostToDevice));
-  CR(hipMemcpy(h->d_gr, h->grc, sizeof(float) * Tr, hipMemcpyHostToDevice));
-#undef CR
+  h->cfg.audio_coeffs = h->au.gc;
+  h->cfg.rds_coeffs = h->rd.gc;
+  h->d_audio_stride = ((size_t)h->au.max_out + 63) & ~(size_t)63;
+  h->d_bb_stride = (2 * (size_t)h->rd.max_out + 63) & ~(size_t)63;
+  const size_t audio_bytes = sizeof(float) * h->d_audio_stride * ns;
+  if (hipMalloc(&h->d_left, audio_bytes) != hipSuccess || hipMalloc(&h->d_right, audio_bytes) != hipSuccess ||
+      hipMalloc(&h->d_bb, sizeof(float) * h->d_bb_stride * ns) != hipSuccess) {
+    bcast_free(h);
+    return SDRFM_ENOMEM;
+  }
   h->step = front_step(bcast_lds, 64, 10, 101, bcast_tg(Ta, Tr), H, PF_FAST_NY, PF_FAST_NY - 1);
   h->fast = !(cfg->flags & SDRFM_BCAST_CFG_FORCE_GENERIC) && T == 64 && D == 10 && P == 101 && h->step.lds <= PF_LDS_BUDGET;
   if (!h->fast) h->step = front_step_generic(bcast_lds, T, D, P, bcast_tg(Ta, Tr), H);
   if (h->fast) snprintf(h->kernel_name, sizeof h->kernel_name, "bcast-fast T64 D10 P101 Ta%u Da%u Tr%u Dr%u", Ta, Da, Tr, Dr);
   else snprintf(h->kernel_name, sizeof h->kernel_name, "bcast-generic T%u D%u P%u Ta%u Da%u Tr%u Dr%u", T, D, P, Ta, Da, Tr, Dr);
-  {
-    // what one unit holds of this handle's kernel: by its LDS and its registers
-    int per_cu = 0;
-    const hipError_t e = h->fast ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bcast<64, 10, 101>, PF_THREADS, h->step.lds)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bcast<0, 0, 0>, PF_THREADS, h->step.lds);
-    if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    h->slots = (uint32_t)per_cu * (uint32_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1);
-  }
+  h->slots = front_slots(k_bcast<64, 10, 101>, k_bcast<0, 0, 0>, h->fast, h->step.lds, prop);
   rc = sdrfm_bcast_reset(h);
   if (rc != SDRFM_OK) { bcast_free(h); return rc; }
   *out = h;
@@ -310,62 +231,49 @@ int sdrfm_bcast_reset(sdrfm_bcast_t* h) {
   if (!h) return SDRFM_EINVAL;
   const int rc = front_reset(h->f);
   if (rc != SDRFM_OK) return rc;
-  h->phase_da = 0;
-  h->phase_dr = 0;
+  decim_reset(h->au);
+  decim_reset(h->rd);
   return SDRFM_OK;
 }
 
 int sdrfm_bcast_counts(const sdrfm_bcast_t* h, uint32_t nbytes, uint32_t* n_audio, uint32_t* n_rds) {
   if (!h || !n_audio || !n_rds) return SDRFM_EINVAL;
   if (nbytes & 1u) return SDRFM_EODD;
-  const uint64_t M = (h->f.phase_x + (uint64_t)(nbytes / 2)) / h->cfg.fir_decim;
-  *n_audio = (uint32_t)((h->phase_da + M) / h->cfg.audio_decim);
-  *n_rds = (uint32_t)((h->phase_dr + M) / h->cfg.rds_decim);
+  const uint64_t M = front_new_d(h->f, nbytes);
+  *n_audio = decim_outputs(h->au, M);
+  *n_rds = decim_outputs(h->rd, M);
   return SDRFM_OK;
 }
 
 // one call on device buffers, enqueued on the handle's stream
 static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, float* d_left, float* d_right, size_t audio_stride,
                          float* d_bb, size_t bb_stride, uint32_t* d_pc, uint32_t* n_audio, uint32_t* n_rds) {
-  const uint32_t Ta = h->cfg.audio_taps, Da = h->cfg.audio_decim, Tr = h->cfg.rds_taps, Dr = h->cfg.rds_decim, ns = h->cfg.n_streams, slots = h->slots;
+  const uint32_t ns = h->cfg.n_streams;
   if (h->step.lds > PF_LDS_BUDGET) return SDRFM_FAIL;            // (no shape within the header's limits gets here: NY = 2 fits them all)
   BcastParams p;
   memset(&p, 0, sizeof p);
   front_fill(h->f, p, d_iq, iq_stride, nbytes, d_pc, h->step);
-  const uint32_t M = p.M, Aa = (h->phase_da + M) / Da, Ar = (h->phase_dr + M) / Dr;
+  const uint32_t M = p.M, Aa = decim_outputs(h->au, M), Ar = decim_outputs(h->rd, M);
   p.left = d_left; p.right = d_right; p.audio_stride = audio_stride;
   p.bb = d_bb; p.bb_stride = bb_stride;
-  p.ga = h->d_ga; p.gr = h->d_gr;
-  p.Ta = Ta; p.Da = Da; p.Tr = Tr; p.Dr = Dr;
+  p.ga = h->au.d_g; p.gr = h->rd.d_g;
+  p.Ta = h->au.T; p.Da = h->au.D; p.Tr = h->rd.T; p.Dr = h->rd.D;
   p.diff_gain = h->cfg.diff_gain;
   p.rds_gain = h->cfg.rds_gain;
   p.Aa = Aa; p.Ar = Ar;
-  p.f0a = (int32_t)(Da - 1 - h->phase_da);
-  p.f0r = (int32_t)(Dr - 1 - h->phase_dr);
-  p.zplane = bcast_zplane(Tr, p.NDT);
-  // workgroups per stream, as the RDS handle chooses them: the machine takes `slots` workgroups at a time, so the call lasts (rounds of
-  // workgroups) x (a workgroup's span plus its prologue, which costs about half as much per d); the split with the shortest such time, the
-  // fewest workgroups among equals, no span below one step.  A stream gets at least one workgroup (the one that hands the state over).
-  // The results do not depend on the split.
-  p.blocks_per_stream = 1;
-  if (M) {
-    const uint32_t most = (M + p.NDT - 1) / p.NDT;
-    uint64_t best = ~(uint64_t)0;
-    for (uint32_t bps = 1; bps <= most && bps <= 64; ++bps) {
-      const uint64_t rounds = ((uint64_t)ns * bps + slots - 1) / slots, span = (M + bps - 1) / bps;
-      const uint64_t cost = rounds * (span + p.H / 2 + 64);
-      if (cost < best) { best = cost; p.blocks_per_stream = bps; }
-    }
-  }
+  p.f0a = decim_f0(h->au);
+  p.f0r = decim_f0(h->rd);
+  p.zplane = rds_zplane(p.Tr, p.NDT);
+  p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, h->slots);   // as the RDS handle chooses them
   p.span = M ? (M + p.blocks_per_stream - 1) / p.blocks_per_stream : 0;
-  if (d_pc && hipMemsetAsync(d_pc, 0, sizeof(uint32_t) * ns, h->f.stream) != hipSuccess) return SDRFM_FAIL;
+  if (front_zero_count(h->f, d_pc, true) != SDRFM_OK) return SDRFM_FAIL;
   const dim3 grid(ns * p.blocks_per_stream), block(PF_THREADS);
   if (h->fast) k_bcast<64, 10, 101><<<grid, block, h->step.lds, h->f.stream>>>(p);
   else k_bcast<0, 0, 0><<<grid, block, h->step.lds, h->f.stream>>>(p);
   if (hipGetLastError() != hipSuccess) return SDRFM_FAIL;
   front_advance(h->f, p.N);
-  h->phase_da = (h->phase_da + M) % Da;
-  h->phase_dr = (h->phase_dr + M) % Dr;
+  decim_advance(h->au, M);
+  decim_advance(h->rd, M);
   *n_audio = Aa;
   *n_rds = Ar;
   return SDRFM_OK;
@@ -379,18 +287,10 @@ int sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_str
   if (nbytes & 1u) return SDRFM_EODD;
   if (nbytes > h->f.max_bytes) return SDRFM_ECAPACITY;
   const uint32_t ns = h->cfg.n_streams;
-  const hipStream_t stream = h->f.stream;
   if (nbytes == 0) {
     *n_audio = 0;
     *n_rds = 0;
-    if (pilot_count) {
-      if (flags & SDRFM_F_DEVICE_PTRS) {
-        if (hipSetDevice(h->f.device) != hipSuccess || hipMemsetAsync(pilot_count, 0, sizeof(uint32_t) * ns, stream) != hipSuccess) return SDRFM_FAIL;
-      } else {
-        memset(pilot_count, 0, sizeof(uint32_t) * ns);
-      }
-    }
-    return SDRFM_OK;
+    return front_empty_call(h->f, pilot_count, flags);
   }
   if (!iq) return SDRFM_EINVAL;
   if (ns > 1 && iq_stride < nbytes) return SDRFM_ECAPACITY;
@@ -403,21 +303,14 @@ int sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_str
   if (flags & SDRFM_F_DEVICE_PTRS)
     return bcast_enqueue(h, iq, iq_stride, nbytes, left, right, audio_stride, bb, bb_stride, pilot_count, n_audio, n_rds);
 
-  if (hipMemcpy2DAsync(h->f.d_iq, h->f.d_iq_stride, iq, ns > 1 ? iq_stride : nbytes, nbytes, ns, hipMemcpyHostToDevice, stream) != hipSuccess)
-    return SDRFM_FAIL;
-  const int rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->d_pc,
+  if (front_stage_in(h->f, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
+  const int rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc,
                                n_audio, n_rds);
   if (rc != SDRFM_OK) return rc;
-  const size_t dsta = (ns > 1 ? audio_stride : Aa) * sizeof(float), srca = h->d_audio_stride * sizeof(float);
-  if (Aa && (hipMemcpy2DAsync(left, dsta, h->d_left, srca, Aa * sizeof(float), ns, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-             hipMemcpy2DAsync(right, dsta, h->d_right, srca, Aa * sizeof(float), ns, hipMemcpyDeviceToHost, stream) != hipSuccess))
-    return SDRFM_FAIL;
-  const size_t dstr = (ns > 1 ? bb_stride : 2 * (size_t)Ar) * sizeof(float), srcr = h->d_bb_stride * sizeof(float);
-  if (Ar && hipMemcpy2DAsync(bb, dstr, h->d_bb, srcr, 2 * (size_t)Ar * sizeof(float), ns, hipMemcpyDeviceToHost, stream) != hipSuccess)
-    return SDRFM_FAIL;
-  if (pilot_count && hipMemcpyAsync(pilot_count, h->d_pc, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, stream) != hipSuccess) return SDRFM_FAIL;
-  if (hipStreamSynchronize(stream) != hipSuccess) return SDRFM_FAIL;
-  return SDRFM_OK;
+  if (front_copy_back(h->f, left, audio_stride, h->d_left, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
+  if (front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
+  if (front_copy_back(h->f, bb, bb_stride, h->d_bb, h->d_bb_stride, 2 * (size_t)Ar) != SDRFM_OK) return SDRFM_FAIL;
+  return front_finish(h->f, pilot_count);
 }
 
 int sdrfm_bcast_set_stream(sdrfm_bcast_t* h, void* hip_stream) {

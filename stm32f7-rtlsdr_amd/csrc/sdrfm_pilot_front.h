@@ -1,6 +1,7 @@
 /*
- * sdrfm_pilot_front.h — what the stereo and the RDS kernels (sdrfm_stereo.hip, sdrfm_rds.hip) have in common: the walk
- * from the input bytes to the pilot filter's q, on the device, and the state that walk carries from call to call, on the host.
+ * sdrfm_pilot_front.h — what the stereo, the RDS and the broadcast kernels (sdrfm_stereo.hip, sdrfm_rds.hip, sdrfm_bcast.hip)
+ * have in common: the walk from the input bytes to the pilot filter's q, on the device; on the host, the state that walk carries from call
+ * to call, the decimators behind d, the split of a call over workgroups and the steps of a call on host buffers.
  *
  * K1-K3 (x, y, d) are the bit-exact kernels' own: the same fmaf chain order and sdrfm_discriminate from sdrfm_math.h, so d is the
  * definition's d.  Behind it, at the discriminator rate, the complex pilot filter q = b * d; what is made of q is the including kernel's.
@@ -41,7 +42,7 @@ constexpr uint32_t PF_THREADS = 256;
 constexpr uint32_t PF_FAST_NY = 4 * PF_THREADS;   // y's per step of the fast kernels (4 per lane)
 constexpr uint32_t PF_LDS_BUDGET = 64u << 10;
 
-// the kernel parameters of the walk; StereoParams and RdsParams derive from it
+// the kernel parameters of the walk; StereoParams, RdsParams and BcastParams derive from it
 struct FrontParams {
   const uint8_t* iq;
   size_t iq_stride;
@@ -282,7 +283,8 @@ __device__ __forceinline__ void front_hand_over(const FrontParams& p, const Fron
 }
 
 // =================================================================================================================
-//  Host side: the part of a handle that serves the walk — taps, carried state in ping-pong sets, input staging, stream.
+//  Host side: the part of a handle that serves the walk — taps, carried state in ping-pong sets, input staging, stream — and what the
+//  three handles do alike around it: a decimator behind d (Decim), the workgroup split, the protocol of a call.
 // =================================================================================================================
 struct PilotFront {
   float* hc = nullptr;                         // T
@@ -298,6 +300,7 @@ struct PilotFront {
   float* d_hist_d[2] = {nullptr, nullptr};
   uint8_t* d_iq = nullptr;                     // host-buffer calls: staging
   size_t d_iq_stride = 0;
+  uint32_t* d_pc = nullptr;                    // host-buffer calls: the pilot counts [ns]
   int cur = 0;
   uint32_t phase_x = 0;
 };
@@ -308,7 +311,7 @@ bool finite_all(const float* v, uint32_t n) {
   return true;
 }
 
-// the config fields both handles have
+// the config fields all three handles have
 bool front_config_ok(uint32_t ns, uint32_t T, uint32_t D, const float* h, uint32_t P, const float* b, float pilot_min) {
   if (!ns || !h || !b) return false;
   if (!T || T > SDRFM_MAX_TAPS || !D || D > SDRFM_MAX_DECIM) return false;
@@ -336,7 +339,7 @@ int front_open_device(int device, hipDeviceProp_t* prop) {
 void front_free(PilotFront& f) {
   (void)hipFree(f.d_h); (void)hipFree(f.d_tp);
   for (int i = 0; i < 2; ++i) { (void)hipFree(f.d_hist_x[i]); (void)hipFree(f.d_yprev[i]); (void)hipFree(f.d_hist_d[i]); }
-  (void)hipFree(f.d_iq);
+  (void)hipFree(f.d_iq); (void)hipFree(f.d_pc);
   if (f.own_stream) (void)hipStreamDestroy(f.own_stream);
   free(f.hc); free(f.bc);
 }
@@ -363,7 +366,7 @@ int front_alloc(PilotFront& f, uint32_t ns, uint32_t T, uint32_t D, const float*
   for (int i = 0; i < 2; ++i)
     ok = ok && hipMalloc(&f.d_hist_x[i], sizeof(float2) * ns * hx) == hipSuccess && hipMalloc(&f.d_yprev[i], sizeof(float2) * ns) == hipSuccess &&
          hipMalloc(&f.d_hist_d[i], sizeof(float) * ns * hd) == hipSuccess;
-  ok = ok && hipMalloc(&f.d_iq, f.d_iq_stride * ns) == hipSuccess &&
+  ok = ok && hipMalloc(&f.d_iq, f.d_iq_stride * ns) == hipSuccess && hipMalloc(&f.d_pc, sizeof(uint32_t) * ns) == hipSuccess &&
        hipMemcpy(f.d_h, f.hc, sizeof(float) * T, hipMemcpyHostToDevice) == hipSuccess &&
        hipMemcpy(f.d_tp, tp, sizeof(float2) * P, hipMemcpyHostToDevice) == hipSuccess;
   free(tp);
@@ -405,6 +408,9 @@ FrontStep front_step_generic(front_lds_fn lds_fn, uint32_t T, uint32_t D, uint32
   return front_step(lds_fn, T, D, P, Tg, H, ny, ny - 1);
 }
 
+// the new d's of a call of nbytes per stream
+uint64_t front_new_d(const PilotFront& f, uint32_t nbytes) { return (f.phase_x + (uint64_t)(nbytes / 2)) / f.D; }
+
 // the walk's part of a call's parameters: a call of nbytes per stream at d_iq, with the step geometry g
 void front_fill(const PilotFront& f, FrontParams& p, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, uint32_t* d_pc, const FrontStep& g) {
   p.iq = d_iq; p.iq_stride = iq_stride;
@@ -416,7 +422,7 @@ void front_fill(const PilotFront& f, FrontParams& p, const uint8_t* d_iq, size_t
   p.h = f.d_h; p.tp = f.d_tp;
   p.T = f.T; p.D = f.D; p.P = f.P; p.H = f.H; p.Dl = (f.P - 1) / 2;
   p.pmin2 = f.pmin2;
-  p.N = nbytes / 2; p.M = (f.phase_x + p.N) / f.D;
+  p.N = nbytes / 2; p.M = (uint32_t)front_new_d(f, nbytes);
   p.e0 = (int32_t)(f.D - 1 - f.phase_x);
   p.vec = ((uintptr_t)d_iq % 16 == 0 && (f.ns == 1 || iq_stride % 16 == 0)) ? 1u : 0u;
   p.NY = g.NY; p.NDT = g.NDT; p.region_words = g.region_words;
@@ -426,6 +432,102 @@ void front_fill(const PilotFront& f, FrontParams& p, const uint8_t* d_iq, size_t
 void front_advance(PilotFront& f, uint32_t N) {
   f.cur ^= 1;
   f.phase_x = (f.phase_x + N) % f.D;
+}
+
+// ---- one decimator behind d: the audio chains, the RDS chains
+struct Decim {
+  uint32_t T = 0, D = 0;                       // taps, decimation
+  uint32_t phase = 0;                          // d's since its last output's newest one
+  uint32_t max_out = 0;                        // the most outputs a call of max_bytes can give
+  float* gc = nullptr;                         // T: the host's copy
+  float* d_g = nullptr;                        // T: the device's
+};
+
+bool decim_config_ok(uint32_t T, uint32_t D, const float* g, float gain) {
+  return g && T && T <= SDRFM_MAX_TAPS && D && D <= SDRFM_MAX_DECIM && std::isfinite(gain) && finite_all(g, T);
+}
+
+// copies the taps to the host's and the device's side of a handle whose front is allocated; SDRFM_OK or SDRFM_ENOMEM (decim_free frees what there is)
+int decim_alloc(Decim& c, const PilotFront& f, uint32_t T, uint32_t D, const float* g) {
+  c.T = T; c.D = D;
+  const uint64_t m = (uint64_t)(f.max_bytes / 2 + f.D - 1) / f.D + 1;
+  c.max_out = (uint32_t)((m + D - 1) / D + 1);
+  c.gc = (float*)malloc(sizeof(float) * T);
+  if (!c.gc) return SDRFM_ENOMEM;
+  memcpy(c.gc, g, sizeof(float) * T);
+  const bool ok = hipMalloc(&c.d_g, sizeof(float) * T) == hipSuccess && hipMemcpy(c.d_g, c.gc, sizeof(float) * T, hipMemcpyHostToDevice) == hipSuccess;
+  return ok ? SDRFM_OK : SDRFM_ENOMEM;
+}
+
+void decim_free(Decim& c) { (void)hipFree(c.d_g); free(c.gc); }
+
+void decim_reset(Decim& c) { c.phase = 0; }
+
+// the outputs of a call of M new d's, the newest d of its output 0 (output j's: f0 + j D), and the phase after it
+uint32_t decim_outputs(const Decim& c, uint64_t M) { return (uint32_t)((c.phase + M) / c.D); }
+int32_t decim_f0(const Decim& c) { return (int32_t)(c.D - 1 - c.phase); }
+void decim_advance(Decim& c, uint32_t M) { c.phase = (c.phase + M) % c.D; }
+
+// ---- the workgroup split of the RDS and the broadcast handles
+// workgroups the device runs at a time of the kernel a handle launches: what one unit holds of it, by its LDS and its registers, x the units
+template <typename K>
+uint32_t front_slots(K kernel_fast, K kernel_generic, bool fast, size_t lds, const hipDeviceProp_t& prop) {
+  int per_cu = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fast ? kernel_fast : kernel_generic, PF_THREADS, lds);
+  if (e != hipSuccess || per_cu < 1) per_cu = 1;
+  return (uint32_t)per_cu * (uint32_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1);
+}
+
+// workgroups per stream: the machine takes `slots` workgroups at a time, so the call lasts (rounds of workgroups) x (a workgroup's span plus
+// its prologue, which costs about half as much per d); the split with the shortest such time, the fewest workgroups among equals, no span
+// below one step.  A stream gets at least one workgroup (the one that hands the state over).  The results do not depend on the split.
+uint32_t front_split(uint32_t M, uint32_t NDT, uint32_t H, uint32_t ns, uint32_t slots) {
+  uint32_t blocks_per_stream = 1;
+  if (M) {
+    const uint32_t most = (M + NDT - 1) / NDT;
+    uint64_t best = ~(uint64_t)0;
+    for (uint32_t bps = 1; bps <= most && bps <= 64; ++bps) {
+      const uint64_t rounds = ((uint64_t)ns * bps + slots - 1) / slots, span = (M + bps - 1) / bps;
+      const uint64_t cost = rounds * (span + H / 2 + 64);
+      if (cost < best) { best = cost; blocks_per_stream = bps; }
+    }
+  }
+  return blocks_per_stream;
+}
+
+// ---- the protocol of a call; each returns SDRFM_OK or SDRFM_FAIL
+// a call's pilot counts start at 0: on the stream where pc is device memory (the launch adds to it), at once where it is the caller's host
+// array; pc may be nullptr (not counted)
+int front_zero_count(const PilotFront& f, uint32_t* pc, bool on_device) {
+  if (pc && !on_device) memset(pc, 0, sizeof(uint32_t) * f.ns);
+  if (pc && on_device && hipMemsetAsync(pc, 0, sizeof(uint32_t) * f.ns, f.stream) != hipSuccess) return SDRFM_FAIL;
+  return SDRFM_OK;
+}
+
+// a call of no bytes: no launch, no outputs, the counts are 0
+int front_empty_call(const PilotFront& f, uint32_t* pilot_count, uint32_t flags) {
+  const bool on_device = (flags & SDRFM_F_DEVICE_PTRS) != 0;
+  if (pilot_count && on_device && hipSetDevice(f.device) != hipSuccess) return SDRFM_FAIL;
+  return front_zero_count(f, pilot_count, on_device);
+}
+
+// a call on host buffers, in stream order: the input -> d_iq, the launch on the handle's own buffers, every output array back, front_finish
+int front_stage_in(const PilotFront& f, const uint8_t* iq, size_t iq_stride, uint32_t nbytes) {
+  const hipError_t e = hipMemcpy2DAsync(f.d_iq, f.d_iq_stride, iq, f.ns > 1 ? iq_stride : nbytes, nbytes, f.ns, hipMemcpyHostToDevice, f.stream);
+  return e == hipSuccess ? SDRFM_OK : SDRFM_FAIL;
+}
+
+// `width` floats per stream from the handle's array (rows of src_stride floats) to the caller's (rows of dst_stride, which one stream need not give)
+int front_copy_back(const PilotFront& f, float* dst, size_t dst_stride, const float* d_src, size_t src_stride, size_t width) {
+  if (!width) return SDRFM_OK;
+  const hipError_t e = hipMemcpy2DAsync(dst, (f.ns > 1 ? dst_stride : width) * sizeof(float), d_src, src_stride * sizeof(float), width * sizeof(float), f.ns,
+                                        hipMemcpyDeviceToHost, f.stream);
+  return e == hipSuccess ? SDRFM_OK : SDRFM_FAIL;
+}
+
+int front_finish(const PilotFront& f, uint32_t* pilot_count) {
+  if (pilot_count && hipMemcpyAsync(pilot_count, f.d_pc, sizeof(uint32_t) * f.ns, hipMemcpyDeviceToHost, f.stream) != hipSuccess) return SDRFM_FAIL;
+  return hipStreamSynchronize(f.stream) == hipSuccess ? SDRFM_OK : SDRFM_FAIL;
 }
 
 }  // namespace

@@ -7,7 +7,7 @@
  *   pilot   q, carrier, z of the step's new d's -> LDS behind the Tr - 1 z's carried from the previous step (the span's first step
  *           computes those Tr - 1 too: that is what the halo's d's are for); the pilot count of the new d's
  *   output  wr, wi -> HBM; one lane per chain (the re lanes first, then the im lanes), zr and zi in planes of their own so that the
- *           lanes' windows, Dr apart, spread over the banks
+ *           lanes' windows, Dr apart, spread over the banks (sdrfm_out_stages.h, shared with the broadcast kernel)
  * The halo is 2.7 times the stereo kernel's at the default shape (354 d's), and the pilot pass is the dearest one: carrying z from step
  * to step keeps it at one evaluation per d, so a step takes NY - 1 new d's whatever Tr is, and the prologue costs K1-K3 only.
  *
@@ -16,6 +16,7 @@
 #include <new>
 
 #include "sdrfm_carrier.h"
+#include "sdrfm_out_stages.h"
 #include "sdrfm_pilot_front.h"
 
 namespace {
@@ -52,7 +53,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_rds(RdsParams p) {
   const int tid = w.tid, nthr = w.nthr, lo = (int)(w.blk * p.span);
   const uint32_t s = w.s;
   const float* ds = w.ds;
-  for (int k = tid; k < (int)Tr; k += nthr) gs[k] = p.g[Tr - 1 - k];
+  rds_taps_to_lds(gs, p.g, Tr, tid, nthr);
   uint32_t cnt = 0;
 
   front_walk(p, w, [&](int a, int b, bool full) {
@@ -63,11 +64,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_rds(RdsParams p) {
       // ---- pilot filter, carrier, z: plane index o stands for m = a - (Tr - 1) + o, its pilot window is ds[o .. o + P).  The span's first
       //      step computes all of [0, C); a later one takes the first Tr - 1 from the step before and computes the new d's only
       const int C = n + (int)Tr - 1, O0 = first ? 0 : (int)Tr - 1;
-      if (!first)
-        for (int k = tid; k < 2 * ((int)Tr - 1); k += nthr) {
-          const int pl = k >= (int)Tr - 1 ? 1 : 0;
-          zs[pl * (int)ZP + (k - pl * ((int)Tr - 1))] = zb[k];
-        }
+      if (!first) rds_tail_restore(zs, zb, Tr, ZP, tid, nthr);
       front_pilot(w, O0, C, [&](int o, f2_t q) __attribute__((always_inline)) {
         float zr, zi;
         const bool on = carrier_rds(p.pmin2, p.rds_gain, q, ds[o + Dl], zr, zi);
@@ -76,40 +73,10 @@ __global__ void __launch_bounds__(PF_THREADS) k_rds(RdsParams p) {
         cnt += (on && o >= (int)Tr - 1) ? 1u : 0u;
       });
       __syncthreads();
-      // ---- output: the j's whose newest d lies in [a, b); lane i < nj serves wr of output jl + i, lane nj + i its wi
-      int jl = a - p.f0 > 0 ? (a - p.f0 + (int)Dr - 1) / (int)Dr : 0;
-      int jh = b - p.f0 > 0 ? (b - p.f0 + (int)Dr - 1) / (int)Dr : 0;
-      if (jh > (int)p.A) jh = (int)p.A;
-      const int nj = jh > jl ? jh - jl : 0;
-      const int per_wave = (2 * nj + nthr / 64 - 1) / (nthr / 64), wv = tid >> 6;   // a contiguous share of the chains for every wave
-      const int i_end = (wv + 1) * per_wave < 2 * nj ? (wv + 1) * per_wave : 2 * nj;
-      for (int i = wv * per_wave + (tid & 63); i < i_end; i += 64) {
-        const int pl = i >= nj ? 1 : 0, j = jl + i - pl * nj;
-        const float* wz = zs + pl * (int)ZP + (p.f0 + j * (int)Dr - a);   // the window's oldest z
-        float acc = 0.0f;
-        uint32_t k = 0;
-        for (; k + 16 <= Tr; k += 16) {                             // 16 z's and taps in flight, then their fmaf's in order: the chain waits for
-          float zv[16];                                             // LDS once per 16 links, not once per link
-          float4 gv[4];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) zv[u] = wz[k + u];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) gv[u] = *reinterpret_cast<const float4*>(gs + k + 4 * u);
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            acc = __builtin_fmaf(gv[u].x, zv[4 * u], acc);
-            acc = __builtin_fmaf(gv[u].y, zv[4 * u + 1], acc);
-            acc = __builtin_fmaf(gv[u].z, zv[4 * u + 2], acc);
-            acc = __builtin_fmaf(gv[u].w, zv[4 * u + 3], acc);
-          }
-        }
-        for (; k < Tr; ++k) acc = __builtin_fmaf(gs[k], wz[k], acc);
-        p.bb[(size_t)s * p.bb_stride + 2 * (size_t)j + pl] = acc;
-      }
-      for (int k = tid; k < 2 * ((int)Tr - 1); k += nthr) {       // the last Tr - 1 z's, for the next step
-        const int pl = k >= (int)Tr - 1 ? 1 : 0;
-        zb[k] = zs[pl * (int)ZP + n + (k - pl * ((int)Tr - 1))];
-      }
+      // ---- output: the j's whose newest d lies in [a, b), their chains shared among all the waves
+      const int2 jr = step_outputs(a, b, p.f0, (int)Dr, (int)p.A);
+      rds_chains(zs, gs, Tr, Dr, ZP, p.f0, a, jr.x, jr.y > jr.x ? jr.y - jr.x : 0, nthr / 64, tid >> 6, tid & 63, p.bb + (size_t)s * p.bb_stride);
+      rds_tail_save(zb, zs, n, Tr, ZP, tid, nthr);
     }
     __syncthreads();
   });
@@ -126,13 +93,9 @@ __global__ void __launch_bounds__(PF_THREADS) k_rds(RdsParams p) {
 struct sdrfm_rds {
   sdrfm_rds_config cfg;                        // taps pointers point at the copies in f and below
   PilotFront f;
-  float* gc = nullptr;                         // Tr
-  uint32_t max_out = 0;
-  float* d_g = nullptr;
+  Decim rd;                                    // the RDS decimator
   float* d_bb = nullptr;
   size_t d_bb_stride = 0;
-  uint32_t* d_pc = nullptr;
-  uint32_t phase_d = 0;
   bool fast = false;
   FrontStep step;                              // of the kernel this handle launches
   uint32_t slots = 1;                          // workgroups the device runs at a time (compute units x workgroups per unit)
@@ -142,8 +105,6 @@ struct sdrfm_rds {
 namespace {
 
 // LDS bytes of a step geometry (see the layout in k_rds)
-uint32_t rds_zplane(uint32_t Tr, uint32_t NDT) { return (Tr - 1 + NDT) | 1u; }
-
 size_t rds_lds(uint32_t T, uint32_t D, uint32_t P, uint32_t Tr, uint32_t H, uint32_t NY, uint32_t NDT, uint32_t* region_words) {
   const size_t nx = (size_t)(NY - 1) * D + T + 4, nds = (size_t)H + NDT + 2 * (size_t)rds_zplane(Tr, NDT);
   size_t rw = nx > nds ? nx : nds;
@@ -156,8 +117,8 @@ size_t rds_lds(uint32_t T, uint32_t D, uint32_t P, uint32_t Tr, uint32_t H, uint
 void rds_free(sdrfm_rds* h) {
   if (!h) return;
   front_free(h->f);
-  (void)hipFree(h->d_g); (void)hipFree(h->d_bb); (void)hipFree(h->d_pc);
-  free(h->gc);
+  decim_free(h->rd);
+  (void)hipFree(h->d_bb);
   delete h;
 }
 
@@ -171,9 +132,8 @@ int sdrfm_rds_create(const sdrfm_rds_config* cfg, sdrfm_rds_t** out) {
   if (!cfg || cfg->struct_size != sizeof(sdrfm_rds_config)) return SDRFM_EINVAL;
   if (!front_config_ok(cfg->n_streams, cfg->fir_taps, cfg->fir_decim, cfg->fir_coeffs, cfg->pilot_taps, cfg->pilot_coeffs, cfg->pilot_min))
     return SDRFM_EINVAL;
-  if (!cfg->rds_coeffs || (cfg->flags & ~SDRFM_RDS_CFG_FORCE_GENERIC)) return SDRFM_EINVAL;
-  if (!cfg->rds_taps || cfg->rds_taps > SDRFM_MAX_TAPS || !cfg->rds_decim || cfg->rds_decim > SDRFM_MAX_DECIM) return SDRFM_EINVAL;
-  if (!std::isfinite(cfg->rds_gain) || !finite_all(cfg->rds_coeffs, cfg->rds_taps)) return SDRFM_EINVAL;
+  if (cfg->flags & ~SDRFM_RDS_CFG_FORCE_GENERIC) return SDRFM_EINVAL;
+  if (!decim_config_ok(cfg->rds_taps, cfg->rds_decim, cfg->rds_coeffs, cfg->rds_gain)) return SDRFM_EINVAL;
   hipDeviceProp_t prop;
   int rc = front_open_device(cfg->device, &prop);
   if (rc != SDRFM_OK) return rc;
@@ -185,36 +145,19 @@ int sdrfm_rds_create(const sdrfm_rds_config* cfg, sdrfm_rds_t** out) {
   const size_t ns = cfg->n_streams;
   rc = front_alloc(h->f, cfg->n_streams, T, D, cfg->fir_coeffs, P, cfg->pilot_coeffs, cfg->pilot_min, H, cfg->max_bytes_per_call, cfg->device);
   if (rc != SDRFM_OK) { rds_free(h); return rc; }
-  {
-    const uint64_t m = (uint64_t)(h->f.max_bytes / 2 + D - 1) / D + 1;
-    h->max_out = (uint32_t)((m + Dr - 1) / Dr + 1);
-  }
-  h->gc = (float*)malloc(sizeof(float) * Tr);
-  if (!h->gc) { rds_free(h); return SDRFM_ENOMEM; }
-  memcpy(h->gc, cfg->rds_coeffs, sizeof(float) * Tr);
+  rc = decim_alloc(h->rd, h->f, Tr, Dr, cfg->rds_coeffs);
+  if (rc != SDRFM_OK) { rds_free(h); return rc; }
   h->cfg.fir_coeffs = h->f.hc;
-  h->cfg.rds_coeffs = h->gc;
+  h->cfg.rds_coeffs = h->rd.gc;
   h->cfg.pilot_coeffs = h->f.bc;
-  h->d_bb_stride = (2 * (size_t)h->max_out + 63) & ~(size_t)63;
-#define CR(expr) do { if ((expr) != hipSuccess) { rds_free(h); return SDRFM_ENOMEM; } } while (0)
-  CR(hipMalloc(&h->d_g, sizeof(float) * Tr));
-  CR(hipMalloc(&h->d_bb, sizeof(float) * h->d_bb_stride * ns));
-  CR(hipMalloc(&h->d_pc, sizeof(uint32_t) * ns));
-  CR(hipMemcpy(h->d_g, h->gc, sizeof(float) * Tr, hipMemcpyHostToDevice));
-#undef CR
+  h->d_bb_stride = (2 * (size_t)h->rd.max_out + 63) & ~(size_t)63;
+  if (hipMalloc(&h->d_bb, sizeof(float) * h->d_bb_stride * ns) != hipSuccess) { rds_free(h); return SDRFM_ENOMEM; }
   h->step = front_step(rds_lds, 64, 10, 101, Tr, H, PF_FAST_NY, PF_FAST_NY - 1);
   h->fast = !(cfg->flags & SDRFM_RDS_CFG_FORCE_GENERIC) && T == 64 && D == 10 && P == 101 && h->step.lds <= PF_LDS_BUDGET;
   if (!h->fast) h->step = front_step_generic(rds_lds, T, D, P, Tr, H);
   if (h->fast) snprintf(h->kernel_name, sizeof h->kernel_name, "rds-fast T64 D10 P101 Tr%u Dr%u", Tr, Dr);
   else snprintf(h->kernel_name, sizeof h->kernel_name, "rds-generic T%u D%u P%u Tr%u Dr%u", T, D, P, Tr, Dr);
-  {
-    // what one unit holds of this handle's kernel: by its LDS and its registers
-    int per_cu = 0;
-    const hipError_t e = h->fast ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_rds<64, 10, 101>, PF_THREADS, h->step.lds)
-                                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_rds<0, 0, 0>, PF_THREADS, h->step.lds);
-    if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    h->slots = (uint32_t)per_cu * (uint32_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1);
-  }
+  h->slots = front_slots(k_rds<64, 10, 101>, k_rds<0, 0, 0>, h->fast, h->step.lds, prop);
   rc = sdrfm_rds_reset(h);
   if (rc != SDRFM_OK) { rds_free(h); return rc; }
   *out = h;
@@ -232,55 +175,42 @@ int sdrfm_rds_reset(sdrfm_rds_t* h) {
   if (!h) return SDRFM_EINVAL;
   const int rc = front_reset(h->f);
   if (rc != SDRFM_OK) return rc;
-  h->phase_d = 0;
+  decim_reset(h->rd);
   return SDRFM_OK;
 }
 
 int sdrfm_rds_count(const sdrfm_rds_t* h, uint32_t nbytes, uint32_t* n_out) {
   if (!h || !n_out) return SDRFM_EINVAL;
   if (nbytes & 1u) return SDRFM_EODD;
-  const uint64_t M = (h->f.phase_x + (uint64_t)(nbytes / 2)) / h->cfg.fir_decim;
-  *n_out = (uint32_t)((h->phase_d + M) / h->cfg.rds_decim);
+  *n_out = decim_outputs(h->rd, front_new_d(h->f, nbytes));
   return SDRFM_OK;
 }
 
 // one call on device buffers, enqueued on the handle's stream
 static int rds_enqueue(sdrfm_rds* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, float* d_bb, size_t bb_stride, uint32_t* d_pc,
                        uint32_t* n_out) {
-  const uint32_t Tr = h->cfg.rds_taps, Dr = h->cfg.rds_decim, ns = h->cfg.n_streams, slots = h->slots;
+  const uint32_t ns = h->cfg.n_streams;
   if (h->step.lds > PF_LDS_BUDGET) return SDRFM_FAIL;            // (no shape within the header's limits gets here: NY = 2 fits them all)
   RdsParams p;
   memset(&p, 0, sizeof p);
   front_fill(h->f, p, d_iq, iq_stride, nbytes, d_pc, h->step);
-  const uint32_t M = p.M, A = (h->phase_d + M) / Dr;
+  const uint32_t M = p.M, A = decim_outputs(h->rd, M);
   p.bb = d_bb; p.bb_stride = bb_stride;
-  p.g = h->d_g;
-  p.Tr = Tr; p.Dr = Dr;
+  p.g = h->rd.d_g;
+  p.Tr = h->rd.T; p.Dr = h->rd.D;
   p.rds_gain = h->cfg.rds_gain;
   p.A = A;
-  p.f0 = (int32_t)(Dr - 1 - h->phase_d);
-  p.zplane = rds_zplane(Tr, p.NDT);
-  // workgroups per stream: the machine takes `slots` workgroups at a time, so the call lasts (rounds of workgroups) x (a workgroup's span plus
-  // its prologue, which costs about half as much per d); the split with the shortest such time, the fewest workgroups among equals, no span
-  // below one step.  A stream gets at least one workgroup (the one that hands the state over).  The results do not depend on the split.
-  p.blocks_per_stream = 1;
-  if (M) {
-    const uint32_t most = (M + p.NDT - 1) / p.NDT;
-    uint64_t best = ~(uint64_t)0;
-    for (uint32_t bps = 1; bps <= most && bps <= 64; ++bps) {
-      const uint64_t rounds = ((uint64_t)ns * bps + slots - 1) / slots, span = (M + bps - 1) / bps;
-      const uint64_t cost = rounds * (span + p.H / 2 + 64);
-      if (cost < best) { best = cost; p.blocks_per_stream = bps; }
-    }
-  }
+  p.f0 = decim_f0(h->rd);
+  p.zplane = rds_zplane(p.Tr, p.NDT);
+  p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, h->slots);
   p.span = M ? (M + p.blocks_per_stream - 1) / p.blocks_per_stream : 0;
-  if (d_pc && hipMemsetAsync(d_pc, 0, sizeof(uint32_t) * ns, h->f.stream) != hipSuccess) return SDRFM_FAIL;
+  if (front_zero_count(h->f, d_pc, true) != SDRFM_OK) return SDRFM_FAIL;
   const dim3 grid(ns * p.blocks_per_stream), block(PF_THREADS);
   if (h->fast) k_rds<64, 10, 101><<<grid, block, h->step.lds, h->f.stream>>>(p);
   else k_rds<0, 0, 0><<<grid, block, h->step.lds, h->f.stream>>>(p);
   if (hipGetLastError() != hipSuccess) return SDRFM_FAIL;
   front_advance(h->f, p.N);
-  h->phase_d = (h->phase_d + M) % Dr;
+  decim_advance(h->rd, M);
   *n_out = A;
   return SDRFM_OK;
 }
@@ -292,17 +222,9 @@ int sdrfm_rds_process_batch(sdrfm_rds_t* h, const uint8_t* iq, size_t iq_stride,
   if (nbytes & 1u) return SDRFM_EODD;
   if (nbytes > h->f.max_bytes) return SDRFM_ECAPACITY;
   const uint32_t ns = h->cfg.n_streams;
-  const hipStream_t stream = h->f.stream;
   if (nbytes == 0) {
     *n_out = 0;
-    if (pilot_count) {
-      if (flags & SDRFM_F_DEVICE_PTRS) {
-        if (hipSetDevice(h->f.device) != hipSuccess || hipMemsetAsync(pilot_count, 0, sizeof(uint32_t) * ns, stream) != hipSuccess) return SDRFM_FAIL;
-      } else {
-        memset(pilot_count, 0, sizeof(uint32_t) * ns);
-      }
-    }
-    return SDRFM_OK;
+    return front_empty_call(h->f, pilot_count, flags);
   }
   if (!iq) return SDRFM_EINVAL;
   if (ns > 1 && iq_stride < nbytes) return SDRFM_ECAPACITY;
@@ -313,16 +235,11 @@ int sdrfm_rds_process_batch(sdrfm_rds_t* h, const uint8_t* iq, size_t iq_stride,
   if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
   if (flags & SDRFM_F_DEVICE_PTRS) return rds_enqueue(h, iq, iq_stride, nbytes, bb, bb_stride, pilot_count, n_out);
 
-  if (hipMemcpy2DAsync(h->f.d_iq, h->f.d_iq_stride, iq, ns > 1 ? iq_stride : nbytes, nbytes, ns, hipMemcpyHostToDevice, stream) != hipSuccess)
-    return SDRFM_FAIL;
-  const int rc = rds_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_bb, h->d_bb_stride, h->d_pc, n_out);
+  if (front_stage_in(h->f, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
+  const int rc = rds_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_bb, h->d_bb_stride, h->f.d_pc, n_out);
   if (rc != SDRFM_OK) return rc;
-  const size_t dst = (ns > 1 ? bb_stride : 2 * (size_t)A) * sizeof(float), src = h->d_bb_stride * sizeof(float);
-  if (A && hipMemcpy2DAsync(bb, dst, h->d_bb, src, 2 * (size_t)A * sizeof(float), ns, hipMemcpyDeviceToHost, stream) != hipSuccess)
-    return SDRFM_FAIL;
-  if (pilot_count && hipMemcpyAsync(pilot_count, h->d_pc, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, stream) != hipSuccess) return SDRFM_FAIL;
-  if (hipStreamSynchronize(stream) != hipSuccess) return SDRFM_FAIL;
-  return SDRFM_OK;
+  if (front_copy_back(h->f, bb, bb_stride, h->d_bb, h->d_bb_stride, 2 * (size_t)A) != SDRFM_OK) return SDRFM_FAIL;
+  return front_finish(h->f, pilot_count);
 }
 
 int sdrfm_rds_set_stream(sdrfm_rds_t* h, void* hip_stream) {

@@ -4,13 +4,14 @@
  * The walk from the input bytes to the pilot filter's q = b * d is sdrfm_pilot_front.h's, shared with the RDS kernel.  What this file
  * adds behind q, at the discriminator rate: the 38 kHz carrier c = -2 qr qi / |q|^2 (gated by |q|^2 >= pilot_min^2; sdrfm_carrier.h), the difference
  * signal s = (c * diff_gain) d[m - Δ] over the step's audio windows -> LDS, and the two audio chains am (on d delayed by Δ) and as
- * (on s), L = am + as, R = am - as -> HBM.  H = P - 1 + Ta - 1.
+ * (on s), L = am + as, R = am - as -> HBM (sdrfm_out_stages.h, shared with the broadcast kernel).  H = P - 1 + Ta - 1.
  *
  * k_stereo<0, 0, 0> and k_stereo<64, 10, 101> are the header's two forms of the walk; the carrier and the audio chains are the same code in both.
  */
 #include <new>
 
 #include "sdrfm_carrier.h"
+#include "sdrfm_out_stages.h"
 #include "sdrfm_pilot_front.h"
 
 namespace {
@@ -59,23 +60,9 @@ __global__ void __launch_bounds__(PF_THREADS) k_stereo(StereoParams p) {
         cnt += (on && o >= (int)Ta - 1) ? 1u : 0u;
       });
       __syncthreads();
-      // ---- audio: outputs j whose newest d lies in [a, b)
-      int jl = a - p.f0 > 0 ? (a - p.f0 + (int)Da - 1) / (int)Da : 0;
-      int jh = b - p.f0 > 0 ? (b - p.f0 + (int)Da - 1) / (int)Da : 0;
-      if (jh > (int)p.A) jh = (int)p.A;
-      for (int j = jl + tid; j < jh; j += nthr) {
-        const int nj = p.f0 + j * (int)Da - a;                   // step-relative index of the newest d of output j
-        const float* wd = ds + (int)H + nj - (int)Dl - (int)(Ta - 1);
-        const float* wsv = ss + nj;
-        float am = 0.0f, as = 0.0f;
-        for (uint32_t k = 0; k < Ta; ++k) {
-          const float c = gs[Ta - 1 - k];
-          am = __builtin_fmaf(c, wd[k], am);
-          as = __builtin_fmaf(c, wsv[k], as);
-        }
-        p.left[(size_t)s * p.audio_stride + j] = am + as;
-        p.right[(size_t)s * p.audio_stride + j] = am - as;
-      }
+      // ---- audio: outputs j whose newest d lies in [a, b), one per lane
+      const int2 jr = step_outputs(a, b, p.f0, (int)Da, (int)p.A);
+      audio_outputs(ds, ss, gs, Ta, Da, p.f0, a, H, Dl, jr.x + tid, nthr, jr.y, p.left + (size_t)s * p.audio_stride, p.right + (size_t)s * p.audio_stride);
     }
     __syncthreads();
   });
@@ -92,14 +79,10 @@ __global__ void __launch_bounds__(PF_THREADS) k_stereo(StereoParams p) {
 struct sdrfm_stereo {
   sdrfm_stereo_config cfg;                     // taps pointers point at the copies in f and below
   PilotFront f;
-  float* gc = nullptr;
-  uint32_t max_audio = 0;
-  float* d_g = nullptr;
+  Decim au;                                    // the audio decimator
   float* d_left = nullptr;
   float* d_right = nullptr;
   size_t d_audio_stride = 0;
-  uint32_t* d_pc = nullptr;
-  uint32_t phase_d = 0;
   bool fast = false;
   FrontStep step;                              // of the kernel this handle launches
   char kernel_name[96];
@@ -119,8 +102,8 @@ size_t stereo_lds(uint32_t T, uint32_t D, uint32_t P, uint32_t Ta, uint32_t H, u
 void stereo_free(sdrfm_stereo* h) {
   if (!h) return;
   front_free(h->f);
-  (void)hipFree(h->d_g); (void)hipFree(h->d_left); (void)hipFree(h->d_right); (void)hipFree(h->d_pc);
-  free(h->gc);
+  decim_free(h->au);
+  (void)hipFree(h->d_left); (void)hipFree(h->d_right);
   delete h;
 }
 
@@ -134,9 +117,8 @@ int sdrfm_stereo_create(const sdrfm_stereo_config* cfg, sdrfm_stereo_t** out) {
   if (!cfg || cfg->struct_size != sizeof(sdrfm_stereo_config)) return SDRFM_EINVAL;
   if (!front_config_ok(cfg->n_streams, cfg->fir_taps, cfg->fir_decim, cfg->fir_coeffs, cfg->pilot_taps, cfg->pilot_coeffs, cfg->pilot_min))
     return SDRFM_EINVAL;
-  if (!cfg->audio_coeffs || (cfg->flags & ~SDRFM_STEREO_CFG_FORCE_GENERIC)) return SDRFM_EINVAL;
-  if (!cfg->audio_taps || cfg->audio_taps > SDRFM_MAX_TAPS || !cfg->audio_decim || cfg->audio_decim > SDRFM_MAX_DECIM) return SDRFM_EINVAL;
-  if (!std::isfinite(cfg->diff_gain) || !finite_all(cfg->audio_coeffs, cfg->audio_taps)) return SDRFM_EINVAL;
+  if (cfg->flags & ~SDRFM_STEREO_CFG_FORCE_GENERIC) return SDRFM_EINVAL;
+  if (!decim_config_ok(cfg->audio_taps, cfg->audio_decim, cfg->audio_coeffs, cfg->diff_gain)) return SDRFM_EINVAL;
   hipDeviceProp_t prop;
   int rc = front_open_device(cfg->device, &prop);
   if (rc != SDRFM_OK) return rc;
@@ -148,24 +130,14 @@ int sdrfm_stereo_create(const sdrfm_stereo_config* cfg, sdrfm_stereo_t** out) {
   const size_t ns = cfg->n_streams;
   rc = front_alloc(h->f, cfg->n_streams, T, D, cfg->fir_coeffs, P, cfg->pilot_coeffs, cfg->pilot_min, H, cfg->max_bytes_per_call, cfg->device);
   if (rc != SDRFM_OK) { stereo_free(h); return rc; }
-  {
-    const uint64_t m = (uint64_t)(h->f.max_bytes / 2 + D - 1) / D + 1;
-    h->max_audio = (uint32_t)((m + Da - 1) / Da + 1);
-  }
-  h->gc = (float*)malloc(sizeof(float) * Ta);
-  if (!h->gc) { stereo_free(h); return SDRFM_ENOMEM; }
-  memcpy(h->gc, cfg->audio_coeffs, sizeof(float) * Ta);
+  rc = decim_alloc(h->au, h->f, Ta, Da, cfg->audio_coeffs);
+  if (rc != SDRFM_OK) { stereo_free(h); return rc; }
   h->cfg.fir_coeffs = h->f.hc;
-  h->cfg.audio_coeffs = h->gc;
+  h->cfg.audio_coeffs = h->au.gc;
   h->cfg.pilot_coeffs = h->f.bc;
-  h->d_audio_stride = ((size_t)h->max_audio + 63) & ~(size_t)63;
-#define CR(expr) do { if ((expr) != hipSuccess) { stereo_free(h); return SDRFM_ENOMEM; } } while (0)
-  CR(hipMalloc(&h->d_g, sizeof(float) * Ta));
-  CR(hipMalloc(&h->d_left, sizeof(float) * h->d_audio_stride * ns));
-  CR(hipMalloc(&h->d_right, sizeof(float) * h->d_audio_stride * ns));
-  CR(hipMalloc(&h->d_pc, sizeof(uint32_t) * ns));
-  CR(hipMemcpy(h->d_g, h->gc, sizeof(float) * Ta, hipMemcpyHostToDevice));
-#undef CR
+  h->d_audio_stride = ((size_t)h->au.max_out + 63) & ~(size_t)63;
+  const size_t audio_bytes = sizeof(float) * h->d_audio_stride * ns;
+  if (hipMalloc(&h->d_left, audio_bytes) != hipSuccess || hipMalloc(&h->d_right, audio_bytes) != hipSuccess) { stereo_free(h); return SDRFM_ENOMEM; }
   const uint32_t ndt_fast = PF_FAST_NY - (Ta > 1 ? Ta - 1 : 1);
   h->step = front_step(stereo_lds, 64, 10, 101, Ta, H, PF_FAST_NY, ndt_fast);
   h->fast = !(cfg->flags & SDRFM_STEREO_CFG_FORCE_GENERIC) && T == 64 && D == 10 && P == 101 && ndt_fast >= 1 && h->step.lds <= PF_LDS_BUDGET;
@@ -189,43 +161,42 @@ int sdrfm_stereo_reset(sdrfm_stereo_t* h) {
   if (!h) return SDRFM_EINVAL;
   const int rc = front_reset(h->f);
   if (rc != SDRFM_OK) return rc;
-  h->phase_d = 0;
+  decim_reset(h->au);
   return SDRFM_OK;
 }
 
 int sdrfm_stereo_audio_count(const sdrfm_stereo_t* h, uint32_t nbytes, uint32_t* n_audio) {
   if (!h || !n_audio) return SDRFM_EINVAL;
   if (nbytes & 1u) return SDRFM_EODD;
-  const uint64_t M = (h->f.phase_x + (uint64_t)(nbytes / 2)) / h->cfg.fir_decim;
-  *n_audio = (uint32_t)((h->phase_d + M) / h->cfg.audio_decim);
+  *n_audio = decim_outputs(h->au, front_new_d(h->f, nbytes));
   return SDRFM_OK;
 }
 
 // one call on device buffers, enqueued on the handle's stream
 static int stereo_enqueue(sdrfm_stereo* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, float* d_left, float* d_right,
                           size_t audio_stride, uint32_t* d_pc, uint32_t* n_audio) {
-  const uint32_t Ta = h->cfg.audio_taps, Da = h->cfg.audio_decim, ns = h->cfg.n_streams;
+  const uint32_t ns = h->cfg.n_streams;
   StereoParams p;
   memset(&p, 0, sizeof p);
   front_fill(h->f, p, d_iq, iq_stride, nbytes, d_pc, h->step);
-  const uint32_t M = p.M, A = (h->phase_d + M) / Da;
+  const uint32_t M = p.M, A = decim_outputs(h->au, M);
   p.left = d_left; p.right = d_right; p.audio_stride = audio_stride;
-  p.g = h->d_g;
-  p.Ta = Ta; p.Da = Da;
+  p.g = h->au.d_g;
+  p.Ta = h->au.T; p.Da = h->au.D;
   p.diff_gain = h->cfg.diff_gain;
   p.A = A;
-  p.f0 = (int32_t)(Da - 1 - h->phase_d);
+  p.f0 = decim_f0(h->au);
   // every workgroup walks ~8 steps after its prologue; a stream gets at least one workgroup (the one that hands the state over)
   const uint32_t per = 8 * p.NDT;
   p.blocks_per_stream = M ? (M + per - 1) / per : 1;
   p.span = M ? (M + p.blocks_per_stream - 1) / p.blocks_per_stream : 0;
-  if (d_pc && hipMemsetAsync(d_pc, 0, sizeof(uint32_t) * ns, h->f.stream) != hipSuccess) return SDRFM_FAIL;
+  if (front_zero_count(h->f, d_pc, true) != SDRFM_OK) return SDRFM_FAIL;
   const dim3 grid(ns * p.blocks_per_stream), block(PF_THREADS);
   if (h->fast) k_stereo<64, 10, 101><<<grid, block, h->step.lds, h->f.stream>>>(p);
   else k_stereo<0, 0, 0><<<grid, block, h->step.lds, h->f.stream>>>(p);
   if (hipGetLastError() != hipSuccess) return SDRFM_FAIL;
   front_advance(h->f, p.N);
-  h->phase_d = (h->phase_d + M) % Da;
+  decim_advance(h->au, M);
   *n_audio = A;
   return SDRFM_OK;
 }
@@ -237,17 +208,9 @@ int sdrfm_stereo_process_batch(sdrfm_stereo_t* h, const uint8_t* iq, size_t iq_s
   if (nbytes & 1u) return SDRFM_EODD;
   if (nbytes > h->f.max_bytes) return SDRFM_ECAPACITY;
   const uint32_t ns = h->cfg.n_streams;
-  const hipStream_t stream = h->f.stream;
   if (nbytes == 0) {
     *n_audio = 0;
-    if (pilot_count) {
-      if (flags & SDRFM_F_DEVICE_PTRS) {
-        if (hipSetDevice(h->f.device) != hipSuccess || hipMemsetAsync(pilot_count, 0, sizeof(uint32_t) * ns, stream) != hipSuccess) return SDRFM_FAIL;
-      } else {
-        memset(pilot_count, 0, sizeof(uint32_t) * ns);
-      }
-    }
-    return SDRFM_OK;
+    return front_empty_call(h->f, pilot_count, flags);
   }
   if (!iq) return SDRFM_EINVAL;
   if (ns > 1 && iq_stride < nbytes) return SDRFM_ECAPACITY;
@@ -258,17 +221,12 @@ int sdrfm_stereo_process_batch(sdrfm_stereo_t* h, const uint8_t* iq, size_t iq_s
   if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
   if (flags & SDRFM_F_DEVICE_PTRS) return stereo_enqueue(h, iq, iq_stride, nbytes, left, right, audio_stride, pilot_count, n_audio);
 
-  if (hipMemcpy2DAsync(h->f.d_iq, h->f.d_iq_stride, iq, ns > 1 ? iq_stride : nbytes, nbytes, ns, hipMemcpyHostToDevice, stream) != hipSuccess)
-    return SDRFM_FAIL;
-  const int rc = stereo_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_pc, n_audio);
+  if (front_stage_in(h->f, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
+  const int rc = stereo_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->f.d_pc, n_audio);
   if (rc != SDRFM_OK) return rc;
-  const size_t dst = (ns > 1 ? audio_stride : A) * sizeof(float), src = h->d_audio_stride * sizeof(float);
-  if (A && (hipMemcpy2DAsync(left, dst, h->d_left, src, A * sizeof(float), ns, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipMemcpy2DAsync(right, dst, h->d_right, src, A * sizeof(float), ns, hipMemcpyDeviceToHost, stream) != hipSuccess))
-    return SDRFM_FAIL;
-  if (pilot_count && hipMemcpyAsync(pilot_count, h->d_pc, sizeof(uint32_t) * ns, hipMemcpyDeviceToHost, stream) != hipSuccess) return SDRFM_FAIL;
-  if (hipStreamSynchronize(stream) != hipSuccess) return SDRFM_FAIL;
-  return SDRFM_OK;
+  if (front_copy_back(h->f, left, audio_stride, h->d_left, h->d_audio_stride, A) != SDRFM_OK) return SDRFM_FAIL;
+  if (front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, A) != SDRFM_OK) return SDRFM_FAIL;
+  return front_finish(h->f, pilot_count);
 }
 
 int sdrfm_stereo_set_stream(sdrfm_stereo_t* h, void* hip_stream) {
