@@ -34,8 +34,11 @@
 #include "../../include/sdrfm_dev.h"
 #include "sdrfm_math.h"
 #include "sdrfm_q.h"
+#include "sdrfm_fm_call.h"
 
 #include "sdrfm_b.h"
+
+static_assert(SDRFM_FM_Q_STEP_OUT == SDRFM_Q_STEP_OUT, "sdrfm_fm_call.h counts design Q's steps");
 
 namespace {
 
@@ -955,26 +958,20 @@ struct sdrfm {
   // small single-stream calls (URB-sized hand-offs): host-mapped pinned buffers the kernel reads / writes directly
   uint8_t* zc_iq; float* zc_audio; uint8_t* zc_iq_dev; float* zc_audio_dev; uint32_t zc_audio_cap; bool zc_off;
   uint32_t max_bytes;
-  // generic kernel geometry
-  uint32_t NA;
-  size_t lds_bytes;
+  FmGeom geo;             // what create fixes of the call path's arithmetic (sdrfm_fm_call.h): the designs there are, their tiles, shares and LDS sizes
+  size_t lds_bytes;       // generic kernel: LDS of a block
   // fast kernel (when one is instantiated for this T/D)
   const FastVariant* fast;
   const FastVariant* fast_s;  // design S variant of this geometry, if one is instantiated (serves the calls it is eligible for)
-  const FastVariant* fast_mix; size_t fast_mix_lds;   // design B with the smallest tile (R = 4): the noisy streams' workgroups beside design Q's
-  bool mix_split_off; double mix_rho;                            // (development library: SDRFM_MIX_SPLIT_OFF keeps the share-only split of the wave slots; SDRFM_MIX_RHO: the weight)
-  uint32_t mix_lds, mix_waves_per_cu, mix_R; double mix_cost;                 // ... or INSIDE design Q's launch (sdrfm_q.hip: k_mix) where an instance exists: LDS bytes of a workgroup (0 = none), workgroups a CU holds
-  uint32_t n_cu;              // compute units of the device
+  const FastVariant* fast_mix;   // design B with the smallest tile (R = 4): the noisy streams' workgroups beside design Q's, or INSIDE design Q's launch (sdrfm_q.hip: k_mix) where
+                                 // an instance exists (geo.mix_lds; development library: SDRFM_MIX_SPLIT_OFF keeps the share-only split of the wave slots, SDRFM_MIX_RHO: the weight)
   char fast_s_name[64];
-  size_t fast_lds;
-  uint32_t waves_target;   // resident waves the fast kernel aims for (CUs x waves that fit by LDS)
-  uint32_t min_subtiles;   // minimum sub-tiles per segment (bounds the per-segment halo recompute)
   uint32_t AB;             // sub-tiles of d buffered per audio flush
   unsigned long long* d_dbg;  // phase profile accumulators (only with SDRFM_PHASE_PROFILE=1)
   uint32_t warm_ahead;        // L2 warm-up distance (sub-tiles)
   uint32_t dbg_launches;      // launches since the debug counters were last reset
   int fast_mode;              // 0 product; 1..7 timing experiments (libsdrfm_dev.so only)
-  uint32_t prio_balance, fold_state_ok;   // design B knobs, fixed at create
+  uint32_t prio_balance;                  // design B knob, fixed at create (geo.fold_state_ok: the other)
   uint32_t end_prio;                      // design S: see CallParams
   uint32_t stream_profile;                // development build: d_dbg holds per-wave time stamps of design S
   char kernel_name[112];
@@ -983,7 +980,7 @@ struct sdrfm {
   // design Q (matrix-pipe FIR, sdrfm_q.hip): operand tables on the device, scale / offset, first K-chunk that holds taps
   int8_t* d_qA;
   float q_scale, q_cst;
-  uint32_t q_c0, q_nslot, q_waves_per_cu;
+  uint32_t q_c0, q_nslot;
   char fast_q_name[64];
   // design Q's conditioning guard: thresholds, the zero-padded taps of the repair path's chain, the last 64 raw samples of
   // every stream (kept like the other state sets), statistics; and what the current state set holds: y[-1] as the definition has it
@@ -1131,11 +1128,7 @@ static void route_retry(sdrfm* h) {
   }
 }
 
-static uint32_t max_audio_for(const sdrfm_config& c, uint32_t nbytes) {
-  const uint64_t n = nbytes / 2;
-  const uint64_t m = (n + c.fir_decim - 1) / c.fir_decim + 1;
-  return (uint32_t)((m + c.audio_decim - 1) / c.audio_decim + 1);
-}
+static uint32_t max_audio_for(const sdrfm_config& c, uint32_t nbytes) { return fm_max_audio(c.fir_decim, c.audio_decim, nbytes); }
 
 // Everything design Q and its per-stream routing own (free_handle; and sdrfm_create when any of it could not be had: the handle then runs the bit-exact
 // kernels, with nothing half-allocated left behind — ADVICE r05).  Every member is null or valid; all are null afterwards.
@@ -1284,7 +1277,7 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
   h->device = cfg->device;
   h->max_bytes = cfg->max_bytes_per_call ? cfg->max_bytes_per_call : (1u << 20);
   h->zc_off = (cfg->flags & SDRFM_CFG_NO_ZEROCOPY) != 0;
-  h->prio_balance = 1; h->fold_state_ok = 1; h->end_prio = (1u | (1u << 2)) << 6;
+  h->prio_balance = 1; h->geo.fold_state_ok = 1; h->end_prio = (1u | (1u << 2)) << 6;
   h->max_bytes &= ~1u;
   float* hc = (float*)malloc(sizeof(float) * cfg->fir_taps);
   float* gc = (float*)malloc(sizeof(float) * cfg->audio_taps);
@@ -1320,7 +1313,7 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
     NA /= 2;
   }
   if (h->lds_bytes > 160 * 1024) { free_handle(h); return SDRFM_NOT_SUPPORTED; }
-  h->NA = NA;
+  h->geo.NA = NA;
   if (h->lds_bytes > 64 * 1024) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_generic), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)h->lds_bytes) != hipSuccess) { free_handle(h); return SDRFM_NOT_SUPPORTED; }
@@ -1338,7 +1331,7 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
     if (const char* e = getenv("SDRFM_AUDIO_BATCH")) ab_env = (uint32_t)atoi(e);
     if (getenv("SDRFM_NO_PRIO")) h->prio_balance = 0;
     if (const char* e = getenv("SDRFM_END_PRIO")) h->end_prio = (uint32_t)strtoul(e, nullptr, 0);
-    if (getenv("SDRFM_NO_FOLD")) h->fold_state_ok = 0;
+    if (getenv("SDRFM_NO_FOLD")) h->geo.fold_state_ok = 0;
 #endif
     for (const FastVariant& v : kFastVariants) {
       if (v.kind != 's' || v.T != cfg->fir_taps || v.D != cfg->fir_decim || v.Ta != cfg->audio_taps || v.Da != cfg->audio_decim) continue;
@@ -1352,7 +1345,7 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
       }
 #endif
       h->fast_s = &v;
-      h->n_cu = (uint32_t)prop.multiProcessorCount;
+      h->geo.n_cu = (uint32_t)prop.multiProcessorCount;
       snprintf(h->fast_s_name, sizeof(h->fast_s_name), "fast-s T%u D%u S%u L%u Ta%u Da%u", v.T, v.D, v.R, v.seg, v.Ta, v.Da);
     }
     // design Q: K2 on the i8 matrix pipe (sdrfm_q.hip).  Not bit-identical to the fmaf-chain kernels (within 1e-6 of the
@@ -1389,17 +1382,17 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
           route_create(h) == SDRFM_OK) {
         h->q_scale = qs; h->q_cst = qc; h->q_c0 = c0 > 1 ? 1 : c0;
         h->q_guard_r = q_R; h->q_guard_a = q_A;
-        h->q_nslot = sdrfm_q_default_nslot(cfg->fir_decim); h->q_waves_per_cu = 12;
-        { const uint32_t lb = sdrfm_q_lds_bytes(h->q_nslot, cfg->fir_decim, cfg->audio_decim); if (lb && 163840u / lb < h->q_waves_per_cu) h->q_waves_per_cu = 163840u / lb; }   // (D = 16: 11 one-wave workgroups fit a CU's LDS)
+        h->q_nslot = sdrfm_q_default_nslot(cfg->fir_decim); h->geo.q_waves_per_cu = 12;
+        { const uint32_t lb = sdrfm_q_lds_bytes(h->q_nslot, cfg->fir_decim, cfg->audio_decim); if (lb && 163840u / lb < h->geo.q_waves_per_cu) h->geo.q_waves_per_cu = 163840u / lb; }   // (D = 16: 11 one-wave workgroups fit a CU's LDS)
 #ifdef SDRFM_DEV
         if (const char* e = getenv("SDRFM_Q_NSLOT")) h->q_nslot = (uint32_t)atoi(e);
-        if (const char* e = getenv("SDRFM_Q_WAVES_PER_CU")) h->q_waves_per_cu = (uint32_t)atoi(e);
+        if (const char* e = getenv("SDRFM_Q_WAVES_PER_CU")) h->geo.q_waves_per_cu = (uint32_t)atoi(e);
         if (const char* e = getenv("SDRFM_Q_GUARD_R")) h->q_guard_r = (float)atof(e);            // 0 and 4: the guard never fires (timing / soak experiments)
         if (const char* e = getenv("SDRFM_Q_GUARD_A")) h->q_guard_a = (float)atof(e);
         if (getenv("SDRFM_NO_Q")) { (void)hipFree(h->d_qA); h->d_qA = nullptr; }
         if (getenv("SDRFM_Q_NO_ADAPT")) h->rt_off = true;                                         // design Q whatever the streams hold (timing experiments)
 #endif
-        h->n_cu = (uint32_t)prop.multiProcessorCount;
+        h->geo.n_cu = (uint32_t)prop.multiProcessorCount;
         snprintf(h->fast_q_name, sizeof(h->fast_q_name), "fast-q T%u D%u Ta%u Da%u %s", cfg->fir_taps, cfg->fir_decim, cfg->audio_taps,
                  cfg->audio_decim, sdrfm_q_kernel_symbol(h->q_c0, h->q_nslot, cfg->fir_decim, cfg->audio_decim));
       } else {
@@ -1439,16 +1432,16 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
       }
 #endif
       h->fast = &v;
-      h->fast_lds = lds;
+      h->geo.fast_lds = lds;
       uint32_t per_cu = (uint32_t)((160 * 1024) / lds);
       if (per_cu > 16) per_cu = 16;
 #ifdef SDRFM_DEV
       if (const char* e = getenv("SDRFM_WAVES_PER_CU")) per_cu = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : per_cu;
 #endif
-      h->waves_target = (uint32_t)prop.multiProcessorCount * per_cu;
-      h->min_subtiles = 4;
+      h->geo.waves_target = (uint32_t)prop.multiProcessorCount * per_cu;
+      h->geo.min_subtiles = 4;
 #ifdef SDRFM_DEV
-      if (const char* e = getenv("SDRFM_MIN_SUBTILES")) h->min_subtiles = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : 4;
+      if (const char* e = getenv("SDRFM_MIN_SUBTILES")) h->geo.min_subtiles = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : 4;
 #endif
       snprintf(h->fast_name, sizeof(h->fast_name), "fast-%c T%u D%u R%u Ta%u Da%u AB%u", v.kind, v.T, v.D, v.R,
                cfg->audio_taps, cfg->audio_decim, AB);
@@ -1462,26 +1455,34 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
       const uint32_t NYT = 64 * v.R, DOFF = (cfg->audio_taps - 1 + 3u) & ~3u;
       if (cfg->audio_taps - 1 > NYT || DOFF + NYT < 2 * (cfg->audio_taps + 1)) continue;
       h->fast_mix = &v;
-      h->fast_mix_lds = (size_t)v.xbytes + (size_t)(DOFF + (uint32_t)fastb_ab((int)v.R) * NYT + v.T + cfg->audio_taps) * 4;
+      h->geo.fast_mix_lds = (size_t)v.xbytes + (size_t)(DOFF + (uint32_t)fastb_ab((int)v.R) * NYT + v.T + cfg->audio_taps) * 4;
       // a stream costs the design-B workgroups about mix_cost times what it costs design Q's: the shares of the wave slots (measured: 2.0 / 2.7 / 3.2 ->
       // 41.2 / 38.9 / 40.3 us serial, 31.5 / 30.8 / 33.0 us overlapped with a quarter of the streams noisy: profiles/r05_mixed_batches.txt)
-      h->mix_R = v.R; h->mix_cost = 2.7; h->mix_rho = 12.7;
+      h->geo.mix_R = v.R; h->geo.mix_cost = 2.7; h->geo.mix_rho = 12.7;
 #ifdef SDRFM_DEV
-      if (const char* e = getenv("SDRFM_MIX_COST")) h->mix_cost = atof(e);
-      if (getenv("SDRFM_MIX_SPLIT_OFF")) h->mix_split_off = true;
-      if (const char* e = getenv("SDRFM_MIX_RHO")) h->mix_rho = atof(e);
+      if (const char* e = getenv("SDRFM_MIX_COST")) h->geo.mix_cost = atof(e);
+      if (getenv("SDRFM_MIX_SPLIT_OFF")) h->geo.mix_split_off = true;
+      if (const char* e = getenv("SDRFM_MIX_RHO")) h->geo.mix_rho = atof(e);
 #endif
-      h->mix_lds = (cfg->audio_taps == SDRFM_Q_TA) ? sdrfm_q_mix_lds(h->q_c0, h->q_nslot, cfg->fir_decim, cfg->audio_decim, v.T, h->mix_R) : 0u;
-      if (h->mix_lds) {
-        const int nb = sdrfm_q_mix_blocks_per_cu(h->q_c0, h->q_nslot, cfg->fir_decim, cfg->audio_decim, v.T, h->mix_R);
-        h->mix_waves_per_cu = nb > 0 ? (uint32_t)nb : 163840u / h->mix_lds;
-        if (h->mix_waves_per_cu > h->q_waves_per_cu) h->mix_waves_per_cu = h->q_waves_per_cu;   // (15 fit; design Q's own 12 are faster: same file)
+      h->geo.mix_lds = (cfg->audio_taps == SDRFM_Q_TA) ? sdrfm_q_mix_lds(h->q_c0, h->q_nslot, cfg->fir_decim, cfg->audio_decim, v.T, h->geo.mix_R) : 0u;
+      if (h->geo.mix_lds) {
+        const int nb = sdrfm_q_mix_blocks_per_cu(h->q_c0, h->q_nslot, cfg->fir_decim, cfg->audio_decim, v.T, h->geo.mix_R);
+        h->geo.mix_waves_per_cu = nb > 0 ? (uint32_t)nb : 163840u / h->geo.mix_lds;
+        if (h->geo.mix_waves_per_cu > h->geo.q_waves_per_cu) h->geo.mix_waves_per_cu = h->geo.q_waves_per_cu;   // (15 fit; design Q's own 12 are faster: same file)
 #ifdef SDRFM_DEV
-        if (getenv("SDRFM_MIX_OFF")) h->mix_lds = 0;
-        if (const char* e = getenv("SDRFM_MIX_WAVES_PER_CU")) h->mix_waves_per_cu = (uint32_t)atoi(e);
+        if (getenv("SDRFM_MIX_OFF")) h->geo.mix_lds = 0;
+        if (const char* e = getenv("SDRFM_MIX_WAVES_PER_CU")) h->geo.mix_waves_per_cu = (uint32_t)atoi(e);
 #endif
       }
     }
+  // the rest of what the call path's arithmetic takes as given (sdrfm_fm_call.h): copies of cfg's shape and of which designs the handle ended up with.
+  // Nothing after this point drops a design or changes cfg; a path that ever does (frees d_qA, clears fast / fast_s / fast_mix) must refresh these with it.
+  FmGeom& geo = h->geo;
+  geo.T = cfg->fir_taps; geo.D = cfg->fir_decim; geo.Ta = cfg->audio_taps; geo.Da = cfg->audio_decim; geo.n_streams = cfg->n_streams;
+  geo.has_q = h->d_qA != nullptr; geo.has_s = h->fast_s != nullptr; geo.has_mix_tile = h->fast_mix != nullptr;
+  geo.has_fast = h->fast != nullptr; geo.fast_is_b = h->fast && h->fast->kind == 'b'; geo.fast_R = h->fast ? h->fast->R : 0u;
+  geo.seg = h->fast_s ? h->fast_s->seg : 0u;
+  geo.q_lds = geo.has_q ? sdrfm_q_lds_bytes(h->q_nslot, cfg->fir_decim, cfg->audio_decim) : 0u;
   const int rc = sdrfm_reset(h);
   if (rc != SDRFM_OK) { free_handle(h); return rc; }
   *out = h;
@@ -1522,9 +1523,7 @@ int sdrfm_reset(sdrfm_t* h) {
 int sdrfm_audio_count(const sdrfm_t* h, uint32_t nbytes, uint32_t* n_audio) {
   if (!h || !n_audio) return SDRFM_EINVAL;
   if (nbytes & 1u) return SDRFM_EODD;
-  const uint64_t N = nbytes / 2;
-  const uint64_t M = (h->phase_x + N) / h->cfg.fir_decim;
-  *n_audio = (uint32_t)((h->phase_d + M) / h->cfg.audio_decim);
+  *n_audio = fm_counts(h->phase_x, h->phase_d, nbytes, h->cfg.fir_decim, h->cfg.audio_decim).A;
   return SDRFM_OK;
 }
 
@@ -1624,38 +1623,119 @@ int sdrfm_synchronize(sdrfm_t* h) {
 
 const char* sdrfm_kernel_name(const sdrfm_t* h) { return h ? h->kernel_name : ""; }
 
-// Do rows [a + i sa, a + i sa + la) and [b + j sb, b + j sb + lb), i, j < n, share a byte?  Exact for equal strides (two views of one
-// buffer at different offsets do not); otherwise the two whole ranges are compared.
-static bool rows_overlap(const uint8_t* a, size_t sa, size_t la, const uint8_t* b, size_t sb, size_t lb, uint32_t n) {
-  if (!a || !b || n == 0 || la == 0 || lb == 0) return false;
-  const uintptr_t ua = (uintptr_t)a, ub = (uintptr_t)b;
-  if (n == 1 || sa != sb || sa == 0) {
-    const uintptr_t ea = ua + (uintptr_t)(n - 1) * sa + la, eb = ub + (uintptr_t)(n - 1) * sb + lb;
-    return ua < eb && ub < ea;
+// ---- enqueue()'s steps: each calls sdrfm_fm_call.h for its numbers, then issues its HIP calls -------------------------------------------------
+
+// Which streams design Q serves at this call (the handle's comment: per-stream routing).
+// The first design-Q call of a window: the statistics of the window that last counted into this window's set take effect HERE, at a call the call
+// sequence fixes (route_take waits for a read-back that has not arrived: a host more than SETS - 1 windows ahead of its device).
+static int route_intake(sdrfm* h) {
+  if (h->rt_win_calls == 0) { const int trc = route_take(h, h->rt_set); if (trc != SDRFM_OK) return trc; }
+  route_retry(h);
+  if (h->rt_dirty) {
+    const int arc = route_apply(h);
+    if (arc != SDRFM_OK) return arc;
   }
-  // row i of a and row j of b start d - (i - j) s apart (d = b - a): they share a byte iff that distance lies in (-lb, la)
-  const long long s = (long long)sa, d = (long long)(ub - ua);
-  long long k = d / s;                                          // i - j candidates: floor(d / s) and its neighbours
-  for (long long kk = k - 1; kk <= k + 1; ++kk) {
-    if (kk <= -(long long)n || kk >= (long long)n) continue;
-    const long long r = d - kk * s;
-    if (r > -(long long)lb && r < (long long)la) return true;
+  return SDRFM_OK;
+}
+
+// The runs' hand-off words of the sink's chain: SDRFM_CHAIN_SETS sets of one word per workgroup of the largest grid, allocated at the first call that
+// may hold the chain.  false: they could not be had (the call goes without the chain).
+static bool ensure_runstate(sdrfm* h) {
+  if (h->d_runstate) return true;
+  h->runstate_cap = h->geo.q_waves_per_cu * h->geo.n_cu;
+  if (hipMalloc(&h->d_runstate, sizeof(unsigned long long) * SDRFM_CHAIN_SETS * h->runstate_cap) != hipSuccess ||
+      // (zeroed BEFORE any launch can see it: hipMemset alone may return before the device has done it, and the internal streams do not wait for the null stream —
+      // a memset landing in the middle of the first launch wiped the runs' published words and their successors waited for ever)
+      hipMemsetAsync(h->d_runstate, 0, sizeof(unsigned long long) * SDRFM_CHAIN_SETS * h->runstate_cap, h->stream) != hipSuccess ||
+      hipStreamSynchronize(h->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    if (h->d_runstate) (void)hipFree(h->d_runstate);
+    h->d_runstate = nullptr;
+    return false;
   }
-  return false;
+  return true;
+}
+
+// The two internal streams of overlapped and mixed calls, their events and ovl_in: created at the first call that needs them.
+static int ensure_overlap_streams(sdrfm* h) {
+  if (h->ovl_done[1]) return SDRFM_OK;                          // (created piece by piece: a failure half-way leaves nothing half-used)
+  if (!h->ovl_in) HIP_TRY(hipEventCreateWithFlags(&h->ovl_in, hipEventDisableTiming), SDRFM_ENOMEM);
+  // Two streams only overlap when they sit on different hardware queues, and the runtime hands streams of one priority a small
+  // shared pool of queues (two streams created back to back were seen on the same one: the calls then ran one after the other).
+  // Queues are pooled per priority, so the two internal streams take the two priorities ordinary streams do not use.
+  int pr_least = 0, pr_greatest = 0;
+  HIP_TRY(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest), SDRFM_FAIL);
+  for (int i = 0; i < 2; ++i) {
+    if (!h->ovl_stream[i]) HIP_TRY(hipStreamCreateWithPriority(&h->ovl_stream[i], hipStreamNonBlocking, i == 0 ? pr_greatest : pr_least), SDRFM_ENOMEM);
+    if (!h->ovl_done[i]) HIP_TRY(hipEventCreateWithFlags(&h->ovl_done[i], hipEventDisableTiming), SDRFM_ENOMEM);
+  }
+  return SDRFM_OK;
+}
+
+// The bit-exact kernels over the streams of p (p.n_streams of them, p.slist; p is the launch's own copy): design S where it pays, else design B cut for
+// bx_waves resident waves, else the generic kernel — on stream bs, bdone (or nullptr) its completion event.  Returns the kernel's name;
+// *halo_bytes is set when the kernel reads its halo as bytes.
+static const char* launch_bx(sdrfm* h, const FmCall& cl, CallParams p, uint32_t bx_waves, bool mixed, hipStream_t bs, hipEvent_t bdone, bool* halo_bytes) {
+  const FmGeom& g = h->geo;
+  const uint32_t nsub = p.n_streams;
+  if (fm_stream_ok(g, cl, nsub, mixed)) {
+    p.tiles_per_stream = fm_s_waves(g, cl);
+    p.fold_state = 1;
+    hipExtLaunchKernelGGL(h->fast_s->kernel[0], dim3(nsub * p.tiles_per_stream), dim3(64), h->fast_s->xbytes, bs, nullptr, bdone, 0, p);
+    *halo_bytes = true;
+    return h->fast_s_name;
+  }
+  if (fm_fast_ok(g, cl)) {
+    const bool small_tile = mixed && h->fast_mix;
+    const FastVariant* fv = small_tile ? h->fast_mix : h->fast;
+    const FmTiles t = fm_b_tiles(g, cl, nsub, bx_waves, small_tile);
+    p.NA = t.NA; p.tiles_per_stream = t.tiles_per_stream; p.fold_state = t.fold_state;
+    hipExtLaunchKernelGGL(fv->kernel[fv == h->fast ? h->fast_mode : 0], dim3(t.grid), dim3(64), small_tile ? g.fast_mix_lds : g.fast_lds, bs, nullptr, bdone, 0, p);
+    *halo_bytes = *halo_bytes || fv->kind == 'b';
+    return h->fast_name;
+  }
+  const FmTiles t = fm_generic_tiles(g, cl, nsub);
+  p.NA = t.NA; p.tiles_per_stream = t.tiles_per_stream;
+  hipExtLaunchKernelGGL(k_generic, dim3(t.grid), dim3(256), h->lds_bytes, bs, nullptr, bdone, 0, p);
+  return h->generic_name;
+}
+
+// A routing window closes: read its statistics back behind its last kernels, on the side stream (nothing here waits, no packet enters a compute queue
+// unless a stream holds kernels of the window that none of the attached events covers — call patterns other than "all on one stream" or "two in turn").
+static int route_window_close(sdrfm* h) {
+  const uint32_t ns_all = h->cfg.n_streams;
+  hipStream_t wst[3] = {h->ovl_stream[0], h->ovl_stream[1], h->stream};
+  const uint32_t i = h->rt_set;
+  for (int kk = 0; kk < 3; ++kk) {
+    if (!h->rt_win_used[kk]) continue;
+    if (h->rt_win_need[kk]) HIP_TRY(hipEventRecord(h->rt_win_evt[i][kk], wst[kk]), SDRFM_FAIL);
+    // (an internal stream's latest kernel carries ovl_done[kk] — enqueue() —: at or behind the window's last kernel on that stream)
+    HIP_TRY(hipStreamWaitEvent(h->rt_mon, (kk < 2 && h->ovl_bound[kk]) ? h->ovl_done[kk] : h->rt_win_evt[i][kk], 0), SDRFM_FAIL);
+    h->rt_win_used[kk] = false; h->rt_win_need[kk] = false;
+  }
+  // (one small kernel instead of a copy and a memset: 12 us of host time instead of 40 — a window that closes while the host is only a call ahead
+  // of the device, as in a 20-call burst from rest, otherwise leaves the queues dry for the difference)
+  hipLaunchKernelGGL(k_route_collect, dim3((ns_all + 255) / 256), dim3(256), 0, h->rt_mon, h->rt_pass_dev[i], h->rt_pass_host_dev[i], ns_all);
+  HIP_TRY(hipEventRecord(h->rt_rb_done[i], h->rt_mon), SDRFM_FAIL);
+  h->rt_rb_pending[i] = true; h->rt_rb_stages[i] = h->rt_win_stages;
+  h->rt_set = (h->rt_set + 1u) % SDRFM_Q_ADAPT_SETS; h->rt_win_calls = 0; h->rt_win_stages = 0;
+  return SDRFM_OK;
 }
 
 // Enqueue one call on device-resident buffers and advance the host-side phases / state set.
 static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, float* d_audio, size_t audio_stride,
                    uint32_t* n_audio, uint32_t call_flags) {
   const sdrfm_config& c = h->cfg;
-  const uint32_t N = nbytes / 2;
-  const uint32_t M = (uint32_t)(((uint64_t)h->phase_x + N) / c.fir_decim);
-  const uint32_t A = (uint32_t)(((uint64_t)h->phase_d + M) / c.audio_decim);
+  const FmGeom& g = h->geo;
+  const FmCounts n = fm_counts(h->phase_x, h->phase_d, nbytes, c.fir_decim, c.audio_decim);
+  const uint32_t N = n.N, M = n.M, A = n.A;
   if (n_audio) *n_audio = A;
   if (N == 0) return SDRFM_OK;
   if (A > audio_stride && c.n_streams > 1) return SDRFM_ECAPACITY;
+  const FmCall cl = {N, M, A, h->phase_x, h->phase_d, h->n_seen, ((uintptr_t)d_iq % 4 == 0) && (iq_stride % 4 == 0),
+                     ((uintptr_t)d_iq % 16 == 0) && (iq_stride % 16 == 0)};
 
-  CallParams p;
+  CallParams p;                                                   // every stream, no tiling yet: each launch fills its own copy
   p.iq = d_iq; p.iq_stride = iq_stride; p.audio = d_audio; p.audio_stride = audio_stride;
   p.hist_x_in = h->d_hist_x[h->cur]; p.hist_x_out = h->d_hist_x[h->cur ^ 1];
   p.yprev_in = h->d_yprev[h->cur]; p.yprev_out = h->d_yprev[h->cur ^ 1];
@@ -1666,6 +1746,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
   p.N = N; p.M = M; p.A = A;
   p.e0 = (int32_t)(c.fir_decim - 1 - h->phase_x);
   p.f0 = (int32_t)(c.audio_decim - 1 - h->phase_d);
+  p.NA = 0; p.tiles_per_stream = 0; p.fold_state = 0;
   p.n_streams = c.n_streams;
   p.phase_x = h->phase_x;
   p.AB = h->AB;
@@ -1674,81 +1755,46 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
   p.end_prio = h->end_prio;
   p.dbg_tag = (h->d_dbg && ++h->dbg_launches == 16) ? 1u : 0u;
   p.warm_ahead = h->warm_ahead;
+  p.slist = nullptr;
   p.iq_prev = nullptr; p.iq_prev_stride = 0; p.N_prev = 0;
-  // Design B cannot express the zero history at the start of a stream in bytes: until T-1 real samples have been seen its
-  // first y_aff outputs are wrong and the generic kernel recomputes the audio that depends on them (below).  The STATE it
-  // hands over (last Ta-1 discriminator outputs, y[M-1]) must not contain any of those outputs either, so a first call that
-  // short runs on the generic kernel entirely.
-  const uint32_t y_aff = (c.fir_taps + c.fir_decim - 1) / c.fir_decim + 1;            // outputs touching never-seen samples
-  const bool short_first = h->fast && h->fast->kind == 'b' && h->n_seen + 1 < c.fir_taps && M < y_aff + c.audio_taps;
-  const bool fast_ok = h->fast && A > 0 && (h->phase_x % 2 == 0) && ((uintptr_t)d_iq % 4 == 0) && (iq_stride % 4 == 0) &&
-                       N < (1u << 30) && !short_first;
-  // Design Q serves whole numbers of audio periods at decimator phase 0 on 16-byte aligned rows, when the call holds enough steps
-  // (128 outputs each) to put at least two waves on every CU; the first call after a reset must be long enough that the state it
-  // hands over holds no output computed from the (inexpressible in bytes) zero history.  It also serves one dongle's second of IQ
-  // (BASELINE configs[1]: 1875 steps cut into two-step runs, 5.7 us against 9.6 - 13 us for design B).
-  const uint32_t q_steps = (M + SDRFM_Q_STEP_OUT - 1) / SDRFM_Q_STEP_OUT;
-  const bool q_fit = h->d_qA && A > 0 && h->phase_x == 0 && h->phase_d == 0 && (N % (c.fir_decim * c.audio_decim * 8u)) == 0 &&
-                    ((uintptr_t)d_iq % 16 == 0) && (iq_stride % 16 == 0) && N < (1u << 30) && M >= c.audio_taps &&
-                    (h->n_seen + 1 >= c.fir_taps || M >= y_aff + c.audio_taps) &&
-                    (uint64_t)c.n_streams * q_steps >= 2ull * h->n_cu;
-  // ---- which streams design Q serves at this call (the handle's comment: per-stream routing) -----------------------------------------------
+
+  // ---- routing intake: which streams design Q serves at this call ------------------------------------------------------------------------------
+  const bool q_fit = fm_q_fit(g, cl);
   const uint32_t ns_all = c.n_streams;
-  if (q_fit && h->rt_noisy && !h->rt_off) {
-    // the first design-Q call of a window: the statistics of the window that last counted into this window's set take effect HERE, at a call the call
-    // sequence fixes (route_take waits for a read-back that has not arrived: a host more than SETS - 1 windows ahead of its device)
-    if (h->rt_win_calls == 0) { const int trc = route_take(h, h->rt_set); if (trc != SDRFM_OK) return trc; }
-    route_retry(h);
-    if (h->rt_dirty) {
-      const int arc = route_apply(h);
-      if (arc != SDRFM_OK) return arc;
-    }
-  }
+  if (q_fit && h->rt_noisy && !h->rt_off) { const int irc = route_intake(h); if (irc != SDRFM_OK) return irc; }
   const uint32_t n_noisy = (q_fit && h->rt_noisy) ? h->rt_n_noisy : 0u, n_clean = ns_all - n_noisy;
-  const bool q_ok = q_fit && n_clean > 0 && 2 * n_noisy < ns_all; // design Q serves n_clean streams (all of them when no stream is noisy); with half of the streams
-                                                                 // noisy the bit-exact kernels take the whole batch (design S fills the machine then)
+  const bool q_ok = fm_q_ok(q_fit, n_noisy, ns_all);
   const bool bx_all = !q_ok;                                     // the bit-exact kernels serve every stream, on the handle's stream (as every call design Q cannot take)
   const bool mixed = q_ok && n_noisy > 0;                        // ... or the noisy ones beside design Q: in its launch (k_mix) or ahead of it
+  const bool fuse = fm_fuse(g, cl, mixed);                       // ... in ONE launch of both kinds of workgroup
   ++h->rt_calls;
+  // sdrfm_process_batch_pcm: will design Q's launch hold the sink's chain (sdrfm_sink_chain.h)?  Every stream's whole audio row from this launch (no routed stream,
+  // no outputs the generic kernel recomputes behind it at the start of a stream), enough quads for runs longer than their predecessor's reach, a sink whose time
+  // constant lets runs be sunk independently.  Any other call is followed by the sink's own kernel.
+  // (a batch with routed streams: where both designs go out in ONE launch its design-Q workgroups hold the chain for the clean streams and the sink's
+  // list kernel follows on the same queue for the routed ones)
+  SdrfmSinkChain chain;
+  bool with_chain = fm_chain_fits(g, cl, q_ok, mixed, fuse) && h->pcm_sink &&
+                    sdrfm_q_has_pcm_chain(h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim) && sdrfm_sink_chain_params(h->pcm_sink, h->device, ns_all, &chain) == 2;
+  if (with_chain) with_chain = ensure_runstate(h);
+
+  // ---- the overlap join or fork ----------------------------------------------------------------------------------------------------------------
   // SDRFM_F_OVERLAP: the call goes to one of two internal streams and warms every stream up from the previous call's buffer instead
   // of reading the carried state, so that it depends on nothing the previous call computes (the state sets are still written, for
   // whatever call comes next without the flag).  Any other call first orders the handle's stream behind the overlapped ones.
   // What the flag asks of the caller is checked where that is cheap: a call whose rows overlap the previous call's rows (one buffer used
   // for every call) or whose audio buffer is the one the previous overlapped call may still be writing runs as if the flag were absent.
-  // sdrfm_process_batch_pcm: will design Q's launch hold the sink's chain (sdrfm_sink_chain.h)?  Every stream's whole audio row from this launch (no routed stream,
-  // no outputs the generic kernel recomputes behind it at the start of a stream), enough quads for runs longer than their predecessor's reach, a sink whose time
-  // constant lets runs be sunk independently.  Any other call is followed by the sink's own kernel.
-  SdrfmSinkChain chain;
-  const uint32_t q_quads = ((M + 7u) / 8u + 3u) / 4u;
-  // (a batch with routed streams: where both designs go out in ONE launch — fuse, below — its design-Q workgroups hold the chain for the clean streams and the sink's
-  // list kernel follows on the same queue for the routed ones)
-  const bool fuse_early = mixed && h->mix_lds && fast_ok && h->fast_mix && M >= c.audio_taps && h->fold_state_ok;
-  bool with_chain = q_ok && h->pcm_sink && (!mixed || fuse_early) && !(h->n_seen + 1 < c.fir_taps) && q_quads >= 13u &&
-                   sdrfm_q_has_pcm_chain(h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim) && sdrfm_sink_chain_params(h->pcm_sink, h->device, ns_all, &chain) == 2;
-  if (with_chain && !h->d_runstate) {                              // per-run hand-off words: SDRFM_CHAIN_SETS sets of one word per workgroup of the largest grid
-    h->runstate_cap = h->q_waves_per_cu * h->n_cu;
-    if (hipMalloc(&h->d_runstate, sizeof(unsigned long long) * SDRFM_CHAIN_SETS * h->runstate_cap) != hipSuccess ||
-        // (zeroed BEFORE any launch can see it: hipMemset alone may return before the device has done it, and the internal streams do not wait for the null stream —
-        // a memset landing in the middle of the first launch wiped the runs' published words and their successors waited for ever)
-        hipMemsetAsync(h->d_runstate, 0, sizeof(unsigned long long) * SDRFM_CHAIN_SETS * h->runstate_cap, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess) {
-      (void)hipGetLastError();
-      if (h->d_runstate) (void)hipFree(h->d_runstate);
-      h->d_runstate = nullptr; with_chain = false;
-    }
-  }
-  const bool ovl = q_ok && (call_flags & SDRFM_F_OVERLAP) && h->prev_iq && h->n_seen + 1 >= c.fir_taps &&
-                   h->prev_nbytes >= 2u * c.fir_decim * SDRFM_Q_STEP_OUT && (h->prev_nbytes % 16 == 0) && ((uintptr_t)h->prev_iq % 16 == 0) &&
-                   (h->prev_stride % 16 == 0) &&
-                   !rows_overlap(h->prev_iq, h->prev_stride, h->prev_nbytes, d_iq, iq_stride, nbytes, c.n_streams) &&
+  const bool ovl = q_ok && (call_flags & SDRFM_F_OVERLAP) && h->prev_iq &&
+                   fm_ovl_geometry_ok(g, cl, h->prev_nbytes, ((uintptr_t)h->prev_iq % 16 == 0) && (h->prev_stride % 16 == 0)) &&
+                   !fm_rows_overlap(h->prev_iq, h->prev_stride, h->prev_nbytes, d_iq, iq_stride, nbytes, c.n_streams) &&
                    // (a call that writes no audio — no buffer given, the chain inside the launch — has no audio rows to collide)
                    !(!(with_chain && h->pcm_no_audio) && h->prev_ovl_audio &&
-                     rows_overlap(reinterpret_cast<const uint8_t*>(h->prev_ovl_audio), h->prev_ovl_audio_stride * sizeof(float),
-                                  h->prev_ovl_audio_n * sizeof(float), reinterpret_cast<const uint8_t*>(d_audio),
-                                  audio_stride * sizeof(float), (size_t)A * sizeof(float), c.n_streams)) &&
-                   !(with_chain && h->prev_ovl_pcm && rows_overlap(reinterpret_cast<const uint8_t*>(h->prev_ovl_pcm), h->prev_ovl_pcm_stride * sizeof(int16_t),
-                                                                   h->prev_ovl_audio_n * 2 * sizeof(int16_t), reinterpret_cast<const uint8_t*>(h->pcm_out),
-                                                                   h->pcm_out_stride * sizeof(int16_t), (size_t)A * 2 * sizeof(int16_t), c.n_streams));
+                     fm_rows_overlap(reinterpret_cast<const uint8_t*>(h->prev_ovl_audio), h->prev_ovl_audio_stride * sizeof(float),
+                                     h->prev_ovl_audio_n * sizeof(float), reinterpret_cast<const uint8_t*>(d_audio),
+                                     audio_stride * sizeof(float), (size_t)A * sizeof(float), c.n_streams)) &&
+                   !(with_chain && h->prev_ovl_pcm && fm_rows_overlap(reinterpret_cast<const uint8_t*>(h->prev_ovl_pcm), h->prev_ovl_pcm_stride * sizeof(int16_t),
+                                                                      h->prev_ovl_audio_n * 2 * sizeof(int16_t), reinterpret_cast<const uint8_t*>(h->pcm_out),
+                                                                      h->pcm_out_stride * sizeof(int16_t), (size_t)A * 2 * sizeof(int16_t), c.n_streams));
   if (!ovl) { const int jrc = join_overlap(h); if (jrc != SDRFM_OK) return jrc; }
   if (bx_all) {
     // A bit-exact kernel takes over from design Q: the y[-1] it is handed must be the definition's (design Q's own is within 1e-4 of it,
@@ -1764,24 +1810,10 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     h->yprev_exact = true; h->hist_q_valid = false;
     h->prev_ovl_audio = nullptr;
   }
-  p.slist = nullptr;
   const uint32_t* list_dev = (h->rt_noisy && n_noisy) ? h->rt_list_dev[h->rt_list_cur] : nullptr;   // [clean streams][noisy streams]
-  char q_name[sizeof(h->kernel_name)] = "";
-  bool halo_bytes = q_ok;                                        // a kernel that reads its halo as bytes served (some of) the call
   bool behind_in = false;                                        // overlapped call: the handle's stream holds work the launches have to be ordered behind
   if (ovl || mixed) {
-    if (!h->ovl_done[1]) {                                      // (created piece by piece: a failure half-way leaves nothing half-used)
-      if (!h->ovl_in) HIP_TRY(hipEventCreateWithFlags(&h->ovl_in, hipEventDisableTiming), SDRFM_ENOMEM);
-      // Two streams only overlap when they sit on different hardware queues, and the runtime hands streams of one priority a small
-      // shared pool of queues (two streams created back to back were seen on the same one: the calls then ran one after the other).
-      // Queues are pooled per priority, so the two internal streams take the two priorities ordinary streams do not use.
-      int pr_least = 0, pr_greatest = 0;
-      HIP_TRY(hipDeviceGetStreamPriorityRange(&pr_least, &pr_greatest), SDRFM_FAIL);
-      for (int i = 0; i < 2; ++i) {
-        if (!h->ovl_stream[i]) HIP_TRY(hipStreamCreateWithPriority(&h->ovl_stream[i], hipStreamNonBlocking, i == 0 ? pr_greatest : pr_least), SDRFM_ENOMEM);
-        if (!h->ovl_done[i]) HIP_TRY(hipEventCreateWithFlags(&h->ovl_done[i], hipEventDisableTiming), SDRFM_ENOMEM);
-      }
-    }
+    { const int src = ensure_overlap_streams(h); if (src != SDRFM_OK) return src; }
     // behind whatever the handle's stream still holds (it may produce iq); an idle stream — the steady state of a caller whose
     // buffers are filled elsewhere — costs one query instead of two packets
     if (ovl && hipStreamQuery(h->stream) != hipSuccess) {
@@ -1794,138 +1826,39 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
   hipStream_t qs = h->stream;
   uint32_t k = 2;                                                 // its slot: internal stream 0 / 1, or 2 = the handle's stream
   if (ovl) { k = h->ovl_next; h->ovl_next ^= 1u; qs = h->ovl_stream[k]; if (behind_in) HIP_TRY(hipStreamWaitEvent(qs, h->ovl_in, 0), SDRFM_FAIL); }
+
+  // ---- the bit-exact launch: every stream (on the handle's stream), or the noisy streams of a mixed call — inside design Q's launch where k_mix has an
+  // instance (fuse: only its parameters are prepared here), else a launch of their own ahead of design Q's on the call's stream
+  const FmSplit split = fm_split(g, cl, mixed, fuse, n_noisy);   // the machine's wave slots between the two kinds of workgroup
   const char* bx_name = nullptr;
-  // Mixed calls share the machine between the two launches: a stream costs the bit-exact kernels about twice what it costs design Q, so design Q's
-  // grid is cut for its share of the CUs' wave slots (fewer runs per stream) and design B's for the LDS that leaves (its launch goes out first: its
-  // waves are the longer ones).
-  // Where the shape has a one-launch kernel (k_mix) both kinds of workgroup go out in ONE grid that fills the machine once: the wave slots are dealt out by
-  // the same shares, a design-B segment is about as long as a design-Q run, and neither launch waits for the other.
-  const bool fuse = fuse_early;
-  uint32_t q_total = h->q_waves_per_cu * h->n_cu, bx_waves = h->waves_target;   // design Q's workgroups, the bit-exact kernels' waves
-  if (mixed) {
-    const double cost = fuse ? h->mix_cost : 2.0;
-    const double share = (cost * n_noisy) / ((double)n_clean + cost * n_noisy);
-    if (fuse) {
-      const uint32_t total = h->mix_waves_per_cu * h->n_cu;
-      bx_waves = (uint32_t)((double)total * share + 0.5);
-      if (bx_waves < n_noisy) bx_waves = n_noisy;
-      // The whole grid is resident at once, so the launch lasts as long as its LONGEST wave, and both kinds of wave come in whole units: a design-B segment walks
-      // ceil(NA Da / 256) sub-tiles (a partly filled one costs a whole one), a design-Q run ceil((quads + runs) / runs) quads.  Around the share above, the number of
-      // segments per routed stream is therefore chosen for the smaller of the two maxima — a sub-tile of design B weighs 12.7 quads of design Q in a wave's time at
-      // this shape (64 taps, / 10: calibrated at 25 % routed streams, where 16 segments of six sub-tiles beside runs of 76 quads balance) —, ties for the fuller
-      // sub-tiles: 28.4 -> 27.1 us per call with a quarter of the streams routed (profiles/r06_mixed_split.txt).  Other shapes keep the share as it is.
-      if (c.fir_taps == 64 && c.fir_decim == 10 && h->mix_R == 4 && A >= 64 && !h->mix_split_off) {
-        const uint32_t nyt = 64u * h->mix_R, qt = ((M + 7u) / 8u + 3u) / 4u, s0 = bx_waves / n_noisy;
-        double best_cost = 1e30, best_eff = 0.0;
-        uint32_t best_s = 0;
-        for (uint32_t sg = s0 > 6u ? s0 - 6u : 1u; sg <= s0 + 4u; ++sg) {
-          const uint32_t na = (A + sg - 1u) / sg, tiles = (A + na - 1u) / na;
-          if ((uint64_t)tiles * n_noisy + n_clean > total) break;
-          const uint32_t sub = (na * c.audio_decim + nyt - 1u) / nyt;
-          uint32_t rr = (total - tiles * n_noisy) / n_clean;
-          if (rr > q_steps / 2u) rr = q_steps / 2u;
-          if (rr < 1u) continue;
-          const uint32_t quads = (qt + rr + rr - 1u) / rr;
-          const double cost = (double)sub * h->mix_rho > (double)quads ? (double)sub * h->mix_rho : (double)quads;
-          const double eff = (double)(na * c.audio_decim) / (double)(sub * nyt);
-          if (cost < best_cost - 1e-9 || (cost < best_cost + 1e-9 && eff > best_eff)) { best_cost = cost; best_eff = eff; best_s = tiles; }
-        }
-        if (best_s) bx_waves = best_s * n_noisy;
-      }
-      q_total = total > bx_waves + n_clean ? total - bx_waves : n_clean;
-    } else {
-      uint32_t q_slots = (uint32_t)((double)h->q_waves_per_cu * (1.0 - share) + 0.5);
-      if (q_slots + 1 > h->q_waves_per_cu) q_slots = h->q_waves_per_cu - 1;
-      if (q_slots < 2) q_slots = 2;
-      const size_t q_lds = sdrfm_q_lds_bytes(h->q_nslot, c.fir_decim, c.audio_decim);
-      const size_t left = 163840u > q_slots * q_lds ? 163840u - q_slots * q_lds : 0u;
-      const size_t b_lds = h->fast_mix ? h->fast_mix_lds : h->fast_lds;
-      uint32_t per_cu = b_lds ? (uint32_t)(left / b_lds) : 1u;
-      if (per_cu < 1) per_cu = 1;
-      bx_waves = h->n_cu * per_cu;
-      q_total = q_slots * h->n_cu;
-    }
+  bool halo_bytes = q_ok;                                        // a kernel that reads its halo as bytes served (some of) the call
+  CallParams pb = p;                                             // the bit-exact kernels' part of the call
+  uint32_t pb_blocks = 0;                                        // fuse: its workgroups in the one launch
+  if (mixed) { pb.slist = list_dev + n_clean; pb.n_streams = n_noisy; }
+  if (fuse) {
+    // inside design Q's launch (below); an overlapped call reads what lies before the call from the previous call's buffer, as design Q does:
+    // no state of the previous call — which may still be running on the other internal stream — is read
+    const FmTiles t = fm_b_tiles(g, cl, n_noisy, split.bx_waves, true);
+    pb.NA = t.NA; pb.tiles_per_stream = t.tiles_per_stream; pb.fold_state = t.fold_state; pb_blocks = t.grid;
+    if (ovl) { pb.iq_prev = h->prev_iq; pb.iq_prev_stride = h->prev_stride; pb.N_prev = h->prev_nbytes / 2; }
+    bx_name = h->fast_name;
+  } else if (mixed) {
+    // The noisy streams' launch goes ahead of design Q's on the call's own stream: no third stream (streams of one priority share a small pool of
+    // hardware queues — one was seen on the queue of the handle's stream, and every dependence across queues costs ~10 us of a queue's time), no
+    // fork and join.  Overlapped calls run it beside the OTHER internal stream's call; it takes the state the previous such launch left, which sits
+    // on that other stream then: behind its completion event (launched a whole call earlier: a wait that is over when it is reached).
+    const hipEvent_t bdone = h->rt_bx_evt[h->rt_bx_slot]; h->rt_bx_slot ^= 1u;   // the launch's own completion event (a stop event: no marker packet)
+    if (h->rt_bx_last && h->rt_bx_last != qs) HIP_TRY(hipStreamWaitEvent(qs, h->rt_bx_evt[h->rt_bx_slot], 0), SDRFM_FAIL);   // (the slot just left: the previous launch's event)
+    h->rt_bx_last = qs;
+    bx_name = launch_bx(h, cl, pb, split.bx_waves, true, qs, bdone, &halo_bytes);
+  } else if (bx_all) {
+    bx_name = launch_bx(h, cl, pb, split.bx_waves, false, h->stream, nullptr, &halo_bytes);
   }
-  CallParams pb;                                                  // fuse: design B's part of the one launch
-  uint32_t pb_blocks = 0, pb_R = 0;
-  // (the bit-exact launch as a closure)
-  auto launch_bx = [&]() -> int {
-    // ---- the bit-exact kernels: every stream (on the handle's stream), or the noisy streams of a mixed call: inside design Q's launch where k_mix has an
-    // instance (fuse: only the parameters are prepared here), else a launch of their own ahead of design Q's on the call's stream
-    const uint32_t nsub = bx_all ? ns_all : n_noisy;
-    hipStream_t bs = h->stream;
-    hipEvent_t bdone = nullptr;                                   // mixed: the launch's own completion event (a stop event: no marker packet)
-    if (mixed && !fuse) {
-      // The noisy streams' launch goes ahead of design Q's on the call's own stream: no third stream (streams of one priority share a small pool of
-      // hardware queues — one was seen on the queue of the handle's stream, and every dependence across queues costs ~10 us of a queue's time), no
-      // fork and join.  Overlapped calls run it beside the OTHER internal stream's call; it takes the state the previous such launch left, which sits
-      // on that other stream then: behind its completion event (launched a whole call earlier: a wait that is over when it is reached).
-      bs = qs;
-      bdone = h->rt_bx_evt[h->rt_bx_slot]; h->rt_bx_slot ^= 1u;
-      if (h->rt_bx_last && h->rt_bx_last != bs) HIP_TRY(hipStreamWaitEvent(bs, h->rt_bx_evt[h->rt_bx_slot], 0), SDRFM_FAIL);   // (the slot just left: the previous launch's event)
-      h->rt_bx_last = bs;
-    }
-    if (mixed) p.slist = list_dev + n_clean;
-    p.n_streams = nsub;
-    const bool stream_ok = fast_ok && h->fast_s && h->phase_x == 0 && h->phase_d == 0 && (N % h->fast_s->seg) == 0 &&
-                           (M % c.audio_decim) == 0 && M >= c.audio_taps && ((uintptr_t)d_iq % 16 == 0) && (iq_stride % 16 == 0) &&
-                           h->fold_state_ok &&
-                           // a lane-segment wave is long (its 64 lanes walk 480 samples each, ~25 us alone on a SIMD): design S pays when
-                           // the launch fills the machine (>= one wave per SIMD); a single dongle's call is served faster by design B,
-                           // which cuts its segments as short as the call needs
-                           (uint64_t)nsub * ((N / h->fast_s->seg + 62) / 63) >= 4ull * h->n_cu &&
-                           !mixed;   // (beside design Q's launch: design B's small tile — a wave of design S needs 16 KB of LDS and lasts 25 us)
-    const char* bname = h->generic_name;
-    if (stream_ok) {
-      const uint32_t segs = N / h->fast_s->seg;
-      p.tiles_per_stream = (segs + 62) / 63;                      // waves per stream: 63 useful lane segments each
-      p.fold_state = 1;
-      hipExtLaunchKernelGGL(h->fast_s->kernel[0], dim3(nsub * p.tiles_per_stream), dim3(64), h->fast_s->xbytes, bs, nullptr, bdone, 0, p);
-      bname = h->fast_s_name; halo_bytes = true;
-    } else if (fast_ok) {
-      // split every stream into segments so that ~waves_target waves are resident; each segment >= min_subtiles sub-tiles
-      const FastVariant* fv = (mixed && h->fast_mix) ? h->fast_mix : h->fast;
-      const size_t flds = (mixed && h->fast_mix) ? h->fast_mix_lds : h->fast_lds;
-      const uint32_t NYT = 64 * (fuse ? h->mix_R : fv->R);
-      const uint32_t sub_total = (M + NYT - 1) / NYT;
-      uint32_t segs = bx_waves / nsub;
-      // a segment pays a fixed prologue, so it normally covers >= min_subtiles sub-tiles; when that would leave most of the
-      // GPU without a wave (few streams: the reference's one dongle), shorter segments win: one stream x 1 s runs in 9.6 us
-      // with single-sub-tile segments against 18.8 us with four
-      uint32_t ms = h->min_subtiles;
-      while (ms > 1 && (uint64_t)nsub * (sub_total / ms) < bx_waves / 2) ms >>= 1;
-      const uint32_t seg_cap = sub_total / ms;
-      if (segs > seg_cap) segs = seg_cap;
-      if (segs < 1) segs = 1;
-      p.NA = (A + segs - 1) / segs;
-      p.tiles_per_stream = (A + p.NA - 1) / p.NA;
-      uint32_t grid = nsub * p.tiles_per_stream + nsub;
-      // design B: state hand-over folded into the last segment's wave (needs M >= Ta so that the d ring alone holds the
-      // new history, and the last sub-tile must contain y[M-1], which the kernel arranges)
-      p.fold_state = (fv->kind == 'b' && M >= c.audio_taps && h->fold_state_ok) ? 1u : 0u;
-      if (p.fold_state) grid -= nsub;
-      if (fuse) {
-        // inside design Q's launch (below); an overlapped call reads what lies before the call from the previous call's buffer, as design Q does:
-        // no state of the previous call — which may still be running on the other internal stream — is read
-        if (ovl) { p.iq_prev = h->prev_iq; p.iq_prev_stride = h->prev_stride; p.N_prev = h->prev_nbytes / 2; }
-        pb = p; pb_blocks = grid; pb_R = h->mix_R;
-        p.iq_prev = nullptr; p.iq_prev_stride = 0; p.N_prev = 0;
-      } else {
-        hipExtLaunchKernelGGL(fv->kernel[fv == h->fast ? h->fast_mode : 0], dim3(grid), dim3(64), flds, bs, nullptr, bdone, 0, p);
-      }
-      bname = h->fast_name; halo_bytes = halo_bytes || fv->kind == 'b';
-    } else {
-      p.NA = h->NA;
-      p.tiles_per_stream = (A + h->NA - 1) / h->NA;
-      const uint32_t grid = nsub * p.tiles_per_stream + nsub;
-      hipExtLaunchKernelGGL(k_generic, dim3(grid), dim3(256), h->lds_bytes, bs, nullptr, bdone, 0, p);
-    }
-    bx_name = bname;
-    p.slist = nullptr; p.n_streams = ns_all;
-    return SDRFM_OK;
-  };
-  if (bx_all || mixed) { const int brc = launch_bx(); if (brc != SDRFM_OK) return brc; }
+
+  // ---- the design-Q launch ---------------------------------------------------------------------------------------------------------------------
+  char q_name[sizeof(h->kernel_name)] = "";
   if (q_ok) {
+    const uint32_t q_steps = fm_q_steps(M);
     SdrfmQParams q;
     q.iq_prev = nullptr; q.iq_prev_stride = 0; q.N_prev = 0;
     if (ovl) { q.iq_prev = h->prev_iq; q.iq_prev_stride = h->prev_stride; q.N_prev = h->prev_nbytes / 2; }
@@ -1942,16 +1875,8 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
                                2 * (size_t)(c.fir_taps - 1), c.n_streams, hipMemcpyDeviceToDevice, h->stream), SDRFM_FAIL);
     q.hpad = h->d_hpad; q.hist_q_in = h->d_hist_q[h->cur]; q.hist_q_out = h->d_hist_q[h->cur ^ 1];
     q.guard_r = h->q_guard_r; q.guard_a = h->q_guard_a; q.yprev_exact = h->yprev_exact ? 1u : 0u; q.n_repaired = h->d_qstat;
-    // runs (waves) per stream: fill the machine once; every run at least four owned steps (a run warms up over a quarter of a step), two
-    // when the call is too small to fill the machine otherwise
-    uint32_t runs = q_total / n_clean;
-    const uint32_t min_steps = ((uint64_t)n_clean * (q_steps / 4) >= (uint64_t)q_total / 2) ? 4u : 2u;
-    if (runs > q_steps / min_steps) runs = q_steps / min_steps;
-    // (the sink's chain inside the launch: every run must own more outputs than its predecessor's state reaches — 13 quads: 12 owned = 76 audio outputs >=
-    // SDRFM_CHAIN_FIX —: a small call is cut into fewer runs for it)
-    if (with_chain && runs > q_quads / 13u) runs = q_quads / 13u;
-    if (runs < 1) runs = 1;
-    q.runs = runs;
+    const FmRuns r = fm_q_runs(cl, split.q_total, n_clean, with_chain, h->runstate_cap);
+    q.runs = r.runs;
     // the window of per-stream repair statistics this call adds to (none while the set's previous read-back is still under way), and
     // whether its kernel's completion carries one of the window's events (the window's last two calls: both internal streams are covered)
     hipEvent_t done = nullptr;
@@ -1970,77 +1895,51 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     // 100-call burst, +3 % per call; un-profiled within the noise): profiles/r05_q_experiments.txt item 15.
     const bool carry = ovl && h->ovl_join_style;
     if (carry) { done = h->ovl_done[k]; if (h->rt_win_used[k]) h->rt_win_need[k] = false; }
-    if (with_chain && (uint64_t)n_clean * runs > h->runstate_cap) with_chain = false;
-    if (fuse && pb_blocks && with_chain) {
-      // one launch of both designs with the chain in design Q's workgroups, then the sink's list kernel for the routed streams on the same queue (their audio is the
-      // launch's design-B workgroups'); the call's completion event rides on that last kernel
+    with_chain = r.with_chain;
+    if (with_chain) {                                             // the sink's chain rides in design Q's workgroups
       chain.pcm = h->pcm_out; chain.pcm_stride = h->pcm_out_stride;
       if (h->pcm_no_audio) q.audio = nullptr;                      // (the clean streams store no audio; the routed ones' goes to the library's own rows)
       chain.run_call = h->chain_calls++;
       chain.runstate = h->d_runstate + (size_t)(chain.run_call % SDRFM_CHAIN_SETS) * h->runstate_cap;
-      HIP_TRY(sdrfm_q_launch_mix_pcm(q, chain, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, pb, pb_blocks, pb_R, qs, nullptr), SDRFM_FAIL);
-      { const int lrc = sdrfm_sink_launch_list_on(h->pcm_sink, chain, list_dev + n_clean, n_noisy, d_audio, audio_stride, A, h->pcm_out, h->pcm_out_stride, qs, done);
-        if (lrc != SDRFM_OK) return lrc; }
-      sdrfm_sink_chain_issued(h->pcm_sink);
-      h->pcm_fused = true;
     }
-    else if (fuse && pb_blocks) HIP_TRY(sdrfm_q_launch_mix(q, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, pb, pb_blocks, pb_R, qs, done), SDRFM_FAIL);
-    else if (with_chain) {
-      chain.pcm = h->pcm_out; chain.pcm_stride = h->pcm_out_stride;
-      if (h->pcm_no_audio) q.audio = nullptr;
-      chain.run_call = h->chain_calls++;
-      chain.runstate = h->d_runstate + (size_t)(chain.run_call % SDRFM_CHAIN_SETS) * h->runstate_cap;
-      HIP_TRY(sdrfm_q_launch_pcm(q, chain, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, qs, done), SDRFM_FAIL);
-      sdrfm_sink_chain_issued(h->pcm_sink);
-      h->pcm_fused = true;
+    if (fuse && with_chain) {
+      // one launch of both designs with the chain in design Q's workgroups, then the sink's list kernel for the routed streams on the same queue (their audio is the
+      // launch's design-B workgroups'); the call's completion event rides on that last kernel
+      HIP_TRY(sdrfm_q_launch_mix_pcm(q, chain, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, pb, pb_blocks, g.mix_R, qs, nullptr), SDRFM_FAIL);
+      const int lrc = sdrfm_sink_launch_list_on(h->pcm_sink, chain, list_dev + n_clean, n_noisy, d_audio, audio_stride, A, h->pcm_out, h->pcm_out_stride, qs, done);
+      if (lrc != SDRFM_OK) return lrc;
     }
+    else if (fuse) HIP_TRY(sdrfm_q_launch_mix(q, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, pb, pb_blocks, g.mix_R, qs, done), SDRFM_FAIL);
+    else if (with_chain) HIP_TRY(sdrfm_q_launch_pcm(q, chain, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, qs, done), SDRFM_FAIL);
     else HIP_TRY(sdrfm_q_launch(q, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, qs, done), SDRFM_FAIL);
+    if (with_chain) { sdrfm_sink_chain_issued(h->pcm_sink); h->pcm_fused = true; }
     if (ovl) { h->ovl_pending[k] = true; h->ovl_bound[k] = carry; }
     h->prev_ovl_audio = (ovl && !(with_chain && h->pcm_no_audio)) ? d_audio : nullptr; h->prev_ovl_audio_stride = audio_stride; h->prev_ovl_audio_n = A;
     h->prev_ovl_pcm = (ovl && with_chain) ? h->pcm_out : nullptr; h->prev_ovl_pcm_stride = h->pcm_out_stride;
     h->yprev_exact = false; h->hist_q_valid = true;
+    // ---- the window close ----------------------------------------------------------------------------------------------------------------------
     if (h->rt_noisy && !h->rt_off) {
-      h->rt_win_stages += (uint64_t)runs * ((q_steps / runs + c.audio_decim - 1) / c.audio_decim);   // audio stages of ONE stream's waves in this call
-      if (++h->rt_win_calls >= SDRFM_Q_ADAPT_WINDOW) {
-        // the window closes: read its statistics back behind its last kernels, on the side stream (nothing here waits, no packet enters a compute queue
-        // unless a stream holds kernels of the window that none of the attached events covers — call patterns other than "all on one stream" or "two in turn")
-        hipStream_t wst[3] = {h->ovl_stream[0], h->ovl_stream[1], h->stream};
-        const uint32_t i = h->rt_set;
-        for (int kk = 0; kk < 3; ++kk) {
-          if (!h->rt_win_used[kk]) continue;
-          if (h->rt_win_need[kk]) HIP_TRY(hipEventRecord(h->rt_win_evt[i][kk], wst[kk]), SDRFM_FAIL);
-          // (an internal stream's latest kernel carries ovl_done[kk] — see above —: at or behind the window's last kernel on that stream)
-          HIP_TRY(hipStreamWaitEvent(h->rt_mon, (kk < 2 && h->ovl_bound[kk]) ? h->ovl_done[kk] : h->rt_win_evt[i][kk], 0), SDRFM_FAIL);
-          h->rt_win_used[kk] = false; h->rt_win_need[kk] = false;
-        }
-        // (one small kernel instead of a copy and a memset: 12 us of host time instead of 40 — a window that closes while the host is only a call ahead
-        // of the device, as in a 20-call burst from rest, otherwise leaves the queues dry for the difference)
-        hipLaunchKernelGGL(k_route_collect, dim3((ns_all + 255) / 256), dim3(256), 0, h->rt_mon, h->rt_pass_dev[i], h->rt_pass_host_dev[i], ns_all);
-        HIP_TRY(hipEventRecord(h->rt_rb_done[i], h->rt_mon), SDRFM_FAIL);
-        h->rt_rb_pending[i] = true; h->rt_rb_stages[i] = h->rt_win_stages;
-        h->rt_set = (h->rt_set + 1u) % SDRFM_Q_ADAPT_SETS; h->rt_win_calls = 0; h->rt_win_stages = 0;
-      }
+      h->rt_win_stages += fm_win_stages(r.runs, q_steps, c.audio_decim);
+      if (++h->rt_win_calls >= SDRFM_Q_ADAPT_WINDOW) { const int wrc = route_window_close(h); if (wrc != SDRFM_OK) return wrc; }
     }
     snprintf(q_name, sizeof(q_name), "%s%s%s", h->fast_q_name, ovl ? " overlapped" : "", h->pcm_fused ? " + pcm" : "");
   }
   if (mixed) {
     const char* sp = strchr(bx_name, ' ');                         // ("fast-b", "fast-s", "generic": the name's first word)
     snprintf(h->kernel_name, sizeof(h->kernel_name), "%s + %.*s (%u streams)%s", q_name, (int)(sp ? sp - bx_name : (long)strlen(bx_name)), bx_name, n_noisy,
-             pb_blocks ? " in one launch" : "");
+             fuse ? " in one launch" : "");
   } else {
     snprintf(h->kernel_name, sizeof(h->kernel_name), "%s", bx_all ? bx_name : q_name);
   }
+  // ---- the first-call fix-up -------------------------------------------------------------------------------------------------------------------
   if (halo_bytes && h->n_seen + 1 < c.fir_taps) {
     // Designs Q, B and S read their halo as bytes, which cannot express the zero history at the start of a stream: the few audio
     // outputs that depend on inputs before the first real sample are recomputed by the generic kernel (tile 0..k only), for every stream
     // (a call this early is never overlapped, so the handle's stream is behind every launch above).
-    const uint32_t a_aff = (y_aff + c.audio_taps + c.audio_decim - 1) / c.audio_decim;  // audio outputs touching them
-    CallParams q = p;
-    q.NA = h->NA;
-    q.tiles_per_stream = (a_aff + h->NA - 1) / h->NA;
-    const uint32_t full = (A + h->NA - 1) / h->NA;
-    if (q.tiles_per_stream > full) q.tiles_per_stream = full;
-    hipLaunchKernelGGL(k_generic, dim3(c.n_streams * q.tiles_per_stream), dim3(256), h->lds_bytes, h->stream, q);
+    CallParams fx = p;
+    fx.NA = g.NA;
+    fx.tiles_per_stream = fm_fixup(g, cl).tiles_per_stream;
+    hipLaunchKernelGGL(k_generic, dim3(c.n_streams * fx.tiles_per_stream), dim3(256), h->lds_bytes, h->stream, fx);
   }
   HIP_TRY(hipGetLastError(), SDRFM_FAIL);
 
@@ -2048,8 +1947,21 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
   h->n_seen += N;
   if (call_flags & SDRFM_F_DEVICE_PTRS) { h->prev_iq = d_iq; h->prev_stride = iq_stride; h->prev_nbytes = nbytes; }
   else h->prev_iq = nullptr;
-  h->phase_x = (uint32_t)(((uint64_t)h->phase_x + N) % c.fir_decim);
-  h->phase_d = (uint32_t)(((uint64_t)h->phase_d + M) % c.audio_decim);
+  h->phase_x = n.phase_x;
+  h->phase_d = n.phase_d;
+  return SDRFM_OK;
+}
+
+// ---- host buffers: stage -> the call on the staging buffers -> copy back (sdrfm_process_batch, sdrfm_process_batch_pcm) --------------------------
+static int stage_iq(sdrfm* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes) {
+  const uint32_t ns = h->cfg.n_streams;
+  HIP_TRY(hipMemcpy2DAsync(h->d_iq, h->d_iq_stride, iq, ns > 1 ? iq_stride : nbytes, nbytes, ns, hipMemcpyHostToDevice, h->stream), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+static int fetch_audio(sdrfm* h, float* audio, size_t audio_stride, uint32_t A) {
+  const uint32_t ns = h->cfg.n_streams;
+  HIP_TRY(hipMemcpy2DAsync(audio, (ns > 1 ? audio_stride : A) * sizeof(float), h->d_audio, h->d_audio_stride * sizeof(float), A * sizeof(float), ns,
+                           hipMemcpyDeviceToHost, h->stream), SDRFM_FAIL);
   return SDRFM_OK;
 }
 
@@ -2086,14 +1998,11 @@ int sdrfm_process_batch(sdrfm_t* h, const uint8_t* iq, size_t iq_stride, uint32_
   }
   int rc = ensure_staging(h);
   if (rc != SDRFM_OK) return rc;
-  HIP_TRY(hipMemcpy2DAsync(h->d_iq, h->d_iq_stride, iq, ns > 1 ? iq_stride : nbytes, nbytes, ns, hipMemcpyHostToDevice,
-                           h->stream), SDRFM_FAIL);
+  rc = stage_iq(h, iq, iq_stride, nbytes);
+  if (rc != SDRFM_OK) return rc;
   rc = enqueue(h, h->d_iq, h->d_iq_stride, nbytes, h->d_audio, h->d_audio_stride, n_audio);
   if (rc != SDRFM_OK) return rc;
-  if (A)
-    HIP_TRY(hipMemcpy2DAsync(audio, (ns > 1 ? audio_stride : A) * sizeof(float), h->d_audio,
-                             h->d_audio_stride * sizeof(float), A * sizeof(float), ns, hipMemcpyDeviceToHost, h->stream),
-            SDRFM_FAIL);
+  if (A) { rc = fetch_audio(h, audio, audio_stride, A); if (rc != SDRFM_OK) return rc; }
   HIP_TRY(hipStreamSynchronize(h->stream), SDRFM_FAIL);
   return SDRFM_OK;
 }
@@ -2125,7 +2034,8 @@ int sdrfm_process_batch_pcm(sdrfm_t* h, sdrfm_pcm_sink_t* sink, const uint8_t* i
     if (rc != SDRFM_OK) return rc;
     const size_t pstride = 2 * h->d_audio_stride;
     if (!h->d_pcm_stage) HIP_TRY(hipMalloc(&h->d_pcm_stage, sizeof(int16_t) * pstride * ns), SDRFM_ENOMEM);
-    HIP_TRY(hipMemcpy2DAsync(h->d_iq, h->d_iq_stride, iq, ns > 1 ? iq_stride : nbytes, nbytes, ns, hipMemcpyHostToDevice, h->stream), SDRFM_FAIL);
+    rc = stage_iq(h, iq, iq_stride, nbytes);
+    if (rc != SDRFM_OK) return rc;
     rc = sdrfm_process_batch_pcm(h, sink, h->d_iq, h->d_iq_stride, nbytes, audio ? h->d_audio : nullptr, h->d_audio_stride, h->d_pcm_stage, pstride, n_audio,
                                  SDRFM_F_DEVICE_PTRS);
     if (rc != SDRFM_OK) return rc;
@@ -2133,9 +2043,7 @@ int sdrfm_process_batch_pcm(sdrfm_t* h, sdrfm_pcm_sink_t* sink, const uint8_t* i
     if (*n_audio) {
       HIP_TRY(hipMemcpy2DAsync(pcm, (ns > 1 ? pcm_stride : 2 * (size_t)*n_audio) * sizeof(int16_t), h->d_pcm_stage, pstride * sizeof(int16_t),
                                2 * (size_t)*n_audio * sizeof(int16_t), ns, hipMemcpyDeviceToHost, h->stream), SDRFM_FAIL);
-      if (audio)
-        HIP_TRY(hipMemcpy2DAsync(audio, (ns > 1 ? audio_stride : *n_audio) * sizeof(float), h->d_audio, h->d_audio_stride * sizeof(float),
-                                 *n_audio * sizeof(float), ns, hipMemcpyDeviceToHost, h->stream), SDRFM_FAIL);
+      if (audio) { rc = fetch_audio(h, audio, audio_stride, *n_audio); if (rc != SDRFM_OK) return rc; }
     }
     HIP_TRY(hipStreamSynchronize(h->stream), SDRFM_FAIL);
     return SDRFM_OK;
