@@ -568,6 +568,53 @@ int  sdrfm_pcm_sink_get_state(sdrfm_pcm_sink_t* k, float* state_out /* n_streams
 int  sdrfm_process_batch_pcm(sdrfm_t* h, sdrfm_pcm_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* audio, size_t audio_stride,
                              int16_t* pcm, size_t pcm_stride, uint32_t* n_audio, uint32_t flags);
 
+/* The STEREO sink on the device, for the L and R rows sdrfm_stereo_process_batch and sdrfm_bcast_process_batch leave:
+ * left[stream * audio_stride + i], right[stream * audio_stride + i] (f32) -> pcm[stream * pcm_stride + 2*i] = L, [... + 2*i + 1] = R (int16), each channel
+ * de-emphasised on its own with the operations of sdrfm_pcm_deemph_s16 in its order — what sdrfm_pcm_deemph_stereo_s16 does for one stream on the host.
+ * The two de-emphasis states of a stream are carried in the handle.  The contract is sdrfm_pcm_sink_*'s:
+ *   create   alpha outside (0, 1], a NaN gain, n_streams == 0 or out == NULL: SDRFM_EINVAL before any device is looked for; a missing or non-gfx950
+ *            device: SDRFM_NO_DEVICE.
+ *   process_batch   flags is a subset of SDRFM_F_DEVICE_PTRS | SDRFM_PCM_F_EXACT (else SDRFM_EINVAL); n == 0 is a no-op; left, right or pcm NULL with
+ *            n > 0: SDRFM_EINVAL; with more than one stream audio_stride < n or pcm_stride < 2*n: SDRFM_ECAPACITY; pcm_stride (int16 elements) odd:
+ *            SDRFM_EINVAL.  With SDRFM_F_DEVICE_PTRS the three buffers are device memory, pcm 4-byte aligned (else SDRFM_EINVAL), and the call only
+ *            enqueues on the sink's stream; give it the demodulator's stream (or synchronise) so that it runs after the audio exists.  With host
+ *            buffers the call stages, runs and copies back, and is synchronous.
+ *   NULL handles answer SDRFM_EINVAL (destroy: nothing).
+ * Two forms of the same recursion (csrc/sdrfm_sink_stereo.hip), both chains of a stream walked by the same lane:
+ *   default            the blocked scan of sdrfm_pcm_sink_process_batch, per channel operation for operation: the even PCM slots are bit for bit what that
+ *                      sink's default form leaves for the L rows, the odd slots what it leaves for the R rows; PCM within 1 LSB of the exact form's,
+ *                      carried states within 1e-6 relative;
+ *   SDRFM_PCM_F_EXACT  one lane per stream: BIT-IDENTICAL to sdrfm_pcm_deemph_stereo_s16, PCM and both states.
+ * Unlike sdrfm_pcm_sink_t this sink takes no part in a demodulator's launch: its state is a plain float[n_streams][2] which a call reads at its start and
+ * writes at its end, and calls are ordered by the HIP stream they are enqueued on — keep all calls on one sink on one stream, or synchronise between them.
+ * sdrfm_pcm_stereo_sink_get_state synchronises the SINK's stream and copies the states: state_out[2s] = L, state_out[2s + 1] = R. */
+typedef struct sdrfm_pcm_stereo_sink sdrfm_pcm_stereo_sink_t;
+int  sdrfm_pcm_stereo_sink_create(uint32_t n_streams, float alpha, float gain, int32_t device, sdrfm_pcm_stereo_sink_t** out);
+void sdrfm_pcm_stereo_sink_destroy(sdrfm_pcm_stereo_sink_t* k);
+int  sdrfm_pcm_stereo_sink_reset(sdrfm_pcm_stereo_sink_t* k);
+int  sdrfm_pcm_stereo_sink_process_batch(sdrfm_pcm_stereo_sink_t* k, const float* left, const float* right, size_t audio_stride, uint32_t n,
+                                         int16_t* pcm, size_t pcm_stride, uint32_t flags);
+int  sdrfm_pcm_stereo_sink_set_stream(sdrfm_pcm_stereo_sink_t* k, void* hip_stream);
+int  sdrfm_pcm_stereo_sink_synchronize(sdrfm_pcm_stereo_sink_t* k);
+int  sdrfm_pcm_stereo_sink_get_state(sdrfm_pcm_stereo_sink_t* k, float* state_out /* 2 * n_streams floats: [2s] = L, [2s+1] = R */);
+
+/* ONE call from IQ bytes to playable stereo PCM: sdrfm_stereo_process_batch (sdrfm_bcast_process_batch) exactly as it stands — the same kernel with the
+ * same arguments, so left, right, bb and pilot_count come out with the same bits — followed ON THE HANDLE'S STREAM by the stereo sink's default form over
+ * this call's L and R rows into pcm.  Not fused: a second launch on the same queue costs microseconds beside a call of hundreds.
+ * left and right may BOTH be NULL: the sink then reads the handle's own rows and the PCM is all the audio the call returns; only one of them NULL is
+ * SDRFM_EINVAL.  The sink must belong to the handle's device and have its n_streams (else SDRFM_EINVAL).  pcm is checked as by
+ * sdrfm_pcm_stereo_sink_process_batch against this call's n_audio (NULL only when that is 0); every other argument as by the handle's own call.  With
+ * SDRFM_F_DEVICE_PTRS every buffer is device memory and the call only enqueues; with host buffers the PCM is copied back beside the rest and the call is
+ * synchronous.  Every check is made before anything is enqueued: a refused call leaves the handle and the sink as they were.
+ * These calls launch the sink on the HANDLE's stream and ignore sdrfm_pcm_stereo_sink_set_stream: do not mix the two on one sink without giving both the same
+ * stream or synchronising between them, and call sdrfm_pcm_stereo_sink_get_state, _reset and _destroy only after the handle's _synchronize. */
+int  sdrfm_stereo_process_batch_pcm(sdrfm_stereo_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes,
+                                    float* left, float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride,
+                                    uint32_t* pilot_count, uint32_t* n_audio, uint32_t flags);
+int  sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes,
+                                   float* left, float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride,
+                                   float* bb, size_t bb_stride, uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,3 +125,43 @@ class BroadcastDemod:
                                                      C.c_void_p(right.data_ptr()), left.stride(0), C.c_void_p(bb.data_ptr()), bb.stride(0),
                                                      pc, C.byref(na), C.byref(nr), _l.F_DEVICE_PTRS), "sdrfm_bcast_process_batch(device)")
         return na.value, nr.value
+
+    def process_batch_pcm(self, sink, iq: np.ndarray, with_audio=True):
+        """sdrfm_bcast_process_batch_pcm on host memory: this call and, behind it, `sink` (a StereoPcmSink) over its L and R rows.
+        Returns (L, R, pcm [n_streams, 2 n_audio] int16, bb, pilot_count); with_audio=False passes no audio rows: L and R are None."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        if iq.ndim == 1:
+            iq = iq[None, :]
+        assert iq.shape[0] == self.cfg.n_streams
+        nbytes = iq.shape[1]
+        ca, cr = (max(v, 1) for v in self.counts(nbytes & ~1))
+        left = np.zeros((iq.shape[0], ca), dtype=np.float32) if with_audio else None
+        right = np.zeros_like(left) if with_audio else None
+        pcm = np.zeros((iq.shape[0], 2 * ca), dtype=np.int16)
+        bb = np.zeros((iq.shape[0], 2 * cr), dtype=np.float32)
+        pc = np.zeros(iq.shape[0], dtype=np.uint32)
+        na, nr = C.c_uint32(), C.c_uint32()
+        self._ck(self._lib.sdrfm_bcast_process_batch_pcm(self._h, sink._h, iq.ctypes.data, nbytes, nbytes, left.ctypes.data if with_audio else None,
+                                                         right.ctypes.data if with_audio else None, ca, pcm.ctypes.data, 2 * ca, bb.ctypes.data, 2 * cr,
+                                                         pc.ctypes.data, C.byref(na), C.byref(nr), 0), "sdrfm_bcast_process_batch_pcm")
+        bbc = np.ascontiguousarray(bb[:, : 2 * nr.value]).view(np.complex64)
+        if not with_audio:
+            return None, None, pcm[:, : 2 * na.value], bbc, pc
+        return left[:, : na.value], right[:, : na.value], pcm[:, : 2 * na.value], bbc, pc
+
+    def process_batch_pcm_device(self, sink, iq, left, right, pcm, bb, pilot_count=None, nbytes=None):
+        """device tensors as process_batch_device takes them, pcm int16 [n_streams, >= 2 n_audio]; left = right = None: the sink reads the
+        handle's own rows.  Enqueue only, sink included, on this handle's stream.  Returns (n_audio, n_rds)."""
+        assert iq.is_cuda and pcm.is_cuda and bb.is_cuda and pcm.stride(1) == 1 and bb.stride(1) == 1 and (left is None) == (right is None)
+        if left is not None:
+            assert left.is_cuda and right.is_cuda and left.stride() == right.stride() and left.stride(1) == 1
+        nbytes = iq.shape[1] if nbytes is None else int(nbytes)
+        pc = C.c_void_p(pilot_count.data_ptr()) if pilot_count is not None else None
+        lp = C.c_void_p(left.data_ptr()) if left is not None else None
+        rp = C.c_void_p(right.data_ptr()) if right is not None else None
+        na, nr = C.c_uint32(), C.c_uint32()
+        self._ck(self._lib.sdrfm_bcast_process_batch_pcm(self._h, sink._h, C.c_void_p(iq.data_ptr()), iq.stride(0), nbytes, lp, rp,
+                                                         left.stride(0) if left is not None else 0, C.c_void_p(pcm.data_ptr()), pcm.stride(0),
+                                                         C.c_void_p(bb.data_ptr()), bb.stride(0), pc, C.byref(na), C.byref(nr), _l.F_DEVICE_PTRS),
+                 "sdrfm_bcast_process_batch_pcm(device)")
+        return na.value, nr.value

@@ -20,6 +20,7 @@
 #include "sdrfm_carrier.h"
 #include "sdrfm_out_stages.h"
 #include "sdrfm_pilot_front.h"
+#include "sdrfm_sink_stereo.h"
 
 namespace {
 
@@ -310,6 +311,56 @@ int sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_str
   if (front_copy_back(h->f, left, audio_stride, h->d_left, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
   if (front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
   if (front_copy_back(h->f, bb, bb_stride, h->d_bb, h->d_bb_stride, 2 * (size_t)Ar) != SDRFM_OK) return SDRFM_FAIL;
+  return front_finish(h->f, pilot_count);
+}
+
+// the call above and, behind it on the handle's stream, the stereo sink's default kernel over this call's L and R rows
+int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left,
+                                  float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride,
+                                  uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
+  if (!h || !sink || !n_audio || !n_rds) return SDRFM_EINVAL;
+  if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;
+  if (!left != !right) return SDRFM_EINVAL;                    // both, or neither: the sink then reads the handle's own rows
+  if (nbytes & 1u) return SDRFM_EODD;
+  if (nbytes > h->f.max_bytes) return SDRFM_ECAPACITY;
+  const uint32_t ns = h->cfg.n_streams;
+  const bool dev = (flags & SDRFM_F_DEVICE_PTRS) != 0;
+  uint32_t Aa = 0, Ar = 0;
+  (void)sdrfm_bcast_counts(h, nbytes, &Aa, &Ar);
+  int rc = sdrfm_stereo_sink_check(sink, h->f.device, ns, Aa, pcm, pcm_stride, dev);
+  if (rc != SDRFM_OK) return rc;
+  if (nbytes == 0) {
+    *n_audio = 0;
+    *n_rds = 0;
+    return front_empty_call(h->f, pilot_count, flags);
+  }
+  if (!iq) return SDRFM_EINVAL;
+  if (ns > 1 && iq_stride < nbytes) return SDRFM_ECAPACITY;
+  if (Ar && !bb) return SDRFM_EINVAL;
+  if (ns > 1 && ((left && audio_stride < Aa) || bb_stride < 2 * (size_t)Ar)) return SDRFM_ECAPACITY;
+  if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
+  if (dev) {
+    float* const l = left ? left : h->d_left;
+    float* const r = left ? right : h->d_right;
+    const size_t as = left ? audio_stride : h->d_audio_stride;
+    rc = bcast_enqueue(h, iq, iq_stride, nbytes, l, r, as, bb, bb_stride, pilot_count, n_audio, n_rds);
+    if (rc != SDRFM_OK) return rc;
+    return sdrfm_stereo_sink_launch_on(sink, l, r, as, Aa, pcm, pcm_stride, h->f.stream);
+  }
+
+  int16_t* d_pcm = nullptr;
+  size_t d_pcm_stride = 0;
+  rc = sdrfm_stereo_sink_reserve(sink, Aa, &d_pcm, &d_pcm_stride);   // (before anything is enqueued: a refusal leaves both handles alone)
+  if (rc != SDRFM_OK) return rc;
+  if (front_stage_in(h->f, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
+  rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc, n_audio, n_rds);
+  if (rc != SDRFM_OK) return rc;
+  rc = sdrfm_stereo_sink_launch_on(sink, h->d_left, h->d_right, h->d_audio_stride, Aa, d_pcm, d_pcm_stride, h->f.stream);
+  if (rc != SDRFM_OK) return rc;
+  if (left && front_copy_back(h->f, left, audio_stride, h->d_left, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
+  if (left && front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
+  if (front_copy_back(h->f, bb, bb_stride, h->d_bb, h->d_bb_stride, 2 * (size_t)Ar) != SDRFM_OK) return SDRFM_FAIL;
+  if (sdrfm_stereo_sink_copy_back(sink, pcm, pcm_stride, Aa, h->f.stream) != SDRFM_OK) return SDRFM_FAIL;
   return front_finish(h->f, pilot_count);
 }
 

@@ -1,0 +1,388 @@
+/*
+ * sdrfm_sink_stereo.hip — the device-side STEREO audio sink behind the sdrfm_pcm_stereo_sink_* C-ABI (include/sdrfm.h): the L and R
+ * rows the stereo and the broadcast handles leave (f32, 48 kHz) -> FM de-emphasis of either channel on its own -> int16 stereo-interleaved PCM in the
+ * layout BSP_AUDIO_OUT_Play consumes, pcm[2i] = L, pcm[2i+1] = R.  Per channel the arithmetic is the host routine sdrfm_pcm_deemph_stereo_s16's
+ * (csrc/pcm_sink.c), operation for operation:
+ *
+ *   y[n]   = fmaf(alpha, x[n] - y[n-1], y[n-1])
+ *   pcm[n] = (int16) rint(clamp(y[n] * gain, -32768, 32767))      one dword per sample: L | R << 16
+ *
+ * The two forms of the mono sink (sdrfm_sink.hip), each walking TWO chains in a lane:
+ *   k_pcm_stereo_sink       SDRFM_PCM_F_EXACT: one lane per stream, 64 streams per wave, the data moved coalesced through two 64 x 65-word LDS tiles
+ *                           (L and R), the packed PCM written back into the L tile in place.  Bit-identical to the host routine, PCM and state.
+ *   k_pcm_stereo_sink_scan  the default: one workgroup of 256 lanes per stream, the lane's 19-sample chunk of L and the same chunk of R in registers,
+ *                           both chains through the three phases of k_pcm_sink_scan<false> (chunk contribution, carries, re-walk) side by side.  The
+ *                           chain is latency-bound (sub -> fma), so the second, independent chain fills slots the first leaves empty.  PER CHANNEL the
+ *                           operations and their order are k_pcm_sink_scan<false>'s — same SINK_NT, SINK_C and segment, the same six shuffle steps with
+ *                           the powers squared on the way, the same combine of the four waves' totals —, so the even PCM slots are bit for bit what the
+ *                           mono default sink leaves for the L rows and the odd slots what it leaves for the R rows (tests/test_pcm_stereo_sink_gpu.py).
+ *                           LDS: two segments + eight carry words, 38 KiB.
+ * What this sink leaves out on purpose: it takes no part in the in-launch chain protocol (sdrfm_sink_chain.h) — no tagged state slots, no waits on the
+ * device, no atomics.  The state is a plain float[n_streams][2]; a stream's workgroup (its lane, in the exact form) reads it at the start and writes
+ * it at the end, and calls on one HIP stream are ordered.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <new>
+
+#include "../../include/sdrfm.h"
+#include "sdrfm_sink_stereo.h"
+
+namespace {
+
+struct StereoSinkParams {
+  const float* left;
+  const float* right;
+  size_t audio_stride;   // floats
+  int16_t* pcm;
+  size_t pcm_stride;     // int16 elements per stream (>= 2 * n)
+  float* state;          // [n_streams][2]: y[n-1] of L, of R
+  uint32_t n_streams, n;
+  float alpha, gain;
+};
+
+// one step of the chain and its PCM word: the operations of sdrfm_pcm_deemph_s16, in its order
+__device__ __forceinline__ unsigned sink_step(float alpha, float gain, float x, float& y) {
+  y = __builtin_fmaf(alpha, x - y, y);
+  float v = y * gain;
+  if (v > 32767.0f) v = 32767.0f;
+  if (v < -32768.0f) v = -32768.0f;
+  return (unsigned)(int)__builtin_rintf(v) & 0xffffu;
+}
+
+__global__ void __launch_bounds__(64) k_pcm_stereo_sink(StereoSinkParams p) {
+  __shared__ unsigned tl[64 * 65], tr[64 * 65];                 // row stride 65 words: conflict-free by rows and by columns
+  const uint32_t lane = threadIdx.x;
+  const uint32_t s0 = blockIdx.x * 64;
+  const uint32_t rows = (p.n_streams - s0 < 64u) ? p.n_streams - s0 : 64u;
+  const uint32_t mine = s0 + lane;
+  float yl = (lane < rows) ? p.state[2 * (size_t)mine] : 0.0f, yr = (lane < rows) ? p.state[2 * (size_t)mine + 1] : 0.0f;
+  for (uint32_t t0 = 0; t0 < p.n; t0 += 64) {
+    const uint32_t cols = (p.n - t0 < 64u) ? p.n - t0 : 64u;
+    if (lane < cols)
+      for (uint32_t r = 0; r < rows; ++r) {
+        tl[r * 65 + lane] = __float_as_uint(p.left[(size_t)(s0 + r) * p.audio_stride + t0 + lane]);
+        tr[r * 65 + lane] = __float_as_uint(p.right[(size_t)(s0 + r) * p.audio_stride + t0 + lane]);
+      }
+    __syncthreads();
+    if (lane < rows) {
+      for (uint32_t i = 0; i < cols; ++i) {
+        const unsigned wl = sink_step(p.alpha, p.gain, __uint_as_float(tl[lane * 65 + i]), yl);
+        const unsigned wr = sink_step(p.alpha, p.gain, __uint_as_float(tr[lane * 65 + i]), yr);
+        tl[lane * 65 + i] = wl | (wr << 16);
+      }
+    }
+    __syncthreads();
+    if (lane < cols)
+      for (uint32_t r = 0; r < rows; ++r)
+        reinterpret_cast<unsigned*>(p.pcm + (size_t)(s0 + r) * p.pcm_stride)[t0 + lane] = tl[r * 65 + lane];
+    __syncthreads();
+  }
+  if (lane < rows) {
+    p.state[2 * (size_t)mine] = yl;
+    p.state[2 * (size_t)mine + 1] = yr;
+  }
+}
+
+// ---- the blocked scan (the default): the mono sink's geometry (sdrfm_sink.hip), which the bitwise yardstick above rests on
+constexpr uint32_t SINK_NT = 256, SINK_C = 19, SINK_SEG = SINK_NT * SINK_C;
+static_assert(SINK_NT == 256, "four waves: the carries between them are combined by hand");
+
+__global__ void __launch_bounds__(256) k_pcm_stereo_sink_scan(StereoSinkParams p, float pc) {
+  __shared__ float x[2][SINK_SEG];                              // the segment's L and R samples; x[0] then takes (in place) the packed PCM words
+  __shared__ float sc[2][4];                                    // per channel: the waves' totals; then the segment's last state
+  unsigned* const xw = reinterpret_cast<unsigned*>(x[0]);
+  const uint32_t s = blockIdx.x, t = threadIdx.x;
+  const float* const row[2] = {p.left + (size_t)s * p.audio_stride, p.right + (size_t)s * p.audio_stride};
+  unsigned* const out = reinterpret_cast<unsigned*>(p.pcm + (size_t)s * p.pcm_stride);
+  float y0[2] = {p.state[2 * (size_t)s], p.state[2 * (size_t)s + 1]};   // the states before the segment (every lane holds them)
+  for (uint32_t base = 0; base < p.n; base += SINK_SEG) {
+    const uint32_t m = (p.n - base < SINK_SEG) ? p.n - base : SINK_SEG;   // samples of this segment
+#pragma unroll
+    for (uint32_t q = 0; q < SINK_C; ++q) {                     // coalesced: 2 SINK_C independent loads per lane in flight
+      const uint32_t i = t + SINK_NT * q;
+      if (i < m) {
+        x[0][i] = row[0][base + i];
+        x[1][i] = row[1][base + i];
+      }
+    }
+    __syncthreads();
+    // the lane's chunk [i0, i0 + cnt) of either channel in registers
+    const uint32_t i0 = t * SINK_C < m ? t * SINK_C : m, cnt = (m - i0 < SINK_C) ? m - i0 : SINK_C;
+    float xr[2][SINK_C];
+#pragma unroll
+    for (uint32_t q = 0; q < SINK_C; ++q) {
+      xr[0][q] = q < cnt ? x[0][i0 + q] : 0.0f;
+      xr[1][q] = q < cnt ? x[1][i0 + q] : 0.0f;
+    }
+    // 1. the chunks' own contributions to their last samples (lane 0 starts from the real states)
+    float y[2] = {t == 0 ? y0[0] : 0.0f, t == 0 ? y0[1] : 0.0f};
+#pragma unroll
+    for (uint32_t q = 0; q < SINK_C; ++q)
+      if (q < cnt) {
+        y[0] = __builtin_fmaf(p.alpha, xr[0][q] - y[0], y[0]);
+        y[1] = __builtin_fmaf(p.alpha, xr[1][q] - y[1], y[1]);
+      }
+    // 2. s[t] = pc s[t-1] + e[t] per channel: six shuffle steps within a wave (the powers squared on the way), the four waves' totals through LDS
+    const uint32_t wl = t & 63u, wv = t >> 6;
+    float sv[2] = {y[0], y[1]}, pw = pc;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const float o = __shfl_up(sv[c], d, 64);
+        const float sn = __builtin_fmaf(pw, o, sv[c]);
+        sv[c] = wl >= d ? sn : sv[c];
+      }
+      pw *= pw;
+    }                                                           // (pw = pc^64 now)
+    if (wl == 63u) {
+      sc[0][wv] = sv[0];
+      sc[1][wv] = sv[1];
+    }
+    float pl = 1.0f, pb = pc;                                   // pc^wl
+#pragma unroll
+    for (uint32_t bit = 0; bit < 6u; ++bit) {
+      pl = ((wl >> bit) & 1u) ? pl * pb : pl;
+      pb *= pb;
+    }
+    const float prev[2] = {__shfl_up(sv[0], 1u, 64), __shfl_up(sv[1], 1u, 64)};
+    __syncthreads();
+    // 3. the exact form's chains from the true carry-ins
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      float cw = 0.0f;                                          // the state at the end of the previous wave's chunks
+      if (wv >= 1u) cw = sc[c][0];
+      if (wv >= 2u) cw = __builtin_fmaf(pw, cw, sc[c][1]);
+      if (wv >= 3u) cw = __builtin_fmaf(pw, cw, sc[c][2]);
+      y[c] = wl == 0u ? (wv == 0u ? y0[c] : cw) : __builtin_fmaf(pl, cw, prev[c]);
+    }
+    __syncthreads();                                            // (every carry-in is in a register before sc[c][0] takes the segment's last state below)
+#pragma unroll
+    for (uint32_t q = 0; q < SINK_C; ++q)
+      if (q < cnt) {
+        const unsigned l = sink_step(p.alpha, p.gain, xr[0][q], y[0]);
+        const unsigned r = sink_step(p.alpha, p.gain, xr[1][q], y[1]);
+        xw[i0 + q] = l | (r << 16);
+      }
+    if (cnt > 0 && i0 + cnt == m) {                             // the lane that holds the segment's last sample: the states behind it
+      sc[0][0] = y[0];
+      sc[1][0] = y[1];
+    }
+    __syncthreads();
+    y0[0] = sc[0][0];
+    y0[1] = sc[1][0];
+#pragma unroll
+    for (uint32_t q = 0; q < SINK_C; ++q) {
+      const uint32_t i = t + SINK_NT * q;
+      if (i < m) out[base + i] = xw[i];
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    p.state[2 * (size_t)s] = y0[0];
+    p.state[2 * (size_t)s + 1] = y0[1];
+  }
+}
+
+}  // namespace
+
+struct sdrfm_pcm_stereo_sink {
+  uint32_t n_streams;
+  float alpha, gain;
+  int device;
+  hipStream_t own_stream, stream;
+  float* d_state;      // [n_streams][2]
+  float* d_left;       // staging for host-pointer calls
+  float* d_right;
+  int16_t* d_pcm;
+  uint32_t cap;        // samples per stream the staging holds
+};
+
+#define STRY(expr, code)                                                                                       \
+  do {                                                                                                         \
+    hipError_t e__ = (expr);                                                                                   \
+    if (e__ != hipSuccess) {                                                                                   \
+      fprintf(stderr, "[sdrfm] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__);  \
+      return (code);                                                                                           \
+    }                                                                                                          \
+  } while (0)
+
+static void stereo_sink_free(sdrfm_pcm_stereo_sink* k) {
+  if (!k) return;
+  (void)hipSetDevice(k->device);
+  if (k->d_state) (void)hipFree(k->d_state);
+  if (k->d_left) (void)hipFree(k->d_left);
+  if (k->d_right) (void)hipFree(k->d_right);
+  if (k->d_pcm) (void)hipFree(k->d_pcm);
+  if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
+  delete k;
+}
+
+static StereoSinkParams stereo_sink_params(const sdrfm_pcm_stereo_sink* k, const float* left, const float* right, size_t audio_stride, uint32_t n,
+                                           int16_t* pcm, size_t pcm_stride) {
+  StereoSinkParams p;
+  p.left = left; p.right = right; p.audio_stride = audio_stride; p.pcm = pcm; p.pcm_stride = pcm_stride;
+  p.state = k->d_state; p.n_streams = k->n_streams; p.n = n; p.alpha = k->alpha; p.gain = k->gain;
+  return p;
+}
+
+// the checks every call makes of its PCM rows against n > 0 outputs
+static int stereo_sink_pcm_ok(uint32_t n_streams, uint32_t n, const int16_t* pcm, size_t pcm_stride, bool device_ptrs) {
+  if (!pcm) return SDRFM_EINVAL;
+  if (n_streams > 1 && pcm_stride < 2 * (size_t)n) return SDRFM_ECAPACITY;
+  if (pcm_stride & 1u) return SDRFM_EINVAL;                        // rows are written as (L, R) dwords
+  if (device_ptrs && (uintptr_t)pcm % 4 != 0) return SDRFM_EINVAL;
+  return SDRFM_OK;
+}
+
+// ---- the sink behind a stereo or a broadcast launch (sdrfm_sink_stereo.h) ----------------------------------------------------------------------------
+int sdrfm_stereo_sink_check(const sdrfm_pcm_stereo_sink* k, int device, uint32_t n_streams, uint32_t n, const int16_t* pcm, size_t pcm_stride,
+                            bool device_ptrs) {
+  if (!k || k->device != device || k->n_streams != n_streams) return SDRFM_EINVAL;
+  return n ? stereo_sink_pcm_ok(n_streams, n, pcm, pcm_stride, device_ptrs) : SDRFM_OK;
+}
+
+int sdrfm_stereo_sink_reserve(sdrfm_pcm_stereo_sink* k, uint32_t n, int16_t** d_pcm, size_t* d_pcm_stride) {
+  if (!k) return SDRFM_EINVAL;
+  if (n > k->cap) {
+    if (k->d_left) (void)hipFree(k->d_left);
+    if (k->d_right) (void)hipFree(k->d_right);
+    if (k->d_pcm) (void)hipFree(k->d_pcm);
+    k->d_left = nullptr; k->d_right = nullptr; k->d_pcm = nullptr; k->cap = 0;
+    const uint32_t cap = (n + 1023u) & ~1023u;
+    if (hipMalloc(&k->d_left, sizeof(float) * (size_t)cap * k->n_streams) != hipSuccess ||
+        hipMalloc(&k->d_right, sizeof(float) * (size_t)cap * k->n_streams) != hipSuccess ||
+        hipMalloc(&k->d_pcm, sizeof(int16_t) * 2 * (size_t)cap * k->n_streams) != hipSuccess) return SDRFM_ENOMEM;
+    k->cap = cap;
+  }
+  if (d_pcm) *d_pcm = k->d_pcm;
+  if (d_pcm_stride) *d_pcm_stride = 2 * (size_t)k->cap;
+  return SDRFM_OK;
+}
+
+int sdrfm_stereo_sink_launch_on(sdrfm_pcm_stereo_sink* k, const float* left, const float* right, size_t audio_stride, uint32_t n, int16_t* pcm,
+                                size_t pcm_stride, hipStream_t stream) {
+  if (!k) return SDRFM_EINVAL;
+  if (n == 0) return SDRFM_OK;
+  const StereoSinkParams p = stereo_sink_params(k, left, right, audio_stride, n, pcm, pcm_stride);
+  hipLaunchKernelGGL(k_pcm_stereo_sink_scan, dim3(k->n_streams), dim3(SINK_NT), 0, stream, p, (float)pow(1.0 - (double)k->alpha, (double)SINK_C));
+  STRY(hipGetLastError(), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+int sdrfm_stereo_sink_copy_back(const sdrfm_pcm_stereo_sink* k, int16_t* pcm, size_t pcm_stride, uint32_t n, hipStream_t stream) {
+  if (!k) return SDRFM_EINVAL;
+  if (n == 0) return SDRFM_OK;
+  const size_t ps = (k->n_streams > 1) ? pcm_stride : 2 * (size_t)n;
+  STRY(hipMemcpy2DAsync(pcm, sizeof(int16_t) * ps, k->d_pcm, sizeof(int16_t) * 2 * k->cap, sizeof(int16_t) * 2 * n, k->n_streams, hipMemcpyDeviceToHost,
+                        stream), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+extern "C" {
+
+int sdrfm_pcm_stereo_sink_create(uint32_t n_streams, float alpha, float gain, int32_t device, sdrfm_pcm_stereo_sink_t** out) {
+  if (!out) return SDRFM_EINVAL;
+  *out = nullptr;
+  if (!n_streams || !(alpha > 0.0f) || alpha > 1.0f || !(gain == gain)) return SDRFM_EINVAL;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return SDRFM_NO_DEVICE;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SDRFM_NO_DEVICE;
+  STRY(hipSetDevice(device), SDRFM_NO_DEVICE);
+  sdrfm_pcm_stereo_sink* k = new (std::nothrow) sdrfm_pcm_stereo_sink();
+  if (!k) return SDRFM_ENOMEM;
+  memset(static_cast<void*>(k), 0, sizeof(*k));
+  k->n_streams = n_streams; k->alpha = alpha; k->gain = gain; k->device = device;
+  if (hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking) != hipSuccess ||
+      hipMalloc(&k->d_state, sizeof(float) * 2 * (size_t)n_streams) != hipSuccess) { stereo_sink_free(k); return SDRFM_ENOMEM; }
+  k->stream = k->own_stream;
+  const int rc = sdrfm_pcm_stereo_sink_reset(k);
+  if (rc != SDRFM_OK) { stereo_sink_free(k); return rc; }
+  *out = k;
+  return SDRFM_OK;
+}
+
+void sdrfm_pcm_stereo_sink_destroy(sdrfm_pcm_stereo_sink_t* k) {
+  if (!k) return;
+  (void)hipSetDevice(k->device);
+  (void)hipStreamSynchronize(k->stream);
+  stereo_sink_free(k);
+}
+
+int sdrfm_pcm_stereo_sink_reset(sdrfm_pcm_stereo_sink_t* k) {
+  if (!k) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipMemsetAsync(k->d_state, 0, sizeof(float) * 2 * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_stereo_sink_set_stream(sdrfm_pcm_stereo_sink_t* k, void* hip_stream) {
+  if (!k) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  k->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : k->own_stream;
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_stereo_sink_synchronize(sdrfm_pcm_stereo_sink_t* k) {
+  if (!k) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_stereo_sink_process_batch(sdrfm_pcm_stereo_sink_t* k, const float* left, const float* right, size_t audio_stride, uint32_t n,
+                                        int16_t* pcm, size_t pcm_stride, uint32_t flags) {
+  if (!k) return SDRFM_EINVAL;
+  if (flags & ~(SDRFM_F_DEVICE_PTRS | SDRFM_PCM_F_EXACT)) return SDRFM_EINVAL;
+  if (n == 0) return SDRFM_OK;
+  if (!left || !right) return SDRFM_EINVAL;
+  if (!pcm) return SDRFM_EINVAL;
+  if (k->n_streams > 1 && audio_stride < n) return SDRFM_ECAPACITY;
+  const bool device_ptrs = (flags & SDRFM_F_DEVICE_PTRS) != 0;
+  const int ok = stereo_sink_pcm_ok(k->n_streams, n, pcm, pcm_stride, device_ptrs);
+  if (ok != SDRFM_OK) return ok;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  const bool exact = (flags & SDRFM_PCM_F_EXACT) != 0;
+  auto launch = [&](const StereoSinkParams& p) {
+    if (exact) hipLaunchKernelGGL(k_pcm_stereo_sink, dim3((k->n_streams + 63) / 64), dim3(64), 0, k->stream, p);
+    else hipLaunchKernelGGL(k_pcm_stereo_sink_scan, dim3(k->n_streams), dim3(SINK_NT), 0, k->stream, p, (float)pow(1.0 - (double)k->alpha, (double)SINK_C));
+  };
+  if (device_ptrs) {
+    launch(stereo_sink_params(k, left, right, audio_stride, n, pcm, pcm_stride));
+    STRY(hipGetLastError(), SDRFM_FAIL);
+    return SDRFM_OK;
+  }
+  // host buffers: stage, run, copy back, synchronous
+  const int rc = sdrfm_stereo_sink_reserve(k, n, nullptr, nullptr);
+  if (rc != SDRFM_OK) return rc;
+  const size_t as = (k->n_streams > 1) ? audio_stride : n;
+  STRY(hipMemcpy2DAsync(k->d_left, sizeof(float) * k->cap, left, sizeof(float) * as, sizeof(float) * n, k->n_streams, hipMemcpyHostToDevice, k->stream),
+       SDRFM_FAIL);
+  STRY(hipMemcpy2DAsync(k->d_right, sizeof(float) * k->cap, right, sizeof(float) * as, sizeof(float) * n, k->n_streams, hipMemcpyHostToDevice, k->stream),
+       SDRFM_FAIL);
+  launch(stereo_sink_params(k, k->d_left, k->d_right, k->cap, n, k->d_pcm, 2 * (size_t)k->cap));
+  STRY(hipGetLastError(), SDRFM_FAIL);
+  const int cb = sdrfm_stereo_sink_copy_back(k, pcm, pcm_stride, n, k->stream);
+  if (cb != SDRFM_OK) return cb;
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+/* Host copy of the carried de-emphasis states of every stream: state_out[2s] = L, state_out[2s + 1] = R. */
+int sdrfm_pcm_stereo_sink_get_state(sdrfm_pcm_stereo_sink_t* k, float* state_out) {
+  if (!k || !state_out) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipMemcpy(state_out, k->d_state, sizeof(float) * 2 * (size_t)k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+}  // extern "C"

@@ -13,6 +13,7 @@
 #include "sdrfm_carrier.h"
 #include "sdrfm_out_stages.h"
 #include "sdrfm_pilot_front.h"
+#include "sdrfm_sink_stereo.h"
 
 namespace {
 
@@ -226,6 +227,53 @@ int sdrfm_stereo_process_batch(sdrfm_stereo_t* h, const uint8_t* iq, size_t iq_s
   if (rc != SDRFM_OK) return rc;
   if (front_copy_back(h->f, left, audio_stride, h->d_left, h->d_audio_stride, A) != SDRFM_OK) return SDRFM_FAIL;
   if (front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, A) != SDRFM_OK) return SDRFM_FAIL;
+  return front_finish(h->f, pilot_count);
+}
+
+// the call above and, behind it on the handle's stream, the stereo sink's default kernel over this call's L and R rows
+int sdrfm_stereo_process_batch_pcm(sdrfm_stereo_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes,
+                                   float* left, float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, uint32_t* pilot_count,
+                                   uint32_t* n_audio, uint32_t flags) {
+  if (!h || !sink || !n_audio) return SDRFM_EINVAL;
+  if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;
+  if (!left != !right) return SDRFM_EINVAL;                    // both, or neither: the sink then reads the handle's own rows
+  if (nbytes & 1u) return SDRFM_EODD;
+  if (nbytes > h->f.max_bytes) return SDRFM_ECAPACITY;
+  const uint32_t ns = h->cfg.n_streams;
+  const bool dev = (flags & SDRFM_F_DEVICE_PTRS) != 0;
+  uint32_t A = 0;
+  (void)sdrfm_stereo_audio_count(h, nbytes, &A);
+  int rc = sdrfm_stereo_sink_check(sink, h->f.device, ns, A, pcm, pcm_stride, dev);
+  if (rc != SDRFM_OK) return rc;
+  if (nbytes == 0) {
+    *n_audio = 0;
+    return front_empty_call(h->f, pilot_count, flags);
+  }
+  if (!iq) return SDRFM_EINVAL;
+  if (ns > 1 && iq_stride < nbytes) return SDRFM_ECAPACITY;
+  if (left && ns > 1 && audio_stride < A) return SDRFM_ECAPACITY;
+  if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
+  if (dev) {
+    float* const l = left ? left : h->d_left;
+    float* const r = left ? right : h->d_right;
+    const size_t as = left ? audio_stride : h->d_audio_stride;
+    rc = stereo_enqueue(h, iq, iq_stride, nbytes, l, r, as, pilot_count, n_audio);
+    if (rc != SDRFM_OK) return rc;
+    return sdrfm_stereo_sink_launch_on(sink, l, r, as, A, pcm, pcm_stride, h->f.stream);
+  }
+
+  int16_t* d_pcm = nullptr;
+  size_t d_pcm_stride = 0;
+  rc = sdrfm_stereo_sink_reserve(sink, A, &d_pcm, &d_pcm_stride);   // (before anything is enqueued: a refusal leaves both handles alone)
+  if (rc != SDRFM_OK) return rc;
+  if (front_stage_in(h->f, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
+  rc = stereo_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->f.d_pc, n_audio);
+  if (rc != SDRFM_OK) return rc;
+  rc = sdrfm_stereo_sink_launch_on(sink, h->d_left, h->d_right, h->d_audio_stride, A, d_pcm, d_pcm_stride, h->f.stream);
+  if (rc != SDRFM_OK) return rc;
+  if (left && front_copy_back(h->f, left, audio_stride, h->d_left, h->d_audio_stride, A) != SDRFM_OK) return SDRFM_FAIL;
+  if (left && front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, A) != SDRFM_OK) return SDRFM_FAIL;
+  if (sdrfm_stereo_sink_copy_back(sink, pcm, pcm_stride, A, h->f.stream) != SDRFM_OK) return SDRFM_FAIL;
   return front_finish(h->f, pilot_count);
 }
 

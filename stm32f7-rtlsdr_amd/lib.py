@@ -32,6 +32,9 @@ ABI_SYMBOLS = [
     "sdrfm_rds_sync_destroy", "sdrfm_rds_sync_reset", "sdrfm_rds_sync_push", "sdrfm_rds_sync_stats",
     "sdrfm_bcast_create", "sdrfm_bcast_destroy", "sdrfm_bcast_reset", "sdrfm_bcast_counts", "sdrfm_bcast_process_batch",
     "sdrfm_bcast_set_stream", "sdrfm_bcast_synchronize", "sdrfm_bcast_kernel_name",
+    "sdrfm_pcm_stereo_sink_create", "sdrfm_pcm_stereo_sink_destroy", "sdrfm_pcm_stereo_sink_reset", "sdrfm_pcm_stereo_sink_process_batch",
+    "sdrfm_pcm_stereo_sink_set_stream", "sdrfm_pcm_stereo_sink_synchronize", "sdrfm_pcm_stereo_sink_get_state",
+    "sdrfm_stereo_process_batch_pcm", "sdrfm_bcast_process_batch_pcm",
 ]
 
 
@@ -316,5 +319,23 @@ def load_library(dev=False):
     lib.sdrfm_pcm_sink_synchronize.restype = C.c_int
     lib.sdrfm_pcm_sink_get_state.argtypes = [vp, C.POINTER(C.c_float)]
     lib.sdrfm_pcm_sink_get_state.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_create.argtypes = [u32, C.c_float, C.c_float, C.c_int32, C.POINTER(vp)]
+    lib.sdrfm_pcm_stereo_sink_create.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_destroy.argtypes = [vp]
+    lib.sdrfm_pcm_stereo_sink_destroy.restype = None
+    lib.sdrfm_pcm_stereo_sink_reset.argtypes = [vp]
+    lib.sdrfm_pcm_stereo_sink_reset.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_process_batch.argtypes = [vp, vp, vp, C.c_size_t, u32, vp, C.c_size_t, u32]
+    lib.sdrfm_pcm_stereo_sink_process_batch.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_set_stream.argtypes = [vp, vp]
+    lib.sdrfm_pcm_stereo_sink_set_stream.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_synchronize.argtypes = [vp]
+    lib.sdrfm_pcm_stereo_sink_synchronize.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_get_state.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.sdrfm_pcm_stereo_sink_get_state.restype = C.c_int
+    lib.sdrfm_stereo_process_batch_pcm.argtypes = [vp, vp, vp, C.c_size_t, u32, vp, vp, C.c_size_t, vp, C.c_size_t, vp, u32p, u32]
+    lib.sdrfm_stereo_process_batch_pcm.restype = C.c_int
+    lib.sdrfm_bcast_process_batch_pcm.argtypes = [vp, vp, vp, C.c_size_t, u32, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, u32p, u32p, u32]
+    lib.sdrfm_bcast_process_batch_pcm.restype = C.c_int
     _libs[dev] = lib
     return lib

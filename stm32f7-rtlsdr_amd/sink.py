@@ -1,5 +1,5 @@
-"""PcmSink — Python mirror of the sdrfm_pcm_sink_* C entry points: de-emphasis + int16 stereo PCM on the device, in the
-layout BSP_AUDIO_OUT_Play takes (Utilities/STM32746G-Discovery/stm32746g_discovery_audio.c:224)."""
+"""PcmSink, StereoPcmSink — Python mirrors of the sdrfm_pcm_sink_* and sdrfm_pcm_stereo_sink_* C entry points: de-emphasis + int16 stereo
+PCM on the device, in the layout BSP_AUDIO_OUT_Play takes (Utilities/STM32746G-Discovery/stm32746g_discovery_audio.c:224)."""
 import ctypes as C
 
 import numpy as np
@@ -108,3 +108,76 @@ def pcm_deemph_stereo_s16_host(left, right, alpha, gain, state=(0.0, 0.0)):
     if rc != _l.OK:
         raise _l.SdrfmError(rc, "sdrfm_pcm_deemph_stereo_s16")
     return pcm, (st[0], st[1])
+
+
+class StereoPcmSink:
+    """The device sink for L and R rows (sdrfm_pcm_stereo_sink_*): pcm[2i] = L, pcm[2i + 1] = R, each channel de-emphasised on its own.
+    exact=False (default): the blocked scan, per channel the mono PcmSink's default form bit for bit (PCM within 1 LSB of the exact form);
+    exact=True: SDRFM_PCM_F_EXACT, one lane per stream, bit-identical to the host routine sdrfm_pcm_deemph_stereo_s16."""
+
+    def __init__(self, n_streams, alpha, gain, device=0, exact=False):
+        self._lib = _l.load_library()
+        self._xf = PCM_F_EXACT if exact else 0
+        self.n_streams = int(n_streams)
+        self._h = C.c_void_p()
+        st = self._lib.sdrfm_pcm_stereo_sink_create(self.n_streams, alpha, gain, device, C.byref(self._h))
+        if st != _l.OK:
+            self._h = None
+            raise _l.SdrfmError(st, "sdrfm_pcm_stereo_sink_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sdrfm_pcm_stereo_sink_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _ck(self, st, where):
+        if st != _l.OK:
+            raise _l.SdrfmError(st, where)
+
+    def reset(self):
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_reset(self._h), "sdrfm_pcm_stereo_sink_reset")
+
+    def set_stream(self, ptr):
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_pcm_stereo_sink_set_stream")
+
+    def synchronize(self):
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_synchronize(self._h), "sdrfm_pcm_stereo_sink_synchronize")
+
+    def state(self):
+        """[n_streams, 2] float32: the carried de-emphasis states (L, R) of every stream"""
+        out = np.zeros((self.n_streams, 2), np.float32)
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_get_state(self._h, out.ctypes.data_as(C.POINTER(C.c_float))), "sdrfm_pcm_stereo_sink_get_state")
+        return out
+
+    def process_batch(self, left: np.ndarray, right: np.ndarray) -> np.ndarray:
+        """host memory: left, right [n_streams, n] float32 -> pcm [n_streams, 2n] int16 (L, R interleaved)"""
+        xl = np.ascontiguousarray(left, dtype=np.float32)
+        xr = np.ascontiguousarray(right, dtype=np.float32)
+        if xl.ndim == 1:
+            xl, xr = xl[None, :], xr[None, :]
+        assert xl.shape == xr.shape and xl.shape[0] == self.n_streams
+        n = xl.shape[1]
+        pcm = np.zeros((self.n_streams, 2 * n), np.int16)
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_process_batch(self._h, xl.ctypes.data, xr.ctypes.data, n, n, pcm.ctypes.data, 2 * n, self._xf),
+                 "sdrfm_pcm_stereo_sink_process_batch")
+        return pcm
+
+    def process_batch_device(self, left, right, pcm, n=None):
+        """torch tensors on the device: left, right float32 [n_streams, >=n] (same strides), pcm int16 [n_streams, >=2n]; only enqueues."""
+        assert left.is_cuda and right.is_cuda and pcm.is_cuda and left.stride() == right.stride() and left.stride(1) == 1 and pcm.stride(1) == 1
+        n = left.shape[1] if n is None else int(n)
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_process_batch(self._h, C.c_void_p(left.data_ptr()), C.c_void_p(right.data_ptr()), left.stride(0), n,
+                                                               C.c_void_p(pcm.data_ptr()), pcm.stride(0), _l.F_DEVICE_PTRS | self._xf),
+                 "sdrfm_pcm_stereo_sink_process_batch(device)")
