@@ -11,6 +11,7 @@
  *     sdrfm_debug_q_guard                          design Q: a handle's guard thresholds and how often its repair path ran
  *     sdrfm_debug_read_ceiling                     what a read-only stream with design Q's access pattern gets out of the memory system
  *     sdrfm_debug_route                            design Q: which streams of a handle the bit-exact kernels serve (read, or set for a test)
+ *     sdrfm_sink_chain_tables                      the PCM sink inside design Q's launch: its tables for an alpha, and whether it may serve that alpha (no GPU)
  *   exported by the development library libsdrfm_dev.so only (built with -DSDRFM_DEV):
  *     sdrfm_debug_phase_cycles, sdrfm_debug_raw    instrumented kernels' counters (SDRFM_PHASE_PROFILE=1 at create)
  *     sdrfm_dev_read_debug                         per-wave time stamps of design S (SDRFM_STREAM_PROFILE=1)
@@ -54,6 +55,11 @@ int sdrfm_debug_q_guard(sdrfm_t* h, float* guard_r, float* guard_a, unsigned lon
  * *n_noisy (may be NULL) = streams the bit-exact kernels serve from the next call on; noisy_out (may be NULL, [n_streams] bytes) = which.
  * SDRFM_NOT_SUPPORTED when the handle has no matrix-pipe kernel. */
 int sdrfm_debug_route(sdrfm_t* h, const uint8_t* mask, uint32_t* n_noisy, uint8_t* noisy_out);
+
+/* The PCM sink's chain inside design Q's launch (csrc/sdrfm_sink_chain.h): *pc = (1 - alpha)^8, w[q] = alpha (1 - alpha)^(7 - q), dinv[k] = (1 - alpha)^-k, q, k < 8, as
+ * the launch's arguments hold them.  Returns 2 when the chain may serve a sink of this alpha (alpha >= 0.231 and (1 - alpha)^8 a normal float), 1 when only the
+ * sink's own kernel may.  Plain host arithmetic. */
+int sdrfm_sink_chain_tables(float alpha, float* pc, float* w, float* dinv);
 
 /* The measured read ceiling bench.py prints beside the 8 TB/s specification: a read-only LDS-DMA stream with design Q's access
  * pattern (one-wave workgroups, 12 per CU, 5 KiB in flight each, non-temporal) over nbufs device buffers of bytes_each bytes, `passes` passes

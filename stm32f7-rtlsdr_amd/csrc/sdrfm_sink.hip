@@ -28,13 +28,15 @@
  *   3. lane t walks its chunk AGAIN, now from its true carry-in s[t-1], with exactly the exact form's operations, and packs the PCM.
  * What differs from the exact chain is therefore only the carry-in of a chunk (re-associated: ~1e-7 relative), and that difference decays with
  * (1 - alpha)^k inside the chunk: the PCM is within 1 LSB of the exact form's (equal but where y * gain sits within 1e-3 of a rounding boundary),
- * the carried state within 2.5e-7 (tests/test_pcm_sink_gpu.py).  The audio row goes through LDS once (coalesced loads, chunk stride odd: conflict-free),
+ * the carried state within 1e-6 relative (2.5e-7 at 75 us, tests/test_pcm_sink_gpu.py; 8e-7 at alpha = 0.001, where a carry-in hardly decays inside its chunk:
+ * tests/test_pcm_sink_params_gpu.py).  The audio row goes through LDS once (coalesced loads, chunk stride odd: conflict-free),
  * the PCM row back the same way; the chunk sits in registers for both walks.  7.0 us per 256 x 4800 launch against the exact form's 1.35 ms
  * (profiles/r06_sink.txt).
  */
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -235,16 +237,22 @@ static void sink_free(sdrfm_pcm_sink* k) {
 }
 
 // ---- the sink inside a demodulator launch (sdrfm_sink_chain.h) ---------------------------------------------------------------------------------------
+extern "C" int sdrfm_sink_chain_tables(float alpha, float* pc, float* w, float* dinv) {
+  const double d = 1.0 - (double)alpha;
+  *pc = (float)pow(d, (double)SDRFM_CHAIN_CH);
+  for (uint32_t q = 0; q < SDRFM_CHAIN_CH; ++q) w[q] = (float)((double)alpha * pow(d, (double)(SDRFM_CHAIN_CH - 1u - q)));
+  for (uint32_t q = 0; q < SDRFM_CHAIN_CH; ++q) dinv[q] = (float)pow(d, -(double)q);
+  // (pc a normal float: w[0] = alpha pc / d is normal and dinv[7] = d / pc finite with it, and a product that underflows in the scan is off by 2^-149 dinv[7] < 1e-11)
+  return (alpha >= SDRFM_CHAIN_MIN_ALPHA && *pc >= FLT_MIN) ? 2 : 1;
+}
+
 int sdrfm_sink_chain_params(sdrfm_pcm_sink* k, int device, uint32_t n_streams, SdrfmSinkChain* out) {
   if (!k || !out || k->device != device || k->n_streams != n_streams) return 0;
   out->pcm = nullptr; out->pcm_stride = 0; out->runstate = nullptr; out->run_call = 0;
   out->sg = k->d_sg; out->n_streams = n_streams; out->dpow = k->d_dpow; out->err = reinterpret_cast<uint32_t*>(k->d_dpow + SDRFM_CHAIN_FIX);
   out->call = k->calls;
   out->alpha = k->alpha; out->gain = k->gain;
-  out->pc = (float)pow(1.0 - (double)k->alpha, (double)SDRFM_CHAIN_CH);
-  for (uint32_t q = 0; q < SDRFM_CHAIN_CH; ++q) out->w[q] = (float)((double)k->alpha * pow(1.0 - (double)k->alpha, (double)(SDRFM_CHAIN_CH - 1u - q)));
-  for (uint32_t q = 0; q < SDRFM_CHAIN_CH; ++q) out->dinv[q] = (float)pow(1.0 - (double)k->alpha, -(double)q);
-  return k->alpha >= SDRFM_CHAIN_MIN_ALPHA ? 2 : 1;
+  return sdrfm_sink_chain_tables(k->alpha, &out->pc, out->w, out->dinv);
 }
 
 void sdrfm_sink_chain_issued(sdrfm_pcm_sink* k) { ++k->calls; }

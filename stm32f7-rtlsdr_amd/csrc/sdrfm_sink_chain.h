@@ -24,6 +24,9 @@
  * four dependent round trips through a saturated memory system at the very end of the launch, which the next launch on that queue waits for.)
  * Against the exact chain: the carry-in of a chunk is re-associated (1e-7 relative) and d^64 * carry is dropped: PCM within 1 LSB (different only where y * gain
  * sits on a rounding boundary), carried state within 1e-6 relative — the stand-alone blocked scan's tolerance (tests/test_pcm_sink_gpu.py).
+ * Which sinks: every one but a sink whose alpha lies outside [0.231, 1 - 1.8e-5] — below it a run's end state still depends on its predecessor's; above it (1 - alpha)^8 is no normal float and (1 - alpha)^-7, by which a run's end state is published, overflows: at alpha = 1 the chain would publish NaN (sdrfm_sink_chain_tables below;
+ * the publish's position in its lane's chunk is (outputs of the run's last flush - 1) % 8, and runs of floor(32 q1 / 5) - floor(32 q0 / 5) outputs end anywhere).  The
+ * stand-alone kernel serves those sinks behind every launch.  tests/test_pcm_chain_cpu.py holds both ends on the CPU, at the launch's own cut into runs.
  *
  * Order between calls: the word {calls applied to stream s, state} is published by the stream's last run of call c with tag c + 1 (in slot tag % 8 of sg: a
  * word is never overwritten while a call that may still read it is incomplete); run 0 of call c + 1 waits (an s_sleep loop of one lane) for that tag.  Call c was launched before call c + 1 and none of its waves waits on anything but its own lower-numbered
@@ -66,8 +69,14 @@ struct SdrfmSinkChain {
 
 // ---- host side (sdrfm_sink.hip) ---------------------------------------------------------------------------------------------------------------------------
 // The parameters for the sink's NEXT call (pcm / pcm_stride / runstate / run_call left for the caller to fill).  0: the sink does not fit the handle (other device, other
-// stream count); 1: it fits, but its time constant is too long for runs to be sunk independently (alpha < SDRFM_CHAIN_MIN_ALPHA): stand-alone kernel only; 2: fits.
+// stream count); 1: it fits, but its alpha is outside the chain's range (sdrfm_sink_chain_tables): stand-alone kernel only; 2: fits.
 int sdrfm_sink_chain_params(sdrfm_pcm_sink* k, int device, uint32_t n_streams, SdrfmSinkChain* out);
+// The chain's tables of one alpha — pc, w[SDRFM_CHAIN_CH], dinv[SDRFM_CHAIN_CH] as SdrfmSinkChain holds them — and whether the chain may serve that alpha: 2 when
+// alpha >= SDRFM_CHAIN_MIN_ALPHA and (1 - alpha)^SDRFM_CHAIN_CH is a normal float (alpha <= 1 - 1.8e-5), else 1.  Above that range dinv[k] = (1 - alpha)^-k overflows
+// (at alpha = 1 it is infinite and the scan value it multiplies is 0: a run whose last flush ends off a multiple of SDRFM_CHAIN_CH outputs — most runs do — would
+// publish NaN), and just below the overflow the products of the scan are subnormal.  Such a sink forgets within a sample; the stand-alone kernel serves it.
+// Plain host arithmetic without a device (tools/pcm_chain_emulate.py and tests/test_pcm_chain_cpu.py call it on the CPU).
+extern "C" int sdrfm_sink_chain_tables(float alpha, float* pc, float* w, float* dinv);
 // The launch that carried `out` is in the queue: the sink's call counter moves on.
 void sdrfm_sink_chain_issued(sdrfm_pcm_sink* k);
 // The stand-alone blocked scan on `stream` (device buffers), as one call of the sink: what a call that no kernel with the chain served is followed by.

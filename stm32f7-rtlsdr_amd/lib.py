@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
 
 
 # include/sdrfm_dev.h: test hooks the product library also exports / development-library-only aids (not the drop-in boundary)
-TEST_HOOK_SYMBOLS = ["sdrfm_host_atan2f", "sdrfm_host_discriminate", "sdrfm_debug_discriminate", "sdrfm_q_build", "sdrfm_q_guard", "sdrfm_q_guard2", "sdrfm_debug_q_guard", "sdrfm_debug_read_ceiling", "sdrfm_debug_route"]
+TEST_HOOK_SYMBOLS = ["sdrfm_host_atan2f", "sdrfm_host_discriminate", "sdrfm_debug_discriminate", "sdrfm_q_build", "sdrfm_q_guard", "sdrfm_q_guard2", "sdrfm_debug_q_guard", "sdrfm_debug_read_ceiling", "sdrfm_debug_route", "sdrfm_sink_chain_tables"]
 DEV_ONLY_SYMBOLS = ["sdrfm_debug_phase_cycles", "sdrfm_debug_raw", "sdrfm_dev_read_debug"]
 
 
@@ -174,6 +174,8 @@ def load_library(dev=False):
     lib.sdrfm_host_atan2f.restype = C.c_float
     lib.sdrfm_host_discriminate.argtypes = [C.c_float] * 4
     lib.sdrfm_host_discriminate.restype = C.c_float
+    lib.sdrfm_sink_chain_tables.argtypes = [C.c_float] + [C.POINTER(C.c_float)] * 3
+    lib.sdrfm_sink_chain_tables.restype = C.c_int
     if dev:
         lib.sdrfm_debug_phase_cycles.argtypes = [vp, C.POINTER(C.c_uint64)]
         lib.sdrfm_debug_phase_cycles.restype = C.c_int

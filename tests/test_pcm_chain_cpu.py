@@ -1,15 +1,31 @@
 """CPU: the arithmetic of the PCM sink inside the demodulator's launch (csrc/sdrfm_sink_chain.h) restated in numpy (tools/pcm_chain_emulate.py), held to the host
-routine sdrfm_pcm_deemph_s16 (csrc/pcm_sink.c) — the bit-exact definition of the sink — without a GPU."""
+routine sdrfm_pcm_deemph_s16 (csrc/pcm_sink.c) — the bit-exact definition of the sink — without a GPU.  The emulator takes the chain's tables from the library
+(sdrfm_sink_chain_tables), publishes a run's end state as the kernel does (scan value times dinv) and cuts a call into the launch's own runs and flushes
+(csrc/sdrfm_fm_call.h through tests/native/pcm_chain_runs.cpp, the run geometry of csrc/sdrfm_q.hip restated in run_cuts).
+
+The written answer on alpha = 1 (test_a_runs_last_flush_ends_off_a_multiple_of_eight_...): at the shapes tests/test_pcm_sink_params_gpu.py runs, every one of the 34
+runs of the chain's two calls (83 to 90 outputs each, one flush) ends its last flush off a multiple of 8 outputs, so dinv[k >= 1] IS applied, and at alpha = 1 it is infinite times a scan value of 0:
+NaN, which then finishes the successor's first 64 outputs and is carried into the next call.  The positions are reachable; alpha = 1 is safe only because
+sdrfm_sink_chain_tables answers 1 (the sink's own kernel) wherever (1 - alpha)^8 is not a normal float."""
 import importlib
 import os
+import shutil
+import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import pcm_params as pp
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 emu = importlib.import_module("pcm_chain_emulate")
+
+GAIN = np.float32(pp.DEFAULT_GAIN)
+# tests/test_pcm_sink_params_gpu.py's plan for the chain: 64 streams, 64 channel taps, / 10 / 5, three calls of 48 000, 48 400 and 96 000 samples on a 256-CU device
+# with 12 design-Q waves per CU (what sdrfm_create arrives at on an MI355X: tests/native/fm_call_check.cpp); the stream's first call goes to the sink's own kernel
+PLAN_NBYTES = [96000, 96800, 192000]
 
 
 def _audio(n, seed):
@@ -19,18 +35,63 @@ def _audio(n, seed):
             0.05 * rng.standard_normal(n)).astype(np.float32)
 
 
+@pytest.fixture(scope="module")
+def plan_runs(tmp_path_factory):
+    """{nbytes: (M, A, runs)} of the plan's calls, from the host arithmetic the launch uses"""
+    if shutil.which("g++") is None:
+        pytest.skip("needs g++")
+    exe = str(tmp_path_factory.mktemp("native") / "pcm_chain_runs")
+    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-o", exe, os.path.join(ROOT, "tests/native/pcm_chain_runs.cpp")], check=True, cwd=ROOT,
+                   capture_output=True, text=True)
+    r = subprocess.run([exe, "64", "10", "32", "5", "64", "256", "12"] + [str(n) for n in PLAN_NBYTES], capture_output=True, text=True, check=True, timeout=60)
+    out = {}
+    for line in r.stdout.splitlines():
+        nbytes, M, A, q_fit, fits, runs, with_chain = (int(v) for v in line.split())
+        assert q_fit and fits and with_chain, line                 # design Q serves every call of the plan, with the chain
+        out[nbytes] = (M, A, runs)
+    assert out == {96000: (4800, 960, 11), 96800: (4840, 968, 11), 192000: (9600, 1920, 23)}, out    # (150, 152 and 300 quads: runs of 13 quads at least)
+    return out
+
+
+def _emulate_plan(pkg, plan_runs, alpha, gain, overlap, seed, force_chain=False):
+    """The plan's three calls of one stream: (PCM values by the library's path for this alpha, the host routine's, emulated state, host state).  The first call is the
+    sink's own kernel's (design Q's first call of a stream holds no chain: the exact chain stands for it), the others the chain's when the library lets it serve."""
+    lib = pkg.load_library()
+    chain = force_chain or emu.chain_tables(alpha)[0] == 2
+    got, want, st, est = [], [], 0.0, 0.0
+    for k, nbytes in enumerate(PLAN_NBYTES):
+        M, A, runs = plan_runs[nbytes]
+        x = _audio(A, seed + k)
+        w, st = pkg.pcm_deemph_s16_host(x, alpha, gain, st)
+        if k == 0 or not chain:
+            g, est = pkg.pcm_deemph_s16_host(x, alpha, gain, est)
+            g = g[0::2].astype(np.int32)
+        else:
+            g, est = emu.chain_emulate(x, alpha, gain, cuts=emu.run_cuts(M, A, runs, 5, overlap), state0=est)
+        got.append(g)
+        want.append(w[0::2].astype(np.int32))
+    return np.concatenate(got), np.concatenate(want), est, st
+
+
+def _hold(got, want, est, st, what):
+    d = np.abs(got - want)
+    assert d.max() <= 1, (what, int(d.max()), int(np.argmax(d)))
+    assert (d > 0).mean() < 0.01, (what, float((d > 0).mean()))     # different only where y * gain sits on a rounding boundary
+    assert abs(est - st) <= 1e-6 * max(abs(st), 0.25), (what, est, st)
+
+
 @pytest.mark.parametrize("tau", [75e-6, 50e-6])
 @pytest.mark.parametrize("run_len", [76, 400, 800, 1500])
 def test_runs_sunk_on_their_own_are_within_one_lsb_of_the_exact_chain(pkg, tau, run_len):
     """Runs of 76 outputs (the shortest the host allows: 12 owned quads), 400 (BASELINE configs[2]), 800 (configs[3]'s share: two flushes per run) and 1500 (three)."""
-    alpha = float(pkg.load_library().sdrfm_pcm_alpha(48000.0, tau))
-    gain = np.float32(32767.0 / (2 * np.pi * 75e3 / 240e3))
+    lib = pkg.load_library()
+    alpha = float(lib.sdrfm_pcm_alpha(48000.0, tau))
     state = 0.0
     emu_state = 0.0
     for call in range(3):
         x = _audio(4800, 10 * call + int(tau * 1e6))
-        want, state = pkg.pcm_deemph_s16_host(x, alpha, gain, state)
-        got, emu_state = emu.chain_emulate(x, alpha, gain, run_len=run_len, state0=emu_state)
+        want, state = pkg.pcm_deemph_s16_host(x, alpha, GAIN, state)
+        got, emu_state = emu.chain_emulate(x, alpha, GAIN, run_len=run_len, state0=emu_state)
         d = np.abs(got - want[0::2].astype(np.int32))
         assert d.max() <= 1, (call, int(d.max()), int(np.argmax(d)))
         assert (d > 0).mean() < 0.01                              # different only where y * gain sits on a rounding boundary
@@ -38,11 +99,11 @@ def test_runs_sunk_on_their_own_are_within_one_lsb_of_the_exact_chain(pkg, tau, 
 
 
 def test_full_scale_and_clipping(pkg):
-    alpha = float(pkg.load_library().sdrfm_pcm_alpha(48000.0, 75e-6))
-    gain = np.float32(32767.0 / (2 * np.pi * 75e3 / 240e3))
+    lib = pkg.load_library()
+    alpha = float(lib.sdrfm_pcm_alpha(48000.0, 75e-6))
     x = (3.0 * _audio(4800, 3)).astype(np.float32)                  # drives the sink into its clamp
-    want, _ = pkg.pcm_deemph_s16_host(x, alpha, gain)
-    got, _ = emu.chain_emulate(x, alpha, gain)
+    want, _ = pkg.pcm_deemph_s16_host(x, alpha, GAIN)
+    got, _ = emu.chain_emulate(x, alpha, GAIN)
     assert want.max() == 32767 and want.min() == -32768
     assert np.abs(got - want[0::2].astype(np.int32)).max() <= 1
 
@@ -52,8 +113,69 @@ def test_why_the_scheme_needs_a_short_memory(pkg):
     constant) a run's first 64 outputs are not all its predecessor reaches and the scheme is off by whole LSBs — which is why such a sink is served by the stand-alone
     kernel instead (sdrfm_sink_chain_params answers 1)."""
     assert (1.0 - 0.231) ** 64 <= 5.1e-8
-    gain = np.float32(32767.0 / (2 * np.pi * 75e3 / 240e3))
     x = (_audio(4800, 9) + np.float32(0.8)).astype(np.float32)     # (a DC offset: a state that matters)
-    want, _ = pkg.pcm_deemph_s16_host(x, 0.05, gain)
-    got, _ = emu.chain_emulate(x, 0.05, gain, run_len=100)
+    want, _ = pkg.pcm_deemph_s16_host(x, 0.05, GAIN)
+    got, _ = emu.chain_emulate(x, 0.05, GAIN, run_len=100)
     assert np.abs(got - want[0::2].astype(np.int32)).max() > 4
+
+
+# ---- which alphas the chain serves ---------------------------------------------------------------------------------------------------------------------------
+def test_the_chain_serves_alpha_from_0_231f_up_to_where_its_tables_stay_normal(pkg):
+    """sdrfm_sink_chain_tables answers 2 for [0.231f, 1 - 1.8e-5] and 1 outside: the float below 0.231f (a run's end state would still depend on its
+    predecessor's), and every alpha so close to 1 that (1 - alpha)^8 is subnormal or 0 — there dinv[7] = (1 - alpha)^-7 overflows or is about to."""
+    lib = pkg.load_library()
+    mode = {name: emu.chain_tables(pp.alpha_of(lib, name))[0] for name in pp.ALPHAS}
+    assert sorted(n for n, m in mode.items() if m == 2) == sorted(pp.CHAIN_ALPHAS) and set(mode.values()) == {1, 2}, mode
+    one = np.float32(1.0)
+    for a, want in ((np.nextafter(one, np.float32(0)), 1), (np.float32(1 - 1e-6), 1), (np.float32(1 - 1e-5), 1), (np.float32(1 - 1.7e-5), 1),
+                    (np.float32(1 - 1.9e-5), 2), (np.float32(1 - 1e-4), 2)):
+        m, pc, w, dinv = emu.chain_tables(a)
+        assert m == want, (float(a), m)
+        if m == 2:
+            assert pc >= np.finfo(np.float32).tiny and w[0] >= np.finfo(np.float32).tiny and np.isfinite(dinv).all(), (float(a), pc, w, dinv)
+    m, pc, w, dinv = emu.chain_tables(1.0)
+    assert pc == 0 and w.tolist() == [0] * 7 + [1] and dinv[0] == 1 and np.isinf(dinv[1:]).all()
+
+
+def test_a_runs_last_flush_ends_off_a_multiple_of_eight_at_the_shapes_the_gpu_tests_run(pkg, plan_runs):
+    """The written answer: can a run's last flush end off a multiple of 8 outputs at a shape design Q accepts?  Yes: every run of these calls does.  A run owns the audio outputs
+    [floor(32 q0 / 5), floor(32 q1 / 5)) (quads of 32 decimated outputs, / 5), 83 to 90 of them here, sunk in one flush: no count is a multiple of 8.  So the publish multiplies
+    the scan's value by dinv[k], k >= 1, and at alpha = 1 (dinv = inf, scan value 0) the chain WOULD publish NaN: shown here with the library's tables and its answer
+    overridden.  Nothing in the geometry protects alpha = 1; sdrfm_sink_chain_tables' answer does."""
+    lib = pkg.load_library()
+    off, total = 0, 0
+    for overlap in (False, True):
+        for nbytes in PLAN_NBYTES[1:]:
+            M, A, runs = plan_runs[nbytes]
+            ends = emu.last_flush_ends(emu.run_cuts(M, A, runs, 5, overlap))
+            assert all(e > 0 for e in ends), ends                  # (at these shapes every run publishes from its last flush's scan)
+            off += sum(e % 8 != 0 for e in ends)
+            total += len(ends)
+    assert total == 68 and off == 68, (off, total)               # (11 + 23 runs, overlapped and not)
+    assert emu.chain_tables(1.0)[0] == 1
+    got, want, est, st = _emulate_plan(pkg, plan_runs, 1.0, GAIN, True, 40, force_chain=True)
+    assert np.isnan(est)                                            # the carried word of the stream's next call
+    assert (got != want).sum() >= 64                                # and the first 64 outputs of every run behind a NaN publish
+
+
+# ---- every alpha the chain serves, at the launch's own cut ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("overlap", [False, True])
+@pytest.mark.parametrize("name", pp.ALPHAS)
+def test_the_launchs_own_runs_meet_the_host_routine_at_every_alpha(pkg, plan_runs, name, overlap):
+    """Every alpha of the GPU sweep by the path the library takes for it: the chain (emulated at the launch's cut, the publish through dinv and the fix-up through
+    dpow included) where sdrfm_sink_chain_tables answers 2, the sink's own kernel otherwise — at alpha = 1 and near it too."""
+    lib = pkg.load_library()
+    alpha = pp.alpha_of(lib, name)
+    for gain in (GAIN, -GAIN, np.float32(0.0)):
+        got, want, est, st = _emulate_plan(pkg, plan_runs, alpha, gain, overlap, 20)
+        _hold(got, want, est, st, (name, float(gain)))
+
+
+@pytest.mark.parametrize("alpha", [1 - 1.9e-5, 1 - 1e-4, 0.999])
+def test_the_chain_just_below_its_upper_end_meets_the_host_routine(pkg, plan_runs, alpha):
+    """The largest alphas the chain serves: (1 - alpha)^8 barely normal, dinv[7] up to 1e33; products that underflow in the scan are off by 2^-149 dinv[7] < 1e-11."""
+    lib = pkg.load_library()
+    alpha = float(np.float32(alpha))
+    assert emu.chain_tables(alpha)[0] == 2
+    got, want, est, st = _emulate_plan(pkg, plan_runs, alpha, GAIN, True, 30)
+    _hold(got, want, est, st, alpha)

@@ -5,7 +5,8 @@ from state 0 (lane 0: from the carried state), six doubling steps within each wa
 combined, every chunk re-walked from its true carry-in with the exact chain's operations.  fp32 throughout (fused multiply-adds as in
 tools/pcm_chain_emulate.py: through float64, exact products, one rounding that differs from a true fma's in ~1e-9 of the cases).
 tests/test_pcm_stereo_scan_cpu.py holds it to the host routine sdrfm_pcm_deemph_stereo_s16 on the inputs of tests/test_pcm_stereo_sink_gpu.py, which
-sink_inputs() below makes for both.  Test infrastructure: nothing here is on a product path."""
+sink_inputs() below makes for both.  mono_scan_emulate() is the mono sink's default form (k_pcm_sink_scan, csrc/sdrfm_sink.hip): the same scan over one
+chain, held to sdrfm_pcm_deemph_s16 by tests/test_pcm_mono_scan_cpu.py.  Test infrastructure: nothing here is on a product path."""
 import numpy as np
 
 from pcm_chain_emulate import F, fma, pcm_word
@@ -94,6 +95,38 @@ def stereo_scan_emulate(left, right, alpha, gain, state=None):
     pcm = np.zeros((ns, 2 * n), np.int16)
     pcm[:, 0::2], pcm[:, 1::2] = vals[:, 0], vals[:, 1]
     return pcm, y
+
+
+def mono_inputs(ns, n):
+    """x float32 [ns, 2n]: the mono sink's analogue of sink_inputs (two calls of n samples per stream, row 0 starting with values that saturate)"""
+    rng = np.random.default_rng(ns * 79 + n)
+    x = (rng.standard_normal((ns, 2 * n)) * 1.5).astype(F)
+    head = np.array([9.0, -9.0, 0.0, 1e-30, 0.5, -0.5], F)[: min(6, 2 * n)]
+    x[0, : head.size] = head
+    return x
+
+
+def mono_scan_emulate(x, alpha, gain, state=None):
+    """x [ns, n] -> (pcm int16 [ns, 2n], L = R; state float32 [ns]) by the mono sink's default form (k_pcm_sink_scan, csrc/sdrfm_sink.hip): the same segments,
+    chunks and operations as one channel of the stereo scan, from state [ns] (None: zeros)."""
+    alpha, gain = F(alpha), F(gain)
+    pc = F((1.0 - float(alpha)) ** C)
+    x = np.asarray(x, F)
+    ns, n = x.shape
+    y = np.zeros(ns, F) if state is None else np.array(state, F).reshape(ns)
+    vals = np.zeros((ns, n), np.int32)
+    for base in range(0, n, SEG):
+        vals[:, base:base + SEG], y = scan_segment(x[:, base:base + SEG], y, alpha, gain, pc)
+    return np.repeat(vals.astype(np.int16), 2, axis=1), y
+
+
+def mono_host_reference(pkg, x, alpha, gain):
+    """sdrfm_pcm_deemph_s16 per stream over the whole rows: (pcm int16 [ns, 2n], state float32 [ns])"""
+    pcm = np.zeros((x.shape[0], 2 * x.shape[1]), np.int16)
+    st = np.zeros(x.shape[0], np.float32)
+    for s in range(x.shape[0]):
+        pcm[s], st[s] = pkg.pcm_deemph_s16_host(x[s], alpha, gain)
+    return pcm, st
 
 
 def host_reference(pkg, left, right, alpha, gain):
