@@ -39,6 +39,7 @@
 #include "sdrfm_b.h"
 
 static_assert(SDRFM_FM_Q_STEP_OUT == SDRFM_Q_STEP_OUT, "sdrfm_fm_call.h counts design Q's steps");
+static_assert(SDRFM_FM_CHAIN_FIX == SDRFM_CHAIN_FIX, "sdrfm_fm_call.h sizes the runs of a launch with the sink's chain");
 
 namespace {
 
@@ -1875,7 +1876,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
                                2 * (size_t)(c.fir_taps - 1), c.n_streams, hipMemcpyDeviceToDevice, h->stream), SDRFM_FAIL);
     q.hpad = h->d_hpad; q.hist_q_in = h->d_hist_q[h->cur]; q.hist_q_out = h->d_hist_q[h->cur ^ 1];
     q.guard_r = h->q_guard_r; q.guard_a = h->q_guard_a; q.yprev_exact = h->yprev_exact ? 1u : 0u; q.n_repaired = h->d_qstat;
-    const FmRuns r = fm_q_runs(cl, split.q_total, n_clean, with_chain, h->runstate_cap);
+    const FmRuns r = fm_q_runs(cl, split.q_total, n_clean, with_chain, h->runstate_cap, fm_chain_run_quads(g.Da));
     q.runs = r.runs;
     // the window of per-stream repair statistics this call adds to (none while the set's previous read-back is still under way), and
     // whether its kernel's completion carries one of the window's events (the window's last two calls: both internal streams are covered)

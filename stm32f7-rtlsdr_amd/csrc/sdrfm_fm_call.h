@@ -14,6 +14,7 @@
 
 #define SDRFM_FM_Q_STEP_OUT 128u   /* design Q: decimated outputs per wave step (sdrfm_q.h: SDRFM_Q_STEP_OUT; sdrfm.hip asserts they agree) */
 #define SDRFM_FM_LDS_PER_CU 163840u
+#define SDRFM_FM_CHAIN_FIX 64u     /* the PCM sink's chain: audio outputs of a run its predecessor's state still reaches (sdrfm_sink_chain.h: SDRFM_CHAIN_FIX; sdrfm.hip asserts they agree) */
 
 // What sdrfm_create fixes and a call never changes.
 struct FmGeom {
@@ -121,11 +122,21 @@ static inline bool fm_ovl_geometry_ok(const FmGeom& g, const FmCall& c, uint32_t
   return c.n_seen + 1 >= g.T &&
          prev_nbytes >= 2u * g.D * SDRFM_FM_Q_STEP_OUT && (prev_nbytes % 16 == 0) && prev_al16;
 }
+// Quads (32 decimated outputs = 32 / Da audio outputs each) a run spans at least when the sink's chain rides in the launch.  A run publishes its end state from
+// its own outputs alone, as if nothing before them mattered, and its first SDRFM_FM_CHAIN_FIX audio outputs are finished with its predecessor's state: both
+// stand only for a run that OWNS more than SDRFM_FM_CHAIN_FIX audio outputs ((1 - alpha)^64 is below rounding for every alpha the chain serves; a run of
+// 48 would publish a state that lacks (1 - alpha)^48 = 1.6e-6 of what came before it at the 75 us alpha).  One warm-up quad and the owned quads that hold
+// SDRFM_FM_CHAIN_FIX + 2 audio periods (a run's first and last audio output are cut by floor(32 q / Da): one period may be lost): 18 at Da = 8 (17 owned:
+// 68 audio outputs); never fewer than the 13 of Da = 5 (12 owned: 76 audio outputs).
+static inline uint32_t fm_chain_run_quads(uint32_t Da) {
+  const uint32_t own = ((SDRFM_FM_CHAIN_FIX + 2u) * Da + 31u) / 32u;
+  return 1u + (own > 12u ? own : 12u);
+}
 // The sink's chain inside design Q's launch, the part that needs no sink: every stream's whole audio row from this launch (no routed stream unless
 // the one launch serves it, no outputs the generic kernel recomputes behind it at the start of a stream), enough quads for runs longer than their
 // predecessor's reach.
 static inline bool fm_chain_fits(const FmGeom& g, const FmCall& c, bool q_ok, bool mixed, bool fuse) {
-  return q_ok && (!mixed || fuse) && !(c.n_seen + 1 < g.T) && fm_q_quads(c.M) >= 13u;
+  return q_ok && (!mixed || fuse) && !(c.n_seen + 1 < g.T) && fm_q_quads(c.M) >= fm_chain_run_quads(g.Da);
 }
 
 // ---- the machine's wave slots ------------------------------------------------------------------------------------------------------------
@@ -239,14 +250,16 @@ struct FmRuns { uint32_t runs; bool with_chain; };
 static inline uint32_t fm_q_min_steps(uint32_t n_clean, uint32_t q_steps, uint32_t q_total) {
   return ((uint64_t)n_clean * (q_steps / 4) >= (uint64_t)q_total / 2) ? 4u : 2u;
 }
-static inline FmRuns fm_q_runs(const FmCall& c, uint32_t q_total, uint32_t n_clean, bool with_chain, uint32_t runstate_cap) {
+// chain_run_quads: fm_chain_run_quads(Da) of the handle (the default is the BASELINE front end's, Da = 5: the least any rate needs)
+static inline FmRuns fm_q_runs(const FmCall& c, uint32_t q_total, uint32_t n_clean, bool with_chain, uint32_t runstate_cap,
+                               uint32_t chain_run_quads = fm_chain_run_quads(5u)) {
   const uint32_t q_steps = fm_q_steps(c.M), q_quads = fm_q_quads(c.M);
   uint32_t runs = q_total / n_clean;
   const uint32_t min_steps = fm_q_min_steps(n_clean, q_steps, q_total);
   if (runs > q_steps / min_steps) runs = q_steps / min_steps;
-  // (the sink's chain inside the launch: every run must own more outputs than its predecessor's state reaches — 13 quads: 12 owned = 76 audio outputs >=
-  // SDRFM_CHAIN_FIX —: a small call is cut into fewer runs for it)
-  if (with_chain && runs > q_quads / 13u) runs = q_quads / 13u;
+  // (the sink's chain inside the launch: every run must own more outputs than its predecessor's state reaches — fm_chain_run_quads —: a small call is cut
+  // into fewer runs for it)
+  if (with_chain && runs > q_quads / chain_run_quads) runs = q_quads / chain_run_quads;
   if (runs < 1) runs = 1;
   // (the runs' hand-off words were allocated for the largest grid: a launch they cannot hold goes without the chain)
   if (with_chain && (uint64_t)n_clean * runs > runstate_cap) with_chain = false;

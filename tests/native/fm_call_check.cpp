@@ -52,6 +52,7 @@ static FmCall call_of(uint32_t phase_x, uint32_t phase_d, uint32_t nbytes, const
 
 // ---- known answers (T 64, D 10, Ta 32, Da 5; 256 CUs, 12 design-Q waves and 12 mixed workgroups per CU) -------------------------------------------
 static void known_answers() {
+  CHECK(fm_chain_run_quads(5) == 13u && fm_chain_run_quads(8) == 18u && fm_chain_run_quads(1) == 13u, "quads per run under the sink's chain: %u, %u", fm_chain_run_quads(5), fm_chain_run_quads(8));
   const uint64_t seen = 1u << 20;                                // (a stream well past its first T-1 samples)
   {  // 256 streams x 480 000 B: design Q fits, 12 runs per stream, 3072 workgroups
     const FmGeom g = geom(64, 10, 32, 5, 256);
@@ -164,13 +165,15 @@ static void one_case(uint32_t T, uint32_t D, uint32_t Ta, uint32_t Da, int top =
   if (q_ok) {
     const uint32_t steps = fm_q_steps(c.M), cap = g.q_waves_per_cu * g.n_cu;
     const bool want_chain = fm_chain_fits(g, c, q_ok, mixed, fuse) && (rnd() & 1);
-    const FmRuns r = fm_q_runs(c, s.q_total, n_clean, want_chain, cap);
+    const FmRuns r = fm_q_runs(c, s.q_total, n_clean, want_chain, cap, fm_chain_run_quads(Da));
     const uint32_t min_steps = fm_q_min_steps(n_clean, steps, s.q_total);
     CHECK(r.runs >= 1 && (r.runs == 1 || (uint64_t)r.runs * min_steps <= steps), "runs %u x %u of %u steps", r.runs, min_steps, steps);
     CHECK((uint64_t)n_clean * r.runs <= 0xffffffffull, "design Q's grid");
-    CHECK(!r.with_chain || (want_chain && fm_q_quads(c.M) / r.runs >= 13u && (uint64_t)n_clean * r.runs <= cap), "chain: %u runs over %u quads", r.runs,
+    const uint32_t rq = fm_chain_run_quads(Da);                   // 13 at Da = 5, 18 at Da = 8: the owned quads hold more than SDRFM_FM_CHAIN_FIX audio outputs wherever the run is cut
+    CHECK(rq >= 13u && (uint64_t)(rq - 1u) * 32u >= (uint64_t)(SDRFM_FM_CHAIN_FIX + 2u) * Da, "%u quads per run at Da %u", rq, Da);
+    CHECK(!r.with_chain || (want_chain && fm_q_quads(c.M) / r.runs >= rq && (uint64_t)n_clean * r.runs <= cap), "chain: %u runs over %u quads", r.runs,
           fm_q_quads(c.M));
-    CHECK(!want_chain || fm_q_quads(c.M) / r.runs >= 13u, "a run of fewer than 13 quads: %u runs over %u quads", r.runs, fm_q_quads(c.M));
+    CHECK(!want_chain || fm_q_quads(c.M) / r.runs >= rq, "a run of fewer than %u quads: %u runs over %u quads", rq, r.runs, fm_q_quads(c.M));
     CHECK(fm_win_stages(r.runs, steps, Da) >= 1, "window stages");
   }
   if (c.n_seen + 1 < T) {

@@ -23,7 +23,7 @@ int main(int argc, char** argv) {
     const FmCall c = {n.N, n.M, n.A, 0, 0, 1u << 20, true, true};
     const bool q_fit = fm_q_fit(g, c), q_ok = fm_q_ok(q_fit, 0, g.n_streams), fits = fm_chain_fits(g, c, q_ok, false, false);
     const FmSplit s = fm_split(g, c, false, false, 0);
-    const FmRuns r = fm_q_runs(c, s.q_total, g.n_streams, fits, g.q_waves_per_cu * g.n_cu);
+    const FmRuns r = fm_q_runs(c, s.q_total, g.n_streams, fits, g.q_waves_per_cu * g.n_cu, fm_chain_run_quads(g.Da));
     printf("%u %u %u %d %d %u %d\n", nbytes, c.M, c.A, (int)q_fit, (int)fits, r.runs, (int)r.with_chain);
   }
   return 0;

@@ -36,13 +36,20 @@ def _audio(n, seed):
 
 
 @pytest.fixture(scope="module")
-def plan_runs(tmp_path_factory):
-    """{nbytes: (M, A, runs)} of the plan's calls, from the host arithmetic the launch uses"""
+def runs_exe(tmp_path_factory):
+    """tests/native/pcm_chain_runs.cpp, built: the host arithmetic the launch uses"""
     if shutil.which("g++") is None:
         pytest.skip("needs g++")
     exe = str(tmp_path_factory.mktemp("native") / "pcm_chain_runs")
     subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-o", exe, os.path.join(ROOT, "tests/native/pcm_chain_runs.cpp")], check=True, cwd=ROOT,
                    capture_output=True, text=True)
+    return exe
+
+
+@pytest.fixture(scope="module")
+def plan_runs(runs_exe):
+    """{nbytes: (M, A, runs)} of the plan's calls"""
+    exe = runs_exe
     r = subprocess.run([exe, "64", "10", "32", "5", "64", "256", "12"] + [str(n) for n in PLAN_NBYTES], capture_output=True, text=True, check=True, timeout=60)
     out = {}
     for line in r.stdout.splitlines():
@@ -179,3 +186,43 @@ def test_the_chain_just_below_its_upper_end_meets_the_host_routine(pkg, plan_run
     assert emu.chain_tables(alpha)[0] == 2
     got, want, est, st = _emulate_plan(pkg, plan_runs, alpha, GAIN, True, 30)
     _hold(got, want, est, st, alpha)
+
+
+# ---- small calls at both audio decimations: every run owns what its predecessor's state reaches ----------------------------------------------------------------
+@pytest.mark.parametrize("D,Da", [(10, 5), (8, 8), (16, 5)])
+def test_every_run_of_a_small_chained_call_owns_more_than_its_predecessors_reach(pkg, runs_exe, D, Da):
+    """A run publishes its end state from its own outputs alone and finishes its first FIX = 64 outputs with its predecessor's state: both need a run that owns more
+    than 64 AUDIO outputs.  The host counted 13 quads of 32 decimated outputs per run at every rate — 76 audio outputs at Da = 5, but 48 at Da = 8: a 2.048 MS/s call
+    of 832 decimated outputs went out as two runs of 52 audio outputs, and the state the sink carried lacked (1 - alpha)^52 of what came before the run (1.1e-6 of
+    max(|st|, 0.25) on tests/test_q_taps_gpu.py's carriers, measured on the device and reproduced here before csrc/sdrfm_fm_call.h counted audio outputs).  264
+    streams on 256 CUs, every call of 1 .. 52 units of 8 D Da samples: wherever the chain rides in the launch every run owns more than 64 audio outputs, and the
+    state behind two such calls is the host routine's within 1e-6 max(|st|, 0.25)."""
+    lib = pkg.load_library()
+    alpha = pp.alpha_of(lib, "75us")
+    unit = 8 * D * Da
+    sizes = [2 * unit * k for k in range(1, 53)]
+    r = subprocess.run([runs_exe, "7", str(D), "32", str(Da), "264", "256", "12"] + [str(n) for n in sizes], capture_output=True, text=True, check=True, timeout=60)
+    chained, shortest, worst = 0, None, 0.0
+    for line in r.stdout.splitlines():
+        nbytes, M, A, q_fit, fits, runs, with_chain = (int(v) for v in line.split())
+        if not q_fit:
+            assert M < 2 * 128 and not with_chain, line             # (one step per stream does not fill the machine: the bit-exact kernels' call)
+            continue
+        if not with_chain:                                          # (a call too short for one such run: the sink's own kernel follows the launch)
+            continue
+        chained += 1
+        for overlap in (False, True):
+            cuts = emu.run_cuts(M, A, runs, Da, overlap)
+            own = min(c["j1"] - c["jlo"] for c in cuts)
+            shortest = own if shortest is None else min(shortest, own)
+            assert own > emu.FIX, (line, overlap, [(c["jlo"], c["j1"]) for c in cuts])
+        if runs >= 2 and A <= 400:                                  # the smallest calls of two runs and more: the emulated state against the host routine's
+            st = est = 0.0
+            for k in range(2):
+                x = (_audio(A, 50 + k) + np.float32(0.5)).astype(np.float32)
+                _, st = pkg.pcm_deemph_s16_host(x, alpha, GAIN, st)
+                _, est = emu.chain_emulate(x, alpha, GAIN, cuts=emu.run_cuts(M, A, runs, Da, False), state0=est)
+            worst = max(worst, abs(est - st) / max(abs(st), 0.25))
+            assert abs(est - st) <= 1e-6 * max(abs(st), 0.25), (line, est, st)
+    assert chained >= 40 and shortest is not None
+    print("D %d Da %d: %d chained calls, the shortest run owns %d audio outputs; worst state difference %.3g of max(|st|, 0.25)" % (D, Da, chained, shortest, worst))

@@ -7,19 +7,16 @@ positions K = 32 (l >> 4) + 16 h + 4 q .. + 3, kept positions {0, 2} in an I row
 tools/ubench/ubench14.hip found on the device), exact i32 sums, the fp32 recombination — against the oracle's y (its fp32 fmaf
 chain): parity 1e-5 on the audio follows (tools/q_emulate.py, gate (a) of VERDICT r02 item 1).
 """
-import ctypes as C
+import time
 
 import numpy as np
 import pytest
 
+import q_tap_sets as qt
+
 
 def _build(pkg, h, D=10):
-    lib = pkg.load_library()
-    h = np.ascontiguousarray(h, dtype=np.float32)
-    A = np.zeros(((D + 3) // 4, 3, 64, 16), dtype=np.int8)
-    q, cst, c0 = C.c_float(), C.c_float(), C.c_uint32()
-    rc = lib.sdrfm_q_build(h.ctypes.data, h.size, D, A.ctypes.data, C.byref(q), C.byref(cst), C.byref(c0))
-    return rc, A, np.float32(q.value), np.float32(cst.value), c0.value
+    return qt.q_build(pkg, h, D)
 
 
 def _dense(A):
@@ -117,3 +114,73 @@ def test_rejects_what_it_cannot_serve(pkg):
     assert _build(pkg, np.ones(91, np.float32))[0] != 0                    # T > 9 D
     bad = h.copy(); bad[3] = np.inf
     assert _build(pkg, bad)[0] != 0
+
+
+# ---- every tap count sdrfm_create offers design Q, through the instruction model ---------------------------------------------------------------------------
+# The GPU suite met design Q at T in {16, 32, 48, 64} only, this file at {16, 32, 64, 90}; sdrfm_create offers it every T <= 64 at three rates, and the tap
+# count decides which K-chunk the kernel starts at (template C0): floor((9 D - T) / 64).  tests/test_q_taps_gpu.py runs the device over the same shapes.
+SWEEP_BLOCKS = 60                                                          # blocks of 8 outputs per case: 480 outputs, the first 16 left out
+
+
+def _sweep_rows(pkg, D):
+    fs = qt.RATES[D][1]
+    return {"fm": pkg.make_iq(1, 8 * D * SWEEP_BLOCKS, mode="fm", fs=fs, first_id=3)[0],
+            "random": pkg.make_iq(1, 8 * D * SWEEP_BLOCKS, mode="random", first_id=4)[0]}
+
+
+def _check_shape(pkg, oracle_mod, h, g, D, want_c0, rows):
+    """-> what is wrong with the tables of taps h at decimation D (an empty list: nothing), and the worst |y - oracle's y|"""
+    rc, A, q, cst, c0 = _build(pkg, h, D)
+    if rc != 0:
+        return ["sdrfm_q_build returned %d" % rc], float("nan")
+    bad = []
+    if c0 != want_c0:
+        bad.append("first chunk %d, want %d" % (c0, want_c0))
+    if A[:c0].any():
+        bad.append("a tap before the first chunk")
+    worst = 0.0
+    for mode, iq in rows.items():
+        o = oracle_mod.Oracle(h, g, D, qt.RATES[D][0])
+        o.process(iq)
+        yo, _ = o.last_stage()
+        ye = _emulate_blocks(A, q, cst, iq, D).reshape(-1, 2)
+        assert yo.shape[0] == 8 * SWEEP_BLOCKS
+        err = float(np.abs(ye[16:yo.shape[0]].astype(np.float64) - yo[16:]).max())   # (16: the outputs touching the zero history / block 0, as above)
+        worst = max(worst, err)
+        if not err <= 2e-4:
+            bad.append("%s row: y %.3g off the oracle" % (mode, err))
+    return bad, worst
+
+
+@pytest.mark.parametrize("D", [10, 8, 16])
+def test_every_tap_count_through_the_instruction_model(pkg, oracle_mod, D):
+    """T = 1 .. 64 at one rate (64 of the 192 shapes): the tables build, the first chunk is floor((9 D - T) / 64), nothing sits before it, the emulated y is
+    the oracle's within 2e-4 on a carrier and on noise — and sdrfm_create's own conditions on the taps hold, so a default handle does run design Q there."""
+    t0 = time.perf_counter()
+    rows = _sweep_rows(pkg, D)
+    fails, worst, chunks = {}, 0.0, {}
+    for T in range(1, 65):
+        h, g = qt.plain_taps(pkg, T, D)
+        assert h.size == T
+        bad, w = _check_shape(pkg, oracle_mod, h, g, D, qt.first_chunk_by_count(T, D), rows)
+        if not qt.create_offers_design_q(pkg, h, g, D):
+            bad.append("sdrfm_create's conditions reject the taps")
+        if bad:
+            fails[T] = bad
+        worst = max(worst, w)
+        chunks.setdefault(qt.first_chunk_by_count(T, D), []).append(T)
+    print("D = %d: 64 tap counts in %.1f s; first chunk by T: %s; worst |y - oracle's y| %.3g; %d failed" % (
+        D, time.perf_counter() - t0, {c: "%d..%d" % (min(t), max(t)) for c, t in sorted(chunks.items())}, worst, len(fails)))
+    assert not fails, fails
+
+
+@pytest.mark.parametrize("name", qt.VALUE_SETS)
+def test_first_chunk_follows_the_digits_not_the_tap_count(pkg, oracle_mod, name):
+    """Taps whose outer entries are zero, or quantise to zero, start at the chunk their DIGITS imply; zeros at the newest samples' end change nothing."""
+    h, g, D, want_c0 = qt.value_taps(pkg, name)
+    assert want_c0 == {"32-tail-zero": 1, "32-tail-tiny": 1, "16-tail-zero": 1, "64-head-zero": 0}[name]
+    assert want_c0 != qt.first_chunk_by_count(h.size, D) or name == "64-head-zero"      # (the tap count alone says otherwise)
+    bad, worst = _check_shape(pkg, oracle_mod, h, g, D, want_c0, _sweep_rows(pkg, D))
+    print("%s (T = %d, D = %d): first chunk %d, worst |y - oracle's y| %.3g" % (name, h.size, D, want_c0, worst))
+    assert not bad, bad
+    assert qt.create_offers_design_q(pkg, h, g, D)
