@@ -454,6 +454,30 @@ int  sdrfm_bcast_set_stream(sdrfm_bcast_t* h, void* hip_stream);
 int  sdrfm_bcast_synchronize(sdrfm_bcast_t* h);
 const char* sdrfm_bcast_kernel_name(const sdrfm_bcast_t* h);
 
+/* Tuning: stream s of a broadcast handle receives the station at an offset f_s of its input — a 2.4 MS/s capture
+ * holds up to a dozen stations beside the one at 0 Hz — and, with SDRFM_TUNE_SHARED_INPUT, all streams read one shared capture.
+ * A tuned stream has complex channel taps hz[k] = (hr[k], hi[k]), k in [0, T), and a rotation rot, both fp32 and given by the caller
+ * as the pilot taps are: the library computes no trigonometry.  The intended values, evaluated in float64 and rounded once, are
+ *     hz[k] = h[k] exp(+j 2 pi f k / fs),      rot = 2 pi f D / fs wrapped into [-pi, pi]
+ * (the low-pass h moved to f; the phase y gains over D inputs from the offset alone).
+ *   K2  two of the frozen definition's real chains, each exactly K2 (fp32 fmaf, oldest sample first, the same x and history) with
+ *       another tap set: A = sum hr[k] x[..] = (Ar, Ai), B = sum hi[k] x[..] = (Br, Bi); yr = Ar - Bi, yi = Ai + Br, one rounding each.
+ *   K3  re, im as in the frozen K3; d = 0 where both are 0 (no rotation is subtracted: d[0] of a stream stays 0); otherwise
+ *       v = atan2f(im, re) - rot, then v -= 2 pi if v > pi, else v += 2 pi if v < -pi (pi = 0x1.921fb6p+1f, 2 pi = 0x1.921fb6p+2f).
+ * Everything behind d — pilot filter, carriers, audio and RDS chains, counts, decimator phases, the PCM one-call form — is untouched.
+ * The carried state keeps its kind: the input history is raw x, the carried y is the tuned one, the carried d's are de-rotated.
+ *
+ * sdrfm_bcast_tune copies ctaps (n_streams x 2T floats: stream s's (hr[k], hi[k]) pairs at ctaps + s * 2T) and rot (n_streams floats),
+ * takes effect with the next call and zeroes the carried state: a re-tune is a restart.  sdrfm_bcast_reset keeps the tuning.
+ * ctaps == NULL with rot == NULL and flags 0 returns the handle to the untuned kernels and their bits.  Non-finite taps or rot,
+ * |rot| > pi (the fp32 constant above), unknown flags, or only one of ctaps / rot NULL: SDRFM_EINVAL, and nothing is changed.
+ * With SDRFM_TUNE_SHARED_INPUT every stream reads row 0 of iq and iq_stride is ignored; a host-buffer call stages that one row.
+ * sdrfm_bcast_process_batch and sdrfm_bcast_process_batch_pcm take a tuned handle as they take any other; the kernel name then reads
+ * "bcast-fast-tuned ..." or "bcast-generic-tuned ...", the same bits either way.
+ * The mono handle, the stereo-only handle and the RDS-only handle have no tuning. */
+#define SDRFM_TUNE_SHARED_INPUT 1u   /* every stream reads row 0 of iq; iq_stride is ignored */
+int  sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uint32_t flags);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Spectrum view of the IQ buffer — the reference's own next task ("Perform some FFT on the samples to check what we are
  * receiving", README.md:29) on the same buffer contract (RTLSDR_CommItfTypedef.buff, usbh_rtlsdr.h:165-173): per stream

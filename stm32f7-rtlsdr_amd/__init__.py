@@ -18,8 +18,8 @@ from .bcast import BroadcastDemod, BroadcastConfig
 from .rds import RdsDemod, RdsConfig, RdsSync, RdsGroup, rds_parse, rds_encode_groups, rds_checkword, rds_group_bits
 from .spectrum import SpectrumView, SpectrumConfig, power_db
 from .sink import PcmSink, StereoPcmSink, pcm_deemph_s16_host, pcm_deemph_stereo_s16_host
-from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain, rds_gain, rds_lowpass_taps
-from .siggen import make_iq, make_iq_stereo, make_iq_rds, MODES
+from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain, rds_gain, rds_lowpass_taps, tuned_channel_taps, tuned_rotation
+from .siggen import make_iq, make_iq_stereo, make_iq_rds, make_iq_stations, MODES
 from .frontend import ReplayFrontEnd, XferState
 from . import fanout
 from . import lib
@@ -27,4 +27,5 @@ from . import lib
 __all__ = [
     "SdrfmError", "load_library", "library_path", "STATUS", "ABI_SYMBOLS", "FmDemod", "FmConfig", "WbfmDemod", "WbfmConfig", "StereoDemod", "StereoConfig", "BroadcastDemod", "BroadcastConfig", "RdsDemod", "RdsConfig", "RdsSync", "RdsGroup", "rds_parse", "rds_encode_groups", "rds_checkword", "rds_group_bits", "rds_gain", "rds_lowpass_taps", "make_iq_rds", "SpectrumView", "SpectrumConfig", "power_db", "PcmSink", "StereoPcmSink", "pcm_deemph_s16_host", "pcm_deemph_stereo_s16_host", "RTLSDR_FIR",
     "rtlsdr_fir16", "lowpass_taps", "default_config", "stereo_pilot_taps", "stereo_diff_gain", "make_iq", "make_iq_stereo", "MODES", "ReplayFrontEnd", "XferState", "fanout",
+    "tuned_channel_taps", "tuned_rotation", "make_iq_stations",
 ]

@@ -48,6 +48,7 @@ class BroadcastDemod:
         c.rds_taps, c.rds_decim, c.rds_coeffs = self._grc.size, cfg.rds_decim, self._grc.ctypes.data_as(fp)
         c.max_bytes_per_call, c.device = cfg.max_bytes_per_call, cfg.device
         c.flags = CFG_FORCE_GENERIC if cfg.force_generic else 0
+        self._shared_input = False
         self._h = C.c_void_p()
         st = self._lib.sdrfm_bcast_create(C.byref(c), C.byref(self._h))
         if st != _l.OK:
@@ -78,6 +79,28 @@ class BroadcastDemod:
     def reset(self):
         self._ck(self._lib.sdrfm_bcast_reset(self._h), "sdrfm_bcast_reset")
 
+    def tune(self, offsets_hz=None, fs=2.4e6, shared_input=False, ctaps=None, rot=None):
+        """sdrfm_bcast_tune: stream s receives the station at offsets_hz[s] of its input (taps.tuned_channel_taps of
+        the handle's fir_coeffs and taps.tuned_rotation at fs), or the caller's own ctaps [n_streams, 2T] and rot [n_streams];
+        shared_input: every stream reads row 0 of the input.  No argument at all returns the handle to the untuned kernels.  The carried
+        state is zeroed either way."""
+        from .taps import tuned_channel_taps, tuned_rotation
+        ns = self.cfg.n_streams
+        if offsets_hz is not None:
+            assert ctaps is None and rot is None, "offsets_hz or ctaps / rot, not both"
+            off = np.broadcast_to(np.asarray(offsets_hz, dtype=np.float64), (ns,))
+            ctaps = np.stack([tuned_channel_taps(self._hc, f, fs) for f in off])
+            rot = np.array([tuned_rotation(f, fs, self.cfg.fir_decim) for f in off], dtype=np.float32)
+        if ctaps is not None:
+            ctaps = np.ascontiguousarray(ctaps, dtype=np.float32)
+            assert ctaps.size == ns * 2 * self._hc.size, (ctaps.shape, ns, self._hc.size)
+        if rot is not None:
+            rot = np.ascontiguousarray(rot, dtype=np.float32)
+            assert rot.size == ns, (rot.shape, ns)
+        self._ck(self._lib.sdrfm_bcast_tune(self._h, ctaps.ctypes.data if ctaps is not None else None, rot.ctypes.data if rot is not None else None,
+                                            _l.TUNE_SHARED_INPUT if shared_input else 0), "sdrfm_bcast_tune")
+        self._shared_input = bool(shared_input) and ctaps is not None
+
     def counts(self, nbytes):
         """(audio outputs per channel, complex RDS outputs) per stream of the NEXT call of nbytes"""
         na, nr = C.c_uint32(), C.c_uint32()
@@ -100,13 +123,14 @@ class BroadcastDemod:
         iq = np.ascontiguousarray(iq, dtype=np.uint8)
         if iq.ndim == 1:
             iq = iq[None, :]
-        assert iq.shape[0] == self.cfg.n_streams
+        ns = self.cfg.n_streams
+        assert iq.shape[0] == (1 if self._shared_input else ns)                # (a shared capture is one row)
         nbytes = iq.shape[1]
         ca, cr = (max(v, 1) for v in self.counts(nbytes & ~1))
-        left = np.zeros((iq.shape[0], ca), dtype=np.float32)
+        left = np.zeros((ns, ca), dtype=np.float32)
         right = np.zeros_like(left)
-        bb = np.zeros((iq.shape[0], 2 * cr), dtype=np.float32)
-        pc = np.zeros(iq.shape[0], dtype=np.uint32)
+        bb = np.zeros((ns, 2 * cr), dtype=np.float32)
+        pc = np.zeros(ns, dtype=np.uint32)
         na, nr = C.c_uint32(), C.c_uint32()
         self._ck(self._lib.sdrfm_bcast_process_batch(self._h, iq.ctypes.data, nbytes, nbytes, left.ctypes.data, right.ctypes.data, ca,
                                                      bb.ctypes.data, 2 * cr, pc.ctypes.data, C.byref(na), C.byref(nr), 0),
@@ -132,14 +156,15 @@ class BroadcastDemod:
         iq = np.ascontiguousarray(iq, dtype=np.uint8)
         if iq.ndim == 1:
             iq = iq[None, :]
-        assert iq.shape[0] == self.cfg.n_streams
+        ns = self.cfg.n_streams
+        assert iq.shape[0] == (1 if self._shared_input else ns)                # (a shared capture is one row)
         nbytes = iq.shape[1]
         ca, cr = (max(v, 1) for v in self.counts(nbytes & ~1))
-        left = np.zeros((iq.shape[0], ca), dtype=np.float32) if with_audio else None
+        left = np.zeros((ns, ca), dtype=np.float32) if with_audio else None
         right = np.zeros_like(left) if with_audio else None
-        pcm = np.zeros((iq.shape[0], 2 * ca), dtype=np.int16)
-        bb = np.zeros((iq.shape[0], 2 * cr), dtype=np.float32)
-        pc = np.zeros(iq.shape[0], dtype=np.uint32)
+        pcm = np.zeros((ns, 2 * ca), dtype=np.int16)
+        bb = np.zeros((ns, 2 * cr), dtype=np.float32)
+        pc = np.zeros(ns, dtype=np.uint32)
         na, nr = C.c_uint32(), C.c_uint32()
         self._ck(self._lib.sdrfm_bcast_process_batch_pcm(self._h, sink._h, iq.ctypes.data, nbytes, nbytes, left.ctypes.data if with_audio else None,
                                                          right.ctypes.data if with_audio else None, ca, pcm.ctypes.data, 2 * ca, bb.ctypes.data, 2 * cr,

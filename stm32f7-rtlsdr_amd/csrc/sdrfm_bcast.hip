@@ -14,6 +14,10 @@
  * chains to some of the waves and the audio outputs to the others where that is the shorter way (bcast_rds_waves).
  *
  * k_bcast<0, 0, 0> and k_bcast<64, 10, 101> are the header's two forms of the walk; the carriers and the chains are the same code in both.
+ *
+ * A tuned handle (sdrfm_bcast_tune) launches the same two with the header's tuned walk: every stream has complex channel
+ * taps and a rotation of its own and receives the station at that offset of its input — or of row 0 of the input, which all streams
+ * then share.  Only K2 and K3 differ; everything behind d is the code above.
  */
 #include <new>
 
@@ -37,6 +41,8 @@ struct BcastParams : FrontParams {
   uint32_t Aa, Ar;             // outputs of the call
   int32_t f0a, f0r;            // the newest d of output 0 of either decimator
   uint32_t zplane;             // words of one z plane: Tr - 1 + NDT, made odd
+  const float* ctaps;          // tuned: [ns][2T], (hr[k], hi[k]) pairs
+  const float* rot;            // tuned: [ns]
 };
 
 // how many of a workgroup's nw waves take a step's nc RDS chains (of Tr links), the others taking its na audio outputs (of 2 Ta links):
@@ -50,16 +56,16 @@ __device__ __forceinline__ int bcast_rds_waves(int nw, int nc, int Tr, int na, i
   return wr;
 }
 
-template <int FT, int FD, int FP>
+template <int FT, int FD, int FP, bool TU>
 __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t T = FT > 0 ? FT : p.T, P = FT > 0 ? FP : p.P;
   const uint32_t Ta = p.Ta, Da = p.Da, Tr = p.Tr, Dr = p.Dr, H = p.H, Dl = p.Dl, NY = p.NY, NDT = p.NDT, ZP = p.zplane;
   const int Tm = (int)(Ta > Tr ? Ta : Tr), oa = Tm - (int)Ta, oz = Tm - (int)Tr;
-  // LDS: region (x as f16 pairs | d's, s's, zr's, zi's) | ys[NY] | hb[H] | tps[P] | grs[Tr] | gas[Ta] | hs[T] | zb[2 (Tr - 1)] | sb[Ta - 1];
+  // LDS: region (x as f16 pairs | d's, s's, zr's, zi's) | ys[NY] | hb[H] | tps[P] | grs[Tr] | gas[Ta] | hs[T; tuned: 2T] | zb[2 (Tr - 1)] | sb[Ta - 1];
   // hb and tps padded so that grs starts on 16 bytes.  grs holds the RDS taps oldest first (grs[k] = gr[Tr - 1 - k]): the output chains
   // read them four at a time
-  FrontWg<FT, FD, FP> w;
+  FrontWg<FT, FD, FP, TU> w;
   w.xs = reinterpret_cast<h2_t*>(smem);
   w.ds = reinterpret_cast<float*>(smem);
   float* ss = w.ds + H + NDT;                                   // [Ta - 1 + NDT]: s of the carried and the new d's
@@ -70,8 +76,13 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   float* grs = reinterpret_cast<float*>(w.tps + ((P + 1) & ~1u));
   float* gas = grs + ((Tr + 3) & ~3u);
   w.hs = gas + Ta;
-  float* zb = w.hs + T;                                         // the last Tr - 1 (zr, zi), plane by plane, for the next step
+  float* zb = w.hs + (TU ? 2 * T : T);                                        // the last Tr - 1 (zr, zi), plane by plane, for the next step
   float* sb = zb + 2 * (Tr - 1);                                // the last Ta - 1 s's
+  if constexpr (TU) {
+    const uint32_t st = blockIdx.x / p.blocks_per_stream;
+    w.ctaps = p.ctaps + (size_t)st * 2 * T;
+    w.rot = p.rot[st];
+  }
   front_begin(p, w);
   const int tid = w.tid, nthr = w.nthr, lo = (int)(w.blk * p.span);
   const uint32_t s = w.s;
@@ -144,6 +155,13 @@ struct sdrfm_bcast {
   FrontStep step;                              // of the kernel this handle launches
   uint32_t slots = 1;                          // workgroups the device runs at a time (compute units x workgroups per unit)
   char kernel_name[112];
+  // the tuned form (sdrfm_bcast_tune): its own kernels, step, slots and name; the taps and rotations the handle was last tuned with
+  bool tuned = false, shared_input = false, fast_tuned = false;
+  FrontStep step_tuned;
+  uint32_t slots_tuned = 1;
+  char kernel_name_tuned[112];
+  float* d_ctaps = nullptr;                    // [ns][2T]
+  float* d_rot = nullptr;                      // [ns]
 };
 
 namespace {
@@ -161,11 +179,17 @@ size_t bcast_lds(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t H, ui
          4 * (size_t)T + 8 * (size_t)(Tr - 1) + 4 * (size_t)(Ta - 1);
 }
 
+// the tuned kernels keep both tap sets in LDS: T more words
+size_t bcast_lds_tuned(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t H, uint32_t NY, uint32_t NDT, uint32_t* region_words) {
+  return bcast_lds(T, D, P, Tg, H, NY, NDT, region_words) + 4 * (size_t)T;
+}
+
 void bcast_free(sdrfm_bcast* h) {
   if (!h) return;
   front_free(h->f);
   decim_free(h->au); decim_free(h->rd);
   (void)hipFree(h->d_left); (void)hipFree(h->d_right); (void)hipFree(h->d_bb);
+  (void)hipFree(h->d_ctaps); (void)hipFree(h->d_rot);
   delete h;
 }
 
@@ -214,7 +238,13 @@ int sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out) {
   if (!h->fast) h->step = front_step_generic(bcast_lds, T, D, P, bcast_tg(Ta, Tr), H);
   if (h->fast) snprintf(h->kernel_name, sizeof h->kernel_name, "bcast-fast T64 D10 P101 Ta%u Da%u Tr%u Dr%u", Ta, Da, Tr, Dr);
   else snprintf(h->kernel_name, sizeof h->kernel_name, "bcast-generic T%u D%u P%u Ta%u Da%u Tr%u Dr%u", T, D, P, Ta, Da, Tr, Dr);
-  h->slots = front_slots(k_bcast<64, 10, 101>, k_bcast<0, 0, 0>, h->fast, h->step.lds, prop);
+  h->slots = front_slots(k_bcast<64, 10, 101, false>, k_bcast<0, 0, 0, false>, h->fast, h->step.lds, prop);
+  h->step_tuned = front_step(bcast_lds_tuned, 64, 10, 101, bcast_tg(Ta, Tr), H, PF_FAST_NY, PF_FAST_NY - 1);
+  h->fast_tuned = !(cfg->flags & SDRFM_BCAST_CFG_FORCE_GENERIC) && T == 64 && D == 10 && P == 101 && h->step_tuned.lds <= PF_LDS_BUDGET;
+  if (!h->fast_tuned) h->step_tuned = front_step_generic(bcast_lds_tuned, T, D, P, bcast_tg(Ta, Tr), H);
+  if (h->fast_tuned) snprintf(h->kernel_name_tuned, sizeof h->kernel_name_tuned, "bcast-fast-tuned T64 D10 P101 Ta%u Da%u Tr%u Dr%u", Ta, Da, Tr, Dr);
+  else snprintf(h->kernel_name_tuned, sizeof h->kernel_name_tuned, "bcast-generic-tuned T%u D%u P%u Ta%u Da%u Tr%u Dr%u", T, D, P, Ta, Da, Tr, Dr);
+  h->slots_tuned = front_slots(k_bcast<64, 10, 101, true>, k_bcast<0, 0, 0, true>, h->fast_tuned, h->step_tuned.lds, prop);
   rc = sdrfm_bcast_reset(h);
   if (rc != SDRFM_OK) { bcast_free(h); return rc; }
   *out = h;
@@ -246,14 +276,25 @@ int sdrfm_bcast_counts(const sdrfm_bcast_t* h, uint32_t nbytes, uint32_t* n_audi
   return SDRFM_OK;
 }
 
+static bool bcast_shared(const sdrfm_bcast* h) { return h->tuned && h->shared_input; }
+
+// a host-buffer call's input -> the handle's staging rows; one row where the streams share it
+static int bcast_stage_in(const sdrfm_bcast* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes) {
+  if (!bcast_shared(h)) return front_stage_in(h->f, iq, iq_stride, nbytes);
+  return hipMemcpyAsync(h->f.d_iq, iq, nbytes, hipMemcpyHostToDevice, h->f.stream) == hipSuccess ? SDRFM_OK : SDRFM_FAIL;
+}
+
 // one call on device buffers, enqueued on the handle's stream
 static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, float* d_left, float* d_right, size_t audio_stride,
                          float* d_bb, size_t bb_stride, uint32_t* d_pc, uint32_t* n_audio, uint32_t* n_rds) {
   const uint32_t ns = h->cfg.n_streams;
-  if (h->step.lds > PF_LDS_BUDGET) return SDRFM_FAIL;            // (no shape within the header's limits gets here: NY = 2 fits them all)
+  const FrontStep& step = h->tuned ? h->step_tuned : h->step;
+  if (step.lds > PF_LDS_BUDGET) return SDRFM_FAIL;               // (no shape within the header's limits gets here: NY = 2 fits them all)
   BcastParams p;
   memset(&p, 0, sizeof p);
-  front_fill(h->f, p, d_iq, iq_stride, nbytes, d_pc, h->step);
+  if (h->tuned && h->shared_input) iq_stride = 0;                // every stream reads row 0
+  front_fill(h->f, p, d_iq, iq_stride, nbytes, d_pc, step);
+  p.ctaps = h->d_ctaps; p.rot = h->d_rot;
   const uint32_t M = p.M, Aa = decim_outputs(h->au, M), Ar = decim_outputs(h->rd, M);
   p.left = d_left; p.right = d_right; p.audio_stride = audio_stride;
   p.bb = d_bb; p.bb_stride = bb_stride;
@@ -265,12 +306,17 @@ static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, 
   p.f0a = decim_f0(h->au);
   p.f0r = decim_f0(h->rd);
   p.zplane = rds_zplane(p.Tr, p.NDT);
-  p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, h->slots);   // as the RDS handle chooses them
+  p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, h->tuned ? h->slots_tuned : h->slots);   // as the RDS handle chooses them
   p.span = M ? (M + p.blocks_per_stream - 1) / p.blocks_per_stream : 0;
   if (front_zero_count(h->f, d_pc, true) != SDRFM_OK) return SDRFM_FAIL;
   const dim3 grid(ns * p.blocks_per_stream), block(PF_THREADS);
-  if (h->fast) k_bcast<64, 10, 101><<<grid, block, h->step.lds, h->f.stream>>>(p);
-  else k_bcast<0, 0, 0><<<grid, block, h->step.lds, h->f.stream>>>(p);
+  if (h->tuned) {
+    if (h->fast_tuned) k_bcast<64, 10, 101, true><<<grid, block, step.lds, h->f.stream>>>(p);
+    else k_bcast<0, 0, 0, true><<<grid, block, step.lds, h->f.stream>>>(p);
+  } else {
+    if (h->fast) k_bcast<64, 10, 101, false><<<grid, block, step.lds, h->f.stream>>>(p);
+    else k_bcast<0, 0, 0, false><<<grid, block, step.lds, h->f.stream>>>(p);
+  }
   if (hipGetLastError() != hipSuccess) return SDRFM_FAIL;
   front_advance(h->f, p.N);
   decim_advance(h->au, M);
@@ -294,7 +340,7 @@ int sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_str
     return front_empty_call(h->f, pilot_count, flags);
   }
   if (!iq) return SDRFM_EINVAL;
-  if (ns > 1 && iq_stride < nbytes) return SDRFM_ECAPACITY;
+  if (ns > 1 && !bcast_shared(h) && iq_stride < nbytes) return SDRFM_ECAPACITY;
   uint32_t Aa = 0, Ar = 0;
   (void)sdrfm_bcast_counts(h, nbytes, &Aa, &Ar);
   if (Aa && (!left || !right)) return SDRFM_EINVAL;
@@ -304,7 +350,7 @@ int sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_str
   if (flags & SDRFM_F_DEVICE_PTRS)
     return bcast_enqueue(h, iq, iq_stride, nbytes, left, right, audio_stride, bb, bb_stride, pilot_count, n_audio, n_rds);
 
-  if (front_stage_in(h->f, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
+  if (bcast_stage_in(h, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
   const int rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc,
                                n_audio, n_rds);
   if (rc != SDRFM_OK) return rc;
@@ -335,7 +381,7 @@ int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sin
     return front_empty_call(h->f, pilot_count, flags);
   }
   if (!iq) return SDRFM_EINVAL;
-  if (ns > 1 && iq_stride < nbytes) return SDRFM_ECAPACITY;
+  if (ns > 1 && !bcast_shared(h) && iq_stride < nbytes) return SDRFM_ECAPACITY;
   if (Ar && !bb) return SDRFM_EINVAL;
   if (ns > 1 && ((left && audio_stride < Aa) || bb_stride < 2 * (size_t)Ar)) return SDRFM_ECAPACITY;
   if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
@@ -352,7 +398,7 @@ int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sin
   size_t d_pcm_stride = 0;
   rc = sdrfm_stereo_sink_reserve(sink, Aa, &d_pcm, &d_pcm_stride);   // (before anything is enqueued: a refusal leaves both handles alone)
   if (rc != SDRFM_OK) return rc;
-  if (front_stage_in(h->f, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
+  if (bcast_stage_in(h, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
   rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc, n_audio, n_rds);
   if (rc != SDRFM_OK) return rc;
   rc = sdrfm_stereo_sink_launch_on(sink, h->d_left, h->d_right, h->d_audio_stride, Aa, d_pcm, d_pcm_stride, h->f.stream);
@@ -376,6 +422,39 @@ int sdrfm_bcast_synchronize(sdrfm_bcast_t* h) {
   return SDRFM_OK;
 }
 
-const char* sdrfm_bcast_kernel_name(const sdrfm_bcast_t* h) { return h ? h->kernel_name : ""; }
+const char* sdrfm_bcast_kernel_name(const sdrfm_bcast_t* h) { return h ? (h->tuned ? h->kernel_name_tuned : h->kernel_name) : ""; }
+
+int sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uint32_t flags) {
+  if (!h) return SDRFM_EINVAL;
+  if (!ctaps != !rot) return SDRFM_EINVAL;
+  if (flags & ~SDRFM_TUNE_SHARED_INPUT) return SDRFM_EINVAL;
+  const uint32_t ns = h->cfg.n_streams, T = h->f.T;
+  if (!ctaps) {                                                  // back to the untuned kernels
+    if (flags) return SDRFM_EINVAL;
+    const int rc = sdrfm_bcast_reset(h);                         // (waits for the handle's stream: no launch reads the taps any more)
+    if (rc != SDRFM_OK) return rc;
+    h->tuned = h->shared_input = false;
+    return SDRFM_OK;
+  }
+  if (!finite_all(ctaps, ns * 2 * T) || !finite_all(rot, ns)) return SDRFM_EINVAL;
+  for (uint32_t s = 0; s < ns; ++s)
+    if (std::fabs(rot[s]) > 0x1.921fb6p+1f) return SDRFM_EINVAL;
+  if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
+  if (!h->d_ctaps) {
+    float *dc = nullptr, *dr = nullptr;
+    if (hipMalloc(&dc, sizeof(float) * ns * 2 * T) != hipSuccess || hipMalloc(&dr, sizeof(float) * ns) != hipSuccess) {
+      (void)hipFree(dc);
+      return SDRFM_ENOMEM;
+    }
+    h->d_ctaps = dc; h->d_rot = dr;
+  }
+  if (hipStreamSynchronize(h->f.stream) != hipSuccess) return SDRFM_FAIL;   // no launch still reads the taps about to be replaced
+  if (hipMemcpy(h->d_ctaps, ctaps, sizeof(float) * ns * 2 * T, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->d_rot, rot, sizeof(float) * ns, hipMemcpyHostToDevice) != hipSuccess)
+    return SDRFM_FAIL;
+  h->tuned = true;
+  h->shared_input = (flags & SDRFM_TUNE_SHARED_INPUT) != 0;
+  return sdrfm_bcast_reset(h);
+}
 
 }  // extern "C"

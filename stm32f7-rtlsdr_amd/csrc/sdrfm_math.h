@@ -53,4 +53,16 @@ SDRFM_HD float sdrfm_discriminate(float yr, float yi, float pr, float pi) {
   return (re == 0.0f && im == 0.0f) ? 0.0f : a;
 }
 
+/* K3 of a tuned stream: the discriminator above with the rotation of D input samples at the stream's offset taken
+ * off and the difference wrapped once into [-pi, pi].  re and im are sdrfm_discriminate's; where both are 0 the result is 0 and no
+ * rotation is subtracted (d[0] of a stream stays 0).  |rot| <= pi, so one wrap is enough. */
+SDRFM_HD float sdrfm_discriminate_tuned(float yr, float yi, float pr, float pi, float rot) {
+  const float re = __builtin_fmaf(yr, pr, yi * pi);
+  const float im = yi * pr - yr * pi;
+  float v = sdrfm_atan2f(im, re) - rot;
+  if (v > 0x1.921fb6p+1f) v -= 0x1.921fb6p+2f;
+  else if (v < -0x1.921fb6p+1f) v += 0x1.921fb6p+2f;
+  return (re == 0.0f && im == 0.0f) ? 0.0f : v;
+}
+
 #endif

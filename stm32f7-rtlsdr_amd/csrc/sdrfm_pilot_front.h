@@ -18,6 +18,10 @@
  * Two forms of every stage, chosen by the kernel's template arguments: <0, 0, 0> takes every shape with runtime loops, one output per
  * lane; <64, 10, 101> keeps the taps in registers and gives each lane 4 consecutive y's (one pass over their inputs) and 4 consecutive
  * pilot outputs (one pass over their d's).  Every chain is evaluated in the same order, so both are bit-identical.
+ *
+ * A fourth template argument gives the tuned form of the walk (the broadcast kernel's only): the stream's own complex
+ * channel taps (hr, hi) and rotation.  K2 is then two of the real chains above over the same staged x — A with hr, B with hi,
+ * y = (Ar - Bi, Ai + Br) — and K3 is sdrfm_discriminate_tuned.  The fast form reloads its 64 tap registers between the two passes.
  */
 #ifndef SDRFM_PILOT_FRONT_H
 #define SDRFM_PILOT_FRONT_H
@@ -67,19 +71,21 @@ struct FrontParams {
 };
 
 // a workgroup's view of the walk: the kernel lays out its LDS and sets the six pointers, front_begin fills in the rest
-template <int FT, int FD, int FP>
+template <int FT, int FD, int FP, bool TU = false>
 struct FrontWg {
   h2_t* xs;                    // region: x as f16 pairs ...
   float* ds;                   // ... or [H + NDT]: the carried d's, then the step's new ones (the kernel's own arrays follow)
   f2_t* ys;                    // [NY]
   float* hb;                   // [H]: the last H d's, for the next step / the hand-over
   f2_t* tps;                   // [P]
-  float* hs;                   // [T]
+  float* hs;                   // [T]; tuned: [2T], hr then hi
   uint32_t T, D, P, s, blk;
   int tid, nthr;
   f2_t yprev;
   const uint8_t* row;
-  float hv[FT > 0 ? FT : 1];
+  const float* ctaps;          // tuned: the stream's 2T floats, (hr[k], hi[k]) pairs; set by the kernel
+  float rot;                   // tuned: the stream's rotation; set by the kernel
+  float hv[(FT > 0 && !TU) ? FT : 1];
 };
 
 __device__ __forceinline__ h2_t pack_x(float a, float b) { return __builtin_amdgcn_cvt_pkrtz(a, b); }   // exact: a, b in {k - 127.5, 0}
@@ -107,15 +113,19 @@ __device__ __forceinline__ float2 x_at_f(const FrontParams& p, uint32_t s, int n
 __device__ __forceinline__ f2_t fma2(f2_t a, f2_t b, f2_t c) { return __builtin_elementwise_fma(a, b, c); }
 
 // the workgroup's stream and place in it, the channel and pilot taps -> LDS (fast: the channel taps -> registers too), the carried y
-template <int FT, int FD, int FP>
-__device__ __forceinline__ void front_begin(const FrontParams& p, FrontWg<FT, FD, FP>& w) {
+template <int FT, int FD, int FP, bool TU>
+__device__ __forceinline__ void front_begin(const FrontParams& p, FrontWg<FT, FD, FP, TU>& w) {
   constexpr bool FAST = FT > 0;
   w.T = FAST ? FT : p.T; w.D = FAST ? FD : p.D; w.P = FAST ? FP : p.P;
   w.tid = (int)threadIdx.x; w.nthr = (int)blockDim.x;
   w.s = blockIdx.x / p.blocks_per_stream; w.blk = blockIdx.x % p.blocks_per_stream;
   for (int k = w.tid; k < (int)w.P; k += w.nthr) { const float2 t = p.tp[k]; w.tps[k] = f2_t{t.x, t.y}; }
-  for (int k = w.tid; k < (int)w.T; k += w.nthr) w.hs[k] = p.h[k];
-  if constexpr (FAST) {
+  if constexpr (TU) {
+    for (int k = w.tid; k < (int)w.T; k += w.nthr) { w.hs[k] = w.ctaps[2 * k]; w.hs[w.T + k] = w.ctaps[2 * k + 1]; }
+  } else {
+    for (int k = w.tid; k < (int)w.T; k += w.nthr) w.hs[k] = p.h[k];
+  }
+  if constexpr (FAST && !TU) {
 #pragma unroll
     for (int k = 0; k < FT; ++k) {
       w.hv[k] = p.h[k];
@@ -126,9 +136,41 @@ __device__ __forceinline__ void front_begin(const FrontParams& p, FrontWg<FT, FD
   w.row = p.iq + (size_t)w.s * p.iq_stride;
 }
 
+// the fast K2 pass: 4 consecutive y's of one lane from one read of their inputs at w4, each chain oldest first with the taps in hv
+template <int FT, int FD>
+__device__ __forceinline__ void front_k2_pass(const uint4* w4, const float (&hv)[FT], f2_t (&acc)[4]) {
+  constexpr int R = 4, NW = (R - 1) * FD + FT, NW4 = (NW + 3) / 4;
+#pragma unroll
+  for (int r = 0; r < R; ++r) acc[r] = f2_t{0.f, 0.f};
+#pragma unroll
+  for (int j4 = 0; j4 < NW4; ++j4) {
+    const uint4 v = w4[j4];
+    const uint32_t ww[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int j = 4 * j4 + q;
+      const f2_t x = unpack_x(__builtin_bit_cast(h2_t, ww[q]));
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int jj = j - r * FD;                            // position in y[u0 + r]'s window, oldest first
+        if (jj >= 0 && jj < FT) acc[r] = fma2(f2_t{hv[FT - 1 - jj], hv[FT - 1 - jj]}, x, acc[r]);
+      }
+    }
+  }
+}
+
+// the fast tuned K2's tap registers: one of the two tap sets from LDS (wave-uniform reads), held in VGPRs as front_begin holds the untuned ones
+template <int FT>
+__device__ __forceinline__ void front_taps_to_regs(const float* hs, float (&hv)[FT]) {
+#pragma unroll
+  for (int k = 0; k < FT; ++k) hv[k] = hs[k];                 // (hs is aligned to 4 bytes only: the kernel's arrays before it have any length)
+#pragma unroll
+  for (int k = 0; k < FT; ++k) asm volatile("" : "+v"(hv[k]));
+}
+
 // a step's d's: stage x, K2, K3.  Leaves ds = [the H carried d's | d[a .. b)] and hb = the last H of them; stores yprev_out at the chunk's end
-template <int FT, int FD, int FP>
-__device__ __forceinline__ void front_d_stage(const FrontParams& p, const FrontWg<FT, FD, FP>& w, int a, int b) {
+template <int FT, int FD, int FP, bool TU>
+__device__ __forceinline__ void front_d_stage(const FrontParams& p, const FrontWg<FT, FD, FP, TU>& w, int a, int b) {
   constexpr bool FAST = FT > 0;
   const uint32_t T = w.T, D = w.D, H = p.H, s = w.s;
   const int tid = w.tid, nthr = w.nthr;
@@ -163,30 +205,37 @@ __device__ __forceinline__ void front_d_stage(const FrontParams& p, const FrontW
   __syncthreads();
   // ---- K2: ys[u] = y[yA + u]
   if constexpr (FAST) {
-    constexpr int R = 4, NW = (R - 1) * FD + FT, NW4 = (NW + 3) / 4;
+    constexpr int R = 4;
     const int u0 = R * tid;
     if (u0 < ny) {
       const uint4* w4 = reinterpret_cast<const uint4*>(xs + u0 * FD);   // 16 * FD * tid bytes: aligned
       f2_t acc[R];
+      if constexpr (TU) {                                     // the pass with hr, the registers reloaded with hi, the pass again
+        float hv[FT];
+        f2_t accb[R];
+        front_taps_to_regs<FT>(w.hs, hv);
+        front_k2_pass<FT, FD>(w4, hv, acc);
+        front_taps_to_regs<FT>(w.hs + FT, hv);
+        front_k2_pass<FT, FD>(w4, hv, accb);
 #pragma unroll
-      for (int r = 0; r < R; ++r) acc[r] = f2_t{0.f, 0.f};
-#pragma unroll
-      for (int j4 = 0; j4 < NW4; ++j4) {
-        const uint4 v = w4[j4];
-        const uint32_t ww[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int j = 4 * j4 + q;
-          const f2_t x = unpack_x(__builtin_bit_cast(h2_t, ww[q]));
-#pragma unroll
-          for (int r = 0; r < R; ++r) {
-            const int jj = j - r * FD;                        // position in y[u0 + r]'s window, oldest first
-            if (jj >= 0 && jj < FT) acc[r] = fma2(f2_t{w.hv[FT - 1 - jj], w.hv[FT - 1 - jj]}, x, acc[r]);
-          }
-        }
+        for (int r = 0; r < R; ++r) acc[r] = f2_t{acc[r].x - accb[r].y, acc[r].y + accb[r].x};
+      } else {
+        front_k2_pass<FT, FD>(w4, w.hv, acc);
       }
 #pragma unroll
       for (int r = 0; r < R; ++r) ys[u0 + r] = acc[r];
+    }
+  } else if constexpr (TU) {
+    for (int u = tid; u < ny; u += nthr) {
+      const h2_t* win = xs + u * (int)D;
+      f2_t acc = f2_t{0.f, 0.f}, accb = f2_t{0.f, 0.f};
+      for (uint32_t j = 0; j < T; ++j) {
+        const float cr = w.hs[T - 1 - j], ci = w.hs[2 * T - 1 - j];
+        const f2_t x = unpack_x(win[j]);
+        acc = fma2(f2_t{cr, cr}, x, acc);
+        accb = fma2(f2_t{ci, ci}, x, accb);
+      }
+      ys[u] = f2_t{acc.x - accb.y, acc.y + accb.x};
     }
   } else {
     for (int u = tid; u < ny; u += nthr) {
@@ -206,7 +255,8 @@ __device__ __forceinline__ void front_d_stage(const FrontParams& p, const FrontW
     } else {
       const f2_t y = ys[i - yA];
       const f2_t pr = (i == 0) ? w.yprev : ys[i - 1 - yA];
-      d = sdrfm_discriminate(y.x, y.y, pr.x, pr.y);
+      if constexpr (TU) d = sdrfm_discriminate_tuned(y.x, y.y, pr.x, pr.y, w.rot);
+      else d = sdrfm_discriminate(y.x, y.y, pr.x, pr.y);
     }
     ds[H + k] = d;
   }
@@ -217,8 +267,8 @@ __device__ __forceinline__ void front_d_stage(const FrontParams& p, const FrontW
 }
 
 // the pilot filter over a step's ds: use(o, q) for every output o in [O0, C) this lane serves, o's window being ds[o .. o + P)
-template <int FT, int FD, int FP, typename Use>
-__device__ __forceinline__ void front_pilot(const FrontWg<FT, FD, FP>& w, int O0, int C, Use use) {
+template <int FT, int FD, int FP, bool TU, typename Use>
+__device__ __forceinline__ void front_pilot(const FrontWg<FT, FD, FP, TU>& w, int O0, int C, Use use) {
   const float* ds = w.ds;
   const f2_t* tps = w.tps;
   if constexpr (FT > 0) {
@@ -254,8 +304,8 @@ __device__ __forceinline__ void front_pilot(const FrontWg<FT, FD, FP>& w, int O0
 }
 
 // the workgroup's span: the prologue's steps (the H d's before it), then its own; step(a, b, full) takes d[a .. b), b - a <= NDT
-template <int FT, int FD, int FP, typename Step>
-__device__ __forceinline__ void front_walk(const FrontParams& p, const FrontWg<FT, FD, FP>& w, Step step) {
+template <int FT, int FD, int FP, bool TU, typename Step>
+__device__ __forceinline__ void front_walk(const FrontParams& p, const FrontWg<FT, FD, FP, TU>& w, Step step) {
   const int NDT = (int)p.NDT, lo = (int)(w.blk * p.span);
   int hi = lo + (int)p.span;
   if (hi > (int)p.M) hi = (int)p.M;
@@ -272,8 +322,8 @@ __device__ __forceinline__ void front_count(const FrontParams& p, uint32_t s, in
 }
 
 // state hand-over by the workgroup that ends the chunk
-template <int FT, int FD, int FP>
-__device__ __forceinline__ void front_hand_over(const FrontParams& p, const FrontWg<FT, FD, FP>& w) {
+template <int FT, int FD, int FP, bool TU>
+__device__ __forceinline__ void front_hand_over(const FrontParams& p, const FrontWg<FT, FD, FP, TU>& w) {
   const uint32_t T = w.T, H = p.H, s = w.s;
   if (w.blk + 1 == p.blocks_per_stream) {
     for (int k = w.tid; k < (int)H; k += w.nthr) p.hist_d_out[(size_t)s * H + k] = w.hb[k];

@@ -11,6 +11,7 @@ STATUS = {
 OK, EINVAL, EODD, ECAPACITY, NO_DEVICE = 0, 16, 17, 18, 19
 F_DEVICE_PTRS = 1
 F_OVERLAP = 2
+TUNE_SHARED_INPUT = 1   # SDRFM_TUNE_SHARED_INPUT
 
 # every symbol include/sdrfm.h declares
 ABI_SYMBOLS = [
@@ -31,7 +32,7 @@ ABI_SYMBOLS = [
     "sdrfm_rds_synchronize", "sdrfm_rds_kernel_name", "sdrfm_rds_checkword", "sdrfm_rds_syndrome", "sdrfm_rds_sync_create",
     "sdrfm_rds_sync_destroy", "sdrfm_rds_sync_reset", "sdrfm_rds_sync_push", "sdrfm_rds_sync_stats",
     "sdrfm_bcast_create", "sdrfm_bcast_destroy", "sdrfm_bcast_reset", "sdrfm_bcast_counts", "sdrfm_bcast_process_batch",
-    "sdrfm_bcast_set_stream", "sdrfm_bcast_synchronize", "sdrfm_bcast_kernel_name",
+    "sdrfm_bcast_set_stream", "sdrfm_bcast_synchronize", "sdrfm_bcast_kernel_name", "sdrfm_bcast_tune",
     "sdrfm_pcm_stereo_sink_create", "sdrfm_pcm_stereo_sink_destroy", "sdrfm_pcm_stereo_sink_reset", "sdrfm_pcm_stereo_sink_process_batch",
     "sdrfm_pcm_stereo_sink_set_stream", "sdrfm_pcm_stereo_sink_synchronize", "sdrfm_pcm_stereo_sink_get_state",
     "sdrfm_stereo_process_batch_pcm", "sdrfm_bcast_process_batch_pcm",
@@ -283,6 +284,8 @@ def load_library(dev=False):
     lib.sdrfm_bcast_synchronize.restype = C.c_int
     lib.sdrfm_bcast_kernel_name.argtypes = [vp]
     lib.sdrfm_bcast_kernel_name.restype = C.c_char_p
+    lib.sdrfm_bcast_tune.argtypes = [vp, vp, vp, u32]
+    lib.sdrfm_bcast_tune.restype = C.c_int
     lib.sdrfm_rds_checkword.argtypes = [C.c_uint16, C.c_int]
     lib.sdrfm_rds_checkword.restype = C.c_uint16
     lib.sdrfm_rds_syndrome.argtypes = [u32]

@@ -90,17 +90,9 @@ def rds_waveform(bits, oversample=128):
     return w / np.abs(w).max()
 
 
-def make_iq_rds(n_streams, n_samples, groups, rds_deviation_hz=3e3, rds_phase=0.0, clock_ppm=0.0, pilot=True, left_hz=1e3, right_hz=3.1e3,
-                deviation_hz=75e3, fs=2.4e6, first_id=0):
-    """uint8 [n_streams, 2*n_samples] of a broadcast-FM station with RDS, in numpy: make_iq_stereo's multiplex with the pilot at 9 % and
-    the RDS term added,
-    m = 0.87 [(L+R)/2 + (L-R)/2 sin 2φ] + 0.09 sin φ + (rds_deviation_hz / deviation_hz) r(t) sin(3φ + rds_phase),
-    r the data signal of `groups` (4-tuples of 16-bit blocks, repeated as long as the samples last; rds_waveform), its bit clock the
-    pilot's frequency / 16, bit 0 starting at t = 0.  clock_ppm scales the pilot (and with it the subcarriers and the bit clock) as a
-    transmitter-against-dongle crystal offset does.  Without `pilot` the station is mono: m = 0.87 (L+R)/2, no subcarriers at all.
-    Carrier offset, start phase and noise per stream as in make_iq_stereo (generator seeded with first_id + s)."""
+def _rds_multiplex(n_samples, groups, rds_deviation_hz, rds_phase, clock_ppm, pilot, left_hz, right_hz, deviation_hz, fs):
+    """the multiplex m(t) of make_iq_rds, float64 [n_samples]"""
     from .rds import rds_group_bits
-    out = np.empty((n_streams, 2 * n_samples), dtype=np.uint8)
     t = np.arange(n_samples, dtype=np.float64) / fs
     f_pilot = 19e3 * (1.0 + clock_ppm * 1e-6)
     ph = 2.0 * np.pi * f_pilot * t
@@ -118,6 +110,20 @@ def make_iq_rds(n_streams, n_samples, groups, rds_deviation_hz=3e3, rds_phase=0.
         m = 0.87 * ((L + R) / 2 + (L - R) / 2 * np.sin(2.0 * ph)) + 0.09 * np.sin(ph) + (rds_deviation_hz / deviation_hz) * r * np.sin(3.0 * ph + rds_phase)
     else:
         m = 0.87 * (L + R) / 2
+    return m
+
+
+def make_iq_rds(n_streams, n_samples, groups, rds_deviation_hz=3e3, rds_phase=0.0, clock_ppm=0.0, pilot=True, left_hz=1e3, right_hz=3.1e3,
+                deviation_hz=75e3, fs=2.4e6, first_id=0):
+    """uint8 [n_streams, 2*n_samples] of a broadcast-FM station with RDS, in numpy: make_iq_stereo's multiplex with the pilot at 9 % and
+    the RDS term added,
+    m = 0.87 [(L+R)/2 + (L-R)/2 sin 2φ] + 0.09 sin φ + (rds_deviation_hz / deviation_hz) r(t) sin(3φ + rds_phase),
+    r the data signal of `groups` (4-tuples of 16-bit blocks, repeated as long as the samples last; rds_waveform), its bit clock the
+    pilot's frequency / 16, bit 0 starting at t = 0.  clock_ppm scales the pilot (and with it the subcarriers and the bit clock) as a
+    transmitter-against-dongle crystal offset does.  Without `pilot` the station is mono: m = 0.87 (L+R)/2, no subcarriers at all.
+    Carrier offset, start phase and noise per stream as in make_iq_stereo (generator seeded with first_id + s)."""
+    m = _rds_multiplex(n_samples, groups, rds_deviation_hz, rds_phase, clock_ppm, pilot, left_hz, right_hz, deviation_hz, fs)
+    out = np.empty((n_streams, 2 * n_samples), dtype=np.uint8)
     for s in range(n_streams):
         rng = np.random.default_rng(first_id + s)
         fc = (rng.random() * 2.0 - 1.0) * 20000.0
@@ -126,4 +132,25 @@ def make_iq_rds(n_streams, n_samples, groups, rds_deviation_hz=3e3, rds_phase=0.
         noise = rng.normal(0.0, 2.0, size=(2, n_samples))
         out[s, 0::2] = np.clip(np.rint(127.5 + 100.0 * np.cos(phase) + noise[0]), 0, 255)
         out[s, 1::2] = np.clip(np.rint(127.5 + 100.0 * np.sin(phase) + noise[1]), 0, 255)
+    return out
+
+
+def make_iq_stations(n_samples, stations, fs=2.4e6, seed=0):
+    """uint8 [1, 2*n_samples]: one capture that holds several make_iq_rds-style stations.  `stations` is a list of dicts with the keys
+    offset_hz (the station's carrier against the capture's centre), amplitude (in byte units; make_iq_rds has 100), left_hz, right_hz,
+    groups and, optionally, rds_phase, clock_ppm, rds_deviation_hz, deviation_hz and pilot, which mean what they mean in make_iq_rds.
+    Station i is amplitude * exp(j (phi_i + 2 pi cumsum(offset_hz + deviation_hz m_i) / fs)) with a start phase phi_i drawn from the
+    generator seeded with `seed`; I/Q = 127.5 + the stations' sum + N(0, 2) noise, rounded and clipped to u8."""
+    rng = np.random.default_rng(seed)
+    z = np.zeros(n_samples, dtype=np.complex128)
+    for st in stations:
+        dev = float(st.get("deviation_hz", 75e3))
+        m = _rds_multiplex(n_samples, st["groups"], float(st.get("rds_deviation_hz", 3e3)), float(st.get("rds_phase", 0.0)),
+                           float(st.get("clock_ppm", 0.0)), bool(st.get("pilot", True)), float(st["left_hz"]), float(st["right_hz"]), dev, fs)
+        phase = rng.random() * 2.0 * np.pi + np.cumsum(2.0 * np.pi * (float(st["offset_hz"]) + dev * m) / fs)
+        z += float(st["amplitude"]) * np.exp(1j * phase)
+    noise = rng.normal(0.0, 2.0, size=(2, n_samples))
+    out = np.empty((1, 2 * n_samples), dtype=np.uint8)
+    out[0, 0::2] = np.clip(np.rint(127.5 + z.real + noise[0]), 0, 255)
+    out[0, 1::2] = np.clip(np.rint(127.5 + z.imag + noise[1]), 0, 255)
     return out

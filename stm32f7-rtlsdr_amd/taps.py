@@ -57,3 +57,22 @@ def rds_gain(D, fs, f_sub=57e3):
 def rds_lowpass_taps(Tr, fs_d, cutoff_hz=3.0e3):
     """The decimating low-pass behind the 57 kHz mixer: lowpass_taps at cutoff_hz / fs_d (the RDS spectrum ends at +-2.4 kHz)."""
     return lowpass_taps(Tr, cutoff_hz / fs_d)
+
+
+def tuned_channel_taps(h, offset_hz, fs):
+    """The channel low-pass h moved to offset_hz: hz[k] = h[k] exp(+j 2 pi offset_hz k / fs), evaluated in float64 and rounded once.
+    Returns float32 [2T], (hr[k], hi[k]) pairs: one stream's row of sdrfm_bcast_tune's ctaps."""
+    h = np.asarray(h, dtype=np.float32).astype(np.float64)
+    k = np.arange(h.size, dtype=np.float64)
+    hz = h * np.exp(1j * 2.0 * np.pi * float(offset_hz) * k / float(fs))
+    out = np.empty(2 * h.size, dtype=np.float32)
+    out[0::2], out[1::2] = hz.real, hz.imag
+    return out
+
+
+def tuned_rotation(offset_hz, fs, D):
+    """The phase a tuned stream's y gains over D inputs from the offset alone, 2 pi offset_hz D / fs wrapped into [-pi, pi] in float64 and
+    rounded once (sdrfm_bcast_tune's rot; the rounding never leaves the fp32 pi the library compares with)."""
+    v = float(np.remainder(2.0 * np.pi * float(offset_hz) * int(D) / float(fs) + np.pi, 2.0 * np.pi) - np.pi)
+    pi_f = float(np.float32(np.pi))
+    return np.float32(min(max(v, -pi_f), pi_f))
