@@ -8,24 +8,21 @@
  *   y[n]   = fmaf(alpha, x[n] - y[n-1], y[n-1])        one rounded difference, one fused multiply-add
  *   pcm[n] = (int16) rint(clamp(y[n] * gain, -32768, 32767))      round-half-even, L = R
  *
+ * Both forms of the recursion are written once, for any number of channels, in sdrfm_sink_kernels.h; the kernels here instantiate them for ONE chain per
+ * stream around the way this sink keeps its state (the tagged words of sdrfm_sink_chain.h), and the stereo sink's (sdrfm_sink_stereo.hip) for two.
+ *
  * Parallelisation: the recursion rounds at every step, so a scan (which re-associates) cannot reproduce it bit for bit;
  * the chain of one stream is therefore walked by ONE lane, 64 streams per wave, and what IS parallel — moving the data —
- * is kept coalesced by transposing 64 x 64 tiles through LDS:
- *
- *   HBM --row r: 64 lanes x 4 B, 256 B coalesced--> LDS tile[r][t] (row stride 65 words: conflict-free both ways)
- *   lane = stream: 64 dependent steps from LDS, packed (L | R << 16) back into the tile in place
- *   LDS --row r--> HBM 256 B coalesced stores of the interleaved int16 pairs
- *
+ * is kept coalesced by transposing 64 x 64 tiles through LDS (sink_exact_tiles).
  * The chain is latency-bound (one lane per stream, and every 64 samples a tile of 64 dependent row loads): measured 1.35 ms per 256 x 4800
  * launch (profiles/r06_sink.txt; rounds 2 - 5 quoted an estimate of 25 us that had never been timed) — sixty demodulator calls.  It is kept
  * as the EXACT form (SDRFM_PCM_F_EXACT): bit-identical to the host routine.
  *
  * The default since round 6 is a BLOCKED SCAN (k_pcm_sink_scan): the recursion is linear — y[n] = (1 - alpha) y[n-1] + alpha x[n] —,
- * so a stream's call is cut into segments of 256 chunks of 19 samples, one lane per chunk, one workgroup of 256 lanes per stream:
- *   1. lane t walks its chunk from state 0 (lane 0: from the carried state) -> e[t], the chunk's own contribution to its last sample;
- *   2. the carries s[t] = (1 - alpha)^c s[t-1] + e[t]: six shuffle steps within each wave (the powers squared on the way), the four waves' totals combined through
- *      four words of LDS (one barrier; the first version's Hillis-Steele scan over 256 lanes in LDS took sixteen: 7.4 -> 7.0 us per launch);
- *   3. lane t walks its chunk AGAIN, now from its true carry-in s[t-1], with exactly the exact form's operations, and packs the PCM.
+ * so a stream's call is cut into segments of 256 chunks of 19 samples, one lane per chunk, one workgroup of 256 lanes per stream, and walked in the three
+ * phases of sink_scan_segments: every chunk's own contribution from state 0, the carries between the chunks, every chunk again from its true carry-in with
+ * exactly the exact form's operations.  (The carries between the four waves go through four words of LDS and one barrier; the first version's Hillis-Steele
+ * scan over 256 lanes in LDS took sixteen: 7.4 -> 7.0 us per launch.)
  * What differs from the exact chain is therefore only the carry-in of a chunk (re-associated: ~1e-7 relative), and that difference decays with
  * (1 - alpha)^k inside the chunk: the PCM is within 1 LSB of the exact form's (equal but where y * gain sits within 1e-3 of a rounding boundary),
  * the carried state within 1e-6 relative (2.5e-7 at 75 us, tests/test_pcm_sink_gpu.py; 8e-7 at alpha = 0.001, where a carry-in hardly decays inside its chunk:
@@ -45,6 +42,7 @@
 
 #include "../../include/sdrfm.h"
 #include "sdrfm_sink_chain.h"
+#include "sdrfm_sink_kernels.h"
 
 namespace {
 
@@ -61,55 +59,29 @@ struct SinkParams {
 };
 
 __global__ void __launch_bounds__(64) k_pcm_sink(SinkParams p) {
-  __shared__ unsigned tile[64 * 65];
+  __shared__ unsigned tile[1][64 * 65];
   const uint32_t lane = threadIdx.x;
   const uint32_t s0 = blockIdx.x * 64;
   const uint32_t rows = (p.n_streams - s0 < 64u) ? p.n_streams - s0 : 64u;
   const uint32_t mine = s0 + lane;
-  float y = (lane < rows) ? __uint_as_float((unsigned)p.sg_in[mine]) : 0.0f;
-  for (uint32_t t0 = 0; t0 < p.n; t0 += 64) {
-    const uint32_t cols = (p.n - t0 < 64u) ? p.n - t0 : 64u;
-    if (lane < cols)
-      for (uint32_t r = 0; r < rows; ++r)
-        tile[r * 65 + lane] = __float_as_uint(p.audio[(size_t)(s0 + r) * p.audio_stride + t0 + lane]);
-    __syncthreads();
-    if (lane < rows) {
-      for (uint32_t i = 0; i < cols; ++i) {
-        const float x = __uint_as_float(tile[lane * 65 + i]);
-        y = __builtin_fmaf(p.alpha, x - y, y);
-        float v = y * p.gain;
-        if (v > 32767.0f) v = 32767.0f;
-        if (v < -32768.0f) v = -32768.0f;
-        const unsigned s = (unsigned)(int)__builtin_rintf(v) & 0xffffu;
-        tile[lane * 65 + i] = s | (s << 16);
-      }
-    }
-    __syncthreads();
-    if (lane < cols)
-      for (uint32_t r = 0; r < rows; ++r)
-        reinterpret_cast<unsigned*>(p.pcm + (size_t)(s0 + r) * p.pcm_stride)[t0 + lane] = tile[r * 65 + lane];
-    __syncthreads();
-  }
-  if (lane < rows) p.sg_out[mine] = ((unsigned long long)p.gen_next << 32) | __float_as_uint(y);
+  float y[1] = {(lane < rows) ? __uint_as_float((unsigned)p.sg_in[mine]) : 0.0f};
+  const float* const in[1] = {p.audio};
+  sink_exact_tiles<1>(tile, in, p.audio_stride, p.pcm, p.pcm_stride, s0, rows, p.n, p.alpha, p.gain, y);
+  if (lane < rows) p.sg_out[mine] = ((unsigned long long)p.gen_next << 32) | __float_as_uint(y[0]);
 }
 
-// ---- the blocked scan (the default): one workgroup of 256 lanes per stream; segments of SINK_NT * SINK_C samples through LDS ------------------------------
+// ---- the blocked scan (the default): one workgroup of 256 lanes per stream around sink_scan_segments<1> (sdrfm_sink_kernels.h) -----------------------------
 // (A variant with ONE WAVE per stream, 75-sample chunks in registers and no LDS at all was built to slip in beside the demodulator's waves, which hold all but
 // 0.9 KiB of a CU's LDS: 10.5 us alone against 7.4 us for this one, and no faster in the consumer loop — profiles/r06_sink.txt.  Not kept.)
-constexpr uint32_t SINK_NT = 256, SINK_C = 19, SINK_SEG = SINK_NT * SINK_C;
-static_assert(SINK_NT == 256, "four waves: the carries between them are combined by hand");   // 4864 samples per segment (BASELINE's 4800 per call: one segment), 19 KiB of LDS;
-                                                                             // lanes SINK_C = 19 words apart (odd): conflict-free LDS accesses
 // LIST: the workgroup's stream is list[blockIdx.x], and the call is PART of a sink call whose other streams the chain inside a demodulator launch serves
 // (sdrfm_sink_chain.h): the state is taken by that protocol — the tagged word of slot sg_in, waited for on the device (bounded) — and published the same way.
 template <bool LIST>
 __global__ void __launch_bounds__(256) k_pcm_sink_scan(SinkParams p, float pc, const uint32_t* list, uint32_t* err) {
-  __shared__ float x[SINK_SEG];                                 // the segment's samples, then (in place) the packed PCM words
-  __shared__ float sc[4];                                       // the waves' totals; then the segment's last state
-  unsigned* const xw = reinterpret_cast<unsigned*>(x);
+  __shared__ float x[1][SINK_SEG];
+  __shared__ float sc[1][4];
   const uint32_t s = LIST ? list[blockIdx.x] : blockIdx.x, t = threadIdx.x;
-  const float* const row = p.audio + (size_t)s * p.audio_stride;
-  unsigned* const out = reinterpret_cast<unsigned*>(p.pcm + (size_t)s * p.pcm_stride);
-  float y0;                                                     // the state before the segment (every lane holds it)
+  const float* const row[1] = {p.audio + (size_t)s * p.audio_stride};
+  float y0[1];
   if constexpr (LIST) {
     if (t == 0) {
       unsigned long long pv = 0ull, zero = 0ull;
@@ -121,81 +93,17 @@ __global__ void __launch_bounds__(256) k_pcm_sink_scan(SinkParams p, float pc, c
         __builtin_amdgcn_s_sleep(16);
       }
       if (it == (1 << 19)) { pv = 0ull; __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-      sc[0] = __uint_as_float((unsigned)pv);
+      sc[0][0] = __uint_as_float((unsigned)pv);
     }
     __syncthreads();
-    y0 = sc[0];
+    y0[0] = sc[0][0];
     __syncthreads();
   } else {
-    y0 = __uint_as_float((unsigned)p.sg_in[s]);
+    y0[0] = __uint_as_float((unsigned)p.sg_in[s]);
   }
-  for (uint32_t base = 0; base < p.n; base += SINK_SEG) {
-    const uint32_t m = (p.n - base < SINK_SEG) ? p.n - base : SINK_SEG;   // samples of this segment
-#pragma unroll
-    for (uint32_t q = 0; q < SINK_C; ++q) {                     // coalesced: SINK_C independent loads per lane in flight
-      const uint32_t i = t + SINK_NT * q;
-      if (i < m) x[i] = row[base + i];
-    }
-    __syncthreads();
-    // the lane's chunk [i0, i0 + cnt) in registers: both walks below then run at the chain's own latency (sub -> fma), no LDS round trip inside
-    const uint32_t i0 = t * SINK_C < m ? t * SINK_C : m, cnt = (m - i0 < SINK_C) ? m - i0 : SINK_C;
-    float xr[SINK_C];
-#pragma unroll
-    for (uint32_t q = 0; q < SINK_C; ++q) xr[q] = q < cnt ? x[i0 + q] : 0.0f;
-    // 1. the chunk's own contribution to its last sample (lane 0 starts from the real state: its chain is the exact one already)
-    float y = t == 0 ? y0 : 0.0f;
-#pragma unroll
-    for (uint32_t q = 0; q < SINK_C; ++q)
-      if (q < cnt) y = __builtin_fmaf(p.alpha, xr[q] - y, y);
-    // 2. s[t] = pc s[t-1] + e[t], pc = (1 - alpha)^SINK_C (only the last non-empty chunk may be short, and nothing follows it): within a wave by six shuffle steps
-    // (the powers squared on the way), between the four waves through four words of LDS — one barrier where a Hillis-Steele scan over 256 lanes in LDS took sixteen
-    const uint32_t wl = t & 63u, wv = t >> 6;
-    float sv = y, pw = pc;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const float o = __shfl_up(sv, d, 64);
-      const float sn = __builtin_fmaf(pw, o, sv);
-      sv = wl >= d ? sn : sv;
-      pw *= pw;
-    }                                                           // (pw = pc^64 now: what a whole wave's chunks leave of a state)
-    if (wl == 63u) sc[wv] = sv;
-    float pl = 1.0f, pb = pc;                                   // pc^wl: what the chunks of this wave before the lane's leave of the wave's carry-in
-#pragma unroll
-    for (uint32_t bit = 0; bit < 6u; ++bit) {
-      pl = ((wl >> bit) & 1u) ? pl * pb : pl;
-      pb *= pb;
-    }
-    const float prev = __shfl_up(sv, 1u, 64);
-    __syncthreads();
-    float cw = 0.0f;                                            // the state at the end of the previous wave's chunks
-    if (wv >= 1u) cw = sc[0];
-    if (wv >= 2u) cw = __builtin_fmaf(pw, cw, sc[1]);
-    if (wv >= 3u) cw = __builtin_fmaf(pw, cw, sc[2]);
-    // 3. the exact form's chain from the true carry-in
-    y = wl == 0u ? (wv == 0u ? y0 : cw) : __builtin_fmaf(pl, cw, prev);
-    __syncthreads();                                            // (every carry-in is in a register before sc[0] takes the segment's last state below)
-#pragma unroll
-    for (uint32_t q = 0; q < SINK_C; ++q)
-      if (q < cnt) {
-        y = __builtin_fmaf(p.alpha, xr[q] - y, y);
-        float v = y * p.gain;
-        if (v > 32767.0f) v = 32767.0f;
-        if (v < -32768.0f) v = -32768.0f;
-        const unsigned w = (unsigned)(int)__builtin_rintf(v) & 0xffffu;
-        xw[i0 + q] = w | (w << 16);
-      }
-    if (cnt > 0 && i0 + cnt == m) sc[0] = y;                     // the lane that holds the segment's last sample: the state behind it
-    __syncthreads();
-    y0 = sc[0];
-#pragma unroll
-    for (uint32_t q = 0; q < SINK_C; ++q) {
-      const uint32_t i = t + SINK_NT * q;
-      if (i < m) out[base + i] = xw[i];
-    }
-    __syncthreads();
-  }
+  sink_scan_segments<1>(x, sc, row, reinterpret_cast<unsigned*>(p.pcm + (size_t)s * p.pcm_stride), p.n, p.alpha, p.gain, pc, y0);
   if (t == 0) {
-    const unsigned long long w = ((unsigned long long)p.gen_next << 32) | __float_as_uint(y0);
+    const unsigned long long w = ((unsigned long long)p.gen_next << 32) | __float_as_uint(y0[0]);
     if constexpr (LIST) __hip_atomic_store(p.sg_out + s, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else p.sg_out[s] = w;
   }
@@ -215,15 +123,6 @@ struct sdrfm_pcm_sink {
   int16_t* d_pcm;
   uint32_t cap;        // samples per stream the staging holds
 };
-
-#define STRY(expr, code)                                                                                       \
-  do {                                                                                                         \
-    hipError_t e__ = (expr);                                                                                   \
-    if (e__ != hipSuccess) {                                                                                   \
-      fprintf(stderr, "[sdrfm] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__);  \
-      return (code);                                                                                           \
-    }                                                                                                          \
-  } while (0)
 
 static void sink_free(sdrfm_pcm_sink* k) {
   if (!k) return;
@@ -257,31 +156,52 @@ int sdrfm_sink_chain_params(sdrfm_pcm_sink* k, int device, uint32_t n_streams, S
 
 void sdrfm_sink_chain_issued(sdrfm_pcm_sink* k) { ++k->calls; }
 
-int sdrfm_sink_launch_on(sdrfm_pcm_sink* k, const float* audio, size_t audio_stride, uint32_t n, int16_t* pcm, size_t pcm_stride, hipStream_t stream) {
-  if (!k) return SDRFM_EINVAL;
-  if (n == 0) return SDRFM_OK;
+// the parameters of the sink's call number `call`: it takes the states of tag `call` and leaves those of tag `call + 1` (sdrfm_sink_chain.h)
+static SinkParams sink_params(const sdrfm_pcm_sink* k, uint32_t call, const float* audio, size_t audio_stride, uint32_t n, int16_t* pcm, size_t pcm_stride) {
   SinkParams p;
-  p.sg_in = k->d_sg + (size_t)(k->calls % SDRFM_CHAIN_SG_SLOTS) * k->n_streams; p.sg_out = k->d_sg + (size_t)((k->calls + 1u) % SDRFM_CHAIN_SG_SLOTS) * k->n_streams;
+  p.sg_in = k->d_sg + (size_t)(call % SDRFM_CHAIN_SG_SLOTS) * k->n_streams; p.sg_out = k->d_sg + (size_t)((call + 1u) % SDRFM_CHAIN_SG_SLOTS) * k->n_streams;
   p.n_streams = k->n_streams; p.n = n; p.alpha = k->alpha; p.gain = k->gain;
-  p.gen_next = k->calls + 1u;
+  p.gen_next = call + 1u;
   p.audio = audio; p.audio_stride = audio_stride; p.pcm = pcm; p.pcm_stride = pcm_stride;
-  hipLaunchKernelGGL(k_pcm_sink_scan<false>, dim3(k->n_streams), dim3(SINK_NT), 0, stream, p, (float)pow(1.0 - (double)k->alpha, (double)SINK_C), nullptr, nullptr);
+  return p;
+}
+
+// one whole call of the sink over device buffers, in either form, on `stream`
+static int sink_launch(sdrfm_pcm_sink* k, const float* audio, size_t audio_stride, uint32_t n, int16_t* pcm, size_t pcm_stride, hipStream_t stream, bool exact) {
+  const SinkParams p = sink_params(k, k->calls, audio, audio_stride, n, pcm, pcm_stride);
+  if (exact) hipLaunchKernelGGL(k_pcm_sink, dim3((k->n_streams + 63) / 64), dim3(64), 0, stream, p);
+  else hipLaunchKernelGGL(k_pcm_sink_scan<false>, dim3(k->n_streams), dim3(SINK_NT), 0, stream, p, sink_carry_factor(k->alpha), nullptr, nullptr);
   STRY(hipGetLastError(), SDRFM_FAIL);
   ++k->calls;
   return SDRFM_OK;
+}
+
+int sdrfm_sink_launch_on(sdrfm_pcm_sink* k, const float* audio, size_t audio_stride, uint32_t n, int16_t* pcm, size_t pcm_stride, hipStream_t stream) {
+  if (!k) return SDRFM_EINVAL;
+  if (n == 0) return SDRFM_OK;
+  return sink_launch(k, audio, audio_stride, n, pcm, pcm_stride, stream, false);
 }
 
 int sdrfm_sink_launch_list_on(sdrfm_pcm_sink* k, const SdrfmSinkChain& c, const uint32_t* list_dev, uint32_t n_list, const float* audio, size_t audio_stride, uint32_t n,
                               int16_t* pcm, size_t pcm_stride, hipStream_t stream, hipEvent_t done) {
   if (!k || !list_dev) return SDRFM_EINVAL;
   if (n == 0 || n_list == 0) return SDRFM_OK;
-  SinkParams p;
-  p.sg_in = k->d_sg + (size_t)(c.call % SDRFM_CHAIN_SG_SLOTS) * k->n_streams; p.sg_out = k->d_sg + (size_t)((c.call + 1u) % SDRFM_CHAIN_SG_SLOTS) * k->n_streams;
-  p.n_streams = k->n_streams; p.n = n; p.alpha = k->alpha; p.gain = k->gain;
-  p.gen_next = c.call + 1u;
-  p.audio = audio; p.audio_stride = audio_stride; p.pcm = pcm; p.pcm_stride = pcm_stride;
-  hipExtLaunchKernelGGL(k_pcm_sink_scan<true>, dim3(n_list), dim3(SINK_NT), 0, stream, nullptr, done, 0, p, (float)pow(1.0 - (double)k->alpha, (double)SINK_C), list_dev, c.err);
+  const SinkParams p = sink_params(k, c.call, audio, audio_stride, n, pcm, pcm_stride);
+  hipExtLaunchKernelGGL(k_pcm_sink_scan<true>, dim3(n_list), dim3(SINK_NT), 0, stream, nullptr, done, 0, p, sink_carry_factor(k->alpha), list_dev, c.err);
   STRY(hipGetLastError(), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+// staging rows for a host-pointer call of n samples per stream
+static int sink_reserve(sdrfm_pcm_sink* k, uint32_t n) {
+  if (n <= k->cap) return SDRFM_OK;
+  if (k->d_audio) (void)hipFree(k->d_audio);
+  if (k->d_pcm) (void)hipFree(k->d_pcm);
+  k->d_audio = nullptr; k->d_pcm = nullptr; k->cap = 0;
+  const uint32_t cap = (n + 1023u) & ~1023u;
+  if (hipMalloc(&k->d_audio, sizeof(float) * (size_t)cap * k->n_streams) != hipSuccess ||
+      hipMalloc(&k->d_pcm, sizeof(int16_t) * 2 * (size_t)cap * k->n_streams) != hipSuccess) return SDRFM_ENOMEM;
+  k->cap = cap;
   return SDRFM_OK;
 }
 
@@ -365,42 +285,19 @@ int sdrfm_pcm_sink_process_batch(sdrfm_pcm_sink_t* k, const float* audio, size_t
   if (k->n_streams > 1 && (audio_stride < n || pcm_stride < 2 * (size_t)n)) return SDRFM_ECAPACITY;
   if (pcm_stride & 1u) return SDRFM_EINVAL;                          // rows are written as (L,R) dwords
   STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  SinkParams p;
-  p.sg_in = k->d_sg + (size_t)(k->calls % SDRFM_CHAIN_SG_SLOTS) * k->n_streams; p.sg_out = k->d_sg + (size_t)((k->calls + 1u) % SDRFM_CHAIN_SG_SLOTS) * k->n_streams;
-  p.n_streams = k->n_streams; p.n = n; p.alpha = k->alpha; p.gain = k->gain;
-  p.gen_next = k->calls + 1u;
-  const dim3 grid((k->n_streams + 63) / 64);
-  const float pc = (float)pow(1.0 - (double)k->alpha, (double)SINK_C);   // the blocked scan's carry factor: (1 - alpha)^(samples per chunk)
   const bool exact = (flags & SDRFM_PCM_F_EXACT) != 0;
-  auto launch = [&]() {
-    if (exact) hipLaunchKernelGGL(k_pcm_sink, grid, dim3(64), 0, k->stream, p);
-    else hipLaunchKernelGGL(k_pcm_sink_scan<false>, dim3(k->n_streams), dim3(SINK_NT), 0, k->stream, p, pc, nullptr, nullptr);
-  };
   if (flags & SDRFM_F_DEVICE_PTRS) {
     if ((uintptr_t)pcm % 4 != 0) return SDRFM_EINVAL;
-    p.audio = audio; p.audio_stride = audio_stride; p.pcm = pcm; p.pcm_stride = pcm_stride;
-    launch();
-    STRY(hipGetLastError(), SDRFM_FAIL);
-    ++k->calls;
-    return SDRFM_OK;
+    return sink_launch(k, audio, audio_stride, n, pcm, pcm_stride, k->stream, exact);
   }
   // host buffers: stage, run, copy back, synchronous
-  if (n > k->cap) {
-    if (k->d_audio) (void)hipFree(k->d_audio);
-    if (k->d_pcm) (void)hipFree(k->d_pcm);
-    k->d_audio = nullptr; k->d_pcm = nullptr; k->cap = 0;
-    const uint32_t cap = (n + 1023u) & ~1023u;
-    if (hipMalloc(&k->d_audio, sizeof(float) * (size_t)cap * k->n_streams) != hipSuccess ||
-        hipMalloc(&k->d_pcm, sizeof(int16_t) * 2 * (size_t)cap * k->n_streams) != hipSuccess) return SDRFM_ENOMEM;
-    k->cap = cap;
-  }
+  int rc = sink_reserve(k, n);
+  if (rc != SDRFM_OK) return rc;
   const size_t as = (k->n_streams > 1) ? audio_stride : n, ps = (k->n_streams > 1) ? pcm_stride : 2 * (size_t)n;
   STRY(hipMemcpy2DAsync(k->d_audio, sizeof(float) * k->cap, audio, sizeof(float) * as, sizeof(float) * n, k->n_streams,
                         hipMemcpyHostToDevice, k->stream), SDRFM_FAIL);
-  p.audio = k->d_audio; p.audio_stride = k->cap; p.pcm = k->d_pcm; p.pcm_stride = 2 * (size_t)k->cap;
-  launch();
-  STRY(hipGetLastError(), SDRFM_FAIL);
-  ++k->calls;
+  rc = sink_launch(k, k->d_audio, k->cap, n, k->d_pcm, 2 * (size_t)k->cap, k->stream, exact);
+  if (rc != SDRFM_OK) return rc;
   STRY(hipMemcpy2DAsync(pcm, sizeof(int16_t) * ps, k->d_pcm, sizeof(int16_t) * 2 * k->cap, sizeof(int16_t) * 2 * n, k->n_streams,
                         hipMemcpyDeviceToHost, k->stream), SDRFM_FAIL);
   STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);

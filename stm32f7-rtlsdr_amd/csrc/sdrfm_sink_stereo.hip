@@ -7,15 +7,15 @@
  *   y[n]   = fmaf(alpha, x[n] - y[n-1], y[n-1])
  *   pcm[n] = (int16) rint(clamp(y[n] * gain, -32768, 32767))      one dword per sample: L | R << 16
  *
- * The two forms of the mono sink (sdrfm_sink.hip), each walking TWO chains in a lane:
- *   k_pcm_stereo_sink       SDRFM_PCM_F_EXACT: one lane per stream, 64 streams per wave, the data moved coalesced through two 64 x 65-word LDS tiles
- *                           (L and R), the packed PCM written back into the L tile in place.  Bit-identical to the host routine, PCM and state.
- *   k_pcm_stereo_sink_scan  the default: one workgroup of 256 lanes per stream, the lane's 19-sample chunk of L and the same chunk of R in registers,
- *                           both chains through the three phases of k_pcm_sink_scan<false> (chunk contribution, carries, re-walk) side by side.  The
- *                           chain is latency-bound (sub -> fma), so the second, independent chain fills slots the first leaves empty.  PER CHANNEL the
- *                           operations and their order are k_pcm_sink_scan<false>'s — same SINK_NT, SINK_C and segment, the same six shuffle steps with
- *                           the powers squared on the way, the same combine of the four waves' totals —, so the even PCM slots are bit for bit what the
- *                           mono default sink leaves for the L rows and the odd slots what it leaves for the R rows (tests/test_pcm_stereo_sink_gpu.py).
+ * The two forms of the mono sink (sdrfm_sink.hip), each walking TWO chains in a lane.  Both sinks instantiate the same two bodies of sdrfm_sink_kernels.h,
+ * the mono sink for one channel and this one for two, so PER CHANNEL the operations and their order are the mono sink's by construction:
+ *   k_pcm_stereo_sink       SDRFM_PCM_F_EXACT, sink_exact_tiles<2>: one lane per stream, 64 streams per wave, the data moved coalesced through two
+ *                           64 x 65-word LDS tiles (L and R), the packed PCM written back into the L tile in place.  Bit-identical to the host routine,
+ *                           PCM and state.
+ *   k_pcm_stereo_sink_scan  the default, sink_scan_segments<2>: one workgroup of 256 lanes per stream, the lane's 19-sample chunk of L and the same chunk
+ *                           of R in registers, both chains through the scan's three phases side by side.  The chain is latency-bound (sub -> fma), so
+ *                           the second, independent chain fills slots the first leaves empty.  The even PCM slots are bit for bit what the mono default
+ *                           sink leaves for the L rows and the odd slots what it leaves for the R rows (tests/test_pcm_stereo_sink_gpu.py confirms it).
  *                           LDS: two segments + eight carry words, 38 KiB.
  * What this sink leaves out on purpose: it takes no part in the in-launch chain protocol (sdrfm_sink_chain.h) — no tagged state slots, no waits on the
  * device, no atomics.  The state is a plain float[n_streams][2]; a stream's workgroup (its lane, in the exact form) reads it at the start and writes
@@ -30,6 +30,7 @@
 #include <new>
 
 #include "../../include/sdrfm.h"
+#include "sdrfm_sink_kernels.h"
 #include "sdrfm_sink_stereo.h"
 
 namespace {
@@ -45,145 +46,29 @@ struct StereoSinkParams {
   float alpha, gain;
 };
 
-// one step of the chain and its PCM word: the operations of sdrfm_pcm_deemph_s16, in its order
-__device__ __forceinline__ unsigned sink_step(float alpha, float gain, float x, float& y) {
-  y = __builtin_fmaf(alpha, x - y, y);
-  float v = y * gain;
-  if (v > 32767.0f) v = 32767.0f;
-  if (v < -32768.0f) v = -32768.0f;
-  return (unsigned)(int)__builtin_rintf(v) & 0xffffu;
-}
-
 __global__ void __launch_bounds__(64) k_pcm_stereo_sink(StereoSinkParams p) {
-  __shared__ unsigned tl[64 * 65], tr[64 * 65];                 // row stride 65 words: conflict-free by rows and by columns
+  __shared__ unsigned tile[2][64 * 65];                         // L and R
   const uint32_t lane = threadIdx.x;
   const uint32_t s0 = blockIdx.x * 64;
   const uint32_t rows = (p.n_streams - s0 < 64u) ? p.n_streams - s0 : 64u;
   const uint32_t mine = s0 + lane;
-  float yl = (lane < rows) ? p.state[2 * (size_t)mine] : 0.0f, yr = (lane < rows) ? p.state[2 * (size_t)mine + 1] : 0.0f;
-  for (uint32_t t0 = 0; t0 < p.n; t0 += 64) {
-    const uint32_t cols = (p.n - t0 < 64u) ? p.n - t0 : 64u;
-    if (lane < cols)
-      for (uint32_t r = 0; r < rows; ++r) {
-        tl[r * 65 + lane] = __float_as_uint(p.left[(size_t)(s0 + r) * p.audio_stride + t0 + lane]);
-        tr[r * 65 + lane] = __float_as_uint(p.right[(size_t)(s0 + r) * p.audio_stride + t0 + lane]);
-      }
-    __syncthreads();
-    if (lane < rows) {
-      for (uint32_t i = 0; i < cols; ++i) {
-        const unsigned wl = sink_step(p.alpha, p.gain, __uint_as_float(tl[lane * 65 + i]), yl);
-        const unsigned wr = sink_step(p.alpha, p.gain, __uint_as_float(tr[lane * 65 + i]), yr);
-        tl[lane * 65 + i] = wl | (wr << 16);
-      }
-    }
-    __syncthreads();
-    if (lane < cols)
-      for (uint32_t r = 0; r < rows; ++r)
-        reinterpret_cast<unsigned*>(p.pcm + (size_t)(s0 + r) * p.pcm_stride)[t0 + lane] = tl[r * 65 + lane];
-    __syncthreads();
-  }
+  float y[2] = {(lane < rows) ? p.state[2 * (size_t)mine] : 0.0f, (lane < rows) ? p.state[2 * (size_t)mine + 1] : 0.0f};
+  const float* const in[2] = {p.left, p.right};
+  sink_exact_tiles<2>(tile, in, p.audio_stride, p.pcm, p.pcm_stride, s0, rows, p.n, p.alpha, p.gain, y);
   if (lane < rows) {
-    p.state[2 * (size_t)mine] = yl;
-    p.state[2 * (size_t)mine + 1] = yr;
+    p.state[2 * (size_t)mine] = y[0];
+    p.state[2 * (size_t)mine + 1] = y[1];
   }
 }
 
-// ---- the blocked scan (the default): the mono sink's geometry (sdrfm_sink.hip), which the bitwise yardstick above rests on
-constexpr uint32_t SINK_NT = 256, SINK_C = 19, SINK_SEG = SINK_NT * SINK_C;
-static_assert(SINK_NT == 256, "four waves: the carries between them are combined by hand");
-
 __global__ void __launch_bounds__(256) k_pcm_stereo_sink_scan(StereoSinkParams p, float pc) {
-  __shared__ float x[2][SINK_SEG];                              // the segment's L and R samples; x[0] then takes (in place) the packed PCM words
-  __shared__ float sc[2][4];                                    // per channel: the waves' totals; then the segment's last state
-  unsigned* const xw = reinterpret_cast<unsigned*>(x[0]);
-  const uint32_t s = blockIdx.x, t = threadIdx.x;
+  __shared__ float x[2][SINK_SEG];
+  __shared__ float sc[2][4];
+  const uint32_t s = blockIdx.x;
   const float* const row[2] = {p.left + (size_t)s * p.audio_stride, p.right + (size_t)s * p.audio_stride};
-  unsigned* const out = reinterpret_cast<unsigned*>(p.pcm + (size_t)s * p.pcm_stride);
-  float y0[2] = {p.state[2 * (size_t)s], p.state[2 * (size_t)s + 1]};   // the states before the segment (every lane holds them)
-  for (uint32_t base = 0; base < p.n; base += SINK_SEG) {
-    const uint32_t m = (p.n - base < SINK_SEG) ? p.n - base : SINK_SEG;   // samples of this segment
-#pragma unroll
-    for (uint32_t q = 0; q < SINK_C; ++q) {                     // coalesced: 2 SINK_C independent loads per lane in flight
-      const uint32_t i = t + SINK_NT * q;
-      if (i < m) {
-        x[0][i] = row[0][base + i];
-        x[1][i] = row[1][base + i];
-      }
-    }
-    __syncthreads();
-    // the lane's chunk [i0, i0 + cnt) of either channel in registers
-    const uint32_t i0 = t * SINK_C < m ? t * SINK_C : m, cnt = (m - i0 < SINK_C) ? m - i0 : SINK_C;
-    float xr[2][SINK_C];
-#pragma unroll
-    for (uint32_t q = 0; q < SINK_C; ++q) {
-      xr[0][q] = q < cnt ? x[0][i0 + q] : 0.0f;
-      xr[1][q] = q < cnt ? x[1][i0 + q] : 0.0f;
-    }
-    // 1. the chunks' own contributions to their last samples (lane 0 starts from the real states)
-    float y[2] = {t == 0 ? y0[0] : 0.0f, t == 0 ? y0[1] : 0.0f};
-#pragma unroll
-    for (uint32_t q = 0; q < SINK_C; ++q)
-      if (q < cnt) {
-        y[0] = __builtin_fmaf(p.alpha, xr[0][q] - y[0], y[0]);
-        y[1] = __builtin_fmaf(p.alpha, xr[1][q] - y[1], y[1]);
-      }
-    // 2. s[t] = pc s[t-1] + e[t] per channel: six shuffle steps within a wave (the powers squared on the way), the four waves' totals through LDS
-    const uint32_t wl = t & 63u, wv = t >> 6;
-    float sv[2] = {y[0], y[1]}, pw = pc;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const float o = __shfl_up(sv[c], d, 64);
-        const float sn = __builtin_fmaf(pw, o, sv[c]);
-        sv[c] = wl >= d ? sn : sv[c];
-      }
-      pw *= pw;
-    }                                                           // (pw = pc^64 now)
-    if (wl == 63u) {
-      sc[0][wv] = sv[0];
-      sc[1][wv] = sv[1];
-    }
-    float pl = 1.0f, pb = pc;                                   // pc^wl
-#pragma unroll
-    for (uint32_t bit = 0; bit < 6u; ++bit) {
-      pl = ((wl >> bit) & 1u) ? pl * pb : pl;
-      pb *= pb;
-    }
-    const float prev[2] = {__shfl_up(sv[0], 1u, 64), __shfl_up(sv[1], 1u, 64)};
-    __syncthreads();
-    // 3. the exact form's chains from the true carry-ins
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      float cw = 0.0f;                                          // the state at the end of the previous wave's chunks
-      if (wv >= 1u) cw = sc[c][0];
-      if (wv >= 2u) cw = __builtin_fmaf(pw, cw, sc[c][1]);
-      if (wv >= 3u) cw = __builtin_fmaf(pw, cw, sc[c][2]);
-      y[c] = wl == 0u ? (wv == 0u ? y0[c] : cw) : __builtin_fmaf(pl, cw, prev[c]);
-    }
-    __syncthreads();                                            // (every carry-in is in a register before sc[c][0] takes the segment's last state below)
-#pragma unroll
-    for (uint32_t q = 0; q < SINK_C; ++q)
-      if (q < cnt) {
-        const unsigned l = sink_step(p.alpha, p.gain, xr[0][q], y[0]);
-        const unsigned r = sink_step(p.alpha, p.gain, xr[1][q], y[1]);
-        xw[i0 + q] = l | (r << 16);
-      }
-    if (cnt > 0 && i0 + cnt == m) {                             // the lane that holds the segment's last sample: the states behind it
-      sc[0][0] = y[0];
-      sc[1][0] = y[1];
-    }
-    __syncthreads();
-    y0[0] = sc[0][0];
-    y0[1] = sc[1][0];
-#pragma unroll
-    for (uint32_t q = 0; q < SINK_C; ++q) {
-      const uint32_t i = t + SINK_NT * q;
-      if (i < m) out[base + i] = xw[i];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
+  float y0[2] = {p.state[2 * (size_t)s], p.state[2 * (size_t)s + 1]};
+  sink_scan_segments<2>(x, sc, row, reinterpret_cast<unsigned*>(p.pcm + (size_t)s * p.pcm_stride), p.n, p.alpha, p.gain, pc, y0);
+  if (threadIdx.x == 0) {
     p.state[2 * (size_t)s] = y0[0];
     p.state[2 * (size_t)s + 1] = y0[1];
   }
@@ -202,15 +87,6 @@ struct sdrfm_pcm_stereo_sink {
   int16_t* d_pcm;
   uint32_t cap;        // samples per stream the staging holds
 };
-
-#define STRY(expr, code)                                                                                       \
-  do {                                                                                                         \
-    hipError_t e__ = (expr);                                                                                   \
-    if (e__ != hipSuccess) {                                                                                   \
-      fprintf(stderr, "[sdrfm] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__);  \
-      return (code);                                                                                           \
-    }                                                                                                          \
-  } while (0)
 
 static void stereo_sink_free(sdrfm_pcm_stereo_sink* k) {
   if (!k) return;
@@ -265,14 +141,21 @@ int sdrfm_stereo_sink_reserve(sdrfm_pcm_stereo_sink* k, uint32_t n, int16_t** d_
   return SDRFM_OK;
 }
 
+// one call of the sink over device buffers, in either form, on `stream`
+static int stereo_sink_launch(sdrfm_pcm_stereo_sink* k, const float* left, const float* right, size_t audio_stride, uint32_t n, int16_t* pcm, size_t pcm_stride,
+                              hipStream_t stream, bool exact) {
+  const StereoSinkParams p = stereo_sink_params(k, left, right, audio_stride, n, pcm, pcm_stride);
+  if (exact) hipLaunchKernelGGL(k_pcm_stereo_sink, dim3((k->n_streams + 63) / 64), dim3(64), 0, stream, p);
+  else hipLaunchKernelGGL(k_pcm_stereo_sink_scan, dim3(k->n_streams), dim3(SINK_NT), 0, stream, p, sink_carry_factor(k->alpha));
+  STRY(hipGetLastError(), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
 int sdrfm_stereo_sink_launch_on(sdrfm_pcm_stereo_sink* k, const float* left, const float* right, size_t audio_stride, uint32_t n, int16_t* pcm,
                                 size_t pcm_stride, hipStream_t stream) {
   if (!k) return SDRFM_EINVAL;
   if (n == 0) return SDRFM_OK;
-  const StereoSinkParams p = stereo_sink_params(k, left, right, audio_stride, n, pcm, pcm_stride);
-  hipLaunchKernelGGL(k_pcm_stereo_sink_scan, dim3(k->n_streams), dim3(SINK_NT), 0, stream, p, (float)pow(1.0 - (double)k->alpha, (double)SINK_C));
-  STRY(hipGetLastError(), SDRFM_FAIL);
-  return SDRFM_OK;
+  return stereo_sink_launch(k, left, right, audio_stride, n, pcm, pcm_stride, stream, false);
 }
 
 int sdrfm_stereo_sink_copy_back(const sdrfm_pcm_stereo_sink* k, int16_t* pcm, size_t pcm_stride, uint32_t n, hipStream_t stream) {
@@ -351,25 +234,17 @@ int sdrfm_pcm_stereo_sink_process_batch(sdrfm_pcm_stereo_sink_t* k, const float*
   if (ok != SDRFM_OK) return ok;
   STRY(hipSetDevice(k->device), SDRFM_FAIL);
   const bool exact = (flags & SDRFM_PCM_F_EXACT) != 0;
-  auto launch = [&](const StereoSinkParams& p) {
-    if (exact) hipLaunchKernelGGL(k_pcm_stereo_sink, dim3((k->n_streams + 63) / 64), dim3(64), 0, k->stream, p);
-    else hipLaunchKernelGGL(k_pcm_stereo_sink_scan, dim3(k->n_streams), dim3(SINK_NT), 0, k->stream, p, (float)pow(1.0 - (double)k->alpha, (double)SINK_C));
-  };
-  if (device_ptrs) {
-    launch(stereo_sink_params(k, left, right, audio_stride, n, pcm, pcm_stride));
-    STRY(hipGetLastError(), SDRFM_FAIL);
-    return SDRFM_OK;
-  }
+  if (device_ptrs) return stereo_sink_launch(k, left, right, audio_stride, n, pcm, pcm_stride, k->stream, exact);
   // host buffers: stage, run, copy back, synchronous
-  const int rc = sdrfm_stereo_sink_reserve(k, n, nullptr, nullptr);
+  int rc = sdrfm_stereo_sink_reserve(k, n, nullptr, nullptr);
   if (rc != SDRFM_OK) return rc;
   const size_t as = (k->n_streams > 1) ? audio_stride : n;
   STRY(hipMemcpy2DAsync(k->d_left, sizeof(float) * k->cap, left, sizeof(float) * as, sizeof(float) * n, k->n_streams, hipMemcpyHostToDevice, k->stream),
        SDRFM_FAIL);
   STRY(hipMemcpy2DAsync(k->d_right, sizeof(float) * k->cap, right, sizeof(float) * as, sizeof(float) * n, k->n_streams, hipMemcpyHostToDevice, k->stream),
        SDRFM_FAIL);
-  launch(stereo_sink_params(k, k->d_left, k->d_right, k->cap, n, k->d_pcm, 2 * (size_t)k->cap));
-  STRY(hipGetLastError(), SDRFM_FAIL);
+  rc = stereo_sink_launch(k, k->d_left, k->d_right, k->cap, n, k->d_pcm, 2 * (size_t)k->cap, k->stream, exact);
+  if (rc != SDRFM_OK) return rc;
   const int cb = sdrfm_stereo_sink_copy_back(k, pcm, pcm_stride, n, k->stream);
   if (cb != SDRFM_OK) return cb;
   STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);

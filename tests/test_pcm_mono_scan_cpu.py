@@ -1,4 +1,4 @@
-"""CPU: the arithmetic of the mono PCM sink's default form (k_pcm_sink_scan, csrc/sdrfm_sink.hip; its LIST instance serves routed streams behind a mixed launch with
+"""CPU: the arithmetic of the mono PCM sink's default form (k_pcm_sink_scan, csrc/sdrfm_sink.hip: sink_scan_segments<1> of csrc/sdrfm_sink_kernels.h; its LIST instance serves routed streams behind a mixed launch with
 the same arithmetic) restated in numpy (mono_scan_emulate, tools/pcm_stereo_scan_emulate.py: one chain of the stereo scan), held to the host routine
 sdrfm_pcm_deemph_s16 (csrc/pcm_sink.c) at the three caps of tests/test_pcm_sink_gpu.py: at the edges of a chunk and of a segment, at every alpha of
 tests/pcm_params.py and at its gains, two calls with the state carried."""

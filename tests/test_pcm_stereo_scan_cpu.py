@@ -1,4 +1,5 @@
-"""CPU: the arithmetic of the stereo PCM sink's default form (k_pcm_stereo_sink_scan, csrc/sdrfm_sink_stereo.hip) restated in numpy
+"""CPU: the arithmetic of the stereo PCM sink's default form (k_pcm_stereo_sink_scan, csrc/sdrfm_sink_stereo.hip: sink_scan_segments<2> of
+csrc/sdrfm_sink_kernels.h) restated in numpy
 (tools/pcm_stereo_scan_emulate.py), held to the host routine sdrfm_pcm_deemph_stereo_s16 (csrc/pcm_sink.c) on the very inputs
 tests/test_pcm_stereo_sink_gpu.py gives the kernel: the three bounds of that test (the mono sink's, tests/test_pcm_sink_gpu.py) hold by the
 arithmetic alone, without a GPU."""

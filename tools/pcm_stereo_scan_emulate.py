@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""tools/pcm_stereo_scan_emulate.py — (CPU) the arithmetic of the stereo PCM sink's default form (k_pcm_stereo_sink_scan, csrc/sdrfm_sink_stereo.hip)
+"""tools/pcm_stereo_scan_emulate.py — (CPU) the arithmetic of the stereo PCM sink's default form (k_pcm_stereo_sink_scan, csrc/sdrfm_sink_stereo.hip; the scan itself: sink_scan_segments, csrc/sdrfm_sink_kernels.h)
 restated in numpy with the kernel's operation order, for both channels side by side: segments of 256 chunks of 19 samples, the chunk's own contribution
 from state 0 (lane 0: from the carried state), six doubling steps within each wave of 64 lanes with the powers squared on the way, the four waves' totals
 combined, every chunk re-walked from its true carry-in with the exact chain's operations.  fp32 throughout (fused multiply-adds as in
 tools/pcm_chain_emulate.py: through float64, exact products, one rounding that differs from a true fma's in ~1e-9 of the cases).
 tests/test_pcm_stereo_scan_cpu.py holds it to the host routine sdrfm_pcm_deemph_stereo_s16 on the inputs of tests/test_pcm_stereo_sink_gpu.py, which
 sink_inputs() below makes for both.  mono_scan_emulate() is the mono sink's default form (k_pcm_sink_scan, csrc/sdrfm_sink.hip): the same scan over one
-chain, held to sdrfm_pcm_deemph_s16 by tests/test_pcm_mono_scan_cpu.py.  Test infrastructure: nothing here is on a product path."""
+chain, as in the kernels, which instantiate one body for one channel and for two, held to sdrfm_pcm_deemph_s16 by tests/test_pcm_mono_scan_cpu.py.  Test infrastructure: nothing here is on a product path."""
 import numpy as np
 
 from pcm_chain_emulate import F, fma, pcm_word
