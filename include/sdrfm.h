@@ -121,7 +121,8 @@ enum {
                                      waiting for the previous call's state —, and (b) audio is not a buffer the previous overlapped
                                      call writes (two audio buffers taken in turn).  Same audio, bit for bit, as without the flag.
                                      Calls that the matrix-pipe kernel does not serve (see SDRFM_CFG_BIT_EXACT), and the first call
-                                     after create / reset / a host-pointer call, run as if the flag were absent */
+                                     after create / reset / a host-pointer call / a call the matrix-pipe kernel did not serve, run
+                                     as if the flag were absent */
 
 typedef struct sdrfm_config {
   uint32_t struct_size;           /* = sizeof(sdrfm_config) */

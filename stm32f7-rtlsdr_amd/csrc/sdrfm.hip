@@ -909,6 +909,7 @@ struct FastVariant {
 #define SDRFM_FASTB2_LITE(T_, D_, R_, TA_, DA_) { 'b', T_, D_, R_, TA_, DA_, {k_fastb<T_, D_, R_, TA_, DA_, 0>, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (uint32_t)fastb_xbytes(T_, D_, R_), 0 }
 #define SDRFM_FASTB(T_, D_, R_) SDRFM_FASTB2(T_, D_, R_, 32, 5)
 #define SDRFM_STREAM(T_, D_, S_, NB_, TA_, DA_) { 's', T_, D_, S_, TA_, DA_, {k_stream<T_, D_, S_, NB_, TA_, DA_>, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 2u * 64u * 128u, (uint32_t)(NB_) * (S_) * (D_) }
+// (tests/native/fm_geom.h restates which shapes have an instance here, for the CPU pre-check of tests/fm_shape_cases.py: keep it in step)
 const FastVariant kFastVariants[] = {
     // design S (streaming lanes): the BASELINE configs[2]/[3] shape; serves calls that are whole numbers of lane segments
     // (a 16-tap instance is correct too but no faster than design B on cold inputs: 35.2 vs 34.1 us; it is not instantiated)
@@ -991,6 +992,7 @@ struct sdrfm {
   uint8_t* d_hist_q[2];
   unsigned int* d_qstat;
   bool yprev_exact, hist_q_valid;
+  bool prev_by_q;         // design Q served (some streams of) the previous call: the state it left is what an overlapped call's warm-up reproduces (route_apply leaves this alone)
   // Which kernel serves a stream is also a matter of what the stream holds: noise-only input sends design Q to its repair path at
   // almost every audio stage (3 x the time of a carrier's call; the bit-exact kernels: 1.4 x), and a kernel lasts as long as its slowest
   // wave — so the choice is made PER STREAM (round 5; rounds 3 - 4: per handle).  Design Q's waves add their repair passes into a word per
@@ -1513,6 +1515,7 @@ int sdrfm_reset(sdrfm_t* h) {
   }
   h->yprev_exact = true;                                          // y[-1] = 0, as the definition has it
   h->hist_q_valid = false;
+  h->prev_by_q = false;
   HIP_TRY(hipStreamSynchronize(h->stream), SDRFM_FAIL);
   { const int rrc = route_reset(h); if (rrc != SDRFM_OK) return rrc; }   // (behind the synchronisation: no kernel is left that could add to the statistics)
   h->cur = 0;
@@ -1785,7 +1788,11 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
   // whatever call comes next without the flag).  Any other call first orders the handle's stream behind the overlapped ones.
   // What the flag asks of the caller is checked where that is cheap: a call whose rows overlap the previous call's rows (one buffer used
   // for every call) or whose audio buffer is the one the previous overlapped call may still be writing runs as if the flag were absent.
-  const bool ovl = q_ok && (call_flags & SDRFM_F_OVERLAP) && h->prev_iq &&
+  // So does a call right behind one design Q did not serve (prev_by_q; NOT hist_q_valid, which route_apply also sets when it refills hist_q from the
+  // bit-exact kernels' samples): the warm-up would recompute y[-1] and the last Ta - 1 discriminator outputs with design Q's arithmetic where the same
+  // call without the flag takes over the definition's from the bit-exact kernels' state — the first audio outputs then differ in their last bits, and
+  // the flag promises the same audio bit for bit (tests/test_fm_shapes_gpu.py: "prev-served-by-b", "prev-served-by-b-then-routed").
+  const bool ovl = q_ok && (call_flags & SDRFM_F_OVERLAP) && h->prev_iq && h->prev_by_q &&
                    fm_ovl_geometry_ok(g, cl, h->prev_nbytes, ((uintptr_t)h->prev_iq % 16 == 0) && (h->prev_stride % 16 == 0)) &&
                    !fm_rows_overlap(h->prev_iq, h->prev_stride, h->prev_nbytes, d_iq, iq_stride, nbytes, c.n_streams) &&
                    // (a call that writes no audio — no buffer given, the chain inside the launch — has no audio rows to collide)
@@ -1808,7 +1815,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
       HIP_TRY(sdrfm_q_fix_yprev(h->d_hist_q[h->cur], h->d_hpad, h->d_yprev[h->cur], c.n_streams - nn, nn ? h->rt_list_dev[h->rt_list_cur] : nullptr, h->stream),
               SDRFM_FAIL);
     }
-    h->yprev_exact = true; h->hist_q_valid = false;
+    h->yprev_exact = true; h->hist_q_valid = false; h->prev_by_q = false;
     h->prev_ovl_audio = nullptr;
   }
   const uint32_t* list_dev = (h->rt_noisy && n_noisy) ? h->rt_list_dev[h->rt_list_cur] : nullptr;   // [clean streams][noisy streams]
@@ -1917,7 +1924,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     if (ovl) { h->ovl_pending[k] = true; h->ovl_bound[k] = carry; }
     h->prev_ovl_audio = (ovl && !(with_chain && h->pcm_no_audio)) ? d_audio : nullptr; h->prev_ovl_audio_stride = audio_stride; h->prev_ovl_audio_n = A;
     h->prev_ovl_pcm = (ovl && with_chain) ? h->pcm_out : nullptr; h->prev_ovl_pcm_stride = h->pcm_out_stride;
-    h->yprev_exact = false; h->hist_q_valid = true;
+    h->yprev_exact = false; h->hist_q_valid = true; h->prev_by_q = true;
     // ---- the window close ----------------------------------------------------------------------------------------------------------------------
     if (h->rt_noisy && !h->rt_off) {
       h->rt_win_stages += fm_win_stages(r.runs, q_steps, c.audio_decim);

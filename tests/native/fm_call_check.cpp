@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "../../stm32f7-rtlsdr_amd/csrc/sdrfm_fm_call.h"
+#include "fm_geom.h"
 
 static int g_failed = 0;
 #define CHECK(cond, ...)                                                         \
@@ -31,19 +32,8 @@ static uint64_t rnd() {                                          // splitmix64
 }
 static uint32_t rnd_in(uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rnd() % ((uint64_t)hi - lo + 1)); }
 
-// a handle of shape (T, D, Ta, Da) on a 256-CU device, every design instantiated: the values sdrfm_create arrives at for the headline shape
-// (tile R = 12 at two waves per SIMD, the R = 4 tile of 6.8 KB beside design Q's waves of 10.9 KB, 12 workgroups of either kind per CU)
-static FmGeom geom(uint32_t T, uint32_t D, uint32_t Ta, uint32_t Da, uint32_t ns) {
-  FmGeom g;
-  memset(&g, 0, sizeof(g));
-  g.T = T; g.D = D; g.Ta = Ta; g.Da = Da; g.n_streams = ns; g.n_cu = 256;
-  g.has_q = true; g.has_fast = true; g.fast_is_b = true; g.has_s = (D == 10 && Da == 5 && Ta == 32 && (T == 64 || T == 32)); g.has_mix_tile = true;
-  g.mix_lds = 17000; g.q_waves_per_cu = (D == 16) ? 11 : 12; g.q_lds = 11164;
-  g.fast_R = (D == 16) ? 8 : 12; g.fast_lds = 19968; g.waves_target = 256 * 8; g.min_subtiles = 4; g.fold_state_ok = 1;
-  g.fast_mix_lds = 6960; g.mix_R = 4; g.mix_waves_per_cu = g.q_waves_per_cu; g.mix_cost = 2.7; g.mix_rho = 12.7; g.mix_split_off = false;
-  g.seg = 6 * 8 * D; g.NA = 64;
-  return g;
-}
+// a handle of shape (T, D, Ta, Da) on a 256-CU device, every design instantiated (tests/native/fm_geom.h)
+static FmGeom geom(uint32_t T, uint32_t D, uint32_t Ta, uint32_t Da, uint32_t ns) { return fm_test_geom(T, D, Ta, Da, ns); }
 
 static FmCall call_of(uint32_t phase_x, uint32_t phase_d, uint32_t nbytes, const FmGeom& g, uint64_t n_seen, bool al4, bool al16) {
   const FmCounts n = fm_counts(phase_x, phase_d, nbytes, g.D, g.Da);
