@@ -480,6 +480,94 @@ const char* sdrfm_bcast_kernel_name(const sdrfm_bcast_t* h);
 int  sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uint32_t flags);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Scan: which offsets of a capture hold a station, how far off the tuning is, how strong the station is and whether
+ * it carries a pilot.  A scan stream is a tuned stream of the section above up to d and the pilot filter — x, the tuned K2 (two real
+ * fmaf chains, yr = Ar - Bi, yi = Ai + Br), sdrfm_discriminate_tuned's K3, the carried state (input history, y[-1], the last P - 1 d's)
+ * and the pilot filter q[m] = sum_k b[k] d[m - k] as two fp32 fmaf chains, oldest first, d[m < 0] = 0 — and nothing behind q.
+ * For every NEW d of a call, index m, five fp32 terms, each rounded once where written:
+ *     p  = fmaf(yr, yr, yi*yi)        |y[m]|^2
+ *     d  = d[m]
+ *     e  = d*d
+ *     pw = fmaf(qr, qr, qi*qi)        q = q[m]: the window that ENDS at the new d m
+ *     g  = pw*pw
+ * Each term becomes an integer by (int64) rintf(term * 2^k) — ties to even; the scaling by a power of two is exact and the conversion
+ * of an integral float is exact — with k = 8 for p, 24 for d, e and pw, 20 for g, and the record of a stream is the sum over the call.
+ * INTEGER SUMS ARE ASSOCIATIVE: the record does not depend on the workgroup split, on the order the waves arrive in, on which kernel
+ * form ran, or on how a capture is cut into calls — the records of consecutive calls ADD UP EXACTLY (sdrfm_scan_meter_add) to the
+ * record of the one call over the concatenated bytes.  That is the point of the fixed-point form.
+ * Bounds that keep every sum inside int64, refused with SDRFM_EINVAL at create and at tune:
+ *     sum_k (|hr[k]| + |hi[k]|) <= 16 per stream     |yr|, |yi| <= 2040, p <= 8 323 200
+ *     sum_k (|br[k]| + |bi[k]|) <= 8                 |qr|, |qi| <= 8 pi, pw <= 1270
+ *     max_bytes_per_call <= 4 MiB                    n <= 2^21 new d's per call
+ * Worst-case sums of one call: |rf_q| < 2^52, |freq_q| < 2^47, dev_q < 2^49, pilot_q < 2^56, pilot2_q < 2^62.  (The intended taps have
+ * sums of about 2 and 3.4.)  sdrfm_scan_meter_add adds without a check: the sum of many calls is the caller's to bound.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct sdrfm_scan_meter {   /* 64 bytes */
+  uint64_t n;         /* new d's of the call (M) */
+  uint64_t n_pilot;   /* those with pw >= pilot_min^2: what pilot_count counts */
+  int64_t  rf_q;      /* sum rint(p  * 2^8)  */
+  int64_t  freq_q;    /* sum rint(d  * 2^24) */
+  int64_t  dev_q;     /* sum rint(e  * 2^24) */
+  int64_t  pilot_q;   /* sum rint(pw * 2^24) */
+  int64_t  pilot2_q;  /* sum rint(g  * 2^20) */
+  uint64_t reserved;  /* 0 */
+} sdrfm_scan_meter;
+
+#define SDRFM_SCAN_CFG_FORCE_GENERIC 1u      /* tests: never the fast kernel */
+#define SDRFM_SCAN_CFG_SHARED_INPUT  2u      /* every stream reads row 0 of iq; iq_stride ignored; a host call stages one row */
+typedef struct sdrfm_scan_config {
+  uint32_t struct_size;           /* = sizeof(sdrfm_scan_config) */
+  uint32_t n_streams;             /* candidates */
+  uint32_t fir_taps;              /* T */
+  uint32_t fir_decim;             /* D */
+  const float* ctaps;             /* n_streams x 2T, (hr[k], hi[k]) pairs, as sdrfm_bcast_tune's */
+  const float* rot;               /* n_streams, |rot| <= pi */
+  uint32_t pilot_taps;            /* P, odd */
+  const float* pilot_coeffs;      /* 2P floats (re, im) */
+  float    pilot_min;             /* the gate n_pilot counts with, as the stereo handle's */
+  uint32_t max_bytes_per_call;    /* per stream; 0 = 1 MiB; at most 4 MiB */
+  int32_t  device;
+  uint32_t flags;                 /* SDRFM_SCAN_CFG_* */
+} sdrfm_scan_config;
+
+typedef struct sdrfm_scan sdrfm_scan_t;
+
+/* The contract is sdrfm_bcast_process_batch's.  Host buffers: a synchronous staged call.  SDRFM_F_DEVICE_PTRS: iq and meters are device
+ * memory (meters 8-byte aligned) and the call is only enqueued on the handle's stream.  SDRFM_F_OVERLAP and unknown flags: SDRFM_EINVAL.
+ * Odd nbytes: SDRFM_EODD.  nbytes above the maximum, or iq_stride < nbytes on unshared rows of more than one stream: SDRFM_ECAPACITY.
+ * meters (n_streams records) is OVERWRITTEN: zeroed on the handle's stream before the launch adds to it; nbytes == 0 gives zero records.
+ * A refused call leaves the carried state alone.  Every refusal of create comes before any device is looked for.
+ * sdrfm_scan_tune replaces both ctaps and rot and restarts the streams (either NULL, a non-finite value, |rot| > pi or a tap sum above
+ * its bound: SDRFM_EINVAL, nothing changed); sdrfm_scan_reset zeroes the carried state and keeps the tuning.
+ * Kernel name: "scan-fast T64 D10 P101" or "scan-generic T.. D.. P.."; the same records either way. */
+int  sdrfm_scan_create(const sdrfm_scan_config* cfg, sdrfm_scan_t** out);
+void sdrfm_scan_destroy(sdrfm_scan_t* h);
+int  sdrfm_scan_reset(sdrfm_scan_t* h);
+int  sdrfm_scan_tune(sdrfm_scan_t* h, const float* ctaps, const float* rot);
+int  sdrfm_scan_process_batch(sdrfm_scan_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, sdrfm_scan_meter* meters, uint32_t flags);
+int  sdrfm_scan_set_stream(sdrfm_scan_t* h, void* hip_stream);
+int  sdrfm_scan_synchronize(sdrfm_scan_t* h);
+const char* sdrfm_scan_kernel_name(const sdrfm_scan_t* h);
+
+/* Host-only (plain C, no GPU): what a record says, in double.  fs is the input rate, D the handle's fir_decim, pilot_gain the gain
+ * H_D(19 kHz) of the discriminator's D-sample boxcar at the pilot (sin(pi f D/fs) / (D sin(pi f/fs)); 0.98982 at D = 10, 2.4 MS/s).
+ * With the means taken over the record's n:
+ *     level_dbfs        10 log10(mean p / 127.5^2)
+ *     freq_err_hz       mean d * fs / (2 pi D)                               the carrier's distance from the tuned offset
+ *     dev_rms_hz        sqrt(mean e - (mean d)^2) * fs / (2 pi D)            the rms deviation about that carrier
+ *     pilot_rms_rad     sqrt(mean pw)                                        rms |q|, the pilot's amplitude in d
+ *     pilot_dev_hz      pilot_rms_rad * fs / (2 pi D) / pilot_gain           the pilot's deviation
+ *     pilot_frac        n_pilot / n
+ *     pilot_steadiness  n * sum g / (sum pw)^2 on the de-scaled sums         1 for a steady pilot, 2 for noise
+ * n == 0: every field is NaN (SDRFM_OK).  NULL m or out, D == 0, fs or pilot_gain not finite and positive: SDRFM_EINVAL. */
+typedef struct sdrfm_scan_report_t {
+  double level_dbfs, freq_err_hz, dev_rms_hz, pilot_rms_rad, pilot_dev_hz, pilot_frac, pilot_steadiness;
+} sdrfm_scan_report_t;
+int  sdrfm_scan_report(const sdrfm_scan_meter* m, double fs, uint32_t D, double pilot_gain, sdrfm_scan_report_t* out);
+/* acc += m, field by field (two's-complement wrap-around, no check); NULL: SDRFM_EINVAL */
+int  sdrfm_scan_meter_add(sdrfm_scan_meter* acc, const sdrfm_scan_meter* m);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Spectrum view of the IQ buffer — the reference's own next task ("Perform some FFT on the samples to check what we are
  * receiving", README.md:29) on the same buffer contract (RTLSDR_CommItfTypedef.buff, usbh_rtlsdr.h:165-173): per stream
  * the windowed nfft-point power spectrum averaged over the consecutive, non-overlapping frames of the buffer, DC in the

@@ -36,6 +36,8 @@ ABI_SYMBOLS = [
     "sdrfm_pcm_stereo_sink_create", "sdrfm_pcm_stereo_sink_destroy", "sdrfm_pcm_stereo_sink_reset", "sdrfm_pcm_stereo_sink_process_batch",
     "sdrfm_pcm_stereo_sink_set_stream", "sdrfm_pcm_stereo_sink_synchronize", "sdrfm_pcm_stereo_sink_get_state",
     "sdrfm_stereo_process_batch_pcm", "sdrfm_bcast_process_batch_pcm",
+    "sdrfm_scan_create", "sdrfm_scan_destroy", "sdrfm_scan_reset", "sdrfm_scan_tune", "sdrfm_scan_process_batch", "sdrfm_scan_set_stream",
+    "sdrfm_scan_synchronize", "sdrfm_scan_kernel_name", "sdrfm_scan_report", "sdrfm_scan_meter_add",
 ]
 
 
@@ -110,6 +112,24 @@ class BcastConfig(C.Structure):
         ("rds_coeffs", C.POINTER(C.c_float)), ("max_bytes_per_call", C.c_uint32), ("device", C.c_int32),
         ("flags", C.c_uint32),
     ]
+
+
+class ScanConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_streams", C.c_uint32), ("fir_taps", C.c_uint32), ("fir_decim", C.c_uint32),
+        ("ctaps", C.POINTER(C.c_float)), ("rot", C.POINTER(C.c_float)), ("pilot_taps", C.c_uint32), ("pilot_coeffs", C.POINTER(C.c_float)),
+        ("pilot_min", C.c_float), ("max_bytes_per_call", C.c_uint32), ("device", C.c_int32), ("flags", C.c_uint32),
+    ]
+
+
+class ScanMeter(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("n_pilot", C.c_uint64), ("rf_q", C.c_int64), ("freq_q", C.c_int64), ("dev_q", C.c_int64),
+                ("pilot_q", C.c_int64), ("pilot2_q", C.c_int64), ("reserved", C.c_uint64)]
+
+
+class ScanReport(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("level_dbfs", "freq_err_hz", "dev_rms_hz", "pilot_rms_rad", "pilot_dev_hz", "pilot_frac",
+                                          "pilot_steadiness")]
 
 
 class RdsGroup(C.Structure):
@@ -342,5 +362,25 @@ def load_library(dev=False):
     lib.sdrfm_stereo_process_batch_pcm.restype = C.c_int
     lib.sdrfm_bcast_process_batch_pcm.argtypes = [vp, vp, vp, C.c_size_t, u32, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, u32p, u32p, u32]
     lib.sdrfm_bcast_process_batch_pcm.restype = C.c_int
+    lib.sdrfm_scan_create.argtypes = [C.POINTER(ScanConfig), C.POINTER(vp)]
+    lib.sdrfm_scan_create.restype = C.c_int
+    lib.sdrfm_scan_destroy.argtypes = [vp]
+    lib.sdrfm_scan_destroy.restype = None
+    lib.sdrfm_scan_reset.argtypes = [vp]
+    lib.sdrfm_scan_reset.restype = C.c_int
+    lib.sdrfm_scan_tune.argtypes = [vp, vp, vp]
+    lib.sdrfm_scan_tune.restype = C.c_int
+    lib.sdrfm_scan_process_batch.argtypes = [vp, vp, C.c_size_t, u32, vp, u32]
+    lib.sdrfm_scan_process_batch.restype = C.c_int
+    lib.sdrfm_scan_set_stream.argtypes = [vp, vp]
+    lib.sdrfm_scan_set_stream.restype = C.c_int
+    lib.sdrfm_scan_synchronize.argtypes = [vp]
+    lib.sdrfm_scan_synchronize.restype = C.c_int
+    lib.sdrfm_scan_kernel_name.argtypes = [vp]
+    lib.sdrfm_scan_kernel_name.restype = C.c_char_p
+    lib.sdrfm_scan_report.argtypes = [vp, C.c_double, u32, C.c_double, C.POINTER(ScanReport)]
+    lib.sdrfm_scan_report.restype = C.c_int
+    lib.sdrfm_scan_meter_add.argtypes = [vp, vp]
+    lib.sdrfm_scan_meter_add.restype = C.c_int
     _libs[dev] = lib
     return lib

@@ -1,0 +1,214 @@
+"""ScanDemod — Python mirror of the sdrfm_scan_* C entry points (the scan handle): one integer record per candidate
+offset of a capture, and on top of it what the records say (meter_report), which candidates are stations (find_stations) and the three
+steps in one (scan_capture), whose result feeds BroadcastDemod.tune."""
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import lib as _l
+from .stereo import _pilot_floats
+from .taps import pilot_gain, stereo_pilot_taps, tuned_channel_taps, tuned_rotation
+
+CFG_FORCE_GENERIC = 1   # SDRFM_SCAN_CFG_FORCE_GENERIC (include/sdrfm.h)
+CFG_SHARED_INPUT = 2    # SDRFM_SCAN_CFG_SHARED_INPUT
+MAX_BYTES_PER_CALL = 4 << 20
+
+# sdrfm_scan_meter as a structured dtype: process_batch returns an array of these
+METER_DTYPE = np.dtype([("n", "<u8"), ("n_pilot", "<u8"), ("rf_q", "<i8"), ("freq_q", "<i8"), ("dev_q", "<i8"), ("pilot_q", "<i8"),
+                        ("pilot2_q", "<i8"), ("reserved", "<u8")])
+assert METER_DTYPE.itemsize == C.sizeof(_l.ScanMeter) == 64
+REPORT_FIELDS = tuple(n for n, _ in _l.ScanReport._fields_)
+
+
+@dataclass
+class ScanConfig:
+    pilot_coeffs: np.ndarray              # b[0..P): complex taps (complex array, or 2P floats re, im), P odd (taps.stereo_pilot_taps)
+    offsets_hz: Optional[np.ndarray] = None   # one candidate per stream, with h and fs ...
+    h: Optional[np.ndarray] = None        # ... the channel low-pass at fs that taps.tuned_channel_taps moves to every offset
+    fs: float = 2.4e6
+    ctaps: Optional[np.ndarray] = None    # or the caller's own [n_streams, 2T] ...
+    rot: Optional[np.ndarray] = None      # ... and [n_streams]
+    pilot_min: float = 0.05
+    fir_decim: int = 10
+    shared_input: bool = False            # every stream reads row 0 of the input
+    max_bytes_per_call: int = 1 << 20     # at most 4 MiB
+    device: int = 0
+    force_generic: bool = False           # SDRFM_SCAN_CFG_FORCE_GENERIC (tests): never the fast kernel
+
+
+def _tuning(offsets_hz, h, fs, D):
+    off = np.atleast_1d(np.asarray(offsets_hz, dtype=np.float64))
+    ctaps = np.stack([tuned_channel_taps(h, f, fs) for f in off])
+    rot = np.array([tuned_rotation(f, fs, D) for f in off], dtype=np.float32)
+    return ctaps, rot
+
+
+class ScanDemod:
+    def __init__(self, cfg: ScanConfig):
+        self._lib = _l.load_library()
+        self.cfg = cfg
+        if cfg.offsets_hz is not None:
+            assert cfg.ctaps is None and cfg.rot is None and cfg.h is not None, "offsets_hz with h, or ctaps with rot"
+            self._hc = np.ascontiguousarray(cfg.h, dtype=np.float32)
+            ctaps, rot = _tuning(cfg.offsets_hz, self._hc, cfg.fs, cfg.fir_decim)
+        else:
+            assert cfg.ctaps is not None and cfg.rot is not None, "offsets_hz with h, or ctaps with rot"
+            self._hc = None if cfg.h is None else np.ascontiguousarray(cfg.h, dtype=np.float32)
+            ctaps, rot = cfg.ctaps, cfg.rot
+        rot = np.ascontiguousarray(rot, dtype=np.float32).reshape(-1)
+        ctaps = np.ascontiguousarray(ctaps, dtype=np.float32).reshape(rot.size, -1)
+        assert ctaps.shape[1] % 2 == 0, ctaps.shape
+        self.n_streams, self._T = rot.size, ctaps.shape[1] // 2
+        self._bc = _pilot_floats(cfg.pilot_coeffs)
+        fp = C.POINTER(C.c_float)
+        c = _l.ScanConfig()
+        c.struct_size = C.sizeof(_l.ScanConfig)
+        c.n_streams, c.fir_taps, c.fir_decim = self.n_streams, self._T, cfg.fir_decim
+        c.ctaps, c.rot = ctaps.ctypes.data_as(fp), rot.ctypes.data_as(fp)
+        c.pilot_taps, c.pilot_coeffs, c.pilot_min = self._bc.size // 2, self._bc.ctypes.data_as(fp), float(cfg.pilot_min)
+        c.max_bytes_per_call, c.device = cfg.max_bytes_per_call, cfg.device
+        c.flags = (CFG_FORCE_GENERIC if cfg.force_generic else 0) | (CFG_SHARED_INPUT if cfg.shared_input else 0)
+        self._h = C.c_void_p()
+        st = self._lib.sdrfm_scan_create(C.byref(c), C.byref(self._h))
+        if st != _l.OK:
+            self._h = None
+            raise _l.SdrfmError(st, "sdrfm_scan_create")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.sdrfm_scan_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _ck(self, st, where):
+        if st != _l.OK:
+            raise _l.SdrfmError(st, where)
+
+    def reset(self):
+        self._ck(self._lib.sdrfm_scan_reset(self._h), "sdrfm_scan_reset")
+
+    def tune(self, offsets_hz=None, fs=None, ctaps=None, rot=None):
+        """sdrfm_scan_tune: new candidates — offsets_hz (moved from the handle's h at fs, the configuration's by default) or the caller's
+        own ctaps [n_streams, 2T] and rot [n_streams] — and a restart of every stream."""
+        if offsets_hz is not None:
+            assert ctaps is None and rot is None and self._hc is not None, "offsets_hz needs the h the handle was made with"
+            ctaps, rot = _tuning(np.broadcast_to(np.asarray(offsets_hz, np.float64), (self.n_streams,)), self._hc,
+                                 self.cfg.fs if fs is None else fs, self.cfg.fir_decim)
+        ctaps = np.ascontiguousarray(ctaps, dtype=np.float32)
+        rot = np.ascontiguousarray(rot, dtype=np.float32)
+        assert ctaps.size == self.n_streams * 2 * self._T and rot.size == self.n_streams, (ctaps.shape, rot.shape)
+        self._ck(self._lib.sdrfm_scan_tune(self._h, ctaps.ctypes.data, rot.ctypes.data), "sdrfm_scan_tune")
+
+    def set_stream(self, ptr):
+        self._ck(self._lib.sdrfm_scan_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_scan_set_stream")
+
+    @property
+    def kernel_name(self):
+        return self._lib.sdrfm_scan_kernel_name(self._h).decode()
+
+    def synchronize(self):
+        self._ck(self._lib.sdrfm_scan_synchronize(self._h), "sdrfm_scan_synchronize")
+
+    def process_batch(self, iq: np.ndarray):
+        """host memory: iq [n_streams, nbytes] uint8 (one row with shared_input) -> records, a METER_DTYPE array [n_streams]"""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        if iq.ndim == 1:
+            iq = iq[None, :]
+        assert iq.shape[0] == (1 if self.cfg.shared_input else self.n_streams), iq.shape
+        nbytes = iq.shape[1]
+        meters = np.zeros(self.n_streams, dtype=METER_DTYPE)
+        self._ck(self._lib.sdrfm_scan_process_batch(self._h, iq.ctypes.data, nbytes, nbytes, meters.ctypes.data, 0), "sdrfm_scan_process_batch")
+        return meters
+
+    def process_batch_device(self, iq, meters, nbytes=None):
+        """device tensors: iq uint8 [n_streams, >= nbytes] (row 0 alone is read with shared_input), meters int64 [n_streams, 8]
+        (sdrfm_scan_meter's eight words); enqueue only"""
+        assert iq.is_cuda and meters.is_cuda and meters.is_contiguous() and meters.element_size() * meters.numel() >= 64 * self.n_streams
+        nbytes = iq.shape[-1] if nbytes is None else int(nbytes)
+        stride = iq.stride(0) if iq.dim() > 1 else nbytes
+        self._ck(self._lib.sdrfm_scan_process_batch(self._h, C.c_void_p(iq.data_ptr()), stride, nbytes, C.c_void_p(meters.data_ptr()),
+                                                    _l.F_DEVICE_PTRS), "sdrfm_scan_process_batch(device)")
+
+
+def meter_add(acc, m):
+    """acc += m through sdrfm_scan_meter_add, record by record (METER_DTYPE arrays of one shape); returns acc"""
+    lib = _l.load_library()
+    assert acc.dtype == METER_DTYPE and m.dtype == METER_DTYPE and acc.shape == m.shape and acc.flags.c_contiguous
+    m = np.ascontiguousarray(m)
+    for k in range(acc.size):
+        st = lib.sdrfm_scan_meter_add(acc.ctypes.data + 64 * k, m.ctypes.data + 64 * k)
+        if st != _l.OK:
+            raise _l.SdrfmError(st, "sdrfm_scan_meter_add")
+    return acc
+
+
+def meter_report(meters, fs, D):
+    """records -> dict of float64 arrays, one entry per field of sdrfm_scan_report_t, through sdrfm_scan_report with
+    pilot_gain = taps.pilot_gain(D, fs)"""
+    lib = _l.load_library()
+    meters = np.ascontiguousarray(np.atleast_1d(meters), dtype=METER_DTYPE)
+    out = {n: np.empty(meters.size, np.float64) for n in REPORT_FIELDS}
+    r = _l.ScanReport()
+    for k in range(meters.size):
+        st = lib.sdrfm_scan_report(meters.ctypes.data + 64 * k, float(fs), int(D), pilot_gain(int(D), float(fs)), C.byref(r))
+        if st != _l.OK:
+            raise _l.SdrfmError(st, "sdrfm_scan_report")
+        for n in REPORT_FIELDS:
+            out[n][k] = getattr(r, n)
+    return out
+
+
+def find_stations(report, offsets_hz, grid_hz, max_dev_rms_hz=55e3, max_steadiness=1.3, pilot_min=0.05):
+    """The candidates of a meter_report that hold a station.  Candidate c is one iff its rms deviation is an FM station's and not noise's
+    (dev_rms_hz <= max_dev_rms_hz: 40 - 46 kHz against 65 kHz and more on an empty channel or beside a station) and its carrier lies
+    nearer to this candidate than to the next (|freq_err_hz| < grid_hz / 2); it is stereo iff its pilot is steady besides
+    (pilot_steadiness <= max_steadiness: 1 for a tone, 2 for noise) and at least pilot_min strong.  Returns a list of dicts:
+    offset_hz (the candidate's offset plus its error), level_dbfs, stereo, candidate."""
+    off = np.atleast_1d(np.asarray(offsets_hz, np.float64))
+    found = []
+    for c in range(off.size):
+        if not (report["dev_rms_hz"][c] <= max_dev_rms_hz and abs(report["freq_err_hz"][c]) < grid_hz / 2):
+            continue
+        stereo = bool(report["pilot_steadiness"][c] <= max_steadiness and report["pilot_rms_rad"][c] >= pilot_min)
+        found.append(dict(offset_hz=float(off[c] + report["freq_err_hz"][c]), level_dbfs=float(report["level_dbfs"][c]), stereo=stereo, candidate=c))
+    return found
+
+
+def scan_grid(fs, grid_hz=100e3, span_hz=None):
+    """the candidate offsets of scan_capture: the multiples of grid_hz within +-span_hz (fs / 2 less one grid step by default)"""
+    span = fs / 2 - grid_hz if span_hz is None else float(span_hz)
+    k = int(np.floor(span / grid_hz + 1e-9))
+    return grid_hz * np.arange(-k, k + 1, dtype=np.float64)
+
+
+def scan_capture(iq_row, fs, h, grid_hz=100e3, span_hz=None, fir_decim=10, pilot_taps=101, pilot_min=0.05, device=0, details=False):
+    """One capture row (uint8, interleaved I/Q at fs) -> the stations in it: a ScanDemod over scan_grid's candidates with the row shared
+    by all of them, walked in calls of at most 4 MiB whose records add up exactly, then meter_report and find_stations.  The result's
+    offsets go straight into BroadcastDemod.tune(offsets_hz=[s["offset_hz"] for s in found], fs=fs, shared_input=True).
+    details=True returns (stations, report, offsets_hz, records) instead."""
+    row = np.ascontiguousarray(iq_row, dtype=np.uint8).reshape(-1)
+    row = row[:row.size & ~1]
+    offsets = scan_grid(fs, grid_hz, span_hz)
+    chunk = min(MAX_BYTES_PER_CALL, max(row.size, 2))
+    cfg = ScanConfig(pilot_coeffs=stereo_pilot_taps(pilot_taps, fs / fir_decim), offsets_hz=offsets, h=h, fs=fs, pilot_min=pilot_min,
+                     fir_decim=fir_decim, shared_input=True, max_bytes_per_call=chunk, device=device)
+    total = np.zeros(offsets.size, dtype=METER_DTYPE)
+    with ScanDemod(cfg) as sc:
+        for pos in range(0, row.size, chunk):
+            meter_add(total, sc.process_batch(row[pos:pos + chunk]))
+    report = meter_report(total, fs, fir_decim)
+    found = find_stations(report, offsets, grid_hz, pilot_min=pilot_min)
+    return (found, report, offsets, total) if details else found
