@@ -35,6 +35,7 @@
 #include "sdrfm_math.h"
 #include "sdrfm_q.h"
 #include "sdrfm_fm_call.h"
+#include "sdrfm_fm_plan.h"
 
 #include "sdrfm_b.h"
 
@@ -887,47 +888,26 @@ __global__ void __launch_bounds__(256) k_route_collect(uint32_t* dev, uint32_t* 
   if (i < n) { host[i] = dev[i]; dev[i] = 0u; }
 }
 
-struct FastVariant {
-  char kind;                         // 'a' = float tile (design A), 'b' = raw-byte tile (design B), 's' = streaming lanes (design S)
-  uint32_t T, D, R;                  // R: outputs per lane and sub-tile (A, B) / accumulator slots (S)
-  uint32_t Ta, Da;                   // design B only: compile-time audio geometry (0 = any)
-  void (*kernel[8])(CallParams);   // [0] product; [1..7] timing experiments (profile / ablations)
-  uint32_t xbytes;                   // LDS bytes of the sample tile (A, B) / of the whole ring (S)
-  uint32_t seg;                      // design S: samples per lane segment (0 otherwise)
-};
-#ifdef SDRFM_DEV
-#define SDRFM_FAST(T_, D_, R_) { 'a', T_, D_, R_, 0, 0, {k_fast<T_, D_, R_, 0>, k_fast<T_, D_, R_, 1>, k_fast<T_, D_, R_, 2>, k_fast<T_, D_, R_, 3>, k_fast<T_, D_, R_, 4>, k_fast<T_, D_, R_, 5>, k_fast<T_, D_, R_, 6>, k_fast<T_, D_, R_, 7>}, (uint32_t)fast_xbytes(T_, D_, R_), 0 }
-#define SDRFM_FAST_LITE(T_, D_, R_) { 'a', T_, D_, R_, 0, 0, {k_fast<T_, D_, R_, 0>, k_fast<T_, D_, R_, 1>, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (uint32_t)fast_xbytes(T_, D_, R_), 0 }
-#define SDRFM_FASTB2(T_, D_, R_, TA_, DA_) { 'b', T_, D_, R_, TA_, DA_, {k_fastb<T_, D_, R_, TA_, DA_, 0>, k_fastb<T_, D_, R_, TA_, DA_, 1>, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (uint32_t)fastb_xbytes(T_, D_, R_), 0 }
-// headline shape only, timing ablations with wrong results (SDRFM_ABLATE=2..5): [2] halo samples not converted, [3] no sample
-// converted, [4] no discriminator, [5] no conversion, no FIR, no discriminator (staging, LDS window reads and audio stage remain)
-#define SDRFM_FASTB2_ABL(T_, D_, R_, TA_, DA_) { 'b', T_, D_, R_, TA_, DA_, {k_fastb<T_, D_, R_, TA_, DA_, 0>, k_fastb<T_, D_, R_, TA_, DA_, 1>, k_fastb<T_, D_, R_, TA_, DA_, 2>, k_fastb<T_, D_, R_, TA_, DA_, 3>, k_fastb<T_, D_, R_, TA_, DA_, 4>, k_fastb<T_, D_, R_, TA_, DA_, 5>, nullptr, nullptr}, (uint32_t)fastb_xbytes(T_, D_, R_), 0 }
-#else   // product library: the result-correct kernel of every shape and nothing else
-#define SDRFM_FASTB2(T_, D_, R_, TA_, DA_) SDRFM_FASTB2_LITE(T_, D_, R_, TA_, DA_)
-#define SDRFM_FASTB2_ABL(T_, D_, R_, TA_, DA_) SDRFM_FASTB2_LITE(T_, D_, R_, TA_, DA_)
+// The handle's tiles: kFmInstances (sdrfm_fm_tiles.h) with their kernels, entry for entry.  [0] product; [1..7] timing experiments (profile / ablations),
+// instantiated where the instance's modes say so (development library) and nullptr elsewhere.
+typedef void (*FmKernel)(CallParams);
+struct FastVariant : FmInstance { FmKernel kernel[8]; };
+template <int T, int D, int S, int NB, int TA, int DA>
+constexpr FmKernel stream_kernel() { return k_stream<T, D, S, NB, TA, DA>; }   // (through a function like the others: the kernels are emitted in the table's order)
+template <int T, int D, int R, int TA, int DA, uint32_t MODES, int M>
+constexpr FmKernel fastb_kernel() { if constexpr ((MODES >> M) & 1u) return k_fastb<T, D, R, TA, DA, M>; else return nullptr; }
+#define SDRFM_FM_EACH_MODE(K, ...) {K<__VA_ARGS__, 0>(), K<__VA_ARGS__, 1>(), K<__VA_ARGS__, 2>(), K<__VA_ARGS__, 3>(), K<__VA_ARGS__, 4>(), K<__VA_ARGS__, 5>(), K<__VA_ARGS__, 6>(), K<__VA_ARGS__, 7>()}
+#define SDRFM_FM_KERNELS_s(T_, D_, S_, NB_, TA_, DA_, M_) {stream_kernel<T_, D_, S_, NB_, TA_, DA_>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}
+#define SDRFM_FM_KERNELS_b(T_, D_, R_, NB_, TA_, DA_, M_) SDRFM_FM_EACH_MODE(fastb_kernel, T_, D_, R_, TA_, DA_, SDRFM_FM_MODES(M_))
+#ifdef SDRFM_DEV   // design A exists in the development library only
+template <int T, int D, int R, uint32_t MODES, int M>
+constexpr FmKernel fast_kernel() { if constexpr ((MODES >> M) & 1u) return k_fast<T, D, R, M>; else return nullptr; }
+#define SDRFM_FM_KERNELS_a(T_, D_, R_, NB_, TA_, DA_, M_) SDRFM_FM_EACH_MODE(fast_kernel, T_, D_, R_, SDRFM_FM_MODES(M_))
 #endif
-#define SDRFM_FASTB2_LITE(T_, D_, R_, TA_, DA_) { 'b', T_, D_, R_, TA_, DA_, {k_fastb<T_, D_, R_, TA_, DA_, 0>, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, (uint32_t)fastb_xbytes(T_, D_, R_), 0 }
-#define SDRFM_FASTB(T_, D_, R_) SDRFM_FASTB2(T_, D_, R_, 32, 5)
-#define SDRFM_STREAM(T_, D_, S_, NB_, TA_, DA_) { 's', T_, D_, S_, TA_, DA_, {k_stream<T_, D_, S_, NB_, TA_, DA_>, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, 2u * 64u * 128u, (uint32_t)(NB_) * (S_) * (D_) }
-// (tests/native/fm_geom.h restates which shapes have an instance here, for the CPU pre-check of tests/fm_shape_cases.py: keep it in step)
-const FastVariant kFastVariants[] = {
-    // design S (streaming lanes): the BASELINE configs[2]/[3] shape; serves calls that are whole numbers of lane segments
-    // (a 16-tap instance is correct too but no faster than design B on cold inputs: 35.2 vs 34.1 us; it is not instantiated)
-    SDRFM_STREAM(64, 10, 8, 6, 32, 5), SDRFM_STREAM(32, 10, 8, 6, 32, 5),
-    // 2.4 MS/s -> 240 kS/s -> 48 kHz: the rate the firmware programs (usbh_rtlsdr.c:898) and the BASELINE configs
-    SDRFM_FASTB2_ABL(64, 10, 12, 32, 5), SDRFM_FASTB2_LITE(64, 10, 8, 32, 5), SDRFM_FASTB(16, 10, 12), SDRFM_FASTB2_LITE(32, 10, 12, 32, 5),
-    // R = 4: the noisy streams' workgroups beside design Q's (per-stream routing; inside design Q's launch: k_mix): 6.8 KB of LDS per wave — a slot one of design Q's waves (10.9 KB) leaves
-    // takes one, which the 19 KB of the R = 12 instance cannot count on while design Q's waves keep coming
-    SDRFM_FASTB2_LITE(64, 10, 4, 32, 5), SDRFM_FASTB2_LITE(32, 10, 4, 32, 5), SDRFM_FASTB2_LITE(16, 10, 4, 32, 5),
-    // the other rates RTLSDR_set_sample_rate accepts and a dongle is commonly run at:
-    // 2.048 MS/s -> 256 kS/s -> 32 kHz, 1.024 MS/s -> 256 kS/s -> 32 kHz, 3.2 MS/s -> 200 kS/s -> 40 kHz
-    SDRFM_FASTB2_LITE(64, 8, 12, 32, 8), SDRFM_FASTB2_LITE(16, 8, 12, 32, 8), SDRFM_FASTB2_LITE(64, 4, 12, 32, 8), SDRFM_FASTB2_LITE(64, 16, 8, 32, 5),
-    SDRFM_FASTB2_LITE(64, 8, 4, 32, 8), SDRFM_FASTB2_LITE(16, 8, 4, 32, 8), SDRFM_FASTB2_LITE(64, 16, 4, 32, 5),
-#ifdef SDRFM_DEV
-    // design A (float tile): kept as the measured alternative; ablation modes only on the documented shape
-    SDRFM_FAST(64, 10, 3), SDRFM_FAST_LITE(16, 10, 2), SDRFM_FAST_LITE(32, 10, 2),
-#endif
-};
+#define SDRFM_FM_VARIANT(kind, T_, D_, R_, NB_, TA_, DA_, M_) \
+  {fm_instance(#kind[0], T_, D_, R_, NB_, TA_, DA_, SDRFM_FM_MODES(M_)), SDRFM_FM_KERNELS_##kind(T_, D_, R_, NB_, TA_, DA_, M_)},
+const FastVariant kFastVariants[] = {SDRFM_FM_INSTANCES(SDRFM_FM_VARIANT)};
+static_assert(sizeof(kFastVariants) / sizeof(kFastVariants[0]) == kFmInstanceCount, "one entry per instance: fm_plan() names a tile by its index");
 
 }  // namespace
 
@@ -1228,6 +1208,62 @@ static int ensure_zero_copy(sdrfm* h) {
   return SDRFM_OK;
 }
 
+// Design Q's operand tables, the repair path's taps, the streams' raw-sample history, the statistics and the routing state: false when any of it could
+// not be had (the caller's q_free takes back what was).
+static bool q_create(sdrfm* h, const int8_t* tab, size_t tab_bytes) {
+  const size_t ns = h->cfg.n_streams;
+  float hpad[SDRFM_Q_TP];
+  for (uint32_t k = 0; k < SDRFM_Q_TP; ++k) hpad[k] = k < h->cfg.fir_taps ? h->cfg.fir_coeffs[k] : 0.0f;
+  return hipMalloc(&h->d_qA, tab_bytes) == hipSuccess && hipMemcpy(h->d_qA, tab, tab_bytes, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMalloc(&h->d_hpad, sizeof(hpad)) == hipSuccess && hipMemcpy(h->d_hpad, hpad, sizeof(hpad), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMalloc(&h->d_hist_q[0], 2 * SDRFM_Q_TP * ns) == hipSuccess && hipMalloc(&h->d_hist_q[1], 2 * SDRFM_Q_TP * ns) == hipSuccess &&
+         hipMalloc(&h->d_qstat, 2 * sizeof(unsigned int)) == hipSuccess && hipMemset(h->d_qstat, 0, 2 * sizeof(unsigned int)) == hipSuccess &&
+         route_create(h) == SDRFM_OK;
+}
+
+// Development library: d_dbg for design S's time stamps (16 words per wave, up to 16384 waves) or for the fast tile's phase profile.
+static bool dbg_create(sdrfm* h, bool stream_profile) {
+  const size_t words = stream_profile ? 32 * 16384 : 560;
+  if (hipMalloc(&h->d_dbg, words * sizeof(unsigned long long)) != hipSuccess) { h->d_dbg = nullptr; return false; }
+  (void)hipMemset(h->d_dbg, 0, words * sizeof(unsigned long long));
+  if (!stream_profile)
+    for (int x = 0; x < 8; ++x) { (void)hipMemset(h->d_dbg + 520 + 4 * x, 0xff, 8); (void)hipMemset(h->d_dbg + 522 + 4 * x, 0xff, 8); }
+  return true;
+}
+
+// Every environment knob is a development aid: read once per create, here, and only in libsdrfm_dev.so.
+static FmKnobs fm_read_knobs() {
+  FmKnobs k;
+#ifdef SDRFM_DEV
+  if (const char* e = getenv("SDRFM_FAST_KIND")) k.fast_kind = e[0];
+  k.fast_r = (k.fast_kind == 'b') ? 12 : 3;
+  if (const char* e = getenv("SDRFM_FAST_R")) k.fast_r = (uint32_t)atoi(e);
+  if (const char* e = getenv("SDRFM_AUDIO_BATCH")) k.audio_batch = (uint32_t)atoi(e);
+  if (getenv("SDRFM_NO_PRIO")) k.prio_balance = 0;
+  if (const char* e = getenv("SDRFM_END_PRIO")) k.end_prio = (uint32_t)strtoul(e, nullptr, 0);
+  if (getenv("SDRFM_NO_FOLD")) k.fold_state_ok = 0;
+  k.no_stream = getenv("SDRFM_NO_STREAM") != nullptr;
+  k.stream_profile = getenv("SDRFM_STREAM_PROFILE") != nullptr;
+  if (const char* e = getenv("SDRFM_Q_NSLOT")) k.q_nslot = (uint32_t)atoi(e);
+  if (const char* e = getenv("SDRFM_Q_WAVES_PER_CU")) k.q_waves_per_cu = (uint32_t)atoi(e);
+  if (const char* e = getenv("SDRFM_Q_GUARD_R")) k.q_guard_r = (float)atof(e);            // 0 and 4: the guard never fires (timing / soak experiments)
+  if (const char* e = getenv("SDRFM_Q_GUARD_A")) k.q_guard_a = (float)atof(e);
+  k.no_q = getenv("SDRFM_NO_Q") != nullptr;
+  k.q_no_adapt = getenv("SDRFM_Q_NO_ADAPT") != nullptr;                                     // design Q whatever the streams hold (timing experiments)
+  if (const char* e = getenv("SDRFM_WARM_AHEAD")) k.warm_ahead = (uint32_t)atoi(e);
+  if (const char* e = getenv("SDRFM_ABLATE")) k.ablate = atoi(e);
+  k.phase_profile = getenv("SDRFM_PHASE_PROFILE") != nullptr;
+  if (const char* e = getenv("SDRFM_WAVES_PER_CU")) k.waves_per_cu = (uint32_t)atoi(e);
+  if (const char* e = getenv("SDRFM_MIN_SUBTILES")) k.min_subtiles = (uint32_t)atoi(e);
+  if (const char* e = getenv("SDRFM_MIX_COST")) k.mix_cost = atof(e);
+  if (const char* e = getenv("SDRFM_MIX_RHO")) k.mix_rho = atof(e);
+  k.mix_split_off = getenv("SDRFM_MIX_SPLIT_OFF") != nullptr;
+  k.mix_off = getenv("SDRFM_MIX_OFF") != nullptr;
+  if (const char* e = getenv("SDRFM_MIX_WAVES_PER_CU")) k.mix_waves_per_cu = (uint32_t)atoi(e);
+#endif
+  return k;
+}
+
 extern "C" {
 
 uint32_t sdrfm_abi_version(void) { return SDRFM_ABI_VERSION; }
@@ -1280,7 +1316,6 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
   h->device = cfg->device;
   h->max_bytes = cfg->max_bytes_per_call ? cfg->max_bytes_per_call : (1u << 20);
   h->zc_off = (cfg->flags & SDRFM_CFG_NO_ZEROCOPY) != 0;
-  h->prio_balance = 1; h->geo.fold_state_ok = 1; h->end_prio = (1u | (1u << 2)) << 6;
   h->max_bytes &= ~1u;
   float* hc = (float*)malloc(sizeof(float) * cfg->fir_taps);
   float* gc = (float*)malloc(sizeof(float) * cfg->audio_taps);
@@ -1307,185 +1342,73 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
   CR(hipMemcpy(h->d_g, gc, sizeof(float) * Ta, hipMemcpyHostToDevice));
 #undef CR
 
-  // generic-kernel tile: as many audio outputs per block as fit ~48 KiB of LDS, capped at 64
-  uint32_t NA = 64;
+  // Which designs the handle owns, their tiles, shares, LDS sizes and names: fm_plan (sdrfm_fm_plan.h).  Its inputs first ...
+  FmKnobs knobs = fm_read_knobs();
+  FmPlanIn in;
+  memset(&in, 0, sizeof(in));
+  in.T = cfg->fir_taps; in.D = cfg->fir_decim; in.Ta = cfg->audio_taps; in.Da = cfg->audio_decim; in.n_streams = cfg->n_streams;
+  in.force_generic = (cfg->flags & SDRFM_CFG_FORCE_GENERIC) != 0; in.bit_exact = (cfg->flags & SDRFM_CFG_BIT_EXACT) != 0;
+  in.n_cu = (uint32_t)prop.multiProcessorCount;
+  in.q_default_nslot = sdrfm_q_default_nslot(in.D);
+  in.q_default_lds = sdrfm_q_lds_bytes(in.q_default_nslot, in.D, in.Da);
+  if (!in.force_generic) in.taps = fm_tap_verdict(hc, in.T, gc, in.Ta, (cfg->flags & SDRFM_CFG_GUARD_WORST_CASE) != 0);
+  const size_t q_tab_bytes = (size_t)SDRFM_Q_SPARSE_CHUNKS(in.D) * SDRFM_Q_DIGITS * 64 * 16;
+  int8_t* q_tab = nullptr;
+  float q_scale = 0.f, q_cst = 0.f;
+  if (fm_plan_offers_q(in, knobs)) {
+    q_tab = (int8_t*)malloc(q_tab_bytes);
+    in.q_built = q_tab && sdrfm_q_build(hc, in.T, in.D, q_tab, &q_scale, &q_cst, &in.q_c0) == 0;   // (false: taps the tables cannot hold)
+    const uint32_t nslot = fm_plan_q_nslot(in, knobs);
+    in.q_lds = sdrfm_q_lds_bytes(nslot, in.D, in.Da);
+    in.q_symbol = sdrfm_q_kernel_symbol(in.q_c0, nslot, in.D, in.Da);
+    in.mix_lds = sdrfm_q_mix_lds(in.q_c0, nslot, in.D, in.Da, in.T, SDRFM_FM_MIX_R);
+    if (in.mix_lds) in.mix_blocks_per_cu = sdrfm_q_mix_blocks_per_cu(in.q_c0, nslot, in.D, in.Da, in.T, SDRFM_FM_MIX_R);
+  }
+  // ... then the plan, taken again without a design the runtime refuses: design Q when its tables or routing state cannot be allocated, a tile when
+  // hipFuncSetAttribute refuses its LDS (development library: a profile when its buffer cannot be allocated)
+  FmRefused refused = {false, 0u};
+  FmPlan plan;
   for (;;) {
-    const size_t ND = (size_t)(NA - 1) * cfg->audio_decim + Ta, NY = ND + 1, NX = (NY - 1) * cfg->fir_decim + T;
-    h->lds_bytes = NX * 8 + NY * 8 + ND * 4 + T * 4 + Ta * 4;
-    if (h->lds_bytes <= 48 * 1024 || NA == 1) break;
-    NA /= 2;
+    plan = fm_plan(in, knobs, refused);
+    if (!plan.supported) break;
+    if (plan.geo.has_q && !h->d_qA && !q_create(h, q_tab, q_tab_bytes)) {
+      // (the handle serves every call with the bit-exact kernels; said once, so that the slower path is not silent)
+      fprintf(stderr, "[sdrfm] the matrix-pipe kernel's tables or routing state could not be allocated: this handle runs the bit-exact kernels only\n");
+      (void)hipGetLastError();
+      q_free(h);
+      refused.q = true;
+      continue;
+    }
+    if (plan.fast >= 0 && plan.geo.fast_lds > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(kFastVariants[plan.fast].kernel[0]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.geo.fast_lds) != hipSuccess) {
+      refused.instances |= 1u << plan.fast;
+      continue;
+    }
+    if ((plan.stream_profile || plan.fast_mode == 1) && !h->d_dbg && !dbg_create(h, plan.stream_profile)) {
+      knobs.stream_profile = knobs.phase_profile = false;
+      continue;
+    }
+    break;
   }
-  if (h->lds_bytes > 160 * 1024) { free_handle(h); return SDRFM_NOT_SUPPORTED; }
-  h->geo.NA = NA;
-  if (h->lds_bytes > 64 * 1024) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_generic), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)h->lds_bytes) != hipSuccess) { free_handle(h); return SDRFM_NOT_SUPPORTED; }
-  }
-  snprintf(h->generic_name, sizeof(h->generic_name), "generic T%u D%u Ta%u Da%u NA%u", cfg->fir_taps, cfg->fir_decim,
-           cfg->audio_taps, cfg->audio_decim, NA);
-  snprintf(h->kernel_name, sizeof(h->kernel_name), "%s", h->generic_name);
-  if (!(cfg->flags & SDRFM_CFG_FORCE_GENERIC)) {
-    char want_kind = 'b';
-    uint32_t want_r = 12, ab_env = 0;
-#ifdef SDRFM_DEV   // every environment knob is a development aid: read once, here, and only in libsdrfm_dev.so
-    if (const char* e = getenv("SDRFM_FAST_KIND")) want_kind = e[0];
-    want_r = (want_kind == 'b') ? 12 : 3;
-    if (const char* e = getenv("SDRFM_FAST_R")) want_r = (uint32_t)atoi(e);
-    if (const char* e = getenv("SDRFM_AUDIO_BATCH")) ab_env = (uint32_t)atoi(e);
-    if (getenv("SDRFM_NO_PRIO")) h->prio_balance = 0;
-    if (const char* e = getenv("SDRFM_END_PRIO")) h->end_prio = (uint32_t)strtoul(e, nullptr, 0);
-    if (getenv("SDRFM_NO_FOLD")) h->geo.fold_state_ok = 0;
-#endif
-    for (const FastVariant& v : kFastVariants) {
-      if (v.kind != 's' || v.T != cfg->fir_taps || v.D != cfg->fir_decim || v.Ta != cfg->audio_taps || v.Da != cfg->audio_decim) continue;
-#ifdef SDRFM_DEV
-      if (getenv("SDRFM_NO_STREAM")) continue;
-#endif
-#ifdef SDRFM_DEV
-      if (getenv("SDRFM_STREAM_PROFILE") && !h->d_dbg) {        // 16 words per wave, up to 16384 waves
-        if (hipMalloc(&h->d_dbg, 32 * 16384 * sizeof(unsigned long long)) != hipSuccess) h->d_dbg = nullptr;
-        else { (void)hipMemset(h->d_dbg, 0, 32 * 16384 * sizeof(unsigned long long)); h->stream_profile = 1; }
-      }
-#endif
-      h->fast_s = &v;
-      h->geo.n_cu = (uint32_t)prop.multiProcessorCount;
-      snprintf(h->fast_s_name, sizeof(h->fast_s_name), "fast-s T%u D%u S%u L%u Ta%u Da%u", v.T, v.D, v.R, v.seg, v.Ta, v.Da);
-    }
-    // design Q: K2 on the i8 matrix pipe (sdrfm_q.hip).  Not bit-identical to the fmaf-chain kernels (within 1e-6 of the
-    // oracle where the phase is well conditioned, repaired to the definition's own d where it is not: the guard below), so a handle
-    // created with SDRFM_CFG_BIT_EXACT never selects it.
-    // PERFORMANCE heuristic, not a correctness condition: it is offered LOW-PASS channel filters only, sum|h| <= 2 |sum h| (a windowed sinc
-    // has 1.2 - 1.5) — with heavy cancellation (no pass band around DC) |y| is small against the chain's partial sums for every input,
-    // the guard sends most outputs to the repair path and the bit-exact kernels are the faster way to the same numbers.
-    double q_abs = 0.0, q_sum = 0.0;
-    for (uint32_t k = 0; k < cfg->fir_taps; ++k) { q_abs += std::fabs((double)hc[k]); q_sum += (double)hc[k]; }
-    // The conditioning guard's thresholds (qtaps.c: sdrfm_q_guard).  A guard that would send a carrier at an eighth of full scale to the
-    // repair path makes design Q pointless for these taps: the bit-exact kernels serve them.
-    float q_R = 0.0f, q_A = 4.0f;
-    // (SDRFM_CFG_GUARD_WORST_CASE: the radius from the proven worst-case bound — 6.9 x at 64 taps; a carrier at a third of full scale must still clear it)
-    const bool q_wc = (cfg->flags & SDRFM_CFG_GUARD_WORST_CASE) != 0;
-    const bool q_guard_ok = sdrfm_q_guard2(hc, cfg->fir_taps, gc, cfg->audio_taps, q_wc ? 1 : 0, &q_R, &q_A) == 0 &&
-                            (double)q_R <= (q_wc ? 0.33 : 0.125) * 127.5 * std::fabs(q_sum) && q_A > 3.0f;
-    // instances: (D, Da) = (10, 5) — the 2.4 MS/s front end of BASELINE —, (8, 8) and (16, 5): the 2.048 and 3.2 MS/s rates
-    // RTLSDR_set_sample_rate accepts (usbh_rtlsdr.c:676-678); 32 audio taps each
-    const size_t q_tab_bytes = (size_t)SDRFM_Q_SPARSE_CHUNKS(cfg->fir_decim) * SDRFM_Q_DIGITS * 64 * 16;
-    if (!(cfg->flags & SDRFM_CFG_BIT_EXACT) && sdrfm_q_geometry_ok(cfg->fir_decim, cfg->audio_decim) && cfg->audio_taps == SDRFM_Q_TA &&
-        cfg->fir_taps <= SDRFM_Q_TP && cfg->fir_taps <= 9 * cfg->fir_decim && q_abs <= 2.0 * std::fabs(q_sum) && q_guard_ok) {
-      int8_t* tab = (int8_t*)malloc(q_tab_bytes);
-      float qs = 0.f, qc = 0.f, hpad[SDRFM_Q_TP];
-      uint32_t c0 = 0;
-      for (uint32_t k = 0; k < SDRFM_Q_TP; ++k) hpad[k] = k < cfg->fir_taps ? hc[k] : 0.0f;
-      const bool q_built = tab && sdrfm_q_build(hc, cfg->fir_taps, cfg->fir_decim, tab, &qs, &qc, &c0) == 0;   // (false: taps the tables cannot hold)
-      if (q_built &&
-          hipMalloc(&h->d_qA, q_tab_bytes) == hipSuccess &&
-          hipMemcpy(h->d_qA, tab, q_tab_bytes, hipMemcpyHostToDevice) == hipSuccess &&
-          hipMalloc(&h->d_hpad, sizeof(hpad)) == hipSuccess && hipMemcpy(h->d_hpad, hpad, sizeof(hpad), hipMemcpyHostToDevice) == hipSuccess &&
-          hipMalloc(&h->d_hist_q[0], 2 * SDRFM_Q_TP * ns) == hipSuccess && hipMalloc(&h->d_hist_q[1], 2 * SDRFM_Q_TP * ns) == hipSuccess &&
-          hipMalloc(&h->d_qstat, 2 * sizeof(unsigned int)) == hipSuccess && hipMemset(h->d_qstat, 0, 2 * sizeof(unsigned int)) == hipSuccess &&
-          route_create(h) == SDRFM_OK) {
-        h->q_scale = qs; h->q_cst = qc; h->q_c0 = c0 > 1 ? 1 : c0;
-        h->q_guard_r = q_R; h->q_guard_a = q_A;
-        h->q_nslot = sdrfm_q_default_nslot(cfg->fir_decim); h->geo.q_waves_per_cu = 12;
-        { const uint32_t lb = sdrfm_q_lds_bytes(h->q_nslot, cfg->fir_decim, cfg->audio_decim); if (lb && 163840u / lb < h->geo.q_waves_per_cu) h->geo.q_waves_per_cu = 163840u / lb; }   // (D = 16: 11 one-wave workgroups fit a CU's LDS)
-#ifdef SDRFM_DEV
-        if (const char* e = getenv("SDRFM_Q_NSLOT")) h->q_nslot = (uint32_t)atoi(e);
-        if (const char* e = getenv("SDRFM_Q_WAVES_PER_CU")) h->geo.q_waves_per_cu = (uint32_t)atoi(e);
-        if (const char* e = getenv("SDRFM_Q_GUARD_R")) h->q_guard_r = (float)atof(e);            // 0 and 4: the guard never fires (timing / soak experiments)
-        if (const char* e = getenv("SDRFM_Q_GUARD_A")) h->q_guard_a = (float)atof(e);
-        if (getenv("SDRFM_NO_Q")) { (void)hipFree(h->d_qA); h->d_qA = nullptr; }
-        if (getenv("SDRFM_Q_NO_ADAPT")) h->rt_off = true;                                         // design Q whatever the streams hold (timing experiments)
-#endif
-        h->geo.n_cu = (uint32_t)prop.multiProcessorCount;
-        snprintf(h->fast_q_name, sizeof(h->fast_q_name), "fast-q T%u D%u Ta%u Da%u %s", cfg->fir_taps, cfg->fir_decim, cfg->audio_taps,
-                 cfg->audio_decim, sdrfm_q_kernel_symbol(h->q_c0, h->q_nslot, cfg->fir_decim, cfg->audio_decim));
-      } else {
-        // (the handle serves every call with the bit-exact kernels; said once, so that the slower path is not silent)
-        if (q_built) fprintf(stderr, "[sdrfm] the matrix-pipe kernel's tables or routing state could not be allocated: this handle runs the bit-exact kernels only\n");
-        (void)hipGetLastError();
-        q_free(h);
-      }
-      free(tab);
-    }
-    for (int pass = 0; pass < 3 && !h->fast; ++pass)
-    for (const FastVariant& v : kFastVariants) {
-      if (v.kind == 's') continue;
-      if (v.T != cfg->fir_taps || v.D != cfg->fir_decim) continue;
-      if (v.Ta && (v.Ta != cfg->audio_taps || v.Da != cfg->audio_decim)) continue;
-      if (pass == 0 && (v.R != want_r || v.kind != want_kind)) continue;
-      if (pass == 1 && v.kind != want_kind) continue;
-      const uint32_t NYT = 64 * v.R, DOFF = (cfg->audio_taps - 1 + 3u) & ~3u;
-      // audio flush every AB sub-tiles: AB = Da makes every flush exactly 64*R outputs (all lanes busy)
-      uint32_t AB = v.kind == 'b' ? (uint32_t)fastb_ab((int)v.R) : (ab_env ? ab_env : cfg->audio_decim);   // (design B: a compile-time property of the tile)
-      if (AB > 8) AB = 8;
-      while (AB > 1 && (size_t)v.xbytes + (size_t)(DOFF + AB * NYT + v.T + cfg->audio_taps) * 4 > 40 * 1024) --AB;
-      if (cfg->audio_taps - 1 > AB * NYT || DOFF + AB * NYT < 2 * (cfg->audio_taps + 1)) continue;
-      const size_t lds = (size_t)v.xbytes + (size_t)(DOFF + AB * NYT + v.T + cfg->audio_taps) * 4;
-      if (lds > 160 * 1024) continue;
-      if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(v.kernel[0]),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        continue;
-      h->AB = AB;
-      h->warm_ahead = 0;
-#ifdef SDRFM_DEV
-      if (const char* e = getenv("SDRFM_WARM_AHEAD")) h->warm_ahead = (uint32_t)atoi(e);
-      if (const char* e = getenv("SDRFM_ABLATE")) { const int m = atoi(e); if (m >= 2 && m <= 7 && v.kernel[m]) h->fast_mode = m; }
-      if (getenv("SDRFM_PHASE_PROFILE") && !h->d_dbg && v.kernel[1] && !h->stream_profile) {
-        if (hipMalloc(&h->d_dbg, 560 * sizeof(unsigned long long)) != hipSuccess) h->d_dbg = nullptr;
-        else { (void)hipMemset(h->d_dbg, 0, 560 * sizeof(unsigned long long)); for (int x = 0; x < 8; ++x) { (void)hipMemset(h->d_dbg + 520 + 4 * x, 0xff, 8); (void)hipMemset(h->d_dbg + 522 + 4 * x, 0xff, 8); } h->fast_mode = 1; }
-      }
-#endif
-      h->fast = &v;
-      h->geo.fast_lds = lds;
-      uint32_t per_cu = (uint32_t)((160 * 1024) / lds);
-      if (per_cu > 16) per_cu = 16;
-#ifdef SDRFM_DEV
-      if (const char* e = getenv("SDRFM_WAVES_PER_CU")) per_cu = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : per_cu;
-#endif
-      h->geo.waves_target = (uint32_t)prop.multiProcessorCount * per_cu;
-      h->geo.min_subtiles = 4;
-#ifdef SDRFM_DEV
-      if (const char* e = getenv("SDRFM_MIN_SUBTILES")) h->geo.min_subtiles = (uint32_t)atoi(e) > 0 ? (uint32_t)atoi(e) : 4;
-#endif
-      snprintf(h->fast_name, sizeof(h->fast_name), "fast-%c T%u D%u R%u Ta%u Da%u AB%u", v.kind, v.T, v.D, v.R,
-               cfg->audio_taps, cfg->audio_decim, AB);
-      snprintf(h->kernel_name, sizeof(h->kernel_name), "%s", h->fast_name);
-      break;
-    }
-  }
-  if (h->fast && h->fast->kind == 'b' && h->d_qA)
-    for (const FastVariant& v : kFastVariants) {
-      if (v.kind != 'b' || v.R != 4 || v.T != cfg->fir_taps || v.D != cfg->fir_decim || (v.Ta && (v.Ta != cfg->audio_taps || v.Da != cfg->audio_decim))) continue;
-      const uint32_t NYT = 64 * v.R, DOFF = (cfg->audio_taps - 1 + 3u) & ~3u;
-      if (cfg->audio_taps - 1 > NYT || DOFF + NYT < 2 * (cfg->audio_taps + 1)) continue;
-      h->fast_mix = &v;
-      h->geo.fast_mix_lds = (size_t)v.xbytes + (size_t)(DOFF + (uint32_t)fastb_ab((int)v.R) * NYT + v.T + cfg->audio_taps) * 4;
-      // a stream costs the design-B workgroups about mix_cost times what it costs design Q's: the shares of the wave slots (measured: 2.0 / 2.7 / 3.2 ->
-      // 41.2 / 38.9 / 40.3 us serial, 31.5 / 30.8 / 33.0 us overlapped with a quarter of the streams noisy: profiles/r05_mixed_batches.txt)
-      h->geo.mix_R = v.R; h->geo.mix_cost = 2.7; h->geo.mix_rho = 12.7;
-#ifdef SDRFM_DEV
-      if (const char* e = getenv("SDRFM_MIX_COST")) h->geo.mix_cost = atof(e);
-      if (getenv("SDRFM_MIX_SPLIT_OFF")) h->geo.mix_split_off = true;
-      if (const char* e = getenv("SDRFM_MIX_RHO")) h->geo.mix_rho = atof(e);
-#endif
-      h->geo.mix_lds = (cfg->audio_taps == SDRFM_Q_TA) ? sdrfm_q_mix_lds(h->q_c0, h->q_nslot, cfg->fir_decim, cfg->audio_decim, v.T, h->geo.mix_R) : 0u;
-      if (h->geo.mix_lds) {
-        const int nb = sdrfm_q_mix_blocks_per_cu(h->q_c0, h->q_nslot, cfg->fir_decim, cfg->audio_decim, v.T, h->geo.mix_R);
-        h->geo.mix_waves_per_cu = nb > 0 ? (uint32_t)nb : 163840u / h->geo.mix_lds;
-        if (h->geo.mix_waves_per_cu > h->geo.q_waves_per_cu) h->geo.mix_waves_per_cu = h->geo.q_waves_per_cu;   // (15 fit; design Q's own 12 are faster: same file)
-#ifdef SDRFM_DEV
-        if (getenv("SDRFM_MIX_OFF")) h->geo.mix_lds = 0;
-        if (const char* e = getenv("SDRFM_MIX_WAVES_PER_CU")) h->geo.mix_waves_per_cu = (uint32_t)atoi(e);
-#endif
-      }
-    }
-  // the rest of what the call path's arithmetic takes as given (sdrfm_fm_call.h): copies of cfg's shape and of which designs the handle ended up with.
-  // Nothing after this point drops a design or changes cfg; a path that ever does (frees d_qA, clears fast / fast_s / fast_mix) must refresh these with it.
-  FmGeom& geo = h->geo;
-  geo.T = cfg->fir_taps; geo.D = cfg->fir_decim; geo.Ta = cfg->audio_taps; geo.Da = cfg->audio_decim; geo.n_streams = cfg->n_streams;
-  geo.has_q = h->d_qA != nullptr; geo.has_s = h->fast_s != nullptr; geo.has_mix_tile = h->fast_mix != nullptr;
-  geo.has_fast = h->fast != nullptr; geo.fast_is_b = h->fast && h->fast->kind == 'b'; geo.fast_R = h->fast ? h->fast->R : 0u;
-  geo.seg = h->fast_s ? h->fast_s->seg : 0u;
-  geo.q_lds = geo.has_q ? sdrfm_q_lds_bytes(h->q_nslot, cfg->fir_decim, cfg->audio_decim) : 0u;
+  free(q_tab);
+  if (!plan.supported || (plan.lds_bytes > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(k_generic), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                                             (int)plan.lds_bytes) != hipSuccess)) { free_handle(h); return SDRFM_NOT_SUPPORTED; }
+  // What the call path takes as given from here on.  Nothing after this point drops a design or changes cfg; a path that ever does must plan again.
+  h->geo = plan.geo;
+  h->lds_bytes = plan.lds_bytes;
+  h->fast = plan.fast >= 0 ? &kFastVariants[plan.fast] : nullptr;
+  h->fast_s = plan.fast_s >= 0 ? &kFastVariants[plan.fast_s] : nullptr;
+  h->fast_mix = plan.fast_mix >= 0 ? &kFastVariants[plan.fast_mix] : nullptr;
+  h->AB = plan.AB; h->warm_ahead = plan.warm_ahead; h->fast_mode = plan.fast_mode; h->stream_profile = plan.stream_profile ? 1u : 0u;
+  h->prio_balance = knobs.prio_balance; h->end_prio = knobs.end_prio;
+  if (plan.geo.has_q) { h->q_scale = q_scale; h->q_cst = q_cst; }
+  h->q_c0 = plan.q_c0; h->q_nslot = plan.q_nslot; h->q_guard_r = plan.q_guard_r; h->q_guard_a = plan.q_guard_a;
+  h->rt_off = knobs.q_no_adapt;
+  snprintf(h->generic_name, sizeof(h->generic_name), "%s", plan.generic_name);
+  snprintf(h->fast_name, sizeof(h->fast_name), "%s", plan.fast_name);
+  snprintf(h->fast_s_name, sizeof(h->fast_s_name), "%s", plan.fast_s_name);
+  snprintf(h->fast_q_name, sizeof(h->fast_q_name), "%s", plan.fast_q_name);
+  snprintf(h->kernel_name, sizeof(h->kernel_name), "%s", plan.kernel_name);
   const int rc = sdrfm_reset(h);
   if (rc != SDRFM_OK) { free_handle(h); return rc; }
   *out = h;

@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "sdrfm_math.h"
+#include "sdrfm_fm_tiles.h"   // the tiles' sizes: fast_xbytes, fastb_hp / _rs / _ab / _xbytes / _lds
 
 typedef float f2_t __attribute__((ext_vector_type(2)));
 typedef float f4_t __attribute__((ext_vector_type(4)));
@@ -161,12 +162,6 @@ __device__ __forceinline__ void pk_fma_bcast(f2_t& acc, f2_t tap_pair, f2_t x) {
 }
 
 constexpr int cgcd(int a, int b) { return b == 0 ? a : cgcd(b, a % b); }
-// bytes of the x tile: positions [0, HP + NST) in rows of R*D samples, last row trimmed, rounded up to 16 B
-constexpr int fast_xbytes(int T, int D, int R) {
-  const int RD = R * D, HP = T - D, NST = 64 * RD, RS = (RD + (((RD / 2) % 2 == 0) ? 2 : 0)) * 8;
-  const int last = HP + NST - 1;
-  return (((last / RD) * RS + (last % RD + 1) * 8) + 15) & ~15;
-}
 
 // ---- packed (2-wide) discriminator: two consecutive outputs per instruction stream --------------------------------
 __device__ __forceinline__ f2_t pk_splat(float c) { return f2_t{c, c}; }
@@ -224,19 +219,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     f(std::integral_constant<int, I>{});
     static_for<I + 1, N>(f);
   }
-}
-
-constexpr int fastb_hp(int T, int D) { return ((T - D) + 7) & ~7; }                      // halo samples (16-B granular)
-constexpr int fastb_rs(int D, int R) { return R * D * 2 + ((((R * D * 2) / 16) % 2 == 0) ? 16 : 0); }  // row stride, B
-// sub-tiles of d's buffered per audio flush: the small tile (R = 4: 256 d's = 51 audio outputs per sub-tile, which leaves the flush's three chains per lane
-// two thirds idle) flushes every third sub-tile
-#ifndef SDRFM_B_AB_SMALL
-#define SDRFM_B_AB_SMALL 3
-#endif
-constexpr int fastb_ab(int R) { return R <= 4 ? SDRFM_B_AB_SMALL : 1; }
-constexpr int fastb_xbytes(int T, int D, int R) {
-  const int RD = R * D, last = fastb_hp(T, D) + 64 * RD - 1;
-  return (((last / RD) * fastb_rs(D, R) + (last % RD + 1) * 2) + 15) & ~15;
 }
 
 // (I - 127.5, Q - 127.5) of the low / high half of a dword holding two I/Q byte pairs

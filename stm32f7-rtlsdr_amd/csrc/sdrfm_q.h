@@ -52,10 +52,8 @@ struct SdrfmQParams {
 
 // geometry the host needs
 #define SDRFM_Q_D 10u            /* FIR decimation of the BASELINE front end (2.4 MS/s); instances exist for D = 8 (2.048 MS/s) and 16 (3.2 MS/s) too */
-#define SDRFM_Q_TA 32u           /* audio taps (every instance) */
 #define SDRFM_Q_DA 5u            /* audio decimation of the BASELINE front end */
 #define SDRFM_Q_STEP_OUT 128u    /* decimated outputs per wave step (16 columns x 8 outputs) */
-#define SDRFM_Q_TP 64u           /* the repair path's chain length: channel taps padded with zeros to this many (design Q serves T <= 64) */
 
 // is there an instance for FIR decimation d and audio decimation da (with SDRFM_Q_TA audio taps)?  its ring size in KiB
 bool sdrfm_q_geometry_ok(uint32_t d, uint32_t da);

@@ -1209,7 +1209,7 @@ typedef void (*MixKernel)(SdrfmQParams, CallParams, uint32_t);
 typedef void (*MixPcmKernel)(MixPcmArgs);
 struct MixVariant { uint32_t c0, nslot, d, da, T, R, lds; MixKernel k; MixPcmKernel kp; uint32_t lds_pcm; };
 template <int T, int D, int R, int TA>
-constexpr uint32_t b_lds() { return (uint32_t)fastb_xbytes(T, D, R) + 4u * (uint32_t)(((TA - 1 + 3) & ~3) + fastb_ab(R) * 64 * R + T + TA); }   // as sdrfm.hip sizes design B's workgroup
+constexpr uint32_t b_lds() { return (uint32_t)fastb_lds(T, D, R, TA); }
 template <int C0, int NSLOT, int D, int DA, int T, int R>
 constexpr uint32_t mix_lds() { return q_lds<D, DA, NSLOT>() > b_lds<T, D, R, (int)SDRFM_Q_TA>() ? q_lds<D, DA, NSLOT>() : b_lds<T, D, R, (int)SDRFM_Q_TA>(); }
 template <int C0, int NSLOT, int D, int DA, int T, int R>

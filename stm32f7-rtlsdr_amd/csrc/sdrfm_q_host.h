@@ -16,6 +16,8 @@ extern "C" {
 #define SDRFM_Q_HMAX (127 * 65793)          /* largest |H| three digits in [-128, 127] can hold: 127 (65536 + 256 + 1) */
 #define SDRFM_Q_MAX_D 16                    /* FIR decimation: even, <= 16 (D / 2 K-chunks of 64 bytes per window) */
 
+#define SDRFM_Q_TA 32u                      /* audio taps (every instance) */
+#define SDRFM_Q_TP 64u                      /* the repair path's chain length: channel taps padded with zeros to this many (design Q serves T <= 64) */
 #define SDRFM_Q_SPARSE_CHUNKS(D) (((D) + 3u) / 4u)   /* K-chunks of 128 window bytes (v_smfmac_i32_16x16x128_i8) per digit */
 
 /* h[0..T) -> A[ceil(D/4)][3][64][16] (sparse chunk, digit, lane, kept slot), the fp32 scale q (y = q * (S0 + 256 S1 + 65536 S2) + cst),

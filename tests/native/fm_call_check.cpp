@@ -5,6 +5,7 @@
  *   known answers   figures DESIGN.md and the code's comments state for the headline shape (not taken from the functions under test)
  *   properties      over a seeded sweep of shapes, stream counts, call sizes and routed fractions, following enqueue()'s order of decisions
  *   fm_rows_overlap against a brute-force byte-set intersection
+ * Every FmGeom is the one the library plans for the shape (csrc/sdrfm_fm_plan.h) from what an MI355X answers (fm_geom.h), not a hand-written one.
  * Prints "ok" and exits 0, or says what failed and exits 1. */
 #include <cinttypes>
 #include <cstdio>
@@ -32,8 +33,9 @@ static uint64_t rnd() {                                          // splitmix64
 }
 static uint32_t rnd_in(uint32_t lo, uint32_t hi) { return lo + (uint32_t)(rnd() % ((uint64_t)hi - lo + 1)); }
 
-// a handle of shape (T, D, Ta, Da) on a 256-CU device, every design instantiated (tests/native/fm_geom.h)
-static FmGeom geom(uint32_t T, uint32_t D, uint32_t Ta, uint32_t Da, uint32_t ns) { return fm_test_geom(T, D, Ta, Da, ns); }
+// a default handle of shape (T, D, Ta, Da) as the library plans it (tests/native/fm_geom.h)
+struct Shape { uint32_t T, D, Ta, Da; };
+static FmGeom geom(const Shape& sh, uint32_t ns, bool bit_exact = false) { return fm_test_geom(sh.T, sh.D, sh.Ta, sh.Da, ns, bit_exact, fm_test_facts_mi355x(sh.T, sh.D, sh.Da)); }
 
 static FmCall call_of(uint32_t phase_x, uint32_t phase_d, uint32_t nbytes, const FmGeom& g, uint64_t n_seen, bool al4, bool al16) {
   const FmCounts n = fm_counts(phase_x, phase_d, nbytes, g.D, g.Da);
@@ -42,10 +44,11 @@ static FmCall call_of(uint32_t phase_x, uint32_t phase_d, uint32_t nbytes, const
 
 // ---- known answers (T 64, D 10, Ta 32, Da 5; 256 CUs, 12 design-Q waves and 12 mixed workgroups per CU) -------------------------------------------
 static void known_answers() {
+  const Shape sh = {64, 10, 32, 5};
   CHECK(fm_chain_run_quads(5) == 13u && fm_chain_run_quads(8) == 18u && fm_chain_run_quads(1) == 13u, "quads per run under the sink's chain: %u, %u", fm_chain_run_quads(5), fm_chain_run_quads(8));
   const uint64_t seen = 1u << 20;                                // (a stream well past its first T-1 samples)
   {  // 256 streams x 480 000 B: design Q fits, 12 runs per stream, 3072 workgroups
-    const FmGeom g = geom(64, 10, 32, 5, 256);
+    const FmGeom g = geom(sh, 256);
     const FmCall c = call_of(0, 0, 480000, g, seen, true, true);
     CHECK(c.N == 240000 && c.M == 24000 && c.A == 4800, "%u %u %u", c.N, c.M, c.A);
     CHECK(fm_q_fit(g, c), "headline batch");
@@ -56,13 +59,13 @@ static void known_answers() {
     CHECK(!fm_q_fit(g, call_of(1, 0, 480000, g, seen, true, true)), "odd phase");
     CHECK(!fm_q_fit(g, call_of(0, 0, 480000 + 2 * 200, g, seen, true, true)), "N %% 400");
     CHECK(!fm_q_fit(g, call_of(0, 0, 480000, g, seen, true, false)), "alignment");
-    FmGeom g1030 = geom(64, 10, 32, 5, 1030);                    // (1030 streams x 1 step fill the machine: only M < Ta is left to refuse 40 outputs)
+    FmGeom g1030 = geom(sh, 1030);                    // (1030 streams x 1 step fill the machine: only M < Ta is left to refuse 40 outputs)
     CHECK(fm_q_fit(g1030, call_of(0, 0, 800, g1030, seen, true, true)), "40 outputs, 32 audio taps");
     g1030.Ta = 48;
     CHECK(!fm_q_fit(g1030, call_of(0, 0, 800, g1030, seen, true, true)), "M < Ta");
   }
   {  // 1 stream x 4 800 000 B: fits, 1875 steps, 937 two-step runs; 1 stream x 480 000 B: 188 steps < 2 per CU
-    const FmGeom g = geom(64, 10, 32, 5, 1);
+    const FmGeom g = geom(sh, 1);
     const FmCall c = call_of(0, 0, 4800000, g, seen, true, true);
     CHECK(fm_q_fit(g, c) && fm_q_steps(c.M) == 1875, "%u", fm_q_steps(c.M));
     const FmRuns r = fm_q_runs(c, fm_split(g, c, false, false, 0).q_total, 1, false, 0);
@@ -71,14 +74,13 @@ static void known_answers() {
     CHECK(fm_q_steps(c1.M) == 188 && !fm_q_fit(g, c1), "%u", fm_q_steps(c1.M));
   }
   {  // 256 streams x 480 000 B on a bit-exact handle: design S, 8 waves per stream
-    FmGeom g = geom(64, 10, 32, 5, 256);
-    g.has_q = false;
+    const FmGeom g = geom(sh, 256, true);
     const FmCall c = call_of(0, 0, 480000, g, seen, true, true);
     CHECK(!fm_q_fit(g, c) && fm_stream_ok(g, c, 256, false) && fm_s_waves(g, c) == 8, "%u", fm_s_waves(g, c));
   }
   {  // 64 of 256 streams routed, one launch: 16 segments of 6 sub-tiles (1024 design-B workgroups), 2048 design-Q workgroups, 10 runs of 76 quads
      // (profiles/r06_mixed_split.txt)
-    const FmGeom g = geom(64, 10, 32, 5, 256);
+    const FmGeom g = geom(sh, 256);
     const FmCall c = call_of(0, 0, 480000, g, seen, true, true);
     CHECK(fm_q_ok(fm_q_fit(g, c), 64, 256) && fm_fuse(g, c, true), "fused");
     const FmSplit s = fm_split(g, c, true, true, 64);
@@ -92,7 +94,7 @@ static void known_answers() {
   CHECK(fm_max_audio(10, 5, 480000) == 4802 && fm_max_audio(10, 5, 0) == 2 && fm_max_audio(8, 8, 2 * 2049) == 34 && fm_max_audio(16, 5, 0xfffffffeu) == 26843547,
         "%u %u %u %u", fm_max_audio(10, 5, 480000), fm_max_audio(10, 5, 0), fm_max_audio(8, 8, 2 * 2049), fm_max_audio(16, 5, 0xfffffffeu));
   {  // the first-call fix-up: 8 outputs touch never-seen samples, 8 audio outputs (<= 64: one tile)
-    const FmGeom g = geom(64, 10, 32, 5, 256);
+    const FmGeom g = geom(sh, 256);
     const FmFixup f = fm_fixup(g, call_of(0, 0, 480000, g, 0, true, true));
     CHECK(f.y_aff == 8 && f.a_aff == 8 && f.tiles_per_stream == 1, "%u %u %u", f.y_aff, f.a_aff, f.tiles_per_stream);
   }
@@ -108,9 +110,10 @@ static void check_tiles(const FmTiles& t, const FmCall& c, uint32_t nsub, const 
 }
 
 // top: 0 = a drawn call size; 1 = the largest call, 2^30 - 1 samples; 2 = the largest one design Q may take (a multiple of 8 D Da below 2^30)
-static void one_case(uint32_t T, uint32_t D, uint32_t Ta, uint32_t Da, int top = 0) {
+static void one_case(const Shape& sh, int top = 0) {
+  const uint32_t T = sh.T, D = sh.D, Da = sh.Da;
   const uint32_t ns = (rnd() & 3) ? rnd_in(1, 1030) : rnd_in(1, 8);
-  FmGeom g = geom(T, D, Ta, Da, ns);
+  FmGeom g = geom(sh, ns);
   if ((rnd() & 15) == 0) g.mix_lds = 0;                          // (no one-launch instance: the two-launch split)
   if ((rnd() & 15) == 0) g.has_s = false;
   if ((rnd() & 31) == 0) g.has_mix_tile = false, g.mix_lds = 0;
@@ -236,12 +239,12 @@ static void rows_overlap_brute() {
 int main() {
   known_answers();
   // every shape the library has fast kernels for: (T, D, Ta, Da); design Q's instances are (D, Da) = (10, 5), (8, 8), (16, 5) at 32 audio taps
-  static const uint32_t shapes[][4] = {{64, 10, 32, 5}, {32, 10, 32, 5}, {16, 10, 32, 5}, {64, 8, 32, 8}, {16, 8, 32, 8}, {64, 4, 32, 8}, {64, 16, 32, 5}};
+  static const Shape shapes[] = {{64, 10, 32, 5}, {32, 10, 32, 5}, {16, 10, 32, 5}, {64, 8, 32, 8}, {16, 8, 32, 8}, {64, 4, 32, 8}, {64, 16, 32, 5}};
   unsigned long cases = 0;
-  for (const auto& sh : shapes)
-    for (int i = 0; i < 40000; ++i, ++cases) one_case(sh[0], sh[1], sh[2], sh[3], i < 400 ? 1 + (i & 1) : 0);
-  for (const auto& sh : shapes)
-    for (int i = 0; i < 3000; ++i) one_cut(sh[1], sh[3]);
+  for (const Shape& sh : shapes)
+    for (int i = 0; i < 40000; ++i, ++cases) one_case(sh, i < 400 ? 1 + (i & 1) : 0);
+  for (const Shape& sh : shapes)
+    for (int i = 0; i < 3000; ++i) one_cut(sh.D, sh.Da);
   printf("sweep: seed 0x5d2f3a11c0ffee01, %lu cases\n", cases);
   rows_overlap_brute();
   if (g_failed) { printf("%d checks failed\n", g_failed); return 1; }

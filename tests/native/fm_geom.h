@@ -1,44 +1,44 @@
-/* The FmGeom sdrfm_create arrives at on a 256-CU device (MI355X) for 32 audio taps, shared by the CPU checks of the FM call path
- * (fm_call_check.cpp, fm_shape_cases.cpp), and which shapes the library has an instance of (csrc/sdrfm.hip: kFastVariants and the design-Q rules of
- * sdrfm_create; a comment there points here: keep the two in step). */
+/* The FmGeom of a handle as the library plans it (csrc/sdrfm_fm_plan.h: fm_plan), for the CPU checks of the FM call path (fm_call_check.cpp,
+ * fm_shape_cases.cpp, fm_plan_case.cpp).  What only a device and design Q's translation unit can say — compute units, design Q's ring and LDS bytes,
+ * the one-launch kernel's LDS bytes and occupancy — is what an MI355X answered (fm_test_facts_mi355x), or comes in on a command line as
+ * "n_cu:q_nslot:q_lds:mix_lds:mix_blocks_per_cu". */
 #ifndef SDRFM_TESTS_FM_GEOM_H
 #define SDRFM_TESTS_FM_GEOM_H
 
-#include <string.h>
+#include <stdio.h>
 
-#include "../../stm32f7-rtlsdr_amd/csrc/sdrfm_fm_call.h"
+#include "../../stm32f7-rtlsdr_amd/csrc/sdrfm_fm_plan.h"
 
-// a handle of shape (T, D, Ta, Da) on a 256-CU device, every design instantiated: the values sdrfm_create arrives at for the headline shape
-// (tile R = 12 at two waves per SIMD, the R = 4 tile of 6.8 KB beside design Q's waves of 10.9 KB, 12 workgroups of either kind per CU)
-static inline FmGeom fm_test_geom(uint32_t T, uint32_t D, uint32_t Ta, uint32_t Da, uint32_t ns) {
-  FmGeom g;
-  memset(&g, 0, sizeof(g));
-  g.T = T; g.D = D; g.Ta = Ta; g.Da = Da; g.n_streams = ns; g.n_cu = 256;
-  g.has_q = true; g.has_fast = true; g.fast_is_b = true; g.has_s = (D == 10 && Da == 5 && Ta == 32 && (T == 64 || T == 32)); g.has_mix_tile = true;
-  g.mix_lds = 17000; g.q_waves_per_cu = (D == 16) ? 11 : 12; g.q_lds = 11164;
-  g.fast_R = (D == 16) ? 8 : 12; g.fast_lds = 19968; g.waves_target = 256 * 8; g.min_subtiles = 4; g.fold_state_ok = 1;
-  g.fast_mix_lds = 6960; g.mix_R = 4; g.mix_waves_per_cu = g.q_waves_per_cu; g.mix_cost = 2.7; g.mix_rho = 12.7; g.mix_split_off = false;
-  g.seg = 6 * 8 * D; g.NA = 64;
-  return g;
+struct FmTestFacts { unsigned n_cu, q_default_nslot, q_default_lds, mix_lds; int mix_blocks_per_cu; };
+static inline bool fm_test_parse_facts(const char* s, FmTestFacts* f) {
+  return sscanf(s, "%u:%u:%u:%u:%d", &f->n_cu, &f->q_default_nslot, &f->q_default_lds, &f->mix_lds, &f->mix_blocks_per_cu) == 5;
 }
 
-// design B's instances at 32 audio taps (kFastVariants, kind 'b'), and its R = 4 tile
-static inline bool fm_test_has_b(uint32_t T, uint32_t D, uint32_t Da) {
-  if (Da == 5) return (D == 10 && (T == 64 || T == 16 || T == 32)) || (D == 16 && T == 64);
-  if (Da == 8) return (D == 8 && (T == 64 || T == 16)) || (D == 4 && T == 64);
-  return false;
+// The answers tests/golden/fm_plan_mi355x.json records under "runtime" (tests/test_fm_plan_cpu.py plans every recorded default handle with these and
+// must arrive at the record): 256 CUs; design Q's ring and a wave's LDS bytes by rate; the one-launch kernel, which exists where design B has an
+// R = 4 tile, takes the larger of the two workgroups' LDS (design Q's everywhere) and the occupancy the runtime reports for it.
+static inline FmTestFacts fm_test_facts_mi355x(uint32_t T, uint32_t D, uint32_t Da) {
+  FmTestFacts f = {256u, 0u, 0u, 0u, 0};
+  if (D == 10 && Da == 5) { f.q_default_nslot = 5; f.q_default_lds = 10864; if (T == 64 || T == 32 || T == 16) f.mix_blocks_per_cu = 15; }
+  if (D == 8 && Da == 8) { f.q_default_nslot = 4; f.q_default_lds = 11344; if (T == 64 || T == 16) f.mix_blocks_per_cu = T == 64 ? 12 : 14; }
+  if (D == 16 && Da == 5) { f.q_default_nslot = 8; f.q_default_lds = 14032; if (T == 64) f.mix_blocks_per_cu = 11; }
+  if (f.mix_blocks_per_cu) f.mix_lds = f.q_default_lds;
+  return f;
 }
-static inline bool fm_test_has_b4(uint32_t T, uint32_t D, uint32_t Da) { return fm_test_has_b(T, D, Da) && D != 4; }
 
-// ... with only the designs the library has an instance of for the shape (low-pass taps the guard accepts; bit_exact: SDRFM_CFG_BIT_EXACT)
-static inline FmGeom fm_test_geom_instances(uint32_t T, uint32_t D, uint32_t Da, uint32_t ns, bool bit_exact) {
-  FmGeom g = fm_test_geom(T, D, 32, Da, ns);
-  const bool q_shape = (D == 10 && Da == 5) || (D == 8 && Da == 8) || (D == 16 && Da == 5);   // sdrfm_q_geometry_ok
-  g.has_q = !bit_exact && q_shape && T <= 64 && T <= 9 * D;
-  g.has_fast = g.fast_is_b = fm_test_has_b(T, D, Da);
-  g.has_mix_tile = g.has_q && fm_test_has_b4(T, D, Da);
-  if (!g.has_mix_tile) g.mix_lds = 0;
-  return g;
+// a handle of shape (T, D, Ta, Da): low-pass taps the guard accepts, whose tables build with a tap in the first chunk
+static inline FmPlanIn fm_test_plan_in(uint32_t T, uint32_t D, uint32_t Ta, uint32_t Da, uint32_t ns, bool bit_exact, const FmTestFacts& f) {
+  FmPlanIn in;
+  memset(&in, 0, sizeof(in));
+  in.T = T; in.D = D; in.Ta = Ta; in.Da = Da; in.n_streams = ns; in.bit_exact = bit_exact; in.n_cu = f.n_cu;
+  in.taps = FmTapVerdict{true, true, 4.7f, 3.14f};
+  in.q_built = true; in.q_c0 = 0;
+  in.q_default_nslot = f.q_default_nslot; in.q_default_lds = in.q_lds = f.q_default_lds; in.q_symbol = "";
+  in.mix_lds = f.mix_lds; in.mix_blocks_per_cu = f.mix_blocks_per_cu;
+  return in;
+}
+static inline FmGeom fm_test_geom(uint32_t T, uint32_t D, uint32_t Ta, uint32_t Da, uint32_t ns, bool bit_exact, const FmTestFacts& f) {
+  return fm_plan(fm_test_plan_in(T, D, Ta, Da, ns, bit_exact, f), FmKnobs(), FmRefused{false, 0u}).geo;
 }
 
 #endif

@@ -9,7 +9,8 @@
  * enqueue()'s prev_by_q) is carried from call to call as enqueue() carries it.  One line per call:
  *   "nsamp M A q_fit q_ok stream_ok fast_ok prev_dev prev_q ovl_geometry_ok overlapped fuse"
  * stream_ok as launch_bx asks it (every stream, not beside design Q); ovl_geometry_ok is fm_ovl_geometry_ok on the previous call's bytes and alignment
- * whatever served it; overlapped = q_ok && the flag && prev_dev && prev_q && ovl_geometry_ok (buffers that share no rows).  The FmGeom: fm_geom.h. */
+ * whatever served it; overlapped = q_ok && the flag && prev_dev && prev_q && ovl_geometry_ok (buffers that share no rows).  The FmGeom is the one the library
+ * plans for the shape at 32 audio taps on an MI355X (fm_geom.h: fm_plan with low-pass taps the guard accepts). */
 #include <cstdio>
 #include <cstdlib>
 
@@ -17,7 +18,8 @@
 
 int main(int argc, char** argv) {
   if (argc < 9) { fprintf(stderr, "usage: %s T D Da n_streams bit_exact n_routed route_at nsamp:cls:overlap:device...\n", argv[0]); return 2; }
-  const FmGeom g = fm_test_geom_instances((uint32_t)atol(argv[1]), (uint32_t)atol(argv[2]), (uint32_t)atol(argv[3]), (uint32_t)atol(argv[4]), atol(argv[5]) != 0);
+  const uint32_t T = (uint32_t)atol(argv[1]), D = (uint32_t)atol(argv[2]), Da = (uint32_t)atol(argv[3]);
+  const FmGeom g = fm_test_geom(T, D, 32u, Da, (uint32_t)atol(argv[4]), atol(argv[5]) != 0, fm_test_facts_mi355x(T, D, Da));
   const uint32_t n_routed = (uint32_t)atol(argv[6]);
   const int route_at = (int)atol(argv[7]);
 

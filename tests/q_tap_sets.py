@@ -56,7 +56,7 @@ def q_build(pkg, h, D):
 
 
 def create_offers_design_q(pkg, h, g, D):
-    """sdrfm_create's conditions on the taps (csrc/sdrfm.hip), on the CPU: the tables build, the performance rule sum|h| <= 2 |sum h|, and a guard
+    """sdrfm_create's conditions on the taps (csrc/sdrfm_fm_plan.h: fm_tap_verdict, fm_plan_offers_q), on the CPU: the tables build, the performance rule sum|h| <= 2 |sum h|, and a guard
     radius that a carrier at an eighth of full scale clears."""
     lib = pkg.load_library()
     h = np.ascontiguousarray(h, dtype=np.float32)

@@ -108,7 +108,7 @@ int main(int argc, char** argv) {
   p.A = d_A; p.g = d_g; p.q0 = q; p.q2 = 65536.0f * q; p.cst = cst;
   p.T = T; p.N = nsamp; p.M = M; p.A_out = A; p.steps_total = (M + 127) / 128; p.runs = runs; p.n_streams = ns; p.dbg = nullptr; p.prio_by_age = getenv("QBENCH_NOPRIO") ? 0u : 1u;
   unsigned int* d_st = nullptr;
-  // the conditioning guard (csrc/sdrfm.hip, sdrfm_create): thresholds as the library derives them; QBENCH_GUARD=0 switches it off.
+  // the conditioning guard (csrc/sdrfm_fm_plan.h, fm_tap_verdict): thresholds as the library derives them; QBENCH_GUARD=0 switches it off.
   // hist_q (the 64 raw samples before the call) = the random history bytes above, y[-1] taken as carried (yprev_exact).
   {
     std::vector<float> hp(SDRFM_Q_TP, 0.0f);
