@@ -728,6 +728,33 @@ int  sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* si
                                    float* left, float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride,
                                    float* bb, size_t bb_stride, uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags);
 
+/* The METERED broadcast call: either broadcast call above and, from the same launch, one sdrfm_scan_meter per stream —
+ * level, tuning error, deviation and pilot quality of what the stream is receiving, so that a running receiver follows a drifting
+ * crystal or a fading station without a second handle that walks the front end again.
+ * The records are the scan section's, term for term, on this handle's own y, d and q: the 64 bytes per stream equal what a scan handle
+ * gives for the same bytes, channel taps (an untuned handle: ctaps = (h[k], 0), rot = 0), pilot taps and pilot_min, in every field and
+ * for any cut into calls; they add up with sdrfm_scan_meter_add and read with sdrfm_scan_report.  n is the call's new d's, n_pilot equals
+ * pilot_count.  The call changes NO bit of left, right, bb, pcm, pilot_count, the counts or the carried state: metered and plain calls
+ * mix freely in one sequence.
+ *   sink == NULL   the contract of sdrfm_bcast_process_batch; pcm must then be NULL (SDRFM_EINVAL).
+ *   sink != NULL   the contract of sdrfm_bcast_process_batch_pcm, left = right = NULL included.
+ *   meters         n_streams records, never NULL (SDRFM_EINVAL).  Host memory for a host-buffer call; with SDRFM_F_DEVICE_PTRS device
+ *                  memory; 8-byte aligned either way (else SDRFM_EINVAL).  OVERWRITTEN: zeroed on the handle's stream before the launch adds to it; nbytes == 0 gives
+ *                  zero records; reserved stays 0.
+ * The record's int64 bounds are the scan section's.  SDRFM_EINVAL for a handle whose CURRENT channel taps — sdrfm_bcast_tune's, or the
+ * configuration's h on an untuned handle — have sum(|hr[k]| + |hi[k]|) > 16 for some stream, or whose pilot taps have
+ * sum(|br[k]| + |bi[k]|) > 8 (looked at at create and at tune, not per call; the plain calls take such a handle as before);
+ * SDRFM_ECAPACITY for nbytes > 4 MiB whatever max_bytes_per_call is.
+ * These three refusals of the metered call's own come first (NULL handle, meters or counts; pcm without sink; the tap sums); every other
+ * check is the chosen form's, in its order, the 4 MiB bound beside max_bytes_per_call's.  All of them before anything is enqueued: a
+ * refused call leaves the handle and the sink as they were.
+ * The kernel name does not change: sdrfm_bcast_kernel_name names the handle's kernel, and a metered call launches that kernel's
+ * metered form. */
+int  sdrfm_bcast_process_batch_metered(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink /* or NULL */, const uint8_t* iq, size_t iq_stride,
+                                       uint32_t nbytes, float* left, float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride,
+                                       float* bb, size_t bb_stride, uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* n_audio,
+                                       uint32_t* n_rds, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,14 @@
 """BroadcastDemod — Python mirror of the sdrfm_bcast_* C entry points (the broadcast receiver): the stereo handle's L
-and R and the RDS handle's complex baseband of the same streams from one kernel launch, bit for bit what StereoDemod and RdsDemod give."""
+and R and the RDS handle's complex baseband of the same streams from one kernel launch, bit for bit what StereoDemod and RdsDemod give.
+The metered calls add the scan handle's record of every stream from that launch: scan.meter_add, scan.meter_report and
+scan.stream_status read it."""
 import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import lib as _l
+from .scan import METER_DTYPE
 from .stereo import _pilot_floats
 
 CFG_FORCE_GENERIC = 1   # SDRFM_BCAST_CFG_FORCE_GENERIC (include/sdrfm.h)
@@ -189,4 +192,59 @@ class BroadcastDemod:
                                                          left.stride(0) if left is not None else 0, C.c_void_p(pcm.data_ptr()), pcm.stride(0),
                                                          C.c_void_p(bb.data_ptr()), bb.stride(0), pc, C.byref(na), C.byref(nr), _l.F_DEVICE_PTRS),
                  "sdrfm_bcast_process_batch_pcm(device)")
+        return na.value, nr.value
+
+    def process_batch_metered(self, iq: np.ndarray, sink=None, with_audio=True):
+        """sdrfm_bcast_process_batch_metered on host memory: what process_batch (sink=None) or process_batch_pcm(sink, iq, with_audio)
+        returns and, behind it, the streams' records of the same launch: a scan.METER_DTYPE array [n_streams]."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        if iq.ndim == 1:
+            iq = iq[None, :]
+        ns = self.cfg.n_streams
+        assert iq.shape[0] == (1 if self._shared_input else ns)                # (a shared capture is one row)
+        assert with_audio or sink is not None, "without a sink the audio rows are all the audio there is"
+        nbytes = iq.shape[1]
+        ca, cr = (max(v, 1) for v in self.counts(nbytes & ~1))
+        left = np.zeros((ns, ca), dtype=np.float32) if with_audio else None
+        right = np.zeros_like(left) if with_audio else None
+        pcm = np.zeros((ns, 2 * ca), dtype=np.int16) if sink is not None else None
+        bb = np.zeros((ns, 2 * cr), dtype=np.float32)
+        pc = np.zeros(ns, dtype=np.uint32)
+        meters = np.zeros(ns, dtype=METER_DTYPE)
+        na, nr = C.c_uint32(), C.c_uint32()
+        self._ck(self._lib.sdrfm_bcast_process_batch_metered(
+            self._h, sink._h if sink is not None else None, iq.ctypes.data, nbytes, nbytes, left.ctypes.data if with_audio else None,
+            right.ctypes.data if with_audio else None, ca, pcm.ctypes.data if sink is not None else None, 2 * ca, bb.ctypes.data, 2 * cr,
+            pc.ctypes.data, meters.ctypes.data, C.byref(na), C.byref(nr), 0), "sdrfm_bcast_process_batch_metered")
+        bbc = np.ascontiguousarray(bb[:, : 2 * nr.value]).view(np.complex64)
+        lr = (left[:, : na.value], right[:, : na.value]) if with_audio else (None, None)
+        if sink is None:
+            return lr + (bbc, pc, meters)
+        return lr + (pcm[:, : 2 * na.value], bbc, pc, meters)
+
+    def process_batch_metered_device(self, iq, left, right, bb, meters, pilot_count=None, nbytes=None, sink=None, pcm=None):
+        """device tensors as process_batch_device (sink=None: left and right given, no pcm) or process_batch_pcm_device (sink and pcm given;
+        left = right = None: the sink reads the handle's own rows) takes them, and meters: int64 [n_streams, 8] (sdrfm_scan_meter's eight
+        words) or the address of n_streams records in device memory, 8-byte aligned.  Enqueue only.  Returns (n_audio, n_rds)."""
+        assert iq.is_cuda and bb.is_cuda and bb.stride(1) == 1 and (left is None) == (right is None)
+        assert (sink is None) == (pcm is None) and (sink is not None or left is not None)
+        if left is not None:
+            assert left.is_cuda and right.is_cuda and left.stride() == right.stride() and left.stride(1) == 1
+        if pcm is not None:
+            assert pcm.is_cuda and pcm.stride(1) == 1
+        if hasattr(meters, "data_ptr"):
+            assert meters.is_cuda and meters.is_contiguous() and meters.element_size() * meters.numel() >= 64 * self.cfg.n_streams
+            mp = C.c_void_p(meters.data_ptr())
+        else:
+            mp = C.c_void_p(int(meters)) if meters else None
+        nbytes = iq.shape[1] if nbytes is None else int(nbytes)
+        pc = C.c_void_p(pilot_count.data_ptr()) if pilot_count is not None else None
+        lp = C.c_void_p(left.data_ptr()) if left is not None else None
+        rp = C.c_void_p(right.data_ptr()) if right is not None else None
+        na, nr = C.c_uint32(), C.c_uint32()
+        self._ck(self._lib.sdrfm_bcast_process_batch_metered(
+            self._h, sink._h if sink is not None else None, C.c_void_p(iq.data_ptr()), iq.stride(0), nbytes, lp, rp,
+            left.stride(0) if left is not None else 0, C.c_void_p(pcm.data_ptr()) if pcm is not None else None,
+            pcm.stride(0) if pcm is not None else 0, C.c_void_p(bb.data_ptr()), bb.stride(0), pc, mp, C.byref(na), C.byref(nr), _l.F_DEVICE_PTRS),
+            "sdrfm_bcast_process_batch_metered(device)")
         return na.value, nr.value

@@ -18,10 +18,15 @@
  * A tuned handle (sdrfm_bcast_tune) launches the same two with the header's tuned walk: every stream has complex channel
  * taps and a rotation of its own and receives the station at that offset of its input — or of row 0 of the input, which all streams
  * then share.  Only K2 and K3 differ; everything behind d is the code above.
+ *
+ * A metered call (sdrfm_bcast_process_batch_metered) launches the fifth template argument's form of either: the same walk
+ * and the same outputs, and every new d besides handed to sdrfm_meter.h's meter stage where its y, the d itself and the q of the pilot
+ * window that ends at it are in LDS and registers anyway — the scan handle's record of the stream, from the launch that receives it.
  */
 #include <new>
 
 #include "sdrfm_carrier.h"
+#include "sdrfm_meter.h"
 #include "sdrfm_out_stages.h"
 #include "sdrfm_pilot_front.h"
 #include "sdrfm_sink_stereo.h"
@@ -43,6 +48,7 @@ struct BcastParams : FrontParams {
   uint32_t zplane;             // words of one z plane: Tr - 1 + NDT, made odd
   const float* ctaps;          // tuned: [ns][2T], (hr[k], hi[k]) pairs
   const float* rot;            // tuned: [ns]
+  unsigned long long* meters;  // metered: [ns][8], sdrfm_scan_meter as eight 64-bit words, zeroed before the launch
 };
 
 // how many of a workgroup's nw waves take a step's nc RDS chains (of Tr links), the others taking its na audio outputs (of 2 Ta links):
@@ -56,7 +62,7 @@ __device__ __forceinline__ int bcast_rds_waves(int nw, int nc, int Tr, int na, i
   return wr;
 }
 
-template <int FT, int FD, int FP, bool TU>
+template <int FT, int FD, int FP, bool TU, bool ME = false>
 __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t T = FT > 0 ? FT : p.T, P = FT > 0 ? FP : p.P;
@@ -65,6 +71,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   // LDS: region (x as f16 pairs | d's, s's, zr's, zi's) | ys[NY] | hb[H] | tps[P] | grs[Tr] | gas[Ta] | hs[T; tuned: 2T] | zb[2 (Tr - 1)] | sb[Ta - 1];
   // hb and tps padded so that grs starts on 16 bytes.  grs holds the RDS taps oldest first (grs[k] = gr[Tr - 1 - k]): the output chains
   // read them four at a time
+  // (a metered kernel adds nothing to it: y, d and q of a new d are there already)
   FrontWg<FT, FD, FP, TU> w;
   w.xs = reinterpret_cast<h2_t*>(smem);
   w.ds = reinterpret_cast<float*>(smem);
@@ -90,6 +97,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   rds_taps_to_lds(grs, p.gr, Tr, tid, nthr);
   for (int k = tid; k < (int)Ta; k += nthr) gas[k] = p.ga[k];
   uint32_t cnt = 0;
+  MeterAcc acc;                                                 // metered: the lane's sums, and the gate's count in place of cnt
 
   front_walk(p, w, [&](int a, int b, bool full) {
     front_d_stage(p, w, a, b);
@@ -100,6 +108,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
       //      ss[o - oa], z at zs[o - oz].  The span's first step computes all of [0, C); a later one takes the tails from the step before
       //      and computes the new d's only
       const int C = n + Tm - 1, O0 = first ? 0 : Tm - 1;
+      const int yo = a - (a - 1 > 0 ? a - 1 : 0);                 // metered: y of the new d a + j lies at ys[j + yo]
       if (!first) {
         rds_tail_restore(zs, zb, Tr, ZP, tid, nthr);
         for (int k = tid; k < (int)Ta - 1; k += nthr) ss[k] = sb[k];
@@ -114,7 +123,16 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
           zs[o - oz] = zr;
           zs[(int)ZP + o - oz] = zi;
         }
-        cnt += (on && o >= Tm - 1) ? 1u : 0u;
+        if constexpr (ME) {
+          // the new d m = a + j, j = o - (Tm - 1): the UNDELAYED d ds[H + j], at which o's pilot window ends (H = P - 1 + Tm - 1).  The
+          // tails a span's first step recomputes (o < Tm - 1) belong to d's before the span: another workgroup's, or an earlier call's
+          if (o >= Tm - 1) {
+            const int j = o - (Tm - 1);
+            meter_take(acc, w.ys[j + yo], ds[H + j], q, p.pmin2);
+          }
+        } else {
+          cnt += (on && o >= Tm - 1) ? 1u : 0u;
+        }
       });
       __syncthreads();
       // ---- the outputs whose newest d lies in [a, b): nja audio outputs from ja.x, njr RDS outputs from jr.x as 2 njr chains (the re ones first)
@@ -133,7 +151,12 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
     __syncthreads();
   });
 
-  front_count(p, s, tid, cnt);
+  if constexpr (ME) {
+    front_count(p, s, tid, acc.on);                             // the same comparison on the same pw as the carriers' gate
+    meter_flush(acc, p.meters + 8 * (size_t)s, tid);
+  } else {
+    front_count(p, s, tid, cnt);
+  }
   front_hand_over(p, w);
 }
 
@@ -162,6 +185,11 @@ struct sdrfm_bcast {
   char kernel_name_tuned[112];
   float* d_ctaps = nullptr;                    // [ns][2T]
   float* d_rot = nullptr;                      // [ns]
+  // the metered form (sdrfm_bcast_process_batch_metered): the slots of its kernels, whether the taps keep a record inside int64 — the pilot
+  // taps and the untuned channel taps looked at at create, the tuned ones at tune
+  uint32_t slots_metered = 1, slots_tuned_metered = 1;
+  bool meter_ok = false, meter_ok_tuned = false;
+  sdrfm_scan_meter* d_meters = nullptr;        // host-buffer calls: the records [ns]
 };
 
 namespace {
@@ -184,12 +212,19 @@ size_t bcast_lds_tuned(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t
   return bcast_lds(T, D, P, Tg, H, NY, NDT, region_words) + 4 * (size_t)T;
 }
 
+// the launch of one of the eight kernels
+template <bool TU, bool ME>
+void bcast_launch(bool fast, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const BcastParams& p) {
+  if (fast) k_bcast<64, 10, 101, TU, ME><<<grid, block, lds, stream>>>(p);
+  else k_bcast<0, 0, 0, TU, ME><<<grid, block, lds, stream>>>(p);
+}
+
 void bcast_free(sdrfm_bcast* h) {
   if (!h) return;
   front_free(h->f);
   decim_free(h->au); decim_free(h->rd);
   (void)hipFree(h->d_left); (void)hipFree(h->d_right); (void)hipFree(h->d_bb);
-  (void)hipFree(h->d_ctaps); (void)hipFree(h->d_rot);
+  (void)hipFree(h->d_ctaps); (void)hipFree(h->d_rot); (void)hipFree(h->d_meters);
   delete h;
 }
 
@@ -229,7 +264,8 @@ int sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out) {
   h->d_bb_stride = (2 * (size_t)h->rd.max_out + 63) & ~(size_t)63;
   const size_t audio_bytes = sizeof(float) * h->d_audio_stride * ns;
   if (hipMalloc(&h->d_left, audio_bytes) != hipSuccess || hipMalloc(&h->d_right, audio_bytes) != hipSuccess ||
-      hipMalloc(&h->d_bb, sizeof(float) * h->d_bb_stride * ns) != hipSuccess) {
+      hipMalloc(&h->d_bb, sizeof(float) * h->d_bb_stride * ns) != hipSuccess ||
+      hipMalloc(&h->d_meters, sizeof(sdrfm_scan_meter) * ns) != hipSuccess) {
     bcast_free(h);
     return SDRFM_ENOMEM;
   }
@@ -245,6 +281,9 @@ int sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out) {
   if (h->fast_tuned) snprintf(h->kernel_name_tuned, sizeof h->kernel_name_tuned, "bcast-fast-tuned T64 D10 P101 Ta%u Da%u Tr%u Dr%u", Ta, Da, Tr, Dr);
   else snprintf(h->kernel_name_tuned, sizeof h->kernel_name_tuned, "bcast-generic-tuned T%u D%u P%u Ta%u Da%u Tr%u Dr%u", T, D, P, Ta, Da, Tr, Dr);
   h->slots_tuned = front_slots(k_bcast<64, 10, 101, true>, k_bcast<0, 0, 0, true>, h->fast_tuned, h->step_tuned.lds, prop);
+  h->slots_metered = front_slots(k_bcast<64, 10, 101, false, true>, k_bcast<0, 0, 0, false, true>, h->fast, h->step.lds, prop);
+  h->slots_tuned_metered = front_slots(k_bcast<64, 10, 101, true, true>, k_bcast<0, 0, 0, true, true>, h->fast_tuned, h->step_tuned.lds, prop);
+  h->meter_ok = meter_taps_ok(h->f.hc, 1, T, METER_MAX_CTAP_SUM) && meter_taps_ok(h->f.bc, 1, 2 * P, METER_MAX_PTAP_SUM);
   rc = sdrfm_bcast_reset(h);
   if (rc != SDRFM_OK) { bcast_free(h); return rc; }
   *out = h;
@@ -284,9 +323,9 @@ static int bcast_stage_in(const sdrfm_bcast* h, const uint8_t* iq, size_t iq_str
   return hipMemcpyAsync(h->f.d_iq, iq, nbytes, hipMemcpyHostToDevice, h->f.stream) == hipSuccess ? SDRFM_OK : SDRFM_FAIL;
 }
 
-// one call on device buffers, enqueued on the handle's stream
+// one call on device buffers, enqueued on the handle's stream; d_meters: a metered call's records, nullptr for a plain call
 static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, float* d_left, float* d_right, size_t audio_stride,
-                         float* d_bb, size_t bb_stride, uint32_t* d_pc, uint32_t* n_audio, uint32_t* n_rds) {
+                         float* d_bb, size_t bb_stride, uint32_t* d_pc, sdrfm_scan_meter* d_meters, uint32_t* n_audio, uint32_t* n_rds) {
   const uint32_t ns = h->cfg.n_streams;
   const FrontStep& step = h->tuned ? h->step_tuned : h->step;
   if (step.lds > PF_LDS_BUDGET) return SDRFM_FAIL;               // (no shape within the header's limits gets here: NY = 2 fits them all)
@@ -306,16 +345,19 @@ static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, 
   p.f0a = decim_f0(h->au);
   p.f0r = decim_f0(h->rd);
   p.zplane = rds_zplane(p.Tr, p.NDT);
-  p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, h->tuned ? h->slots_tuned : h->slots);   // as the RDS handle chooses them
+  p.meters = reinterpret_cast<unsigned long long*>(d_meters);
+  const uint32_t slots = d_meters ? (h->tuned ? h->slots_tuned_metered : h->slots_metered) : (h->tuned ? h->slots_tuned : h->slots);
+  p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, slots);   // as the RDS handle chooses them
   p.span = M ? (M + p.blocks_per_stream - 1) / p.blocks_per_stream : 0;
   if (front_zero_count(h->f, d_pc, true) != SDRFM_OK) return SDRFM_FAIL;
+  if (d_meters && hipMemsetAsync(d_meters, 0, sizeof(sdrfm_scan_meter) * ns, h->f.stream) != hipSuccess) return SDRFM_FAIL;
   const dim3 grid(ns * p.blocks_per_stream), block(PF_THREADS);
   if (h->tuned) {
-    if (h->fast_tuned) k_bcast<64, 10, 101, true><<<grid, block, step.lds, h->f.stream>>>(p);
-    else k_bcast<0, 0, 0, true><<<grid, block, step.lds, h->f.stream>>>(p);
+    if (d_meters) bcast_launch<true, true>(h->fast_tuned, grid, block, step.lds, h->f.stream, p);
+    else bcast_launch<true, false>(h->fast_tuned, grid, block, step.lds, h->f.stream, p);
   } else {
-    if (h->fast) k_bcast<64, 10, 101, false><<<grid, block, step.lds, h->f.stream>>>(p);
-    else k_bcast<0, 0, 0, false><<<grid, block, step.lds, h->f.stream>>>(p);
+    if (d_meters) bcast_launch<false, true>(h->fast, grid, block, step.lds, h->f.stream, p);
+    else bcast_launch<false, false>(h->fast, grid, block, step.lds, h->f.stream, p);
   }
   if (hipGetLastError() != hipSuccess) return SDRFM_FAIL;
   front_advance(h->f, p.N);
@@ -326,18 +368,41 @@ static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, 
   return SDRFM_OK;
 }
 
-int sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left, float* right,
-                              size_t audio_stride, float* bb, size_t bb_stride, uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds,
-                              uint32_t flags) {
+// the most bytes per stream a call takes: a metered one at most what keeps its records inside int64
+static uint32_t bcast_max_bytes(const sdrfm_bcast* h, bool metered) {
+  return metered && h->f.max_bytes > METER_MAX_BYTES ? METER_MAX_BYTES : h->f.max_bytes;
+}
+
+// a call of no bytes: no launch, no outputs, the counts and a metered call's records are 0
+static int bcast_empty_call(const sdrfm_bcast* h, uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t flags) {
+  const size_t bytes = sizeof(sdrfm_scan_meter) * h->cfg.n_streams;
+  if (meters && !(flags & SDRFM_F_DEVICE_PTRS)) memset(meters, 0, bytes);
+  if (meters && (flags & SDRFM_F_DEVICE_PTRS) &&
+      (hipSetDevice(h->f.device) != hipSuccess || hipMemsetAsync(meters, 0, bytes, h->f.stream) != hipSuccess))
+    return SDRFM_FAIL;
+  return front_empty_call(h->f, pilot_count, flags);
+}
+
+// a host-buffer call's records back, in stream order before front_finish
+static int bcast_meters_back(const sdrfm_bcast* h, sdrfm_scan_meter* meters) {
+  if (!meters) return SDRFM_OK;
+  const hipError_t e = hipMemcpyAsync(meters, h->d_meters, sizeof(sdrfm_scan_meter) * h->cfg.n_streams, hipMemcpyDeviceToHost, h->f.stream);
+  return e == hipSuccess ? SDRFM_OK : SDRFM_FAIL;
+}
+
+// sdrfm_bcast_process_batch, and with `meters` the metered call of its form: the same checks in the same order, the same launch geometry
+static int bcast_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left, float* right, size_t audio_stride,
+                       float* bb, size_t bb_stride, uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* n_audio, uint32_t* n_rds,
+                       uint32_t flags) {
   if (!h || !n_audio || !n_rds) return SDRFM_EINVAL;
   if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;       // SDRFM_F_OVERLAP: not for this handle
   if (nbytes & 1u) return SDRFM_EODD;
-  if (nbytes > h->f.max_bytes) return SDRFM_ECAPACITY;
+  if (nbytes > bcast_max_bytes(h, meters != nullptr)) return SDRFM_ECAPACITY;
   const uint32_t ns = h->cfg.n_streams;
   if (nbytes == 0) {
     *n_audio = 0;
     *n_rds = 0;
-    return front_empty_call(h->f, pilot_count, flags);
+    return bcast_empty_call(h, pilot_count, meters, flags);
   }
   if (!iq) return SDRFM_EINVAL;
   if (ns > 1 && !bcast_shared(h) && iq_stride < nbytes) return SDRFM_ECAPACITY;
@@ -348,27 +413,35 @@ int sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_str
   if (ns > 1 && (audio_stride < Aa || bb_stride < 2 * (size_t)Ar)) return SDRFM_ECAPACITY;
   if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
   if (flags & SDRFM_F_DEVICE_PTRS)
-    return bcast_enqueue(h, iq, iq_stride, nbytes, left, right, audio_stride, bb, bb_stride, pilot_count, n_audio, n_rds);
+    return bcast_enqueue(h, iq, iq_stride, nbytes, left, right, audio_stride, bb, bb_stride, pilot_count, meters, n_audio, n_rds);
 
   if (bcast_stage_in(h, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
   const int rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc,
-                               n_audio, n_rds);
+                               meters ? h->d_meters : nullptr, n_audio, n_rds);
   if (rc != SDRFM_OK) return rc;
   if (front_copy_back(h->f, left, audio_stride, h->d_left, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
   if (front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
   if (front_copy_back(h->f, bb, bb_stride, h->d_bb, h->d_bb_stride, 2 * (size_t)Ar) != SDRFM_OK) return SDRFM_FAIL;
+  if (bcast_meters_back(h, meters) != SDRFM_OK) return SDRFM_FAIL;
   return front_finish(h->f, pilot_count);
 }
 
-// the call above and, behind it on the handle's stream, the stereo sink's default kernel over this call's L and R rows
-int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left,
-                                  float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride,
-                                  uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
+int sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left, float* right,
+                              size_t audio_stride, float* bb, size_t bb_stride, uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds,
+                              uint32_t flags) {
+  return bcast_batch(h, iq, iq_stride, nbytes, left, right, audio_stride, bb, bb_stride, pilot_count, nullptr, n_audio, n_rds, flags);
+}
+
+// the call above and, behind it on the handle's stream, the stereo sink's default kernel over this call's L and R rows;
+// with `meters` the metered call of this form
+static int bcast_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left,
+                           float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride,
+                           uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
   if (!h || !sink || !n_audio || !n_rds) return SDRFM_EINVAL;
   if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;
   if (!left != !right) return SDRFM_EINVAL;                    // both, or neither: the sink then reads the handle's own rows
   if (nbytes & 1u) return SDRFM_EODD;
-  if (nbytes > h->f.max_bytes) return SDRFM_ECAPACITY;
+  if (nbytes > bcast_max_bytes(h, meters != nullptr)) return SDRFM_ECAPACITY;
   const uint32_t ns = h->cfg.n_streams;
   const bool dev = (flags & SDRFM_F_DEVICE_PTRS) != 0;
   uint32_t Aa = 0, Ar = 0;
@@ -378,7 +451,7 @@ int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sin
   if (nbytes == 0) {
     *n_audio = 0;
     *n_rds = 0;
-    return front_empty_call(h->f, pilot_count, flags);
+    return bcast_empty_call(h, pilot_count, meters, flags);
   }
   if (!iq) return SDRFM_EINVAL;
   if (ns > 1 && !bcast_shared(h) && iq_stride < nbytes) return SDRFM_ECAPACITY;
@@ -389,7 +462,7 @@ int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sin
     float* const l = left ? left : h->d_left;
     float* const r = left ? right : h->d_right;
     const size_t as = left ? audio_stride : h->d_audio_stride;
-    rc = bcast_enqueue(h, iq, iq_stride, nbytes, l, r, as, bb, bb_stride, pilot_count, n_audio, n_rds);
+    rc = bcast_enqueue(h, iq, iq_stride, nbytes, l, r, as, bb, bb_stride, pilot_count, meters, n_audio, n_rds);
     if (rc != SDRFM_OK) return rc;
     return sdrfm_stereo_sink_launch_on(sink, l, r, as, Aa, pcm, pcm_stride, h->f.stream);
   }
@@ -399,7 +472,8 @@ int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sin
   rc = sdrfm_stereo_sink_reserve(sink, Aa, &d_pcm, &d_pcm_stride);   // (before anything is enqueued: a refusal leaves both handles alone)
   if (rc != SDRFM_OK) return rc;
   if (bcast_stage_in(h, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
-  rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc, n_audio, n_rds);
+  rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc,
+                     meters ? h->d_meters : nullptr, n_audio, n_rds);
   if (rc != SDRFM_OK) return rc;
   rc = sdrfm_stereo_sink_launch_on(sink, h->d_left, h->d_right, h->d_audio_stride, Aa, d_pcm, d_pcm_stride, h->f.stream);
   if (rc != SDRFM_OK) return rc;
@@ -407,7 +481,29 @@ int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sin
   if (left && front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
   if (front_copy_back(h->f, bb, bb_stride, h->d_bb, h->d_bb_stride, 2 * (size_t)Ar) != SDRFM_OK) return SDRFM_FAIL;
   if (sdrfm_stereo_sink_copy_back(sink, pcm, pcm_stride, Aa, h->f.stream) != SDRFM_OK) return SDRFM_FAIL;
+  if (bcast_meters_back(h, meters) != SDRFM_OK) return SDRFM_FAIL;
   return front_finish(h->f, pilot_count);
+}
+
+int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left,
+                                  float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride,
+                                  uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
+  return bcast_batch_pcm(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, nullptr, n_audio,
+                         n_rds, flags);
+}
+
+// either call above with the streams' records from the same launch.  What is the metered call's own is refused first:
+// no records to write, PCM without a sink, taps whose sums could leave int64; the form's own checks follow in its own order
+int sdrfm_bcast_process_batch_metered(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes,
+                                      float* left, float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride,
+                                      uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
+  if (!h || !meters || !n_audio || !n_rds) return SDRFM_EINVAL;
+  if (!sink && pcm) return SDRFM_EINVAL;
+  if ((uintptr_t)meters % 8) return SDRFM_EINVAL;
+  if (!(h->tuned ? h->meter_ok_tuned : h->meter_ok)) return SDRFM_EINVAL;
+  if (!sink) return bcast_batch(h, iq, iq_stride, nbytes, left, right, audio_stride, bb, bb_stride, pilot_count, meters, n_audio, n_rds, flags);
+  return bcast_batch_pcm(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, meters, n_audio,
+                         n_rds, flags);
 }
 
 int sdrfm_bcast_set_stream(sdrfm_bcast_t* h, void* hip_stream) {
@@ -433,7 +529,7 @@ int sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uin
     if (flags) return SDRFM_EINVAL;
     const int rc = sdrfm_bcast_reset(h);                         // (waits for the handle's stream: no launch reads the taps any more)
     if (rc != SDRFM_OK) return rc;
-    h->tuned = h->shared_input = false;
+    h->tuned = h->shared_input = h->meter_ok_tuned = false;
     return SDRFM_OK;
   }
   if (!finite_all(ctaps, ns * 2 * T) || !finite_all(rot, ns)) return SDRFM_EINVAL;
@@ -454,6 +550,7 @@ int sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uin
     return SDRFM_FAIL;
   h->tuned = true;
   h->shared_input = (flags & SDRFM_TUNE_SHARED_INPUT) != 0;
+  h->meter_ok_tuned = meter_taps_ok(ctaps, ns, 2 * T, METER_MAX_CTAP_SUM) && meter_taps_ok(h->f.bc, 1, 2 * h->f.P, METER_MAX_PTAP_SUM);
   return sdrfm_bcast_reset(h);
 }
 

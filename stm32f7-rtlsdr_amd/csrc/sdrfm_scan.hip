@@ -4,14 +4,14 @@
  * channel power |y|^2, d and d^2, the pilot power |q|^2 and its square, and how many d's passed the pilot gate.
  *
  * The walk is the tuned broadcast kernel's up to q (K2 with the stream's complex taps, sdrfm_discriminate_tuned, the pilot filter), with
- * nothing behind q: H = P - 1, no carriers, no output chains, no tails.  Every new d of the call gives five fp32 terms, each turned into
- * an integer by rintf(term * 2^k); a lane sums its integers in registers over the whole span, a wave reduces them once and adds them to
- * the stream's record with one 64-bit atomic per field.  Integer sums are associative, so the record depends on nothing but the bytes.
+ * nothing behind q: H = P - 1, no carriers, no output chains, no tails.  What a new d adds to the record and how the lanes' sums reach it
+ * is sdrfm_meter.h's, which the broadcast handle's metered kernels call as well.
  *
  * k_scan<0, 0, 0, true> and k_scan<64, 10, 101, true> are the header's two forms of the tuned walk; the meters are the same code in both.
  */
 #include <new>
 
+#include "sdrfm_meter.h"
 #include "sdrfm_pilot_front.h"
 
 namespace {
@@ -21,15 +21,6 @@ struct ScanParams : FrontParams {
   const float* ctaps;          // [ns][2T], (hr[k], hi[k]) pairs
   const float* rot;            // [ns]
 };
-
-constexpr float SCAN_Q_RF = 0x1p+8f, SCAN_Q_D = 0x1p+24f, SCAN_Q_G = 0x1p+20f;   // the scalings of the header (powers of two: exact)
-
-__device__ __forceinline__ long long scan_fix(float term, float scale) { return (long long)__builtin_rintf(term * scale); }
-
-__device__ __forceinline__ unsigned long long scan_wave_sum(unsigned long long v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 template <int FT, int FD, int FP, bool TU>
 __global__ void __launch_bounds__(PF_THREADS) k_scan(ScanParams p) {
@@ -51,8 +42,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_scan(ScanParams p) {
   const int tid = w.tid;
   const float* ds = w.ds;
   const f2_t* ys = w.ys;
-  long long rf = 0, fq = 0, dv = 0, pq = 0, p2 = 0;
-  uint32_t cnt = 0, on = 0;
+  MeterAcc acc;
 
   front_walk(p, w, [&](int a, int b, bool full) {
     front_d_stage(p, w, a, b);
@@ -60,30 +50,13 @@ __global__ void __launch_bounds__(PF_THREADS) k_scan(ScanParams p) {
       // ---- output o stands for the new d a + o: its y lies at ys[a + o - yA], its d at ds[H + o], its pilot window ds[o .. o + P) ends at it
       const int yo = a - (a - 1 > 0 ? a - 1 : 0);
       front_pilot(w, 0, b - a, [&](int o, f2_t q) __attribute__((always_inline)) {
-        const f2_t y = ys[o + yo];
-        const float d = ds[H + o];
-        const float pw = __builtin_fmaf(q.x, q.x, q.y * q.y);
-        rf += scan_fix(__builtin_fmaf(y.x, y.x, y.y * y.y), SCAN_Q_RF);
-        fq += (long long)(int)__builtin_rintf(d * SCAN_Q_D);       // |d| <= pi and d^2 <= pi^2 (one ulp more at the most): both fit 32 bits
-        dv += (long long)(int)__builtin_rintf((d * d) * SCAN_Q_D);
-        pq += scan_fix(pw, SCAN_Q_D);
-        p2 += scan_fix(pw * pw, SCAN_Q_G);
-        on += pw >= p.pmin2 ? 1u : 0u;
-        cnt += 1u;
+        meter_take(acc, ys[o + yo], ds[H + o], q, p.pmin2);
       });
     }
     __syncthreads();
   });
 
-  // ---- the lanes' sums -> meters[s]: one wave reduction and one atomic per field and wave (a field no lane added to is skipped)
-  const unsigned long long v[7] = {cnt, on, (unsigned long long)rf, (unsigned long long)fq, (unsigned long long)dv, (unsigned long long)pq,
-                                   (unsigned long long)p2};
-  unsigned long long* m = p.meters + 8 * (size_t)w.s;
-#pragma unroll
-  for (int k = 0; k < 7; ++k) {
-    const unsigned long long t = scan_wave_sum(v[k]);
-    if ((tid & 63) == 0 && t) atomicAdd(m + k, t);
-  }
+  meter_flush(acc, p.meters + 8 * (size_t)w.s, tid);
   front_hand_over(p, w);
 }
 
@@ -106,8 +79,7 @@ struct sdrfm_scan {
 
 namespace {
 
-static_assert(sizeof(sdrfm_scan_meter) == 64, "the kernel addresses a record as eight 64-bit words");
-constexpr uint32_t SCAN_MAX_BYTES = 4u << 20;
+constexpr uint32_t SCAN_MAX_BYTES = METER_MAX_BYTES;
 
 // LDS bytes of a step geometry (see the layout in k_scan); Tg is not used
 size_t scan_lds(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t H, uint32_t NY, uint32_t NDT, uint32_t* region_words) {
@@ -121,15 +93,8 @@ size_t scan_lds(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t H, uin
 
 // the tuning a handle takes: finite, |rot| <= pi, and per stream sum(|hr| + |hi|) <= 16 (the header's int64 bounds)
 bool scan_tuning_ok(const float* ctaps, const float* rot, uint32_t ns, uint32_t T) {
-  if (!ctaps || !rot) return false;
+  if (!ctaps || !rot || !meter_taps_ok(ctaps, ns, 2 * T, METER_MAX_CTAP_SUM)) return false;
   for (uint32_t s = 0; s < ns; ++s) {
-    const float* c = ctaps + (size_t)s * 2 * T;
-    double sum = 0.0;
-    for (uint32_t k = 0; k < 2 * T; ++k) {
-      if (!std::isfinite(c[k])) return false;
-      sum += std::fabs((double)c[k]);
-    }
-    if (!(sum <= 16.0)) return false;
     if (!std::isfinite(rot[s]) || std::fabs(rot[s]) > 0x1.921fb6p+1f) return false;
   }
   return true;
@@ -164,9 +129,7 @@ int sdrfm_scan_create(const sdrfm_scan_config* cfg, sdrfm_scan_t** out) {
   if (cfg->flags & ~(SDRFM_SCAN_CFG_FORCE_GENERIC | SDRFM_SCAN_CFG_SHARED_INPUT)) return SDRFM_EINVAL;
   if (cfg->max_bytes_per_call > SCAN_MAX_BYTES) return SDRFM_EINVAL;
   if (!scan_tuning_ok(cfg->ctaps, cfg->rot, cfg->n_streams, cfg->fir_taps)) return SDRFM_EINVAL;
-  double bsum = 0.0;
-  for (uint32_t k = 0; k < 2 * cfg->pilot_taps; ++k) bsum += std::fabs((double)cfg->pilot_coeffs[k]);
-  if (!(bsum <= 8.0)) return SDRFM_EINVAL;
+  if (!meter_taps_ok(cfg->pilot_coeffs, 1, 2 * cfg->pilot_taps, METER_MAX_PTAP_SUM)) return SDRFM_EINVAL;
   hipDeviceProp_t prop;
   int rc = front_open_device(cfg->device, &prop);
   if (rc != SDRFM_OK) return rc;

@@ -1,6 +1,7 @@
 """ScanDemod — Python mirror of the sdrfm_scan_* C entry points (the scan handle): one integer record per candidate
 offset of a capture, and on top of it what the records say (meter_report), which candidates are stations (find_stations) and the three
-steps in one (scan_capture), whose result feeds BroadcastDemod.tune."""
+steps in one (scan_capture), whose result feeds BroadcastDemod.tune.  stream_status reads the same records where they come from a running
+receiver (BroadcastDemod.process_batch_metered): find_stations' policy, per tuned stream."""
 import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
@@ -171,7 +172,21 @@ def meter_report(meters, fs, D):
     return out
 
 
-def find_stations(report, offsets_hz, grid_hz, max_dev_rms_hz=55e3, max_steadiness=1.3, pilot_min=0.05):
+# the thresholds of find_stations and stream_status, and the two rules both apply to entry c of a meter_report
+MAX_DEV_RMS_HZ, MAX_STEADINESS, PILOT_MIN = 55e3, 1.3, 0.05
+
+
+def _fm_like(report, c, max_dev_rms_hz):
+    """an FM station's rms deviation and not noise's"""
+    return bool(report["dev_rms_hz"][c] <= max_dev_rms_hz)
+
+
+def _stereo(report, c, max_steadiness, pilot_min):
+    """a steady pilot, at least pilot_min strong"""
+    return bool(report["pilot_steadiness"][c] <= max_steadiness and report["pilot_rms_rad"][c] >= pilot_min)
+
+
+def find_stations(report, offsets_hz, grid_hz, max_dev_rms_hz=MAX_DEV_RMS_HZ, max_steadiness=MAX_STEADINESS, pilot_min=PILOT_MIN):
     """The candidates of a meter_report that hold a station.  Candidate c is one iff its rms deviation is an FM station's and not noise's
     (dev_rms_hz <= max_dev_rms_hz: 40 - 46 kHz against 65 kHz and more on an empty channel or beside a station) and its carrier lies
     nearer to this candidate than to the next (|freq_err_hz| < grid_hz / 2); it is stereo iff its pilot is steady besides
@@ -180,11 +195,27 @@ def find_stations(report, offsets_hz, grid_hz, max_dev_rms_hz=55e3, max_steadine
     off = np.atleast_1d(np.asarray(offsets_hz, np.float64))
     found = []
     for c in range(off.size):
-        if not (report["dev_rms_hz"][c] <= max_dev_rms_hz and abs(report["freq_err_hz"][c]) < grid_hz / 2):
+        if not (_fm_like(report, c, max_dev_rms_hz) and abs(report["freq_err_hz"][c]) < grid_hz / 2):
             continue
-        stereo = bool(report["pilot_steadiness"][c] <= max_steadiness and report["pilot_rms_rad"][c] >= pilot_min)
+        stereo = _stereo(report, c, max_steadiness, pilot_min)
         found.append(dict(offset_hz=float(off[c] + report["freq_err_hz"][c]), level_dbfs=float(report["level_dbfs"][c]), stereo=stereo, candidate=c))
     return found
+
+
+def stream_status(report, offsets_hz, max_dev_rms_hz=MAX_DEV_RMS_HZ, max_steadiness=MAX_STEADINESS, pilot_min=PILOT_MIN, max_err_hz=None):
+    """find_stations' policy for the streams of a tuned receiver: report is the meter_report of its records (a metered broadcast call's, or
+    several added up), offsets_hz the offsets the streams are tuned to.  One dict per stream, none dropped: present (the deviation rule of
+    find_stations and, where max_err_hz is given, |freq_err_hz| < max_err_hz), stereo (find_stations' rule, on a present stream),
+    offset_hz (the tuned offset plus the error where present, the tuned offset as it is otherwise), level_dbfs, stream.
+    [s["offset_hz"] for s in status] goes straight back into BroadcastDemod.tune(offsets_hz=...)."""
+    off = np.atleast_1d(np.asarray(offsets_hz, np.float64))
+    status = []
+    for c in range(off.size):
+        err = float(report["freq_err_hz"][c])
+        present = _fm_like(report, c, max_dev_rms_hz) and (max_err_hz is None or abs(err) < max_err_hz)
+        status.append(dict(present=present, stereo=present and _stereo(report, c, max_steadiness, pilot_min),
+                           offset_hz=float(off[c] + err) if present else float(off[c]), level_dbfs=float(report["level_dbfs"][c]), stream=c))
+    return status
 
 
 def scan_grid(fs, grid_hz=100e3, span_hz=None):
