@@ -755,6 +755,47 @@ int  sdrfm_bcast_process_batch_metered(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t
                                        float* bb, size_t bb_stride, uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* n_audio,
                                        uint32_t* n_rds, uint32_t flags);
 
+/* RE-TUNING a running broadcast receiver: new channel taps and rotations between two calls, the streams kept running.
+ * sdrfm_bcast_tune is a restart of every stream; this call is what a drift correction, or the replacement of one station among many, uses.
+ *
+ * The re-tune takes effect between two calls, on the handle's stream: every call enqueued before it runs with the old tuning and every
+ * call after it with the new one.  It WAITS for the handle's stream, as sdrfm_bcast_tune does, before it replaces the taps; the transform
+ * of the carried state is then enqueued on that stream and the call returns.  It copies all four arrays before it returns.
+ * It changes neither the input phase, nor the audio and RDS decimator phases, nor hist_x (the raw input history), nor any sink.
+ *
+ * Let rot_old[s] be the stream's current rotation, 0 on an untuned handle.  An untuned handle may be re-tuned; it becomes a tuned one.
+ * The carried state has the same three kinds in both forms (the tuning section above).  Per stream:
+ *   restart[s] != 0   the stream's hist_x, yprev and hist_d become 0, and nothing else changes.  This is the definition's stream whose
+ *                     earlier x were all 0.0f: y = 0 gives d = 0, which K3 already defines.  The phases stay where they are, because they
+ *                     belong to the handle.
+ *   restart[s] == 0   all fp32, each operation rounded on its own except the fmaf's:
+ *     yprev    if (cr, ci) is bitwise (1.0f, +0.0f), it is untouched.  Otherwise
+ *                  t = yi*ci;  yr' = fmaf(yr, cr, -t);  u = yi*cr;  yi' = fmaf(yr, ci, u).
+ *     hist_d   sh = rot_old - rot_new, then the tuning section's single wrap: sh -= 2 pi if sh > pi, else sh += 2 pi if sh < -pi, with
+ *              that section's two constants.  If sh == 0.0f, hist_d is untouched.  Otherwise hist_d[i] = hist_d[i] + sh for all H
+ *              entries.  The entries may then lie outside [-pi, pi]; they are history for FIR chains only.
+ *     The two "untouched" rules are part of the definition.  They make the identity re-tune an exact no-op, signs of zero included.
+ *     The transform is mechanical.  A re-tune before a stream's first d shifts the zeros of its hist_d; for that case use
+ *     sdrfm_bcast_tune or restart[s] = 1.
+ * Two re-tunes with no call between them compose: the carry is applied twice and the shifts add.
+ * sdrfm_bcast_reset keeps the new tuning.  Whether the metered call takes the handle is decided again, as sdrfm_bcast_tune decides it.
+ *
+ * From the re-tune on, y[m] of a kept stream is bit for bit y[m] of a stream that had the new taps all along (hist_x holds raw x and the
+ * tuned y carries no oscillator phase), so d[m] is from the second d on, and L, R and bb are once their windows have passed the switch.
+ *
+ * The intended values, evaluated in float64 and rounded once as everywhere in this library (the library computes no trigonometry):
+ * ctaps and rot as sdrfm_bcast_tune's for the new offsets, and
+ *     carry = exp(+j 2 pi (f_new - f_old) (T - 1) / 2 / fs)
+ * — the phase by which the moved low-pass's y differs for a signal inside both passbands, for a symmetric h under the tuning section's
+ * convention (tap k multiplies x[n - k]).  carry == NULL is (1, 0) everywhere; restart == NULL keeps every stream.
+ *
+ * SDRFM_EINVAL, with nothing changed and nothing enqueued: NULL handle, ctaps or rot (un-tuning stays sdrfm_bcast_tune's job);
+ * non-finite ctaps, rot or carry; |rot| > pi; unknown flags; a restart byte above 1.
+ * flags: SDRFM_TUNE_SHARED_INPUT or 0, as sdrfm_bcast_tune's — the setting is replaced, not kept. */
+int  sdrfm_bcast_retune(sdrfm_bcast_t* h, const float* ctaps /* n_streams x 2T */, const float* rot /* n_streams */,
+                        const float* carry /* n_streams x 2 (cr, ci), or NULL */, const uint8_t* restart /* n_streams, or NULL */,
+                        uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,7 @@ class BroadcastDemod:
         c.max_bytes_per_call, c.device = cfg.max_bytes_per_call, cfg.device
         c.flags = CFG_FORCE_GENERIC if cfg.force_generic else 0
         self._shared_input = False
+        self._untuned()
         self._h = C.c_void_p()
         st = self._lib.sdrfm_bcast_create(C.byref(c), C.byref(self._h))
         if st != _l.OK:
@@ -82,16 +83,18 @@ class BroadcastDemod:
     def reset(self):
         self._ck(self._lib.sdrfm_bcast_reset(self._h), "sdrfm_bcast_reset")
 
-    def tune(self, offsets_hz=None, fs=2.4e6, shared_input=False, ctaps=None, rot=None):
-        """sdrfm_bcast_tune (DESIGN.md §4.12): stream s receives the station at offsets_hz[s] of its input (taps.tuned_channel_taps of
-        the handle's fir_coeffs and taps.tuned_rotation at fs), or the caller's own ctaps [n_streams, 2T] and rot [n_streams];
-        shared_input: every stream reads row 0 of the input.  No argument at all returns the handle to the untuned kernels.  The carried
-        state is zeroed either way."""
+    def _untuned(self):
+        """what the handle remembers of its tuning: the offsets of its last tune / retune (0 on an untuned handle, None after raw ctaps), the
+        fs they were given at, and the taps and rotations themselves (None on an untuned handle: (h, 0) and 0)"""
+        self._offsets_hz, self._fs, self._ctaps, self._rot = np.zeros(self.cfg.n_streams, np.float64), 2.4e6, None, None
+
+    def _tuning(self, offsets_hz, fs, ctaps, rot):
+        """(offsets [n_streams] or None, ctaps [n_streams, 2T], rot [n_streams]) of tune's and retune's arguments"""
         from .taps import tuned_channel_taps, tuned_rotation
-        ns = self.cfg.n_streams
+        ns, off = self.cfg.n_streams, None
         if offsets_hz is not None:
             assert ctaps is None and rot is None, "offsets_hz or ctaps / rot, not both"
-            off = np.broadcast_to(np.asarray(offsets_hz, dtype=np.float64), (ns,))
+            off = np.array(np.broadcast_to(np.asarray(offsets_hz, dtype=np.float64), (ns,)))
             ctaps = np.stack([tuned_channel_taps(self._hc, f, fs) for f in off])
             rot = np.array([tuned_rotation(f, fs, self.cfg.fir_decim) for f in off], dtype=np.float32)
         if ctaps is not None:
@@ -100,9 +103,66 @@ class BroadcastDemod:
         if rot is not None:
             rot = np.ascontiguousarray(rot, dtype=np.float32)
             assert rot.size == ns, (rot.shape, ns)
+        return off, ctaps, rot
+
+    def tune(self, offsets_hz=None, fs=2.4e6, shared_input=False, ctaps=None, rot=None):
+        """sdrfm_bcast_tune (DESIGN.md §4.12): stream s receives the station at offsets_hz[s] of its input (taps.tuned_channel_taps of
+        the handle's fir_coeffs and taps.tuned_rotation at fs), or the caller's own ctaps [n_streams, 2T] and rot [n_streams];
+        shared_input: every stream reads row 0 of the input.  No argument at all returns the handle to the untuned kernels.  The carried
+        state is zeroed either way."""
+        off, ctaps, rot = self._tuning(offsets_hz, fs, ctaps, rot)
         self._ck(self._lib.sdrfm_bcast_tune(self._h, ctaps.ctypes.data if ctaps is not None else None, rot.ctypes.data if rot is not None else None,
                                             _l.TUNE_SHARED_INPUT if shared_input else 0), "sdrfm_bcast_tune")
         self._shared_input = bool(shared_input) and ctaps is not None
+        if ctaps is None:
+            self._untuned()
+        else:
+            self._offsets_hz, self._fs, self._ctaps, self._rot = off, float(fs), ctaps.reshape(self.cfg.n_streams, -1).copy(), rot.reshape(-1).copy()
+
+    def retune(self, offsets_hz=None, fs=2.4e6, restart=None, shared_input=None, ctaps=None, rot=None, carry=None):
+        """sdrfm_bcast_retune: new taps and rotations between two calls, the streams kept running — offsets_hz at fs as
+        tune takes them, or the caller's own ctaps and rot.  restart: [n_streams] of 0 / 1, the streams whose state is zeroed (None: none).
+        carry: [n_streams, 2] (cr, ci); None with offsets_hz on a handle that remembers its offsets: taps.retune_carry of the old and the
+        new offset per stream; None otherwise: (1, 0).  shared_input=None keeps the current setting.  An untuned handle becomes a tuned one."""
+        from .taps import retune_carry
+        ns = self.cfg.n_streams
+        off, ctaps, rot = self._tuning(offsets_hz, fs, ctaps, rot)
+        if carry is None and off is not None and self._offsets_hz is not None:
+            carry = np.stack([retune_carry(o, n, self._hc.size, fs) for o, n in zip(self._offsets_hz, off)])
+        if carry is not None:
+            carry = np.ascontiguousarray(carry, dtype=np.float32)
+            assert carry.size == 2 * ns, (carry.shape, ns)
+        if restart is not None:
+            restart = np.ascontiguousarray(np.broadcast_to(np.asarray(restart), (ns,)), dtype=np.uint8)
+        shared = self._shared_input if shared_input is None else bool(shared_input)
+        self._ck(self._lib.sdrfm_bcast_retune(self._h, ctaps.ctypes.data if ctaps is not None else None, rot.ctypes.data if rot is not None else None,
+                                              carry.ctypes.data if carry is not None else None, restart.ctypes.data if restart is not None else None,
+                                              _l.TUNE_SHARED_INPUT if shared else 0), "sdrfm_bcast_retune")
+        self._shared_input = shared
+        self._offsets_hz, self._fs, self._ctaps, self._rot = off, float(fs), ctaps.reshape(ns, -1).copy(), rot.reshape(-1).copy()
+
+    def follow(self, status, deadband_hz=200.0):
+        """One drift correction of a running receiver: status is scan.stream_status' list of this handle's streams.  The
+        streams scan.follow_selection picks — present, and more than deadband_hz from their tuned offset — are re-tuned to their offset_hz with
+        their state kept; the others keep their taps bit for bit and get carry (1, 0).  Returns the list of stream indexes it moved."""
+        from .scan import follow_selection
+        from .taps import retune_carry, tuned_channel_taps, tuned_rotation
+        assert self._offsets_hz is not None, "the handle was last tuned with raw ctaps: it does not know its offsets"
+        ns, fs = self.cfg.n_streams, self._fs
+        moved, new = follow_selection(status, self._offsets_hz, deadband_hz)
+        if not moved:
+            return moved
+        if self._ctaps is None:                                      # an untuned handle: (h, 0) and rot 0
+            ctaps, rot = np.stack([tuned_channel_taps(self._hc, 0.0, fs)] * ns), np.zeros(ns, np.float32)
+        else:
+            ctaps, rot = self._ctaps.copy(), self._rot.copy()
+        carry = np.tile(np.array([1.0, 0.0], np.float32), (ns, 1))
+        for s in moved:
+            ctaps[s], rot[s] = tuned_channel_taps(self._hc, new[s], fs), tuned_rotation(new[s], fs, self.cfg.fir_decim)
+            carry[s] = retune_carry(self._offsets_hz[s], new[s], self._hc.size, fs)
+        self.retune(fs=fs, ctaps=ctaps, rot=rot, carry=carry)
+        self._offsets_hz = new
+        return moved
 
     def counts(self, nbytes):
         """(audio outputs per channel, complex RDS outputs) per stream of the NEXT call of nbytes"""

@@ -22,6 +22,10 @@
  * A metered call (sdrfm_bcast_process_batch_metered) launches the fifth template argument's form of either: the same walk
  * and the same outputs, and every new d besides handed to sdrfm_meter.h's meter stage where its y, the d itself and the q of the pilot
  * window that ends at it are in LDS and registers anyway — the scan handle's record of the stream, from the launch that receives it.
+ *
+ * A re-tune (sdrfm_bcast_retune) replaces the taps and rotations between two calls and keeps the streams running:
+ * k_bcast_retune rewrites the current set of the carried state in place — the carried y turned by the caller's carry, the carried d's
+ * re-referenced to the new rotation, or all three kinds zeroed for a stream that restarts — and k_bcast is not touched.
  */
 #include <new>
 
@@ -160,6 +164,38 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   front_hand_over(p, w);
 }
 
+// ---- the re-tune's transform of the carried state.  One record per stream, made by the host: what to do and with what
+struct RetuneOp {
+  float cr, ci;                // the carry: yprev' = yprev (cr + j ci)
+  float sh;                    // the shift: hist_d' = hist_d + sh (rot_old - rot_new, wrapped once)
+  uint32_t mode;               // RT_*
+};
+constexpr uint32_t RT_RESTART = 1, RT_CARRY = 2, RT_SHIFT = 4;
+constexpr uint32_t RT_STREAMS = PF_THREADS / 64;               // streams per workgroup: a wave each
+
+// in place on the current state set: per stream one float2, H floats and, for a restart, T - 1 float2's
+__global__ void __launch_bounds__(PF_THREADS) k_bcast_retune(const RetuneOp* ops, float2* hist_x, float2* yprev, float* hist_d, uint32_t ns, uint32_t T,
+                                                             uint32_t H) {
+  const uint32_t s = blockIdx.x * RT_STREAMS + threadIdx.x / 64, ln = threadIdx.x & 63;
+  if (s >= ns) return;
+  const RetuneOp op = ops[s];
+  float2* hx = hist_x + (size_t)s * (T - 1);
+  float* hd = hist_d + (size_t)s * H;
+  if (op.mode & RT_RESTART) {                                   // the stream whose earlier x were all 0
+    for (uint32_t k = ln; k + 1 < T; k += 64) hx[k] = make_float2(0.0f, 0.0f);
+    for (uint32_t k = ln; k < H; k += 64) hd[k] = 0.0f;
+    if (ln == 0) yprev[s] = make_float2(0.0f, 0.0f);
+    return;
+  }
+  if ((op.mode & RT_CARRY) && ln == 0) {
+    const float2 y = yprev[s];
+    const float t = y.y * op.ci, u = y.y * op.cr;                // (the TU is built with -ffp-contract=off: two rounded products)
+    yprev[s] = make_float2(__builtin_fmaf(y.x, op.cr, -t), __builtin_fmaf(y.x, op.ci, u));
+  }
+  if (op.mode & RT_SHIFT)
+    for (uint32_t k = ln; k < H; k += 64) hd[k] = hd[k] + op.sh;
+}
+
 }  // namespace
 
 // =================================================================================================================
@@ -185,6 +221,10 @@ struct sdrfm_bcast {
   char kernel_name_tuned[112];
   float* d_ctaps = nullptr;                    // [ns][2T]
   float* d_rot = nullptr;                      // [ns]
+  float* rot_host = nullptr;                   // [ns]: the rotations the device holds, 0 on an untuned handle (a re-tune's rot_old)
+  // the re-tune (sdrfm_bcast_retune): its per-stream records, the host's and the device's
+  RetuneOp* ops_host = nullptr;
+  RetuneOp* d_ops = nullptr;
   // the metered form (sdrfm_bcast_process_batch_metered): the slots of its kernels, whether the taps keep a record inside int64 — the pilot
   // taps and the untuned channel taps looked at at create, the tuned ones at tune
   uint32_t slots_metered = 1, slots_tuned_metered = 1;
@@ -224,7 +264,8 @@ void bcast_free(sdrfm_bcast* h) {
   front_free(h->f);
   decim_free(h->au); decim_free(h->rd);
   (void)hipFree(h->d_left); (void)hipFree(h->d_right); (void)hipFree(h->d_bb);
-  (void)hipFree(h->d_ctaps); (void)hipFree(h->d_rot); (void)hipFree(h->d_meters);
+  (void)hipFree(h->d_ctaps); (void)hipFree(h->d_rot); (void)hipFree(h->d_meters); (void)hipFree(h->d_ops);
+  free(h->rot_host); free(h->ops_host);
   delete h;
 }
 
@@ -265,10 +306,13 @@ int sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out) {
   const size_t audio_bytes = sizeof(float) * h->d_audio_stride * ns;
   if (hipMalloc(&h->d_left, audio_bytes) != hipSuccess || hipMalloc(&h->d_right, audio_bytes) != hipSuccess ||
       hipMalloc(&h->d_bb, sizeof(float) * h->d_bb_stride * ns) != hipSuccess ||
-      hipMalloc(&h->d_meters, sizeof(sdrfm_scan_meter) * ns) != hipSuccess) {
+      hipMalloc(&h->d_meters, sizeof(sdrfm_scan_meter) * ns) != hipSuccess || hipMalloc(&h->d_ops, sizeof(RetuneOp) * ns) != hipSuccess) {
     bcast_free(h);
     return SDRFM_ENOMEM;
   }
+  h->rot_host = (float*)calloc(ns, sizeof(float));
+  h->ops_host = (RetuneOp*)malloc(sizeof(RetuneOp) * ns);
+  if (!h->rot_host || !h->ops_host) { bcast_free(h); return SDRFM_ENOMEM; }
   h->step = front_step(bcast_lds, 64, 10, 101, bcast_tg(Ta, Tr), H, PF_FAST_NY, PF_FAST_NY - 1);
   h->fast = !(cfg->flags & SDRFM_BCAST_CFG_FORCE_GENERIC) && T == 64 && D == 10 && P == 101 && h->step.lds <= PF_LDS_BUDGET;
   if (!h->fast) h->step = front_step_generic(bcast_lds, T, D, P, bcast_tg(Ta, Tr), H);
@@ -530,6 +574,7 @@ int sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uin
     const int rc = sdrfm_bcast_reset(h);                         // (waits for the handle's stream: no launch reads the taps any more)
     if (rc != SDRFM_OK) return rc;
     h->tuned = h->shared_input = h->meter_ok_tuned = false;
+    memset(h->rot_host, 0, sizeof(float) * ns);
     return SDRFM_OK;
   }
   if (!finite_all(ctaps, ns * 2 * T) || !finite_all(rot, ns)) return SDRFM_EINVAL;
@@ -551,7 +596,58 @@ int sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uin
   h->tuned = true;
   h->shared_input = (flags & SDRFM_TUNE_SHARED_INPUT) != 0;
   h->meter_ok_tuned = meter_taps_ok(ctaps, ns, 2 * T, METER_MAX_CTAP_SUM) && meter_taps_ok(h->f.bc, 1, 2 * h->f.P, METER_MAX_PTAP_SUM);
+  memcpy(h->rot_host, rot, sizeof(float) * ns);
   return sdrfm_bcast_reset(h);
+}
+
+// the taps and rotations replaced between two calls, the streams kept running.  Every check comes before any device work;
+// like sdrfm_bcast_tune the call waits for the handle's stream before it replaces the taps a launch may still read, then enqueues the
+// transform of the carried state and returns
+int sdrfm_bcast_retune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, const float* carry, const uint8_t* restart, uint32_t flags) {
+  if (!h || !ctaps || !rot) return SDRFM_EINVAL;
+  if (flags & ~SDRFM_TUNE_SHARED_INPUT) return SDRFM_EINVAL;
+  const uint32_t ns = h->cfg.n_streams, T = h->f.T, H = h->f.H;
+  if (!finite_all(ctaps, ns * 2 * T) || !finite_all(rot, ns) || (carry && !finite_all(carry, 2 * ns))) return SDRFM_EINVAL;
+  for (uint32_t s = 0; s < ns; ++s)
+    if (std::fabs(rot[s]) > 0x1.921fb6p+1f || (restart && restart[s] > 1)) return SDRFM_EINVAL;
+  if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
+  if (!h->d_ctaps) {
+    float *dc = nullptr, *dr = nullptr;
+    if (hipMalloc(&dc, sizeof(float) * ns * 2 * T) != hipSuccess || hipMalloc(&dr, sizeof(float) * ns) != hipSuccess) {
+      (void)hipFree(dc);
+      return SDRFM_ENOMEM;
+    }
+    h->d_ctaps = dc; h->d_rot = dr;
+  }
+  uint32_t any = 0;
+  for (uint32_t s = 0; s < ns; ++s) {
+    RetuneOp& op = h->ops_host[s];
+    op.cr = carry ? carry[2 * s] : 1.0f;
+    op.ci = carry ? carry[2 * s + 1] : 0.0f;
+    float sh = h->rot_host[s] - rot[s];
+    if (sh > 0x1.921fb6p+1f) sh -= 0x1.921fb6p+2f;
+    else if (sh < -0x1.921fb6p+1f) sh += 0x1.921fb6p+2f;
+    op.sh = sh;
+    const bool identity = op.cr == 1.0f && op.ci == 0.0f && !std::signbit(op.ci);   // bitwise (1.0f, +0.0f)
+    op.mode = (restart && restart[s]) ? RT_RESTART : ((identity ? 0u : RT_CARRY) | (sh == 0.0f ? 0u : RT_SHIFT));
+    any |= op.mode;
+  }
+  if (hipStreamSynchronize(h->f.stream) != hipSuccess) return SDRFM_FAIL;   // no launch still reads the taps about to be replaced
+  if (hipMemcpy(h->d_ctaps, ctaps, sizeof(float) * ns * 2 * T, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(h->d_rot, rot, sizeof(float) * ns, hipMemcpyHostToDevice) != hipSuccess)
+    return SDRFM_FAIL;
+  if (any) {                                                     // (the identity re-tune launches nothing)
+    if (hipMemcpy(h->d_ops, h->ops_host, sizeof(RetuneOp) * ns, hipMemcpyHostToDevice) != hipSuccess) return SDRFM_FAIL;
+    const int c = h->f.cur;
+    k_bcast_retune<<<dim3((ns + RT_STREAMS - 1) / RT_STREAMS), dim3(PF_THREADS), 0, h->f.stream>>>(h->d_ops, h->f.d_hist_x[c], h->f.d_yprev[c],
+                                                                                                 h->f.d_hist_d[c], ns, T, H);
+    if (hipGetLastError() != hipSuccess) return SDRFM_FAIL;
+  }
+  h->tuned = true;
+  h->shared_input = (flags & SDRFM_TUNE_SHARED_INPUT) != 0;
+  h->meter_ok_tuned = meter_taps_ok(ctaps, ns, 2 * T, METER_MAX_CTAP_SUM) && meter_taps_ok(h->f.bc, 1, 2 * h->f.P, METER_MAX_PTAP_SUM);
+  memcpy(h->rot_host, rot, sizeof(float) * ns);
+  return SDRFM_OK;
 }
 
 }  // extern "C"

@@ -218,6 +218,22 @@ def stream_status(report, offsets_hz, max_dev_rms_hz=MAX_DEV_RMS_HZ, max_steadin
     return status
 
 
+def follow_selection(status, tuned_hz, deadband_hz=200.0):
+    """Which streams of a tuned receiver a drift correction moves (BroadcastDemod.follow): status is stream_status' list,
+    tuned_hz the offsets the streams are tuned to.  A stream moves iff it is present and its offset_hz lies more than deadband_hz from its
+    tuned offset; an absent stream never moves.  Returns (the stream indexes that move, the new offsets: offset_hz of those, the tuned
+    offset as it is of the others)."""
+    tuned = np.atleast_1d(np.asarray(tuned_hz, np.float64))
+    assert len(status) == tuned.size, (len(status), tuned.size)
+    new, moved = tuned.copy(), []
+    for st in status:
+        s = int(st["stream"])
+        if st["present"] and abs(float(st["offset_hz"]) - tuned[s]) > deadband_hz:
+            new[s] = float(st["offset_hz"])
+            moved.append(s)
+    return moved, new
+
+
 def scan_grid(fs, grid_hz=100e3, span_hz=None):
     """the candidate offsets of scan_capture: the multiples of grid_hz within +-span_hz (fs / 2 less one grid step by default)"""
     span = fs / 2 - grid_hz if span_hz is None else float(span_hz)

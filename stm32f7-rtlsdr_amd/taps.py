@@ -78,6 +78,14 @@ def tuned_rotation(offset_hz, fs, D):
     return np.float32(min(max(v, -pi_f), pi_f))
 
 
+def retune_carry(old_hz, new_hz, T, fs):
+    """The carry of a re-tune from old_hz to new_hz (sdrfm_bcast_retune's carry): exp(+j 2 pi (new - old) (T - 1) / 2 / fs)
+    in float64, rounded once — the phase by which the moved low-pass's y differs for a signal inside both passbands, for the symmetric h of
+    lowpass_taps under tuned_channel_taps' convention (tap k multiplies x[n - k]).  Returns float32 [2]: (cr, ci)."""
+    c = np.exp(1j * 2.0 * np.pi * (float(new_hz) - float(old_hz)) * (int(T) - 1) / 2.0 / float(fs))
+    return np.array([c.real, c.imag], dtype=np.float32)
+
+
 def pilot_gain(D, fs, f_pilot=19e3):
     """H_D(f_pilot), the gain of the discriminator's D-sample boxcar at the pilot (the H_D of stereo_diff_gain; 0.98982 at D = 10,
     2.4 MS/s): a pilot of deviation v Hz has |q| = 2 pi v D / fs * H_D, which is how sdrfm_scan_report turns pilot_rms_rad into Hz."""
