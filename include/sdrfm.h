@@ -796,6 +796,45 @@ int  sdrfm_bcast_retune(sdrfm_bcast_t* h, const float* ctaps /* n_streams x 2T *
                         const float* carry /* n_streams x 2 (cr, ci), or NULL */, const uint8_t* restart /* n_streams, or NULL */,
                         uint32_t flags);
 
+/* CONDITIONING the audio of a running broadcast receiver: a per-stream stereo blend and a per-stream output gain, applied
+ * inside the handle's own launch where L and R are formed, both ramped per audio output so that a change never clicks.  The host sets them
+ * from what the metered call's records say: blend a weak stereo station towards mono, mute a stream whose station has gone.
+ *
+ * State.  Per stream two integers in [0, 32768] (Q15, 32768 = 1.0): the blend b and the gain v, each with a target bt, vt; one handle-wide
+ * slew in 1 .. 32768, the units either moves per audio output.  A handle is created with b = bt = v = vt = 32768.
+ *
+ * Ramp.  With b0 the blend at the last sdrfm_bcast_set_audio and J the audio outputs of the calls since then, output j (0-based) of the
+ * next call uses
+ *     k    = min(J + j + 1, cdiv(|bt - b0|, slew))
+ *     b[j] = b0 + sgn(bt - b0) * min(k * slew, |bt - b0|)
+ * — "move towards the target by at most slew per output" in closed form, in integers (k * slew < 65536), and so the same for any cut of a
+ * capture into calls; v[j] likewise.  The ramp is evaluated from these values, not from carried device state.
+ *
+ * Audio.  With am and as exactly the two chains' results of the stereo section (sum and difference channel of output j), all fp32:
+ *     beta = (float)b[j] * 2^-15,  mu = (float)v[j] * 2^-15        (exact)
+ *     t = beta * as                                                (one rounding; never contracted into the sums below)
+ *     L[j] = mu * (am + t),   R[j] = mu * (am - t)                 (each sum and each product rounded once)
+ * beta = mu = 1 gives the plain kernels' bits; beta = 0 gives L == R == mu * am; a power-of-two beta is a plain handle whose diff_gain is
+ * scaled by it; a power-of-two mu scales L and R exactly.  bb, pilot_count, the metered call's records, both decimator phases and all
+ * carried state are untouched.  Every plain, PCM and metered call form works on a conditioned handle: the PCM forms sink the conditioned
+ * L and R.
+ *
+ * sdrfm_bcast_set_audio WAITS for the handle's stream, as sdrfm_bcast_tune does; it moves b0, v0 to the values the ramps have reached,
+ * takes the new targets (a NULL array keeps that kind's targets) and the new slew, sets J = 0 and takes effect with the next call.  From
+ * then on the handle launches the blended forms of its kernels and sdrfm_bcast_kernel_name ends in " blend".  A slew of 32768 is a jump:
+ * the next output is at its target.  sdrfm_bcast_set_audio(h, NULL, NULL, 0) returns the handle to the plain kernels, their name and their
+ * bits: b = bt = v = vt = 32768.
+ * sdrfm_bcast_reset and sdrfm_bcast_tune keep the settings and complete the ramps (b = bt, v = vt); sdrfm_bcast_retune leaves them running.
+ * SDRFM_EINVAL, with nothing changed and before the device is touched: a NULL handle; a value above 32768; a slew of 0 with a non-NULL
+ * array; a slew above 32768.
+ *
+ * sdrfm_bcast_get_audio gives, per stream, the values the next output starts from (b and v after the J outputs so far) and the targets;
+ * each array holds n_streams entries and any may be NULL.  It touches no device. */
+int  sdrfm_bcast_set_audio(sdrfm_bcast_t* h, const uint16_t* blend_q15 /* n_streams, or NULL: targets kept */,
+                           const uint16_t* gain_q15 /* n_streams, or NULL: targets kept */, uint32_t slew_q15);
+int  sdrfm_bcast_get_audio(const sdrfm_bcast_t* h, uint16_t* blend_q15, uint16_t* gain_q15, uint16_t* blend_target_q15,
+                           uint16_t* gain_target_q15 /* any may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ from .demod import FmDemod, FmConfig
 from .wbfm import WbfmDemod, WbfmConfig
 from .stereo import StereoDemod, StereoConfig
 from .bcast import BroadcastDemod, BroadcastConfig
-from .scan import ScanDemod, ScanConfig, METER_DTYPE, meter_add, meter_report, find_stations, stream_status, follow_selection, scan_grid, scan_capture
+from .scan import ScanDemod, ScanConfig, METER_DTYPE, meter_add, meter_report, find_stations, stream_status, follow_selection, scan_grid, scan_capture, pilot_snr_db, audio_policy
 from .rds import RdsDemod, RdsConfig, RdsSync, RdsGroup, rds_parse, rds_encode_groups, rds_checkword, rds_group_bits
 from .spectrum import SpectrumView, SpectrumConfig, power_db
 from .sink import PcmSink, StereoPcmSink, pcm_deemph_s16_host, pcm_deemph_stereo_s16_host
@@ -30,5 +30,5 @@ __all__ = [
     "rtlsdr_fir16", "lowpass_taps", "default_config", "stereo_pilot_taps", "stereo_diff_gain", "make_iq", "make_iq_stereo", "MODES", "ReplayFrontEnd", "XferState", "fanout",
     "tuned_channel_taps", "tuned_rotation", "make_iq_stations",
     "ScanDemod", "ScanConfig", "METER_DTYPE", "meter_add", "meter_report", "find_stations", "stream_status", "scan_grid", "scan_capture", "pilot_gain",
-    "retune_carry", "follow_selection",
+    "retune_carry", "follow_selection", "pilot_snr_db", "audio_policy",
 ]

@@ -1,7 +1,8 @@
 """BroadcastDemod — Python mirror of the sdrfm_bcast_* C entry points (the broadcast receiver): the stereo handle's L
 and R and the RDS handle's complex baseband of the same streams from one kernel launch, bit for bit what StereoDemod and RdsDemod give.
 The metered calls add the scan handle's record of every stream from that launch: scan.meter_add, scan.meter_report and
-scan.stream_status read it."""
+scan.stream_status read it.  set_audio / clear_audio / audio_state / condition give every stream a stereo blend and an output
+gain, ramped per audio output inside the launch; scan.audio_policy makes them from the records."""
 import ctypes as C
 from dataclasses import dataclass
 
@@ -163,6 +164,50 @@ class BroadcastDemod:
         self.retune(fs=fs, ctaps=ctaps, rot=rot, carry=carry)
         self._offsets_hz = new
         return moved
+
+    def _q15(self, v, what):
+        """None, or floats in [0, 1] / Q15 ints in [0, 32768] (one value or one per stream) -> uint16 [n_streams]; what a uint16 cannot
+        hold is refused here with the C call's status, a value above 32768 that it can hold by the C call itself"""
+        if v is None:
+            return None
+        a = np.array(np.broadcast_to(np.asarray(v), (self.cfg.n_streams,)))
+        q = np.rint(a * 32768.0) if a.dtype.kind == "f" else a.astype(np.int64)
+        if not np.all(np.isfinite(q)) or q.min() < 0 or q.max() > 65535:
+            raise _l.SdrfmError(_l.EINVAL, "sdrfm_bcast_set_audio: %s outside [0, 1]" % what)
+        return np.ascontiguousarray(q, dtype=np.uint16)
+
+    def set_audio(self, blend=None, gain=None, ramp_ms=50.0):
+        """sdrfm_bcast_set_audio: per-stream stereo blend (1 = full stereo, 0 = mono) and output gain (0 = muted), floats
+        in [0, 1] or Q15 ints in [0, 32768], one value or one per stream; None keeps that kind's targets.  Both move to their targets
+        over ramp_ms of audio at most (a full-scale change takes that long): slew = max(1, ceil(32768 / (ramp_ms audio rate / 1000))) with
+        the audio rate 2.4 MS/s / (fir_decim audio_decim), or the rate of the last tune; ramp_ms = 0 is a jump."""
+        b, g = self._q15(blend, "blend"), self._q15(gain, "gain")
+        rate = self._fs / (self.cfg.fir_decim * self.cfg.audio_decim)
+        n = float(ramp_ms) * rate / 1000.0
+        if not n >= 0.0:
+            raise _l.SdrfmError(_l.EINVAL, "sdrfm_bcast_set_audio: ramp_ms")
+        slew = 32768 if n <= 1.0 else max(1, int(np.ceil(32768.0 / n)))
+        self._ck(self._lib.sdrfm_bcast_set_audio(self._h, b.ctypes.data if b is not None else None, g.ctypes.data if g is not None else None, slew),
+                 "sdrfm_bcast_set_audio")
+        return slew
+
+    def clear_audio(self):
+        """back to the plain kernels, their name and their bits: blend = gain = 1"""
+        self._ck(self._lib.sdrfm_bcast_set_audio(self._h, None, None, 0), "sdrfm_bcast_set_audio")
+
+    def audio_state(self):
+        """sdrfm_bcast_get_audio: dict of uint16 [n_streams] arrays — blend, gain (what the next output starts from), blend_target, gain_target"""
+        out = {k: np.zeros(self.cfg.n_streams, np.uint16) for k in ("blend", "gain", "blend_target", "gain_target")}
+        self._ck(self._lib.sdrfm_bcast_get_audio(self._h, *(out[k].ctypes.data for k in ("blend", "gain", "blend_target", "gain_target"))),
+                 "sdrfm_bcast_get_audio")
+        return out
+
+    def condition(self, report, status, ramp_ms=50.0, **policy):
+        """set_audio(*scan.audio_policy(report, status, **policy), ramp_ms): the blend and gain the records ask for.  Returns (blend, gain)."""
+        from .scan import audio_policy
+        blend, gain = audio_policy(report, status, **policy)
+        self.set_audio(blend, gain, ramp_ms)
+        return blend, gain
 
     def counts(self, nbytes):
         """(audio outputs per channel, complex RDS outputs) per stream of the NEXT call of nbytes"""

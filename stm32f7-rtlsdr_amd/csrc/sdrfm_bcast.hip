@@ -26,6 +26,10 @@
  * A re-tune (sdrfm_bcast_retune) replaces the taps and rotations between two calls and keeps the streams running:
  * k_bcast_retune rewrites the current set of the carried state in place — the carried y turned by the caller's carry, the carried d's
  * re-referenced to the new rotation, or all three kinds zeroed for a stream that restarts — and k_bcast is not touched.
+ *
+ * A conditioned handle (sdrfm_bcast_set_audio) launches the sixth template argument's form of any of those: the same walk,
+ * carriers and chains, and where L and R are formed the stream's stereo blend and output gain, both ramped per audio output by
+ * sdrfm_audio_ctl.h's closed form from one small record per stream — values, not carried state, so nothing new is handed over.
  */
 #include <new>
 
@@ -53,6 +57,8 @@ struct BcastParams : FrontParams {
   const float* ctaps;          // tuned: [ns][2T], (hr[k], hi[k]) pairs
   const float* rot;            // tuned: [ns]
   unsigned long long* meters;  // metered: [ns][8], sdrfm_scan_meter as eight 64-bit words, zeroed before the launch
+  const AudioCtlRec* actl;     // blended: [ns], the streams' ramps
+  uint32_t slew, J;            // blended: the ramps' units per audio output, the audio outputs between the set and this call
 };
 
 // how many of a workgroup's nw waves take a step's nc RDS chains (of Tr links), the others taking its na audio outputs (of 2 Ta links):
@@ -66,7 +72,7 @@ __device__ __forceinline__ int bcast_rds_waves(int nw, int nc, int Tr, int na, i
   return wr;
 }
 
-template <int FT, int FD, int FP, bool TU, bool ME = false>
+template <int FT, int FD, int FP, bool TU, bool ME = false, bool BL = false>
 __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t T = FT > 0 ? FT : p.T, P = FT > 0 ? FP : p.P;
@@ -100,6 +106,12 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   const float* ds = w.ds;
   rds_taps_to_lds(grs, p.gr, Tr, tid, nthr);
   for (int k = tid; k < (int)Ta; k += nthr) gas[k] = p.ga[k];
+  AudioBlend bl;                                                // blended: the stream's ramps
+  if constexpr (BL) {
+    bl.rec = p.actl[s];
+    bl.slew = p.slew;
+    bl.J = p.J;
+  }
   uint32_t cnt = 0;
   MeterAcc acc;                                                 // metered: the lane's sums, and the gate's count in place of cnt
 
@@ -147,8 +159,8 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
       const int wa0 = wr < nw ? wr : 0, wa = nw - wa0;            // the audio waves: [wa0, nw)
       if (wv < wr) rds_chains(zs, grs, Tr, Dr, ZP, p.f0r, a, jr.x, njr, wr, wv, ln, p.bb + (size_t)s * p.bb_stride);
       if (wv >= wa0)                                              // one output per lane of the waves that take them
-        audio_outputs(ds, ss, gas, Ta, Da, p.f0a, a, H, Dl, ja.x + (wv - wa0) * 64 + ln, 64 * wa, ja.y, p.left + (size_t)s * p.audio_stride,
-                      p.right + (size_t)s * p.audio_stride);
+        audio_outputs<BL>(ds, ss, gas, Ta, Da, p.f0a, a, H, Dl, ja.x + (wv - wa0) * 64 + ln, 64 * wa, ja.y, p.left + (size_t)s * p.audio_stride,
+                          p.right + (size_t)s * p.audio_stride, &bl);
       rds_tail_save(zb, zs, n, Tr, ZP, tid, nthr);                // the tails, for the next step
       for (int k = tid; k < (int)Ta - 1; k += nthr) sb[k] = ss[n + k];
     }
@@ -230,6 +242,14 @@ struct sdrfm_bcast {
   uint32_t slots_metered = 1, slots_tuned_metered = 1;
   bool meter_ok = false, meter_ok_tuned = false;
   sdrfm_scan_meter* d_meters = nullptr;        // host-buffer calls: the records [ns]
+  // the conditioned form (sdrfm_bcast_set_audio): the streams' ramps on the host and, from the first set on, on the device; the handle's
+  // slew and the audio outputs since the last set (saturated); the slots and names of its kernels, [tuned][metered] and [tuned]
+  bool blend = false;
+  AudioCtlRec* actl_host = nullptr;
+  AudioCtlRec* d_actl = nullptr;
+  uint32_t slew = SDRFM_ACTL_ONE, J = SDRFM_ACTL_J_MAX;
+  uint32_t slots_blend[2][2] = {{1, 1}, {1, 1}};
+  char kernel_name_blend[2][120];
 };
 
 namespace {
@@ -252,20 +272,29 @@ size_t bcast_lds_tuned(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t
   return bcast_lds(T, D, P, Tg, H, NY, NDT, region_words) + 4 * (size_t)T;
 }
 
-// the launch of one of the eight kernels
-template <bool TU, bool ME>
+// the launch of one of the sixteen kernels
+template <bool TU, bool ME, bool BL>
 void bcast_launch(bool fast, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const BcastParams& p) {
-  if (fast) k_bcast<64, 10, 101, TU, ME><<<grid, block, lds, stream>>>(p);
-  else k_bcast<0, 0, 0, TU, ME><<<grid, block, lds, stream>>>(p);
+  if (fast) k_bcast<64, 10, 101, TU, ME, BL><<<grid, block, lds, stream>>>(p);
+  else k_bcast<0, 0, 0, TU, ME, BL><<<grid, block, lds, stream>>>(p);
 }
+
+template <bool TU, bool ME>
+void bcast_launch(bool blend, bool fast, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const BcastParams& p) {
+  if (blend) bcast_launch<TU, ME, true>(fast, grid, block, lds, stream, p);
+  else bcast_launch<TU, ME, false>(fast, grid, block, lds, stream, p);
+}
+
+// every ramp at its target: what a restart of the streams leaves of the conditioning (the settings stay)
+void bcast_ramps_complete(sdrfm_bcast* h) { h->J = SDRFM_ACTL_J_MAX; }
 
 void bcast_free(sdrfm_bcast* h) {
   if (!h) return;
   front_free(h->f);
   decim_free(h->au); decim_free(h->rd);
   (void)hipFree(h->d_left); (void)hipFree(h->d_right); (void)hipFree(h->d_bb);
-  (void)hipFree(h->d_ctaps); (void)hipFree(h->d_rot); (void)hipFree(h->d_meters); (void)hipFree(h->d_ops);
-  free(h->rot_host); free(h->ops_host);
+  (void)hipFree(h->d_ctaps); (void)hipFree(h->d_rot); (void)hipFree(h->d_meters); (void)hipFree(h->d_ops); (void)hipFree(h->d_actl);
+  free(h->rot_host); free(h->ops_host); free(h->actl_host);
   delete h;
 }
 
@@ -312,7 +341,9 @@ int sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out) {
   }
   h->rot_host = (float*)calloc(ns, sizeof(float));
   h->ops_host = (RetuneOp*)malloc(sizeof(RetuneOp) * ns);
-  if (!h->rot_host || !h->ops_host) { bcast_free(h); return SDRFM_ENOMEM; }
+  h->actl_host = (AudioCtlRec*)malloc(sizeof(AudioCtlRec) * ns);
+  if (!h->rot_host || !h->ops_host || !h->actl_host) { bcast_free(h); return SDRFM_ENOMEM; }
+  for (size_t s = 0; s < ns; ++s) h->actl_host[s] = AudioCtlRec{SDRFM_ACTL_ONE, SDRFM_ACTL_ONE, SDRFM_ACTL_ONE, SDRFM_ACTL_ONE};
   h->step = front_step(bcast_lds, 64, 10, 101, bcast_tg(Ta, Tr), H, PF_FAST_NY, PF_FAST_NY - 1);
   h->fast = !(cfg->flags & SDRFM_BCAST_CFG_FORCE_GENERIC) && T == 64 && D == 10 && P == 101 && h->step.lds <= PF_LDS_BUDGET;
   if (!h->fast) h->step = front_step_generic(bcast_lds, T, D, P, bcast_tg(Ta, Tr), H);
@@ -327,6 +358,12 @@ int sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out) {
   h->slots_tuned = front_slots(k_bcast<64, 10, 101, true>, k_bcast<0, 0, 0, true>, h->fast_tuned, h->step_tuned.lds, prop);
   h->slots_metered = front_slots(k_bcast<64, 10, 101, false, true>, k_bcast<0, 0, 0, false, true>, h->fast, h->step.lds, prop);
   h->slots_tuned_metered = front_slots(k_bcast<64, 10, 101, true, true>, k_bcast<0, 0, 0, true, true>, h->fast_tuned, h->step_tuned.lds, prop);
+  h->slots_blend[0][0] = front_slots(k_bcast<64, 10, 101, false, false, true>, k_bcast<0, 0, 0, false, false, true>, h->fast, h->step.lds, prop);
+  h->slots_blend[0][1] = front_slots(k_bcast<64, 10, 101, false, true, true>, k_bcast<0, 0, 0, false, true, true>, h->fast, h->step.lds, prop);
+  h->slots_blend[1][0] = front_slots(k_bcast<64, 10, 101, true, false, true>, k_bcast<0, 0, 0, true, false, true>, h->fast_tuned, h->step_tuned.lds, prop);
+  h->slots_blend[1][1] = front_slots(k_bcast<64, 10, 101, true, true, true>, k_bcast<0, 0, 0, true, true, true>, h->fast_tuned, h->step_tuned.lds, prop);
+  snprintf(h->kernel_name_blend[0], sizeof h->kernel_name_blend[0], "%s blend", h->kernel_name);
+  snprintf(h->kernel_name_blend[1], sizeof h->kernel_name_blend[1], "%s blend", h->kernel_name_tuned);
   h->meter_ok = meter_taps_ok(h->f.hc, 1, T, METER_MAX_CTAP_SUM) && meter_taps_ok(h->f.bc, 1, 2 * P, METER_MAX_PTAP_SUM);
   rc = sdrfm_bcast_reset(h);
   if (rc != SDRFM_OK) { bcast_free(h); return rc; }
@@ -347,6 +384,7 @@ int sdrfm_bcast_reset(sdrfm_bcast_t* h) {
   if (rc != SDRFM_OK) return rc;
   decim_reset(h->au);
   decim_reset(h->rd);
+  bcast_ramps_complete(h);
   return SDRFM_OK;
 }
 
@@ -390,23 +428,26 @@ static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, 
   p.f0r = decim_f0(h->rd);
   p.zplane = rds_zplane(p.Tr, p.NDT);
   p.meters = reinterpret_cast<unsigned long long*>(d_meters);
-  const uint32_t slots = d_meters ? (h->tuned ? h->slots_tuned_metered : h->slots_metered) : (h->tuned ? h->slots_tuned : h->slots);
+  p.actl = h->d_actl; p.slew = h->slew; p.J = h->J;
+  const uint32_t slots = h->blend ? h->slots_blend[h->tuned ? 1 : 0][d_meters ? 1 : 0]
+                                  : d_meters ? (h->tuned ? h->slots_tuned_metered : h->slots_metered) : (h->tuned ? h->slots_tuned : h->slots);
   p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, slots);   // as the RDS handle chooses them
   p.span = M ? (M + p.blocks_per_stream - 1) / p.blocks_per_stream : 0;
   if (front_zero_count(h->f, d_pc, true) != SDRFM_OK) return SDRFM_FAIL;
   if (d_meters && hipMemsetAsync(d_meters, 0, sizeof(sdrfm_scan_meter) * ns, h->f.stream) != hipSuccess) return SDRFM_FAIL;
   const dim3 grid(ns * p.blocks_per_stream), block(PF_THREADS);
   if (h->tuned) {
-    if (d_meters) bcast_launch<true, true>(h->fast_tuned, grid, block, step.lds, h->f.stream, p);
-    else bcast_launch<true, false>(h->fast_tuned, grid, block, step.lds, h->f.stream, p);
+    if (d_meters) bcast_launch<true, true>(h->blend, h->fast_tuned, grid, block, step.lds, h->f.stream, p);
+    else bcast_launch<true, false>(h->blend, h->fast_tuned, grid, block, step.lds, h->f.stream, p);
   } else {
-    if (d_meters) bcast_launch<false, true>(h->fast, grid, block, step.lds, h->f.stream, p);
-    else bcast_launch<false, false>(h->fast, grid, block, step.lds, h->f.stream, p);
+    if (d_meters) bcast_launch<false, true>(h->blend, h->fast, grid, block, step.lds, h->f.stream, p);
+    else bcast_launch<false, false>(h->blend, h->fast, grid, block, step.lds, h->f.stream, p);
   }
   if (hipGetLastError() != hipSuccess) return SDRFM_FAIL;
   front_advance(h->f, p.N);
   decim_advance(h->au, M);
   decim_advance(h->rd, M);
+  h->J = audio_ctl_advance(h->J, Aa);
   *n_audio = Aa;
   *n_rds = Ar;
   return SDRFM_OK;
@@ -562,7 +603,11 @@ int sdrfm_bcast_synchronize(sdrfm_bcast_t* h) {
   return SDRFM_OK;
 }
 
-const char* sdrfm_bcast_kernel_name(const sdrfm_bcast_t* h) { return h ? (h->tuned ? h->kernel_name_tuned : h->kernel_name) : ""; }
+const char* sdrfm_bcast_kernel_name(const sdrfm_bcast_t* h) {
+  if (!h) return "";
+  if (h->blend) return h->kernel_name_blend[h->tuned ? 1 : 0];
+  return h->tuned ? h->kernel_name_tuned : h->kernel_name;
+}
 
 int sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uint32_t flags) {
   if (!h) return SDRFM_EINVAL;
@@ -647,6 +692,48 @@ int sdrfm_bcast_retune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, c
   h->shared_input = (flags & SDRFM_TUNE_SHARED_INPUT) != 0;
   h->meter_ok_tuned = meter_taps_ok(ctaps, ns, 2 * T, METER_MAX_CTAP_SUM) && meter_taps_ok(h->f.bc, 1, 2 * h->f.P, METER_MAX_PTAP_SUM);
   memcpy(h->rot_host, rot, sizeof(float) * ns);
+  return SDRFM_OK;
+}
+
+// the streams' stereo blend and output gain.  Every check comes before any device work; like sdrfm_bcast_tune the call
+// waits for the handle's stream before it replaces the records a launch may still read
+int sdrfm_bcast_set_audio(sdrfm_bcast_t* h, const uint16_t* blend_q15, const uint16_t* gain_q15, uint32_t slew_q15) {
+  if (!h) return SDRFM_EINVAL;
+  if (slew_q15 > SDRFM_ACTL_ONE) return SDRFM_EINVAL;
+  if (!slew_q15 && (blend_q15 || gain_q15)) return SDRFM_EINVAL;
+  const uint32_t ns = h->cfg.n_streams;
+  for (uint32_t s = 0; s < ns; ++s)
+    if ((blend_q15 && blend_q15[s] > SDRFM_ACTL_ONE) || (gain_q15 && gain_q15[s] > SDRFM_ACTL_ONE)) return SDRFM_EINVAL;
+  if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
+  if (!slew_q15) {                                               // back to the plain kernels: b = v = 1, nothing to ramp
+    if (hipStreamSynchronize(h->f.stream) != hipSuccess) return SDRFM_FAIL;
+    for (uint32_t s = 0; s < ns; ++s) h->actl_host[s] = AudioCtlRec{SDRFM_ACTL_ONE, SDRFM_ACTL_ONE, SDRFM_ACTL_ONE, SDRFM_ACTL_ONE};
+    h->blend = false;
+    h->slew = SDRFM_ACTL_ONE;
+    bcast_ramps_complete(h);
+    return SDRFM_OK;
+  }
+  if (!h->d_actl && hipMalloc(&h->d_actl, sizeof(AudioCtlRec) * ns) != hipSuccess) return SDRFM_ENOMEM;
+  if (hipStreamSynchronize(h->f.stream) != hipSuccess) return SDRFM_FAIL;   // no launch still reads the records about to be replaced
+  for (uint32_t s = 0; s < ns; ++s)
+    audio_ctl_rebase(&h->actl_host[s], h->slew, h->J, blend_q15 ? blend_q15 + s : nullptr, gain_q15 ? gain_q15 + s : nullptr);
+  h->slew = slew_q15;
+  h->J = 0;
+  h->blend = true;
+  if (hipMemcpy(h->d_actl, h->actl_host, sizeof(AudioCtlRec) * ns, hipMemcpyHostToDevice) != hipSuccess) return SDRFM_FAIL;
+  return SDRFM_OK;
+}
+
+// the values the next output starts from, and the targets; any pointer may be NULL
+int sdrfm_bcast_get_audio(const sdrfm_bcast_t* h, uint16_t* blend_q15, uint16_t* gain_q15, uint16_t* blend_target_q15, uint16_t* gain_target_q15) {
+  if (!h) return SDRFM_EINVAL;
+  for (uint32_t s = 0; s < h->cfg.n_streams; ++s) {
+    const AudioCtlRec& r = h->actl_host[s];
+    if (blend_q15) blend_q15[s] = (uint16_t)audio_ctl_ramp(r.b0, r.bt, h->slew, h->J);
+    if (gain_q15) gain_q15[s] = (uint16_t)audio_ctl_ramp(r.v0, r.vt, h->slew, h->J);
+    if (blend_target_q15) blend_target_q15[s] = (uint16_t)r.bt;
+    if (gain_target_q15) gain_target_q15[s] = (uint16_t)r.vt;
+  }
   return SDRFM_OK;
 }
 

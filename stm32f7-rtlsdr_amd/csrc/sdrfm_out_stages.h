@@ -3,10 +3,13 @@
  * of a decimator belong to a step, the audio chains of sdrfm_stereo.hip and sdrfm_bcast.hip, the RDS chains and the carry of their z's
  * of sdrfm_rds.hip and sdrfm_bcast.hip.  The broadcast kernel's outputs are bit for bit the other two kernels' because these are the
  * same functions.  Where the arrays lie in LDS, which lanes take which outputs and what else is carried is the calling kernel's.
+ * audio_outputs<true> is the broadcast kernel's blended form: the same chains, and L and R formed under the stream's
+ * ramped blend and gain (sdrfm_audio_ctl.h); audio_outputs<> is the code it was.
  */
 #ifndef SDRFM_OUT_STAGES_H
 #define SDRFM_OUT_STAGES_H
 
+#include "sdrfm_audio_ctl.h"
 #include "sdrfm_pilot_front.h"
 
 namespace {
@@ -24,8 +27,28 @@ __device__ __forceinline__ int2 step_outputs(int a, int b, int f0, int D, int A)
 // ---- audio: outputs j0, j0 + stride, ... < jh of the step that starts at d[a]; am on the delayed d, as on s, the taps newest first.
 //      ds = [the H carried d's | the step's], ss[k] = s of d[a - (Ta - 1) + k];
 //      left, right: the stream's rows
+
+// the blended stage's stream: its ramps' record, the handle's slew and the audio outputs between the set and this call's output 0
+struct AudioBlend {
+  AudioCtlRec rec;
+  uint32_t slew, J;
+};
+
+// L and R of one output from its two chains' ends under the ramps' values b and v (Q15): beta = b 2^-15 and mu = v 2^-15 are exact,
+// t = beta as, L = mu (am + t), R = mu (am - t), every product and every sum rounded on its own whatever the translation unit is built with
+__device__ __forceinline__ void audio_blend(float am, float as, uint32_t b, uint32_t v, float& l, float& r) {
+#pragma clang fp contract(off)
+  const float beta = (float)b * 0x1p-15f, mu = (float)v * 0x1p-15f;
+  const float t = beta * as;
+  const float sum = am + t, dif = am - t;
+  l = mu * sum;
+  r = mu * dif;
+}
+
+// BL: the broadcast handle's blended form — the same two chains in the same order, audio_blend behind them
+template <bool BL = false>
 __device__ __forceinline__ void audio_outputs(const float* ds, const float* ss, const float* gas, uint32_t Ta, uint32_t Da, int f0, int a, uint32_t H,
-                                              uint32_t Dl, int j0, int stride, int jh, float* left, float* right) {
+                                              uint32_t Dl, int j0, int stride, int jh, float* left, float* right, const AudioBlend* bl = nullptr) {
   for (int j = j0; j < jh; j += stride) {
     const int nj = f0 + j * (int)Da - a;                         // step-relative index of the newest d of output j
     const float* wd = ds + (int)H + nj - (int)Dl - (int)(Ta - 1);
@@ -36,8 +59,13 @@ __device__ __forceinline__ void audio_outputs(const float* ds, const float* ss, 
       am = __builtin_fmaf(c, wd[k], am);
       as = __builtin_fmaf(c, wsv[k], as);
     }
-    left[j] = am + as;
-    right[j] = am - as;
+    if constexpr (BL) {
+      const uint32_t n = bl->J + (uint32_t)j + 1u;                // outputs since the set, this one included
+      audio_blend(am, as, audio_ctl_ramp(bl->rec.b0, bl->rec.bt, bl->slew, n), audio_ctl_ramp(bl->rec.v0, bl->rec.vt, bl->slew, n), left[j], right[j]);
+    } else {
+      left[j] = am + as;
+      right[j] = am - as;
+    }
   }
 }
 

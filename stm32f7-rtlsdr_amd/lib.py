@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     "sdrfm_stereo_process_batch_pcm", "sdrfm_bcast_process_batch_pcm",
     "sdrfm_scan_create", "sdrfm_scan_destroy", "sdrfm_scan_reset", "sdrfm_scan_tune", "sdrfm_scan_process_batch", "sdrfm_scan_set_stream",
     "sdrfm_scan_synchronize", "sdrfm_scan_kernel_name", "sdrfm_scan_report", "sdrfm_scan_meter_add",
-    "sdrfm_bcast_process_batch_metered", "sdrfm_bcast_retune",
+    "sdrfm_bcast_process_batch_metered", "sdrfm_bcast_retune", "sdrfm_bcast_set_audio", "sdrfm_bcast_get_audio",
 ]
 
 
@@ -388,5 +388,9 @@ def load_library(dev=False):
     lib.sdrfm_bcast_process_batch_metered.restype = C.c_int
     lib.sdrfm_bcast_retune.argtypes = [vp, vp, vp, vp, vp, u32]
     lib.sdrfm_bcast_retune.restype = C.c_int
+    lib.sdrfm_bcast_set_audio.argtypes = [vp, vp, vp, u32]
+    lib.sdrfm_bcast_set_audio.restype = C.c_int
+    lib.sdrfm_bcast_get_audio.argtypes = [vp, vp, vp, vp, vp]
+    lib.sdrfm_bcast_get_audio.restype = C.c_int
     _libs[dev] = lib
     return lib

@@ -234,6 +234,43 @@ def follow_selection(status, tuned_hz, deadband_hz=200.0):
     return moved, new
 
 
+def pilot_snr_db(report):
+    """The pilot's signal-to-noise ratio (dB) in the pilot filter's band, per entry of a meter_report, from pilot_steadiness alone.  The
+    steadiness is E|q|^4 / (E|q|^2)^2 of the pilot filter's output q; for a tone in complex Gaussian noise at power ratio rho it is
+    s = 1 + (2 rho + 1) / (rho + 1)^2 — 1 for the tone alone, 2 for noise alone — and with u = 1 / (rho + 1) that is s = 1 + 2 u - u^2,
+    so u = 1 - sqrt(2 - s) and rho = 1 / u - 1.  s <= 1 gives +inf, s >= 2 (or no steadiness at all) -inf."""
+    s = np.atleast_1d(np.asarray(report["pilot_steadiness"], np.float64))
+    out = np.full(s.shape, -np.inf)
+    out[s <= 1.0] = np.inf
+    mid = (s > 1.0) & (s < 2.0)
+    u = 1.0 - np.sqrt(2.0 - s[mid])
+    out[mid] = 10.0 * np.log10(1.0 / u - 1.0)
+    return out
+
+
+# audio_policy's two corners (dB of pilot_snr_db): full stereo from STEREO_FULL_DB up, mono from STEREO_OFF_DB down.  From the ladder of
+# tools/audio_ladder.py (profiles/audio_ladder.txt): at 24 dB the stereo decoder still costs nothing against mono, at 18 dB it has lost
+STEREO_FULL_DB, STEREO_OFF_DB = 22.0, 12.0
+
+
+def audio_policy(report, status, stereo_full_db=STEREO_FULL_DB, stereo_off_db=STEREO_OFF_DB, mute_absent=True):
+    """What BroadcastDemod.set_audio should be given for the streams of a tuned receiver: report is the meter_report of its records,
+    status stream_status' list of the same streams.  Returns (blend_q15, gain_q15), uint16 [n_streams].  The blend is 0 where the stream is
+    not stereo, else rint(32768 clamp((pilot_snr_db - stereo_off_db) / (stereo_full_db - stereo_off_db), 0, 1)); the gain is 0 where the
+    stream is not present and mute_absent is set, else 32768.  No hysteresis: the ramps of set_audio are what keeps a change smooth."""
+    assert stereo_full_db > stereo_off_db, (stereo_full_db, stereo_off_db)
+    snr = pilot_snr_db(report)
+    assert len(status) == snr.size, (len(status), snr.size)
+    blend, gain = np.zeros(snr.size, np.uint16), np.full(snr.size, 32768, np.uint16)
+    for st in status:
+        s = int(st["stream"])
+        if st["stereo"]:
+            blend[s] = int(np.rint(32768.0 * np.clip((snr[s] - stereo_off_db) / (stereo_full_db - stereo_off_db), 0.0, 1.0)))
+        if mute_absent and not st["present"]:
+            gain[s] = 0
+    return blend, gain
+
+
 def scan_grid(fs, grid_hz=100e3, span_hz=None):
     """the candidate offsets of scan_capture: the multiples of grid_hz within +-span_hz (fs / 2 less one grid step by default)"""
     span = fs / 2 - grid_hz if span_hz is None else float(span_hz)
