@@ -225,89 +225,28 @@ class BroadcastDemod:
     def synchronize(self):
         self._ck(self._lib.sdrfm_bcast_synchronize(self._h), "sdrfm_bcast_synchronize")
 
-    def process_batch(self, iq: np.ndarray):
-        """host memory: iq [n_streams, nbytes] uint8 -> (L, R [n_streams, n_audio] float32, bb [n_streams, n_rds] complex64,
-        pilot_count [n_streams] uint32)"""
-        iq = np.ascontiguousarray(iq, dtype=np.uint8)
-        if iq.ndim == 1:
-            iq = iq[None, :]
-        ns = self.cfg.n_streams
-        assert iq.shape[0] == (1 if self._shared_input else ns)                # (a shared capture is one row)
-        nbytes = iq.shape[1]
-        ca, cr = (max(v, 1) for v in self.counts(nbytes & ~1))
-        left = np.zeros((ns, ca), dtype=np.float32)
-        right = np.zeros_like(left)
-        bb = np.zeros((ns, 2 * cr), dtype=np.float32)
-        pc = np.zeros(ns, dtype=np.uint32)
+    def _entry(self, name, sink, iq, audio, pcm, bb, pc, meters, flags):
+        """one call of the C entry `name` on addresses: iq (address, row stride, nbytes), audio (left, right, row stride), pcm and bb
+        (address, row stride).  Raises SdrfmError with the entry's status, returns (n_audio, n_rds)."""
         na, nr = C.c_uint32(), C.c_uint32()
-        self._ck(self._lib.sdrfm_bcast_process_batch(self._h, iq.ctypes.data, nbytes, nbytes, left.ctypes.data, right.ctypes.data, ca,
-                                                     bb.ctypes.data, 2 * cr, pc.ctypes.data, C.byref(na), C.byref(nr), 0),
-                 "sdrfm_bcast_process_batch")
-        return left[:, : na.value], right[:, : na.value], np.ascontiguousarray(bb[:, : 2 * nr.value]).view(np.complex64), pc
-
-    def process_batch_device(self, iq, left, right, bb, pilot_count=None, nbytes=None):
-        """device tensors: iq uint8 [n_streams, >=nbytes], left / right float32 [n_streams, >= n_audio] (same strides), bb float32
-        [n_streams, >= 2 n_rds] ((re, im) pairs), pilot_count int32 / uint32 [n_streams] or None; enqueue only.  Returns (n_audio, n_rds)."""
-        assert iq.is_cuda and left.is_cuda and right.is_cuda and bb.is_cuda
-        assert left.stride() == right.stride() and left.stride(1) == 1 and bb.stride(1) == 1
-        nbytes = iq.shape[1] if nbytes is None else int(nbytes)
-        pc = C.c_void_p(pilot_count.data_ptr()) if pilot_count is not None else None
-        na, nr = C.c_uint32(), C.c_uint32()
-        self._ck(self._lib.sdrfm_bcast_process_batch(self._h, C.c_void_p(iq.data_ptr()), iq.stride(0), nbytes, C.c_void_p(left.data_ptr()),
-                                                     C.c_void_p(right.data_ptr()), left.stride(0), C.c_void_p(bb.data_ptr()), bb.stride(0),
-                                                     pc, C.byref(na), C.byref(nr), _l.F_DEVICE_PTRS), "sdrfm_bcast_process_batch(device)")
+        front, back, counts = (*iq, *audio), (*bb, pc), (C.byref(na), C.byref(nr), flags)
+        if name == "sdrfm_bcast_process_batch":
+            st = self._lib.sdrfm_bcast_process_batch(self._h, *front, *back, *counts)
+        elif name == "sdrfm_bcast_process_batch_pcm":
+            st = self._lib.sdrfm_bcast_process_batch_pcm(self._h, sink._h, *front, *pcm, *back, *counts)
+        else:
+            st = self._lib.sdrfm_bcast_process_batch_metered(self._h, sink._h if sink is not None else None, *front, *pcm, *back, meters, *counts)
+        self._ck(st, name + ("(device)" if flags else ""))
         return na.value, nr.value
 
-    def process_batch_pcm(self, sink, iq: np.ndarray, with_audio=True):
-        """sdrfm_bcast_process_batch_pcm on host memory: this call and, behind it, `sink` (a StereoPcmSink) over its L and R rows.
-        Returns (L, R, pcm [n_streams, 2 n_audio] int16, bb, pilot_count); with_audio=False passes no audio rows: L and R are None."""
+    def _host_call(self, name, iq, sink=None, with_audio=True):
+        """a host-memory call of the C entry `name`: (L, R, pcm, bb, pilot_count, meters) trimmed to the call's counts, None what the call
+        has not — L and R without with_audio, pcm without a sink, meters of any entry but the metered one"""
         iq = np.ascontiguousarray(iq, dtype=np.uint8)
         if iq.ndim == 1:
             iq = iq[None, :]
         ns = self.cfg.n_streams
         assert iq.shape[0] == (1 if self._shared_input else ns)                # (a shared capture is one row)
-        nbytes = iq.shape[1]
-        ca, cr = (max(v, 1) for v in self.counts(nbytes & ~1))
-        left = np.zeros((ns, ca), dtype=np.float32) if with_audio else None
-        right = np.zeros_like(left) if with_audio else None
-        pcm = np.zeros((ns, 2 * ca), dtype=np.int16)
-        bb = np.zeros((ns, 2 * cr), dtype=np.float32)
-        pc = np.zeros(ns, dtype=np.uint32)
-        na, nr = C.c_uint32(), C.c_uint32()
-        self._ck(self._lib.sdrfm_bcast_process_batch_pcm(self._h, sink._h, iq.ctypes.data, nbytes, nbytes, left.ctypes.data if with_audio else None,
-                                                         right.ctypes.data if with_audio else None, ca, pcm.ctypes.data, 2 * ca, bb.ctypes.data, 2 * cr,
-                                                         pc.ctypes.data, C.byref(na), C.byref(nr), 0), "sdrfm_bcast_process_batch_pcm")
-        bbc = np.ascontiguousarray(bb[:, : 2 * nr.value]).view(np.complex64)
-        if not with_audio:
-            return None, None, pcm[:, : 2 * na.value], bbc, pc
-        return left[:, : na.value], right[:, : na.value], pcm[:, : 2 * na.value], bbc, pc
-
-    def process_batch_pcm_device(self, sink, iq, left, right, pcm, bb, pilot_count=None, nbytes=None):
-        """device tensors as process_batch_device takes them, pcm int16 [n_streams, >= 2 n_audio]; left = right = None: the sink reads the
-        handle's own rows.  Enqueue only, sink included, on this handle's stream.  Returns (n_audio, n_rds)."""
-        assert iq.is_cuda and pcm.is_cuda and bb.is_cuda and pcm.stride(1) == 1 and bb.stride(1) == 1 and (left is None) == (right is None)
-        if left is not None:
-            assert left.is_cuda and right.is_cuda and left.stride() == right.stride() and left.stride(1) == 1
-        nbytes = iq.shape[1] if nbytes is None else int(nbytes)
-        pc = C.c_void_p(pilot_count.data_ptr()) if pilot_count is not None else None
-        lp = C.c_void_p(left.data_ptr()) if left is not None else None
-        rp = C.c_void_p(right.data_ptr()) if right is not None else None
-        na, nr = C.c_uint32(), C.c_uint32()
-        self._ck(self._lib.sdrfm_bcast_process_batch_pcm(self._h, sink._h, C.c_void_p(iq.data_ptr()), iq.stride(0), nbytes, lp, rp,
-                                                         left.stride(0) if left is not None else 0, C.c_void_p(pcm.data_ptr()), pcm.stride(0),
-                                                         C.c_void_p(bb.data_ptr()), bb.stride(0), pc, C.byref(na), C.byref(nr), _l.F_DEVICE_PTRS),
-                 "sdrfm_bcast_process_batch_pcm(device)")
-        return na.value, nr.value
-
-    def process_batch_metered(self, iq: np.ndarray, sink=None, with_audio=True):
-        """sdrfm_bcast_process_batch_metered on host memory: what process_batch (sink=None) or process_batch_pcm(sink, iq, with_audio)
-        returns and, behind it, the streams' records of the same launch: a scan.METER_DTYPE array [n_streams]."""
-        iq = np.ascontiguousarray(iq, dtype=np.uint8)
-        if iq.ndim == 1:
-            iq = iq[None, :]
-        ns = self.cfg.n_streams
-        assert iq.shape[0] == (1 if self._shared_input else ns)                # (a shared capture is one row)
-        assert with_audio or sink is not None, "without a sink the audio rows are all the audio there is"
         nbytes = iq.shape[1]
         ca, cr = (max(v, 1) for v in self.counts(nbytes & ~1))
         left = np.zeros((ns, ca), dtype=np.float32) if with_audio else None
@@ -315,17 +254,54 @@ class BroadcastDemod:
         pcm = np.zeros((ns, 2 * ca), dtype=np.int16) if sink is not None else None
         bb = np.zeros((ns, 2 * cr), dtype=np.float32)
         pc = np.zeros(ns, dtype=np.uint32)
-        meters = np.zeros(ns, dtype=METER_DTYPE)
-        na, nr = C.c_uint32(), C.c_uint32()
-        self._ck(self._lib.sdrfm_bcast_process_batch_metered(
-            self._h, sink._h if sink is not None else None, iq.ctypes.data, nbytes, nbytes, left.ctypes.data if with_audio else None,
-            right.ctypes.data if with_audio else None, ca, pcm.ctypes.data if sink is not None else None, 2 * ca, bb.ctypes.data, 2 * cr,
-            pc.ctypes.data, meters.ctypes.data, C.byref(na), C.byref(nr), 0), "sdrfm_bcast_process_batch_metered")
-        bbc = np.ascontiguousarray(bb[:, : 2 * nr.value]).view(np.complex64)
-        lr = (left[:, : na.value], right[:, : na.value]) if with_audio else (None, None)
-        if sink is None:
-            return lr + (bbc, pc, meters)
-        return lr + (pcm[:, : 2 * na.value], bbc, pc, meters)
+        meters = np.zeros(ns, dtype=METER_DTYPE) if name.endswith("_metered") else None
+        adr = lambda a: a.ctypes.data if a is not None else None
+        na, nr = self._entry(name, sink, (adr(iq), nbytes, nbytes), (adr(left), adr(right), ca), (adr(pcm), 2 * ca), (adr(bb), 2 * cr), adr(pc),
+                             adr(meters), 0)
+        trim = lambda a, n: a[:, :n] if a is not None else None
+        return trim(left, na), trim(right, na), trim(pcm, 2 * na), np.ascontiguousarray(bb[:, : 2 * nr]).view(np.complex64), pc, meters
+
+    def _device_call(self, name, iq, left, right, bb, pilot_count, nbytes, sink=None, pcm=None, meters=None):
+        """a device-tensor call of the C entry `name`, enqueue only: (n_audio, n_rds).  A tensor that is None goes as NULL with stride 0;
+        meters is an address"""
+        adr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        row = lambda t: t.stride(0) if t is not None else 0
+        nbytes = iq.shape[1] if nbytes is None else int(nbytes)
+        return self._entry(name, sink, (adr(iq), iq.stride(0), nbytes), (adr(left), adr(right), row(left)), (adr(pcm), row(pcm)),
+                           (adr(bb), bb.stride(0)), adr(pilot_count), meters, _l.F_DEVICE_PTRS)
+
+    def process_batch(self, iq: np.ndarray):
+        """host memory: iq [n_streams, nbytes] uint8 -> (L, R [n_streams, n_audio] float32, bb [n_streams, n_rds] complex64,
+        pilot_count [n_streams] uint32)"""
+        left, right, _, bb, pc, _ = self._host_call("sdrfm_bcast_process_batch", iq)
+        return left, right, bb, pc
+
+    def process_batch_device(self, iq, left, right, bb, pilot_count=None, nbytes=None):
+        """device tensors: iq uint8 [n_streams, >=nbytes], left / right float32 [n_streams, >= n_audio] (same strides), bb float32
+        [n_streams, >= 2 n_rds] ((re, im) pairs), pilot_count int32 / uint32 [n_streams] or None; enqueue only.  Returns (n_audio, n_rds)."""
+        assert iq.is_cuda and left.is_cuda and right.is_cuda and bb.is_cuda
+        assert left.stride() == right.stride() and left.stride(1) == 1 and bb.stride(1) == 1
+        return self._device_call("sdrfm_bcast_process_batch", iq, left, right, bb, pilot_count, nbytes)
+
+    def process_batch_pcm(self, sink, iq: np.ndarray, with_audio=True):
+        """sdrfm_bcast_process_batch_pcm on host memory: this call and, behind it, `sink` (a StereoPcmSink) over its L and R rows.
+        Returns (L, R, pcm [n_streams, 2 n_audio] int16, bb, pilot_count); with_audio=False passes no audio rows: L and R are None."""
+        return self._host_call("sdrfm_bcast_process_batch_pcm", iq, sink, with_audio)[:5]
+
+    def process_batch_pcm_device(self, sink, iq, left, right, pcm, bb, pilot_count=None, nbytes=None):
+        """device tensors as process_batch_device takes them, pcm int16 [n_streams, >= 2 n_audio]; left = right = None: the sink reads the
+        handle's own rows.  Enqueue only, sink included, on this handle's stream.  Returns (n_audio, n_rds)."""
+        assert iq.is_cuda and pcm.is_cuda and bb.is_cuda and pcm.stride(1) == 1 and bb.stride(1) == 1 and (left is None) == (right is None)
+        if left is not None:
+            assert left.is_cuda and right.is_cuda and left.stride() == right.stride() and left.stride(1) == 1
+        return self._device_call("sdrfm_bcast_process_batch_pcm", iq, left, right, bb, pilot_count, nbytes, sink, pcm)
+
+    def process_batch_metered(self, iq: np.ndarray, sink=None, with_audio=True):
+        """sdrfm_bcast_process_batch_metered on host memory: what process_batch (sink=None) or process_batch_pcm(sink, iq, with_audio)
+        returns and, behind it, the streams' records of the same launch: a scan.METER_DTYPE array [n_streams]."""
+        assert with_audio or sink is not None, "without a sink the audio rows are all the audio there is"
+        out = self._host_call("sdrfm_bcast_process_batch_metered", iq, sink, with_audio)
+        return out if sink is not None else out[:2] + out[3:]
 
     def process_batch_metered_device(self, iq, left, right, bb, meters, pilot_count=None, nbytes=None, sink=None, pcm=None):
         """device tensors as process_batch_device (sink=None: left and right given, no pcm) or process_batch_pcm_device (sink and pcm given;
@@ -342,14 +318,4 @@ class BroadcastDemod:
             mp = C.c_void_p(meters.data_ptr())
         else:
             mp = C.c_void_p(int(meters)) if meters else None
-        nbytes = iq.shape[1] if nbytes is None else int(nbytes)
-        pc = C.c_void_p(pilot_count.data_ptr()) if pilot_count is not None else None
-        lp = C.c_void_p(left.data_ptr()) if left is not None else None
-        rp = C.c_void_p(right.data_ptr()) if right is not None else None
-        na, nr = C.c_uint32(), C.c_uint32()
-        self._ck(self._lib.sdrfm_bcast_process_batch_metered(
-            self._h, sink._h if sink is not None else None, C.c_void_p(iq.data_ptr()), iq.stride(0), nbytes, lp, rp,
-            left.stride(0) if left is not None else 0, C.c_void_p(pcm.data_ptr()) if pcm is not None else None,
-            pcm.stride(0) if pcm is not None else 0, C.c_void_p(bb.data_ptr()), bb.stride(0), pc, mp, C.byref(na), C.byref(nr), _l.F_DEVICE_PTRS),
-            "sdrfm_bcast_process_batch_metered(device)")
-        return na.value, nr.value
+        return self._device_call("sdrfm_bcast_process_batch_metered", iq, left, right, bb, pilot_count, nbytes, sink, pcm, mp)

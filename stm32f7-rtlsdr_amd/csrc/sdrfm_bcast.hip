@@ -212,7 +212,19 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast_retune(const RetuneOp* ops
 
 // =================================================================================================================
 //  Host side: handle, argument checks (all before any device work), launch geometry.  The walk's state is the header's PilotFront.
+//  bcast_kernel names the sixteen instantiations, once; a BcastForm for the untuned and one for the tuned kernels holds what a launch
+//  looks up (step, slots, name); the three process_batch entries are one call path (bcast_batch), tune and retune one installation.
 // =================================================================================================================
+typedef void (*bcast_kernel_fn)(BcastParams);
+
+// what the untuned and the tuned kernels each have of their own
+struct BcastForm {
+  FrontStep step;                              // of the kernels of this form
+  bool fast = false;
+  uint32_t slots[2][2] = {{1, 1}, {1, 1}};     // [metered][blend]: workgroups the device runs at a time (compute units x workgroups per unit)
+  char name[2][120];                           // [blend]
+};
+
 struct sdrfm_bcast {
   sdrfm_bcast_config cfg;                      // taps pointers point at the copies in f and below
   PilotFront f;
@@ -222,34 +234,25 @@ struct sdrfm_bcast {
   size_t d_audio_stride = 0;
   float* d_bb = nullptr;
   size_t d_bb_stride = 0;
-  bool fast = false;
-  FrontStep step;                              // of the kernel this handle launches
-  uint32_t slots = 1;                          // workgroups the device runs at a time (compute units x workgroups per unit)
-  char kernel_name[112];
-  // the tuned form (sdrfm_bcast_tune): its own kernels, step, slots and name; the taps and rotations the handle was last tuned with
-  bool tuned = false, shared_input = false, fast_tuned = false;
-  FrontStep step_tuned;
-  uint32_t slots_tuned = 1;
-  char kernel_name_tuned[112];
+  BcastForm form[2];                           // [tuned]
+  // the tuned form (sdrfm_bcast_tune): the taps and rotations the handle was last tuned with
+  bool tuned = false, shared_input = false;
   float* d_ctaps = nullptr;                    // [ns][2T]
   float* d_rot = nullptr;                      // [ns]
   float* rot_host = nullptr;                   // [ns]: the rotations the device holds, 0 on an untuned handle (a re-tune's rot_old)
   // the re-tune (sdrfm_bcast_retune): its per-stream records, the host's and the device's
   RetuneOp* ops_host = nullptr;
   RetuneOp* d_ops = nullptr;
-  // the metered form (sdrfm_bcast_process_batch_metered): the slots of its kernels, whether the taps keep a record inside int64 — the pilot
-  // taps and the untuned channel taps looked at at create, the tuned ones at tune
-  uint32_t slots_metered = 1, slots_tuned_metered = 1;
+  // the metered form (sdrfm_bcast_process_batch_metered): whether the taps keep a record inside int64 — the pilot taps and the untuned
+  // channel taps looked at at create, the tuned ones at tune
   bool meter_ok = false, meter_ok_tuned = false;
   sdrfm_scan_meter* d_meters = nullptr;        // host-buffer calls: the records [ns]
   // the conditioned form (sdrfm_bcast_set_audio): the streams' ramps on the host and, from the first set on, on the device; the handle's
-  // slew and the audio outputs since the last set (saturated); the slots and names of its kernels, [tuned][metered] and [tuned]
+  // slew and the audio outputs since the last set (saturated)
   bool blend = false;
   AudioCtlRec* actl_host = nullptr;
   AudioCtlRec* d_actl = nullptr;
   uint32_t slew = SDRFM_ACTL_ONE, J = SDRFM_ACTL_J_MAX;
-  uint32_t slots_blend[2][2] = {{1, 1}, {1, 1}};
-  char kernel_name_blend[2][120];
 };
 
 namespace {
@@ -272,17 +275,18 @@ size_t bcast_lds_tuned(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t
   return bcast_lds(T, D, P, Tg, H, NY, NDT, region_words) + 4 * (size_t)T;
 }
 
-// the launch of one of the sixteen kernels
-template <bool TU, bool ME, bool BL>
-void bcast_launch(bool fast, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const BcastParams& p) {
-  if (fast) k_bcast<64, 10, 101, TU, ME, BL><<<grid, block, lds, stream>>>(p);
-  else k_bcast<0, 0, 0, TU, ME, BL><<<grid, block, lds, stream>>>(p);
-}
-
-template <bool TU, bool ME>
-void bcast_launch(bool blend, bool fast, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const BcastParams& p) {
-  if (blend) bcast_launch<TU, ME, true>(fast, grid, block, lds, stream, p);
-  else bcast_launch<TU, ME, false>(fast, grid, block, lds, stream, p);
+// the sixteen kernels
+bcast_kernel_fn bcast_kernel(bool fast, bool tuned, bool metered, bool blend) {
+  static const bcast_kernel_fn k[2][2][2][2] = {                 // [tuned][metered][blend][fast]
+      {{{k_bcast<0, 0, 0, false, false, false>, k_bcast<64, 10, 101, false, false, false>},
+        {k_bcast<0, 0, 0, false, false, true>, k_bcast<64, 10, 101, false, false, true>}},
+       {{k_bcast<0, 0, 0, false, true, false>, k_bcast<64, 10, 101, false, true, false>},
+        {k_bcast<0, 0, 0, false, true, true>, k_bcast<64, 10, 101, false, true, true>}}},
+      {{{k_bcast<0, 0, 0, true, false, false>, k_bcast<64, 10, 101, true, false, false>},
+        {k_bcast<0, 0, 0, true, false, true>, k_bcast<64, 10, 101, true, false, true>}},
+       {{k_bcast<0, 0, 0, true, true, false>, k_bcast<64, 10, 101, true, true, false>},
+        {k_bcast<0, 0, 0, true, true, true>, k_bcast<64, 10, 101, true, true, true>}}}};
+  return k[tuned][metered][blend][fast];
 }
 
 // every ramp at its target: what a restart of the streams leaves of the conditioning (the settings stay)
@@ -344,26 +348,18 @@ int sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out) {
   h->actl_host = (AudioCtlRec*)malloc(sizeof(AudioCtlRec) * ns);
   if (!h->rot_host || !h->ops_host || !h->actl_host) { bcast_free(h); return SDRFM_ENOMEM; }
   for (size_t s = 0; s < ns; ++s) h->actl_host[s] = AudioCtlRec{SDRFM_ACTL_ONE, SDRFM_ACTL_ONE, SDRFM_ACTL_ONE, SDRFM_ACTL_ONE};
-  h->step = front_step(bcast_lds, 64, 10, 101, bcast_tg(Ta, Tr), H, PF_FAST_NY, PF_FAST_NY - 1);
-  h->fast = !(cfg->flags & SDRFM_BCAST_CFG_FORCE_GENERIC) && T == 64 && D == 10 && P == 101 && h->step.lds <= PF_LDS_BUDGET;
-  if (!h->fast) h->step = front_step_generic(bcast_lds, T, D, P, bcast_tg(Ta, Tr), H);
-  if (h->fast) snprintf(h->kernel_name, sizeof h->kernel_name, "bcast-fast T64 D10 P101 Ta%u Da%u Tr%u Dr%u", Ta, Da, Tr, Dr);
-  else snprintf(h->kernel_name, sizeof h->kernel_name, "bcast-generic T%u D%u P%u Ta%u Da%u Tr%u Dr%u", T, D, P, Ta, Da, Tr, Dr);
-  h->slots = front_slots(k_bcast<64, 10, 101, false>, k_bcast<0, 0, 0, false>, h->fast, h->step.lds, prop);
-  h->step_tuned = front_step(bcast_lds_tuned, 64, 10, 101, bcast_tg(Ta, Tr), H, PF_FAST_NY, PF_FAST_NY - 1);
-  h->fast_tuned = !(cfg->flags & SDRFM_BCAST_CFG_FORCE_GENERIC) && T == 64 && D == 10 && P == 101 && h->step_tuned.lds <= PF_LDS_BUDGET;
-  if (!h->fast_tuned) h->step_tuned = front_step_generic(bcast_lds_tuned, T, D, P, bcast_tg(Ta, Tr), H);
-  if (h->fast_tuned) snprintf(h->kernel_name_tuned, sizeof h->kernel_name_tuned, "bcast-fast-tuned T64 D10 P101 Ta%u Da%u Tr%u Dr%u", Ta, Da, Tr, Dr);
-  else snprintf(h->kernel_name_tuned, sizeof h->kernel_name_tuned, "bcast-generic-tuned T%u D%u P%u Ta%u Da%u Tr%u Dr%u", T, D, P, Ta, Da, Tr, Dr);
-  h->slots_tuned = front_slots(k_bcast<64, 10, 101, true>, k_bcast<0, 0, 0, true>, h->fast_tuned, h->step_tuned.lds, prop);
-  h->slots_metered = front_slots(k_bcast<64, 10, 101, false, true>, k_bcast<0, 0, 0, false, true>, h->fast, h->step.lds, prop);
-  h->slots_tuned_metered = front_slots(k_bcast<64, 10, 101, true, true>, k_bcast<0, 0, 0, true, true>, h->fast_tuned, h->step_tuned.lds, prop);
-  h->slots_blend[0][0] = front_slots(k_bcast<64, 10, 101, false, false, true>, k_bcast<0, 0, 0, false, false, true>, h->fast, h->step.lds, prop);
-  h->slots_blend[0][1] = front_slots(k_bcast<64, 10, 101, false, true, true>, k_bcast<0, 0, 0, false, true, true>, h->fast, h->step.lds, prop);
-  h->slots_blend[1][0] = front_slots(k_bcast<64, 10, 101, true, false, true>, k_bcast<0, 0, 0, true, false, true>, h->fast_tuned, h->step_tuned.lds, prop);
-  h->slots_blend[1][1] = front_slots(k_bcast<64, 10, 101, true, true, true>, k_bcast<0, 0, 0, true, true, true>, h->fast_tuned, h->step_tuned.lds, prop);
-  snprintf(h->kernel_name_blend[0], sizeof h->kernel_name_blend[0], "%s blend", h->kernel_name);
-  snprintf(h->kernel_name_blend[1], sizeof h->kernel_name_blend[1], "%s blend", h->kernel_name_tuned);
+  for (int tu = 0; tu < 2; ++tu) {
+    BcastForm& f = h->form[tu];
+    const front_lds_fn lds = tu ? bcast_lds_tuned : bcast_lds;
+    f.step = front_step(lds, 64, 10, 101, bcast_tg(Ta, Tr), H, PF_FAST_NY, PF_FAST_NY - 1);
+    f.fast = !(cfg->flags & SDRFM_BCAST_CFG_FORCE_GENERIC) && T == 64 && D == 10 && P == 101 && f.step.lds <= PF_LDS_BUDGET;
+    if (!f.fast) f.step = front_step_generic(lds, T, D, P, bcast_tg(Ta, Tr), H);
+    snprintf(f.name[0], sizeof f.name[0], "bcast-%s%s T%u D%u P%u Ta%u Da%u Tr%u Dr%u", f.fast ? "fast" : "generic", tu ? "-tuned" : "", T, D, P, Ta,
+             Da, Tr, Dr);
+    snprintf(f.name[1], sizeof f.name[1], "%s blend", f.name[0]);
+    for (int me = 0; me < 2; ++me)
+      for (int bl = 0; bl < 2; ++bl) f.slots[me][bl] = front_slots(bcast_kernel(f.fast, tu, me, bl), f.step.lds, prop);
+  }
   h->meter_ok = meter_taps_ok(h->f.hc, 1, T, METER_MAX_CTAP_SUM) && meter_taps_ok(h->f.bc, 1, 2 * P, METER_MAX_PTAP_SUM);
   rc = sdrfm_bcast_reset(h);
   if (rc != SDRFM_OK) { bcast_free(h); return rc; }
@@ -409,7 +405,8 @@ static int bcast_stage_in(const sdrfm_bcast* h, const uint8_t* iq, size_t iq_str
 static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, float* d_left, float* d_right, size_t audio_stride,
                          float* d_bb, size_t bb_stride, uint32_t* d_pc, sdrfm_scan_meter* d_meters, uint32_t* n_audio, uint32_t* n_rds) {
   const uint32_t ns = h->cfg.n_streams;
-  const FrontStep& step = h->tuned ? h->step_tuned : h->step;
+  const BcastForm& form = h->form[h->tuned];
+  const FrontStep& step = form.step;
   if (step.lds > PF_LDS_BUDGET) return SDRFM_FAIL;               // (no shape within the header's limits gets here: NY = 2 fits them all)
   BcastParams p;
   memset(&p, 0, sizeof p);
@@ -429,20 +426,14 @@ static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, 
   p.zplane = rds_zplane(p.Tr, p.NDT);
   p.meters = reinterpret_cast<unsigned long long*>(d_meters);
   p.actl = h->d_actl; p.slew = h->slew; p.J = h->J;
-  const uint32_t slots = h->blend ? h->slots_blend[h->tuned ? 1 : 0][d_meters ? 1 : 0]
-                                  : d_meters ? (h->tuned ? h->slots_tuned_metered : h->slots_metered) : (h->tuned ? h->slots_tuned : h->slots);
-  p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, slots);   // as the RDS handle chooses them
+  const bool metered = d_meters != nullptr;
+  p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, form.slots[metered][h->blend]);   // as the RDS handle chooses them
   p.span = M ? (M + p.blocks_per_stream - 1) / p.blocks_per_stream : 0;
   if (front_zero_count(h->f, d_pc, true) != SDRFM_OK) return SDRFM_FAIL;
   if (d_meters && hipMemsetAsync(d_meters, 0, sizeof(sdrfm_scan_meter) * ns, h->f.stream) != hipSuccess) return SDRFM_FAIL;
   const dim3 grid(ns * p.blocks_per_stream), block(PF_THREADS);
-  if (h->tuned) {
-    if (d_meters) bcast_launch<true, true>(h->blend, h->fast_tuned, grid, block, step.lds, h->f.stream, p);
-    else bcast_launch<true, false>(h->blend, h->fast_tuned, grid, block, step.lds, h->f.stream, p);
-  } else {
-    if (d_meters) bcast_launch<false, true>(h->blend, h->fast, grid, block, step.lds, h->f.stream, p);
-    else bcast_launch<false, false>(h->blend, h->fast, grid, block, step.lds, h->f.stream, p);
-  }
+  const bcast_kernel_fn kernel = bcast_kernel(form.fast, h->tuned, metered, h->blend);
+  kernel<<<grid, block, step.lds, h->f.stream>>>(p);
   if (hipGetLastError() != hipSuccess) return SDRFM_FAIL;
   front_advance(h->f, p.N);
   decim_advance(h->au, M);
@@ -475,15 +466,23 @@ static int bcast_meters_back(const sdrfm_bcast* h, sdrfm_scan_meter* meters) {
   return e == hipSuccess ? SDRFM_OK : SDRFM_FAIL;
 }
 
-// sdrfm_bcast_process_batch, and with `meters` the metered call of its form: the same checks in the same order, the same launch geometry
-static int bcast_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left, float* right, size_t audio_stride,
-                       float* bb, size_t bb_stride, uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* n_audio, uint32_t* n_rds,
-                       uint32_t flags) {
+// the three process_batch entries.  sink == nullptr: the plain call.  With a sink, behind the launch on the handle's stream the stereo sink's
+// default kernel over this call's L and R rows, which are the handle's own where the caller gives none.  With `meters` the
+// metered call of either form: the same checks in the same order, the same launch geometry
+static int bcast_batch(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left,
+                       float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride, uint32_t* pilot_count,
+                       sdrfm_scan_meter* meters, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
   if (!h || !n_audio || !n_rds) return SDRFM_EINVAL;
   if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;       // SDRFM_F_OVERLAP: not for this handle
+  if (sink && !left != !right) return SDRFM_EINVAL;            // both, or neither: the sink then reads the handle's own rows
   if (nbytes & 1u) return SDRFM_EODD;
   if (nbytes > bcast_max_bytes(h, meters != nullptr)) return SDRFM_ECAPACITY;
   const uint32_t ns = h->cfg.n_streams;
+  const bool dev = (flags & SDRFM_F_DEVICE_PTRS) != 0;
+  uint32_t Aa = 0, Ar = 0;
+  (void)sdrfm_bcast_counts(h, nbytes, &Aa, &Ar);
+  int rc = sink ? sdrfm_stereo_sink_check(sink, h->f.device, ns, Aa, pcm, pcm_stride, dev) : SDRFM_OK;
+  if (rc != SDRFM_OK) return rc;
   if (nbytes == 0) {
     *n_audio = 0;
     *n_rds = 0;
@@ -491,22 +490,34 @@ static int bcast_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_stride, ui
   }
   if (!iq) return SDRFM_EINVAL;
   if (ns > 1 && !bcast_shared(h) && iq_stride < nbytes) return SDRFM_ECAPACITY;
-  uint32_t Aa = 0, Ar = 0;
-  (void)sdrfm_bcast_counts(h, nbytes, &Aa, &Ar);
-  if (Aa && (!left || !right)) return SDRFM_EINVAL;
+  if (!sink && Aa && (!left || !right)) return SDRFM_EINVAL;
   if (Ar && !bb) return SDRFM_EINVAL;
-  if (ns > 1 && (audio_stride < Aa || bb_stride < 2 * (size_t)Ar)) return SDRFM_ECAPACITY;
+  if (ns > 1 && ((left && audio_stride < Aa) || bb_stride < 2 * (size_t)Ar)) return SDRFM_ECAPACITY;
   if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
-  if (flags & SDRFM_F_DEVICE_PTRS)
-    return bcast_enqueue(h, iq, iq_stride, nbytes, left, right, audio_stride, bb, bb_stride, pilot_count, meters, n_audio, n_rds);
+  if (dev) {
+    const bool own = sink && !left;
+    float* const l = own ? h->d_left : left;
+    float* const r = own ? h->d_right : right;
+    const size_t as = own ? h->d_audio_stride : audio_stride;
+    rc = bcast_enqueue(h, iq, iq_stride, nbytes, l, r, as, bb, bb_stride, pilot_count, meters, n_audio, n_rds);
+    if (rc != SDRFM_OK || !sink) return rc;
+    return sdrfm_stereo_sink_launch_on(sink, l, r, as, Aa, pcm, pcm_stride, h->f.stream);
+  }
 
-  if (bcast_stage_in(h, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
-  const int rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc,
-                               meters ? h->d_meters : nullptr, n_audio, n_rds);
+  int16_t* d_pcm = nullptr;
+  size_t d_pcm_stride = 0;
+  if (sink) rc = sdrfm_stereo_sink_reserve(sink, Aa, &d_pcm, &d_pcm_stride);   // (before anything is enqueued: a refusal leaves both handles alone)
   if (rc != SDRFM_OK) return rc;
-  if (front_copy_back(h->f, left, audio_stride, h->d_left, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
-  if (front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
+  if (bcast_stage_in(h, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
+  rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc,
+                     meters ? h->d_meters : nullptr, n_audio, n_rds);
+  if (rc != SDRFM_OK) return rc;
+  if (sink) rc = sdrfm_stereo_sink_launch_on(sink, h->d_left, h->d_right, h->d_audio_stride, Aa, d_pcm, d_pcm_stride, h->f.stream);
+  if (rc != SDRFM_OK) return rc;
+  if (left && front_copy_back(h->f, left, audio_stride, h->d_left, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
+  if (left && front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
   if (front_copy_back(h->f, bb, bb_stride, h->d_bb, h->d_bb_stride, 2 * (size_t)Ar) != SDRFM_OK) return SDRFM_FAIL;
+  if (sink && sdrfm_stereo_sink_copy_back(sink, pcm, pcm_stride, Aa, h->f.stream) != SDRFM_OK) return SDRFM_FAIL;
   if (bcast_meters_back(h, meters) != SDRFM_OK) return SDRFM_FAIL;
   return front_finish(h->f, pilot_count);
 }
@@ -514,67 +525,16 @@ static int bcast_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_stride, ui
 int sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left, float* right,
                               size_t audio_stride, float* bb, size_t bb_stride, uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds,
                               uint32_t flags) {
-  return bcast_batch(h, iq, iq_stride, nbytes, left, right, audio_stride, bb, bb_stride, pilot_count, nullptr, n_audio, n_rds, flags);
-}
-
-// the call above and, behind it on the handle's stream, the stereo sink's default kernel over this call's L and R rows;
-// with `meters` the metered call of this form
-static int bcast_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left,
-                           float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride,
-                           uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
-  if (!h || !sink || !n_audio || !n_rds) return SDRFM_EINVAL;
-  if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;
-  if (!left != !right) return SDRFM_EINVAL;                    // both, or neither: the sink then reads the handle's own rows
-  if (nbytes & 1u) return SDRFM_EODD;
-  if (nbytes > bcast_max_bytes(h, meters != nullptr)) return SDRFM_ECAPACITY;
-  const uint32_t ns = h->cfg.n_streams;
-  const bool dev = (flags & SDRFM_F_DEVICE_PTRS) != 0;
-  uint32_t Aa = 0, Ar = 0;
-  (void)sdrfm_bcast_counts(h, nbytes, &Aa, &Ar);
-  int rc = sdrfm_stereo_sink_check(sink, h->f.device, ns, Aa, pcm, pcm_stride, dev);
-  if (rc != SDRFM_OK) return rc;
-  if (nbytes == 0) {
-    *n_audio = 0;
-    *n_rds = 0;
-    return bcast_empty_call(h, pilot_count, meters, flags);
-  }
-  if (!iq) return SDRFM_EINVAL;
-  if (ns > 1 && !bcast_shared(h) && iq_stride < nbytes) return SDRFM_ECAPACITY;
-  if (Ar && !bb) return SDRFM_EINVAL;
-  if (ns > 1 && ((left && audio_stride < Aa) || bb_stride < 2 * (size_t)Ar)) return SDRFM_ECAPACITY;
-  if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
-  if (dev) {
-    float* const l = left ? left : h->d_left;
-    float* const r = left ? right : h->d_right;
-    const size_t as = left ? audio_stride : h->d_audio_stride;
-    rc = bcast_enqueue(h, iq, iq_stride, nbytes, l, r, as, bb, bb_stride, pilot_count, meters, n_audio, n_rds);
-    if (rc != SDRFM_OK) return rc;
-    return sdrfm_stereo_sink_launch_on(sink, l, r, as, Aa, pcm, pcm_stride, h->f.stream);
-  }
-
-  int16_t* d_pcm = nullptr;
-  size_t d_pcm_stride = 0;
-  rc = sdrfm_stereo_sink_reserve(sink, Aa, &d_pcm, &d_pcm_stride);   // (before anything is enqueued: a refusal leaves both handles alone)
-  if (rc != SDRFM_OK) return rc;
-  if (bcast_stage_in(h, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
-  rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc,
-                     meters ? h->d_meters : nullptr, n_audio, n_rds);
-  if (rc != SDRFM_OK) return rc;
-  rc = sdrfm_stereo_sink_launch_on(sink, h->d_left, h->d_right, h->d_audio_stride, Aa, d_pcm, d_pcm_stride, h->f.stream);
-  if (rc != SDRFM_OK) return rc;
-  if (left && front_copy_back(h->f, left, audio_stride, h->d_left, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
-  if (left && front_copy_back(h->f, right, audio_stride, h->d_right, h->d_audio_stride, Aa) != SDRFM_OK) return SDRFM_FAIL;
-  if (front_copy_back(h->f, bb, bb_stride, h->d_bb, h->d_bb_stride, 2 * (size_t)Ar) != SDRFM_OK) return SDRFM_FAIL;
-  if (sdrfm_stereo_sink_copy_back(sink, pcm, pcm_stride, Aa, h->f.stream) != SDRFM_OK) return SDRFM_FAIL;
-  if (bcast_meters_back(h, meters) != SDRFM_OK) return SDRFM_FAIL;
-  return front_finish(h->f, pilot_count);
+  return bcast_batch(h, nullptr, iq, iq_stride, nbytes, left, right, audio_stride, nullptr, 0, bb, bb_stride, pilot_count, nullptr, n_audio, n_rds,
+                     flags);
 }
 
 int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left,
                                   float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride,
                                   uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
-  return bcast_batch_pcm(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, nullptr, n_audio,
-                         n_rds, flags);
+  if (!sink) return SDRFM_EINVAL;                                // (this entry has no plain form)
+  return bcast_batch(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, nullptr, n_audio, n_rds,
+                     flags);
 }
 
 // either call above with the streams' records from the same launch.  What is the metered call's own is refused first:
@@ -586,9 +546,8 @@ int sdrfm_bcast_process_batch_metered(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t*
   if (!sink && pcm) return SDRFM_EINVAL;
   if ((uintptr_t)meters % 8) return SDRFM_EINVAL;
   if (!(h->tuned ? h->meter_ok_tuned : h->meter_ok)) return SDRFM_EINVAL;
-  if (!sink) return bcast_batch(h, iq, iq_stride, nbytes, left, right, audio_stride, bb, bb_stride, pilot_count, meters, n_audio, n_rds, flags);
-  return bcast_batch_pcm(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, meters, n_audio,
-                         n_rds, flags);
+  return bcast_batch(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, meters, n_audio, n_rds,
+                     flags);
 }
 
 int sdrfm_bcast_set_stream(sdrfm_bcast_t* h, void* hip_stream) {
@@ -604,27 +563,22 @@ int sdrfm_bcast_synchronize(sdrfm_bcast_t* h) {
 }
 
 const char* sdrfm_bcast_kernel_name(const sdrfm_bcast_t* h) {
-  if (!h) return "";
-  if (h->blend) return h->kernel_name_blend[h->tuned ? 1 : 0];
-  return h->tuned ? h->kernel_name_tuned : h->kernel_name;
+  return h ? h->form[h->tuned].name[h->blend] : "";
 }
 
-int sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uint32_t flags) {
-  if (!h) return SDRFM_EINVAL;
-  if (!ctaps != !rot) return SDRFM_EINVAL;
-  if (flags & ~SDRFM_TUNE_SHARED_INPUT) return SDRFM_EINVAL;
-  const uint32_t ns = h->cfg.n_streams, T = h->f.T;
-  if (!ctaps) {                                                  // back to the untuned kernels
-    if (flags) return SDRFM_EINVAL;
-    const int rc = sdrfm_bcast_reset(h);                         // (waits for the handle's stream: no launch reads the taps any more)
-    if (rc != SDRFM_OK) return rc;
-    h->tuned = h->shared_input = h->meter_ok_tuned = false;
-    memset(h->rot_host, 0, sizeof(float) * ns);
-    return SDRFM_OK;
-  }
-  if (!finite_all(ctaps, ns * 2 * T) || !finite_all(rot, ns)) return SDRFM_EINVAL;
+// sdrfm_bcast_tune's and sdrfm_bcast_retune's taps and rotations: all finite, every rotation within [-pi, pi]
+static bool bcast_tuning_ok(const sdrfm_bcast* h, const float* ctaps, const float* rot) {
+  const uint32_t ns = h->cfg.n_streams;
+  if (!finite_all(ctaps, ns * 2 * h->f.T) || !finite_all(rot, ns)) return false;
   for (uint32_t s = 0; s < ns; ++s)
-    if (std::fabs(rot[s]) > 0x1.921fb6p+1f) return SDRFM_EINVAL;
+    if (std::fabs(rot[s]) > 0x1.921fb6p+1f) return false;
+  return true;
+}
+
+// checked taps and rotations -> the device (allocated at the first tuning) and the handle's record of its tuning.  Waits for the handle's
+// stream: no launch still reads the taps about to be replaced.  The carried state is the caller's to reset or to transform
+static int bcast_install_tuning(sdrfm_bcast* h, const float* ctaps, const float* rot, uint32_t flags) {
+  const uint32_t ns = h->cfg.n_streams, T = h->f.T;
   if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
   if (!h->d_ctaps) {
     float *dc = nullptr, *dr = nullptr;
@@ -634,7 +588,7 @@ int sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uin
     }
     h->d_ctaps = dc; h->d_rot = dr;
   }
-  if (hipStreamSynchronize(h->f.stream) != hipSuccess) return SDRFM_FAIL;   // no launch still reads the taps about to be replaced
+  if (hipStreamSynchronize(h->f.stream) != hipSuccess) return SDRFM_FAIL;
   if (hipMemcpy(h->d_ctaps, ctaps, sizeof(float) * ns * 2 * T, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(h->d_rot, rot, sizeof(float) * ns, hipMemcpyHostToDevice) != hipSuccess)
     return SDRFM_FAIL;
@@ -642,7 +596,24 @@ int sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uin
   h->shared_input = (flags & SDRFM_TUNE_SHARED_INPUT) != 0;
   h->meter_ok_tuned = meter_taps_ok(ctaps, ns, 2 * T, METER_MAX_CTAP_SUM) && meter_taps_ok(h->f.bc, 1, 2 * h->f.P, METER_MAX_PTAP_SUM);
   memcpy(h->rot_host, rot, sizeof(float) * ns);
-  return sdrfm_bcast_reset(h);
+  return SDRFM_OK;
+}
+
+int sdrfm_bcast_tune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, uint32_t flags) {
+  if (!h) return SDRFM_EINVAL;
+  if (!ctaps != !rot) return SDRFM_EINVAL;
+  if (flags & ~SDRFM_TUNE_SHARED_INPUT) return SDRFM_EINVAL;
+  if (!ctaps) {                                                  // back to the untuned kernels
+    if (flags) return SDRFM_EINVAL;
+    const int rc = sdrfm_bcast_reset(h);                         // (waits for the handle's stream: no launch reads the taps any more)
+    if (rc != SDRFM_OK) return rc;
+    h->tuned = h->shared_input = h->meter_ok_tuned = false;
+    memset(h->rot_host, 0, sizeof(float) * h->cfg.n_streams);
+    return SDRFM_OK;
+  }
+  if (!bcast_tuning_ok(h, ctaps, rot)) return SDRFM_EINVAL;
+  const int rc = bcast_install_tuning(h, ctaps, rot, flags);
+  return rc == SDRFM_OK ? sdrfm_bcast_reset(h) : rc;
 }
 
 // the taps and rotations replaced between two calls, the streams kept running.  Every check comes before any device work;
@@ -652,19 +623,10 @@ int sdrfm_bcast_retune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, c
   if (!h || !ctaps || !rot) return SDRFM_EINVAL;
   if (flags & ~SDRFM_TUNE_SHARED_INPUT) return SDRFM_EINVAL;
   const uint32_t ns = h->cfg.n_streams, T = h->f.T, H = h->f.H;
-  if (!finite_all(ctaps, ns * 2 * T) || !finite_all(rot, ns) || (carry && !finite_all(carry, 2 * ns))) return SDRFM_EINVAL;
+  if (!bcast_tuning_ok(h, ctaps, rot) || (carry && !finite_all(carry, 2 * ns))) return SDRFM_EINVAL;
   for (uint32_t s = 0; s < ns; ++s)
-    if (std::fabs(rot[s]) > 0x1.921fb6p+1f || (restart && restart[s] > 1)) return SDRFM_EINVAL;
-  if (hipSetDevice(h->f.device) != hipSuccess) return SDRFM_FAIL;
-  if (!h->d_ctaps) {
-    float *dc = nullptr, *dr = nullptr;
-    if (hipMalloc(&dc, sizeof(float) * ns * 2 * T) != hipSuccess || hipMalloc(&dr, sizeof(float) * ns) != hipSuccess) {
-      (void)hipFree(dc);
-      return SDRFM_ENOMEM;
-    }
-    h->d_ctaps = dc; h->d_rot = dr;
-  }
-  uint32_t any = 0;
+    if (restart && restart[s] > 1) return SDRFM_EINVAL;
+  uint32_t any = 0;                                              // the streams' records, from the rotations the device still holds
   for (uint32_t s = 0; s < ns; ++s) {
     RetuneOp& op = h->ops_host[s];
     op.cr = carry ? carry[2 * s] : 1.0f;
@@ -677,10 +639,8 @@ int sdrfm_bcast_retune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, c
     op.mode = (restart && restart[s]) ? RT_RESTART : ((identity ? 0u : RT_CARRY) | (sh == 0.0f ? 0u : RT_SHIFT));
     any |= op.mode;
   }
-  if (hipStreamSynchronize(h->f.stream) != hipSuccess) return SDRFM_FAIL;   // no launch still reads the taps about to be replaced
-  if (hipMemcpy(h->d_ctaps, ctaps, sizeof(float) * ns * 2 * T, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(h->d_rot, rot, sizeof(float) * ns, hipMemcpyHostToDevice) != hipSuccess)
-    return SDRFM_FAIL;
+  const int rc = bcast_install_tuning(h, ctaps, rot, flags);
+  if (rc != SDRFM_OK) return rc;
   if (any) {                                                     // (the identity re-tune launches nothing)
     if (hipMemcpy(h->d_ops, h->ops_host, sizeof(RetuneOp) * ns, hipMemcpyHostToDevice) != hipSuccess) return SDRFM_FAIL;
     const int c = h->f.cur;
@@ -688,10 +648,6 @@ int sdrfm_bcast_retune(sdrfm_bcast_t* h, const float* ctaps, const float* rot, c
                                                                                                  h->f.d_hist_d[c], ns, T, H);
     if (hipGetLastError() != hipSuccess) return SDRFM_FAIL;
   }
-  h->tuned = true;
-  h->shared_input = (flags & SDRFM_TUNE_SHARED_INPUT) != 0;
-  h->meter_ok_tuned = meter_taps_ok(ctaps, ns, 2 * T, METER_MAX_CTAP_SUM) && meter_taps_ok(h->f.bc, 1, 2 * h->f.P, METER_MAX_PTAP_SUM);
-  memcpy(h->rot_host, rot, sizeof(float) * ns);
   return SDRFM_OK;
 }
 

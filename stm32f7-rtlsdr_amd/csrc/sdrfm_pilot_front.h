@@ -521,9 +521,9 @@ void decim_advance(Decim& c, uint32_t M) { c.phase = (c.phase + M) % c.D; }
 // ---- the workgroup split of the RDS and the broadcast handles
 // workgroups the device runs at a time of the kernel a handle launches: what one unit holds of it, by its LDS and its registers, x the units
 template <typename K>
-uint32_t front_slots(K kernel_fast, K kernel_generic, bool fast, size_t lds, const hipDeviceProp_t& prop) {
+uint32_t front_slots(K kernel, size_t lds, const hipDeviceProp_t& prop) {
   int per_cu = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fast ? kernel_fast : kernel_generic, PF_THREADS, lds);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, PF_THREADS, lds);
   if (e != hipSuccess || per_cu < 1) per_cu = 1;
   return (uint32_t)per_cu * (uint32_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1);
 }

@@ -157,7 +157,7 @@ int sdrfm_rds_create(const sdrfm_rds_config* cfg, sdrfm_rds_t** out) {
   if (!h->fast) h->step = front_step_generic(rds_lds, T, D, P, Tr, H);
   if (h->fast) snprintf(h->kernel_name, sizeof h->kernel_name, "rds-fast T64 D10 P101 Tr%u Dr%u", Tr, Dr);
   else snprintf(h->kernel_name, sizeof h->kernel_name, "rds-generic T%u D%u P%u Tr%u Dr%u", T, D, P, Tr, Dr);
-  h->slots = front_slots(k_rds<64, 10, 101>, k_rds<0, 0, 0>, h->fast, h->step.lds, prop);
+  h->slots = front_slots(h->fast ? k_rds<64, 10, 101> : k_rds<0, 0, 0>, h->step.lds, prop);
   rc = sdrfm_rds_reset(h);
   if (rc != SDRFM_OK) { rds_free(h); return rc; }
   *out = h;

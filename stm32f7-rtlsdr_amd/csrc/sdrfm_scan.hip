@@ -156,7 +156,7 @@ int sdrfm_scan_create(const sdrfm_scan_config* cfg, sdrfm_scan_t** out) {
   if (!h->fast) h->step = front_step_generic(scan_lds, T, D, P, 0, H);
   if (h->fast) snprintf(h->kernel_name, sizeof h->kernel_name, "scan-fast T64 D10 P101");
   else snprintf(h->kernel_name, sizeof h->kernel_name, "scan-generic T%u D%u P%u", T, D, P);
-  h->slots = front_slots(k_scan<64, 10, 101, true>, k_scan<0, 0, 0, true>, h->fast, h->step.lds, prop);
+  h->slots = front_slots(h->fast ? k_scan<64, 10, 101, true> : k_scan<0, 0, 0, true>, h->step.lds, prop);
   rc = sdrfm_scan_reset(h);
   if (rc != SDRFM_OK) { scan_free(h); return rc; }
   *out = h;
