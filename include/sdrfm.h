@@ -835,6 +835,56 @@ int  sdrfm_bcast_set_audio(sdrfm_bcast_t* h, const uint16_t* blend_q15 /* n_stre
 int  sdrfm_bcast_get_audio(const sdrfm_bcast_t* h, uint16_t* blend_q15, uint16_t* gain_q15, uint16_t* blend_target_q15,
                            uint16_t* gain_target_q15 /* any may be NULL */);
 
+/* A per-stream, ramped HIGH-CUT in the stereo PCM sink: the step after the blend.  Once the blend has reached mono a weakening
+ * station keeps losing audio SNR; a broadcast tuner then lengthens the de-emphasis time constant, which trades treble for hiss.  Here that is one
+ * integer per stream that scales the sink's alpha, ramped per audio sample so that a change never clicks.
+ *
+ * State.  Per stream one Q15 integer h in [SDRFM_HICUT_MIN, 32768] with a target ht; one sink-wide slew in 1 .. 32768, the units h moves per audio
+ * sample.  A sink is created with h = ht = 32768 and is then NOT conditioned: it launches the plain kernels.
+ *
+ * Definition.  With h0 the value at the last sdrfm_pcm_stereo_sink_set_hicut and J the samples the sink has taken since (saturating at 65536), sample
+ * i (0-based) of the next call uses, all fp32,
+ *     h[i]     = the ramp of sdrfm_bcast_set_audio: h0 moved towards ht by min(min(J + i + 1, 65536) * slew, |ht - h0|)
+ *     alpha[i] = alpha * ((float)h[i] * 2^-15)        the inner product exact, the outer one rounded once, never contracted
+ *     y[i]     = fmaf(alpha[i], x[i] - y[i-1], y[i-1])
+ *     pcm[i]   = (int16) lrintf(clamp(y[i] * gain, -32768, 32767))
+ * L and R of a stream use the same alpha[i]; each carries its own y.  The ramp is a function of values (h0, ht, slew, J), not of carried device
+ * state: any cut of the samples into calls gives the same coefficients.  h = 32768 gives alpha * 1.0f == alpha: the plain recursion bit for bit.
+ * The -3 dB corner of a settled stream is -ln(1 - alpha h / 32768) fs / (2 pi): at 75 us and 48 kHz 2122 Hz at h = 32768, about 480 Hz at h = 8192.
+ *
+ * sdrfm_pcm_deemph_stereo_hicut_s16 is the definition in plain C for one stream, and the reference of everything below.  SDRFM_EINVAL for what
+ * sdrfm_pcm_deemph_stereo_s16 refuses, for h0 or ht outside [SDRFM_HICUT_MIN, 32768] and for a slew outside 1 .. 32768.  J above 65536 is 65536.
+ *
+ * sdrfm_pcm_stereo_sink_set_hicut WAITS for the sink's stream; it moves every h0 to the value its ramp has reached, takes the new targets (NULL:
+ * the targets are kept) and the slew, sets J = 0 and takes effect with the next call.  From then on the sink is conditioned and every call form
+ * launches the conditioned kernels: sdrfm_pcm_stereo_sink_process_batch in both forms, and the sink's launch behind sdrfm_stereo_process_batch_pcm,
+ * sdrfm_bcast_process_batch_pcm and sdrfm_bcast_process_batch_metered.  J advances by n with every call that sinks n samples.  A slew of 32768 is a
+ * jump.  (k, NULL, 0) returns the sink to the plain kernels and their bits: h = ht = 32768.  sdrfm_pcm_stereo_sink_reset keeps the settings and
+ * completes the ramps (h = ht).
+ * SDRFM_EINVAL, with nothing changed and before a device is touched: a NULL sink; a value outside [SDRFM_HICUT_MIN, 32768]; a slew of 0 with a
+ * non-NULL array; a slew above 32768; and, for a slew other than 0, a sink whose alpha * 0.03125f < 0.001f — the smallest effective coefficient
+ * then stays at or above 0.001; far below that the fp32 recursion stops being linear and no blocked scan follows it.
+ *
+ * Two forms, as for the plain sink (csrc/sdrfm_sink_hicut.h):
+ *   SDRFM_PCM_F_EXACT  one lane per stream, the coefficient taken per sample: BIT-IDENTICAL to sdrfm_pcm_deemph_stereo_hicut_s16, PCM and both
+ *                      states, at every alpha the set accepts.
+ *   default            a blocked scan over affine maps: beside its chunk's contribution every lane carries the chunk's own decay, and the scan
+ *                      combines the pairs.  PCM within 1 LSB of the exact form's, a share of differing outputs of at most 1e-3 + 2 / size, carried
+ *                      states within 1e-6 max(|state|, 0.25): CLAIMED AND TESTED AT THE TWO BROADCAST ALPHAS ONLY, sdrfm_pcm_alpha(48 kHz, 50 us)
+ *                      and (48 kHz, 75 us).  At other alphas the default form still runs and follows the exact one closely, but a prototype
+ *                      at alpha = 0.05 with h = 2622 held flat left 1.55e-3 of the outputs 1 LSB off and a state 1.04e-6 off: use the exact
+ *                      form there if the caps matter.
+ *
+ * sdrfm_pcm_stereo_sink_get_hicut gives, per stream, the value the next sample starts from and the target; *slew_q15 is 0 on a sink that is not
+ * conditioned.  Any pointer may be NULL.  It touches no device.
+ * Around the one-call forms, which launch on the HANDLE's stream, call set and get only after the handle's _synchronize — the rule of
+ * sdrfm_pcm_stereo_sink_get_state. */
+#define SDRFM_HICUT_MIN 1024u
+int  sdrfm_pcm_deemph_stereo_hicut_s16(const float* left, const float* right, uint32_t n, float alpha, float gain, uint16_t h0, uint16_t ht,
+                                       uint32_t slew, uint32_t J, float* state, int16_t* pcm_stereo);
+int  sdrfm_pcm_stereo_sink_set_hicut(sdrfm_pcm_stereo_sink_t* k, const uint16_t* hicut_q15 /* n_streams, or NULL: targets kept */, uint32_t slew_q15);
+int  sdrfm_pcm_stereo_sink_get_hicut(const sdrfm_pcm_stereo_sink_t* k, uint16_t* hicut_q15, uint16_t* target_q15, uint32_t* slew_q15);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,11 +15,11 @@ from .demod import FmDemod, FmConfig
 from .wbfm import WbfmDemod, WbfmConfig
 from .stereo import StereoDemod, StereoConfig
 from .bcast import BroadcastDemod, BroadcastConfig
-from .scan import ScanDemod, ScanConfig, METER_DTYPE, meter_add, meter_report, find_stations, stream_status, follow_selection, scan_grid, scan_capture, pilot_snr_db, audio_policy
+from .scan import ScanDemod, ScanConfig, METER_DTYPE, meter_add, meter_report, find_stations, stream_status, follow_selection, scan_grid, scan_capture, pilot_snr_db, audio_policy, hicut_policy
 from .rds import RdsDemod, RdsConfig, RdsSync, RdsGroup, rds_parse, rds_encode_groups, rds_checkword, rds_group_bits
 from .spectrum import SpectrumView, SpectrumConfig, power_db
-from .sink import PcmSink, StereoPcmSink, pcm_deemph_s16_host, pcm_deemph_stereo_s16_host
-from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain, rds_gain, rds_lowpass_taps, tuned_channel_taps, tuned_rotation, retune_carry, pilot_gain
+from .sink import PcmSink, StereoPcmSink, pcm_deemph_s16_host, pcm_deemph_stereo_s16_host, pcm_deemph_stereo_hicut_s16_host, hicut_slew
+from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain, rds_gain, rds_lowpass_taps, tuned_channel_taps, tuned_rotation, retune_carry, pilot_gain, hicut_corner_hz
 from .siggen import make_iq, make_iq_stereo, make_iq_rds, make_iq_stations, MODES
 from .frontend import ReplayFrontEnd, XferState
 from . import fanout
@@ -31,4 +31,5 @@ __all__ = [
     "tuned_channel_taps", "tuned_rotation", "make_iq_stations",
     "ScanDemod", "ScanConfig", "METER_DTYPE", "meter_add", "meter_report", "find_stations", "stream_status", "scan_grid", "scan_capture", "pilot_gain",
     "retune_carry", "follow_selection", "pilot_snr_db", "audio_policy",
+    "pcm_deemph_stereo_hicut_s16_host", "hicut_slew", "hicut_corner_hz", "hicut_policy",
 ]

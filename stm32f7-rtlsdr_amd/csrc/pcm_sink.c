@@ -9,9 +9,11 @@
  *   pcm[n] = sat16(lrintf(y[n] * gain))                 gain: radians -> full scale, e.g. 32767 / (2*pi*75e3/240e3)
  */
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/sdrfm.h"
+#include "sdrfm_audio_ctl.h"
 
 int sdrfm_pcm_deemph_s16(const float* audio, uint32_t n, float alpha, float gain, float* state, int16_t* pcm_stereo) {
   if ((n && (!audio || !pcm_stereo)) || !state || !(alpha > 0.0f) || alpha > 1.0f) return SDRFM_EINVAL;
@@ -47,6 +49,32 @@ int sdrfm_pcm_deemph_stereo_s16(const float* left, const float* right, uint32_t 
   if ((n && (!left || !right || !pcm_stereo)) || !state || !(alpha > 0.0f) || alpha > 1.0f) return SDRFM_EINVAL;
   deemph_channel(left, n, alpha, gain, &state[0], pcm_stereo);
   deemph_channel(right, n, alpha, gain, &state[1], pcm_stereo + 1);
+  return SDRFM_OK;
+}
+
+/* The stereo form with a ramped high-cut (include/sdrfm.h): the coefficient of sample i is alpha scaled by the ramp's Q15 value
+ * after J + i + 1 samples; L and R share it and carry their own y.  The definition, in its order: the reference of the device sink's conditioned forms. */
+int sdrfm_pcm_deemph_stereo_hicut_s16(const float* left, const float* right, uint32_t n, float alpha, float gain, uint16_t h0, uint16_t ht,
+                                      uint32_t slew, uint32_t J, float* state, int16_t* pcm_stereo) {
+  if ((n && (!left || !right || !pcm_stereo)) || !state || !(alpha > 0.0f) || alpha > 1.0f) return SDRFM_EINVAL;
+  if (h0 < SDRFM_HICUT_MIN || h0 > SDRFM_ACTL_ONE || ht < SDRFM_HICUT_MIN || ht > SDRFM_ACTL_ONE) return SDRFM_EINVAL;
+  if (slew < 1u || slew > SDRFM_ACTL_ONE) return SDRFM_EINVAL;
+  float yl = state[0], yr = state[1];
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t h = audio_ctl_ramp(h0, ht, slew, audio_ctl_advance(J, i + 1u));
+    const float a = alpha * ((float)h * 0x1p-15f);
+    yl = fmaf(a, left[i] - yl, yl);
+    yr = fmaf(a, right[i] - yr, yr);
+    float vl = yl * gain, vr = yr * gain;
+    if (vl > 32767.0f) vl = 32767.0f;
+    if (vl < -32768.0f) vl = -32768.0f;
+    if (vr > 32767.0f) vr = 32767.0f;
+    if (vr < -32768.0f) vr = -32768.0f;
+    pcm_stereo[2 * (size_t)i] = (int16_t)lrintf(vl);
+    pcm_stereo[2 * (size_t)i + 1] = (int16_t)lrintf(vr);
+  }
+  state[0] = yl;
+  state[1] = yr;
   return SDRFM_OK;
 }
 

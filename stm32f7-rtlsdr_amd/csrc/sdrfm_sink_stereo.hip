@@ -17,6 +17,10 @@
  *                           the second, independent chain fills slots the first leaves empty.  The even PCM slots are bit for bit what the mono default
  *                           sink leaves for the L rows and the odd slots what it leaves for the R rows (tests/test_pcm_stereo_sink_gpu.py confirms it).
  *                           LDS: two segments + eight carry words, 38 KiB.
+ * A CONDITIONED sink (sdrfm_pcm_stereo_sink_set_hicut) launches the two kernels of sdrfm_sink_hicut.h's bodies in their place: the same
+ * two geometries with a coefficient that differs per stream and moves per sample.  A sink that never asks for a high-cut launches the two above.
+ *   k_pcm_stereo_sink_hicut       SDRFM_PCM_F_EXACT: bit-identical to sdrfm_pcm_deemph_stereo_hicut_s16, PCM and both states.
+ *   k_pcm_stereo_sink_hicut_scan  the default: the blocked scan over affine maps, a chunk's decay walked beside its contribution.
  * What this sink leaves out on purpose: it takes no part in the in-launch chain protocol (sdrfm_sink_chain.h) — no tagged state slots, no waits on the
  * device, no atomics.  The state is a plain float[n_streams][2]; a stream's workgroup (its lane, in the exact form) reads it at the start and writes
  * it at the end, and calls on one HIP stream are ordered.
@@ -26,10 +30,13 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 
 #include "../../include/sdrfm.h"
+#include "sdrfm_audio_ctl.h"
+#include "sdrfm_sink_hicut.h"
 #include "sdrfm_sink_kernels.h"
 #include "sdrfm_sink_stereo.h"
 
@@ -74,6 +81,36 @@ __global__ void __launch_bounds__(256) k_pcm_stereo_sink_scan(StereoSinkParams p
   }
 }
 
+// ---- the conditioned forms: the same geometries, the lane's (the workgroup's) record beside the state ------------------------------------------------------
+__global__ void __launch_bounds__(64) k_pcm_stereo_sink_hicut(StereoSinkParams p, HicutParams hp) {
+  __shared__ unsigned tile[2][64 * 65];                         // L and R
+  const uint32_t lane = threadIdx.x;
+  const uint32_t s0 = blockIdx.x * 64;
+  const uint32_t rows = (p.n_streams - s0 < 64u) ? p.n_streams - s0 : 64u;
+  const uint32_t mine = s0 + lane;
+  float y[2] = {(lane < rows) ? p.state[2 * (size_t)mine] : 0.0f, (lane < rows) ? p.state[2 * (size_t)mine + 1] : 0.0f};
+  const HicutRec r = (lane < rows) ? hp.rec[mine] : HicutRec{(uint16_t)SDRFM_ACTL_ONE, (uint16_t)SDRFM_ACTL_ONE};
+  const float* const in[2] = {p.left, p.right};
+  hicut_exact_tiles(tile, in, p.audio_stride, p.pcm, p.pcm_stride, s0, rows, p.n, p.alpha, p.gain, r, hp.slew, hp.J, y);
+  if (lane < rows) {
+    p.state[2 * (size_t)mine] = y[0];
+    p.state[2 * (size_t)mine + 1] = y[1];
+  }
+}
+
+__global__ void __launch_bounds__(256) k_pcm_stereo_sink_hicut_scan(StereoSinkParams p, HicutParams hp) {
+  __shared__ float x[2][SINK_SEG];
+  __shared__ float sc[3][4];                                    // the waves' totals: s of L, s of R, A
+  const uint32_t s = blockIdx.x;
+  const float* const row[2] = {p.left + (size_t)s * p.audio_stride, p.right + (size_t)s * p.audio_stride};
+  float y0[2] = {p.state[2 * (size_t)s], p.state[2 * (size_t)s + 1]};
+  hicut_scan_segments(x, sc, row, reinterpret_cast<unsigned*>(p.pcm + (size_t)s * p.pcm_stride), p.n, p.alpha, p.gain, hp.rec[s], hp.slew, hp.J, y0);
+  if (threadIdx.x == 0) {
+    p.state[2 * (size_t)s] = y0[0];
+    p.state[2 * (size_t)s + 1] = y0[1];
+  }
+}
+
 }  // namespace
 
 struct sdrfm_pcm_stereo_sink {
@@ -86,7 +123,15 @@ struct sdrfm_pcm_stereo_sink {
   float* d_right;
   int16_t* d_pcm;
   uint32_t cap;        // samples per stream the staging holds
+  // the high-cut (sdrfm_pcm_stereo_sink_set_hicut): the streams' ramps on the host and, from the first set on, on the device; the sink's slew and the
+  // samples taken since the last set (saturated).  hicut: the sink is conditioned and launches the conditioned kernels
+  HicutRec* hc_host;   // [n_streams]
+  HicutRec* d_hc;
+  uint32_t slew, J;
+  bool hicut;
 };
+
+static const HicutRec HICUT_FLAT = {(uint16_t)SDRFM_ACTL_ONE, (uint16_t)SDRFM_ACTL_ONE};
 
 static void stereo_sink_free(sdrfm_pcm_stereo_sink* k) {
   if (!k) return;
@@ -95,6 +140,8 @@ static void stereo_sink_free(sdrfm_pcm_stereo_sink* k) {
   if (k->d_left) (void)hipFree(k->d_left);
   if (k->d_right) (void)hipFree(k->d_right);
   if (k->d_pcm) (void)hipFree(k->d_pcm);
+  if (k->d_hc) (void)hipFree(k->d_hc);
+  free(k->hc_host);
   if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
   delete k;
 }
@@ -145,9 +192,14 @@ int sdrfm_stereo_sink_reserve(sdrfm_pcm_stereo_sink* k, uint32_t n, int16_t** d_
 static int stereo_sink_launch(sdrfm_pcm_stereo_sink* k, const float* left, const float* right, size_t audio_stride, uint32_t n, int16_t* pcm, size_t pcm_stride,
                               hipStream_t stream, bool exact) {
   const StereoSinkParams p = stereo_sink_params(k, left, right, audio_stride, n, pcm, pcm_stride);
-  if (exact) hipLaunchKernelGGL(k_pcm_stereo_sink, dim3((k->n_streams + 63) / 64), dim3(64), 0, stream, p);
+  if (k->hicut) {
+    const HicutParams hp = {k->d_hc, k->slew, k->J};
+    if (exact) hipLaunchKernelGGL(k_pcm_stereo_sink_hicut, dim3((k->n_streams + 63) / 64), dim3(64), 0, stream, p, hp);
+    else hipLaunchKernelGGL(k_pcm_stereo_sink_hicut_scan, dim3(k->n_streams), dim3(SINK_NT), 0, stream, p, hp);
+  } else if (exact) hipLaunchKernelGGL(k_pcm_stereo_sink, dim3((k->n_streams + 63) / 64), dim3(64), 0, stream, p);
   else hipLaunchKernelGGL(k_pcm_stereo_sink_scan, dim3(k->n_streams), dim3(SINK_NT), 0, stream, p, sink_carry_factor(k->alpha));
   STRY(hipGetLastError(), SDRFM_FAIL);
+  k->J = audio_ctl_advance(k->J, n);                            // the samples since the last set: the next call's ramps go on from here
   return SDRFM_OK;
 }
 
@@ -182,6 +234,10 @@ int sdrfm_pcm_stereo_sink_create(uint32_t n_streams, float alpha, float gain, in
   if (!k) return SDRFM_ENOMEM;
   memset(static_cast<void*>(k), 0, sizeof(*k));
   k->n_streams = n_streams; k->alpha = alpha; k->gain = gain; k->device = device;
+  k->slew = SDRFM_ACTL_ONE; k->J = SDRFM_ACTL_J_MAX;
+  k->hc_host = (HicutRec*)malloc(sizeof(HicutRec) * (size_t)n_streams);
+  if (!k->hc_host) { stereo_sink_free(k); return SDRFM_ENOMEM; }
+  for (size_t s = 0; s < n_streams; ++s) k->hc_host[s] = HICUT_FLAT;
   if (hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking) != hipSuccess ||
       hipMalloc(&k->d_state, sizeof(float) * 2 * (size_t)n_streams) != hipSuccess) { stereo_sink_free(k); return SDRFM_ENOMEM; }
   k->stream = k->own_stream;
@@ -203,6 +259,7 @@ int sdrfm_pcm_stereo_sink_reset(sdrfm_pcm_stereo_sink_t* k) {
   STRY(hipSetDevice(k->device), SDRFM_FAIL);
   STRY(hipMemsetAsync(k->d_state, 0, sizeof(float) * 2 * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
   STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  k->J = SDRFM_ACTL_J_MAX;                                      // the high-cut's settings stay, its ramps are complete
   return SDRFM_OK;
 }
 
@@ -257,6 +314,51 @@ int sdrfm_pcm_stereo_sink_get_state(sdrfm_pcm_stereo_sink_t* k, float* state_out
   STRY(hipSetDevice(k->device), SDRFM_FAIL);
   STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
   STRY(hipMemcpy(state_out, k->d_state, sizeof(float) * 2 * (size_t)k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+// the streams' high-cut.  Every check comes before any device work; the call waits for the sink's stream before it replaces the
+// records a launch may still read
+int sdrfm_pcm_stereo_sink_set_hicut(sdrfm_pcm_stereo_sink_t* k, const uint16_t* hicut_q15, uint32_t slew_q15) {
+  if (!k) return SDRFM_EINVAL;
+  if (slew_q15 > SDRFM_ACTL_ONE) return SDRFM_EINVAL;
+  if (!slew_q15 && hicut_q15) return SDRFM_EINVAL;
+  const uint32_t ns = k->n_streams;
+  for (uint32_t s = 0; hicut_q15 && s < ns; ++s)
+    if (hicut_q15[s] < SDRFM_HICUT_MIN || hicut_q15[s] > SDRFM_ACTL_ONE) return SDRFM_EINVAL;
+  if (slew_q15 && k->alpha * 0.03125f < 0.001f) return SDRFM_EINVAL;   // the smallest effective coefficient, alpha SDRFM_HICUT_MIN / 32768, stays >= 0.001
+  if (hipSetDevice(k->device) != hipSuccess) return SDRFM_FAIL;
+  if (!slew_q15) {                                               // back to the plain kernels: h = 1, nothing to ramp
+    if (hipStreamSynchronize(k->stream) != hipSuccess) return SDRFM_FAIL;
+    for (uint32_t s = 0; s < ns; ++s) k->hc_host[s] = HICUT_FLAT;
+    k->hicut = false;
+    k->slew = SDRFM_ACTL_ONE;
+    k->J = SDRFM_ACTL_J_MAX;
+    return SDRFM_OK;
+  }
+  if (!k->d_hc && hipMalloc(&k->d_hc, sizeof(HicutRec) * ns) != hipSuccess) return SDRFM_ENOMEM;
+  if (hipStreamSynchronize(k->stream) != hipSuccess) return SDRFM_FAIL;   // no launch still reads the records about to be replaced
+  for (uint32_t s = 0; s < ns; ++s) {
+    HicutRec& r = k->hc_host[s];
+    r.h0 = (uint16_t)audio_ctl_ramp(r.h0, r.ht, k->slew, k->J);
+    if (hicut_q15) r.ht = hicut_q15[s];
+  }
+  k->slew = slew_q15;
+  k->J = 0;
+  k->hicut = true;
+  if (hipMemcpy(k->d_hc, k->hc_host, sizeof(HicutRec) * ns, hipMemcpyHostToDevice) != hipSuccess) return SDRFM_FAIL;
+  return SDRFM_OK;
+}
+
+// the value the next sample starts from, and the target; any pointer may be NULL
+int sdrfm_pcm_stereo_sink_get_hicut(const sdrfm_pcm_stereo_sink_t* k, uint16_t* hicut_q15, uint16_t* target_q15, uint32_t* slew_q15) {
+  if (!k) return SDRFM_EINVAL;
+  for (uint32_t s = 0; s < k->n_streams; ++s) {
+    const HicutRec& r = k->hc_host[s];
+    if (hicut_q15) hicut_q15[s] = (uint16_t)audio_ctl_ramp(r.h0, r.ht, k->slew, k->J);
+    if (target_q15) target_q15[s] = r.ht;
+  }
+  if (slew_q15) *slew_q15 = k->hicut ? k->slew : 0u;
   return SDRFM_OK;
 }
 

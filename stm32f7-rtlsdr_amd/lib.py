@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "sdrfm_scan_create", "sdrfm_scan_destroy", "sdrfm_scan_reset", "sdrfm_scan_tune", "sdrfm_scan_process_batch", "sdrfm_scan_set_stream",
     "sdrfm_scan_synchronize", "sdrfm_scan_kernel_name", "sdrfm_scan_report", "sdrfm_scan_meter_add",
     "sdrfm_bcast_process_batch_metered", "sdrfm_bcast_retune", "sdrfm_bcast_set_audio", "sdrfm_bcast_get_audio",
+    "sdrfm_pcm_deemph_stereo_hicut_s16", "sdrfm_pcm_stereo_sink_set_hicut", "sdrfm_pcm_stereo_sink_get_hicut",
 ]
 
 
@@ -392,5 +393,11 @@ def load_library(dev=False):
     lib.sdrfm_bcast_set_audio.restype = C.c_int
     lib.sdrfm_bcast_get_audio.argtypes = [vp, vp, vp, vp, vp]
     lib.sdrfm_bcast_get_audio.restype = C.c_int
+    lib.sdrfm_pcm_deemph_stereo_hicut_s16.argtypes = [vp, vp, u32, C.c_float, C.c_float, C.c_uint16, C.c_uint16, u32, u32, C.POINTER(C.c_float), vp]
+    lib.sdrfm_pcm_deemph_stereo_hicut_s16.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_set_hicut.argtypes = [vp, vp, u32]
+    lib.sdrfm_pcm_stereo_sink_set_hicut.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_get_hicut.argtypes = [vp, vp, vp, u32p]
+    lib.sdrfm_pcm_stereo_sink_get_hicut.restype = C.c_int
     _libs[dev] = lib
     return lib

@@ -271,6 +271,31 @@ def audio_policy(report, status, stereo_full_db=STEREO_FULL_DB, stereo_off_db=ST
     return blend, gain
 
 
+# hicut_policy's floor (dB of pilot_snr_db, Q15): from the ladder of tools/hicut_ladder.py (profiles/hicut_ladder.txt) by the rule written there
+HICUT_FLOOR_DB, HICUT_FLOOR_Q15 = 10.0, 16384
+
+
+def hicut_policy(report, status, full_db=STEREO_OFF_DB, floor_db=HICUT_FLOOR_DB, floor_q15=HICUT_FLOOR_Q15):
+    """What StereoPcmSink.set_hicut should be given for the streams of a tuned receiver: report is the meter_report of its
+    records, status stream_status' list of the same streams.  Returns hicut_q15, uint16 [n_streams].  A stereo stream gets 32768 where
+    pilot_snr_db >= full_db, floor_q15 where pilot_snr_db <= floor_db and in between the value linear in dB, rounded to nearest.  full_db
+    defaults to STEREO_OFF_DB: the high-cut begins where audio_policy's blend has reached mono.  A stream that is not stereo, or not
+    present, gets 32768: the only quality measure here is the pilot's, and a mono station has no pilot to judge it by — a weak mono
+    station is not treated, and an absent stream is audio_policy's to mute.  No hysteresis: the ramp of set_hicut is what keeps a change
+    smooth."""
+    assert full_db > floor_db, (full_db, floor_db)
+    assert 1024 <= int(floor_q15) <= 32768, floor_q15
+    snr = pilot_snr_db(report)
+    assert len(status) == snr.size, (len(status), snr.size)
+    hicut = np.full(snr.size, 32768, np.uint16)
+    for st in status:
+        s = int(st["stream"])
+        if st["present"] and st["stereo"]:
+            w = float(np.clip((snr[s] - floor_db) / (full_db - floor_db), 0.0, 1.0))
+            hicut[s] = int(np.rint(int(floor_q15) + w * (32768 - int(floor_q15))))
+    return hicut
+
+
 def scan_grid(fs, grid_hz=100e3, span_hz=None):
     """the candidate offsets of scan_capture: the multiples of grid_hz within +-span_hz (fs / 2 less one grid step by default)"""
     span = fs / 2 - grid_hz if span_hz is None else float(span_hz)

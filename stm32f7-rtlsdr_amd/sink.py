@@ -110,6 +110,39 @@ def pcm_deemph_stereo_s16_host(left, right, alpha, gain, state=(0.0, 0.0)):
     return pcm, (st[0], st[1])
 
 
+HICUT_MIN = 1024   # SDRFM_HICUT_MIN (include/sdrfm.h)
+
+
+def pcm_deemph_stereo_hicut_s16_host(left, right, alpha, gain, h0, ht, slew, J=0, state=(0.0, 0.0)):
+    """sdrfm_pcm_deemph_stereo_hicut_s16 (host-side C, the definition of the high-cut: DESIGN.md §4.17) on one stream whose ramp started at h0,
+    goes to ht (Q15 ints in [1024, 32768]) at slew units per sample and has run for J samples: returns (pcm int16 [2n]: L, R interleaved,
+    new (state_L, state_R)).  The caller carries J: the next call's is min(J + n, 65536)."""
+    lib = _l.load_library()
+    xl = np.ascontiguousarray(left, dtype=np.float32)
+    xr = np.ascontiguousarray(right, dtype=np.float32)
+    assert xl.shape == xr.shape and xl.ndim == 1
+    for v in (h0, ht):
+        if not 0 <= int(v) <= 65535:
+            raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_deemph_stereo_hicut_s16: a value outside [1024, 32768]")
+    if not 0 <= int(slew) <= 0xFFFFFFFF or not 0 <= int(J) <= 0xFFFFFFFF:
+        raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_deemph_stereo_hicut_s16: slew or J")
+    st = (C.c_float * 2)(*state)
+    pcm = np.zeros(2 * xl.size, np.int16)
+    rc = lib.sdrfm_pcm_deemph_stereo_hicut_s16(xl.ctypes.data, xr.ctypes.data, xl.size, alpha, gain, int(h0), int(ht), int(slew), int(J), st, pcm.ctypes.data)
+    if rc != _l.OK:
+        raise _l.SdrfmError(rc, "sdrfm_pcm_deemph_stereo_hicut_s16")
+    return pcm, (st[0], st[1])
+
+
+def hicut_slew(ramp_ms, rate_hz=48000.0):
+    """the slew of a ramp time, as BroadcastDemod.set_audio computes its own: a full-scale change takes ramp_ms of audio at most,
+    slew = max(1, ceil(32768 / (ramp_ms rate_hz / 1000))); ramp_ms = 0 (or less than one sample) is a jump, 32768"""
+    n = float(ramp_ms) * float(rate_hz) / 1000.0
+    if not n >= 0.0:
+        raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_stereo_sink_set_hicut: ramp_ms")
+    return 32768 if n <= 1.0 else max(1, int(np.ceil(32768.0 / n)))
+
+
 class StereoPcmSink:
     """The device sink for L and R rows (sdrfm_pcm_stereo_sink_*): pcm[2i] = L, pcm[2i + 1] = R, each channel de-emphasised on its own.
     exact=False (default): the blocked scan, per channel the mono PcmSink's default form bit for bit (PCM within 1 LSB of the exact form);
@@ -160,6 +193,43 @@ class StereoPcmSink:
         out = np.zeros((self.n_streams, 2), np.float32)
         self._ck(self._lib.sdrfm_pcm_stereo_sink_get_state(self._h, out.ctypes.data_as(C.POINTER(C.c_float))), "sdrfm_pcm_stereo_sink_get_state")
         return out
+
+    def _hq15(self, v):
+        """floats in [1/32, 1] / Q15 ints in [1024, 32768] (one value or one per stream) -> uint16 [n_streams]; what a uint16 cannot hold is
+        refused here with the C call's status, any other value outside the range by the C call itself"""
+        a = np.array(np.broadcast_to(np.asarray(v), (self.n_streams,)))
+        q = np.rint(a * 32768.0) if a.dtype.kind == "f" else a.astype(np.int64)
+        if not np.all(np.isfinite(q)) or q.min() < 0 or q.max() > 65535:
+            raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_stereo_sink_set_hicut: hicut outside [1/32, 1]")
+        return np.ascontiguousarray(q, dtype=np.uint16)
+
+    def set_hicut(self, hicut=None, ramp_ms=50.0, rate_hz=48000.0):
+        """sdrfm_pcm_stereo_sink_set_hicut: the per-stream high-cut, the factor on the sink's alpha (1 = the plain de-emphasis,
+        1/4 = a corner near 480 Hz at 75 us) as floats in [1/32, 1] or Q15 ints in [1024, 32768], one value or one per stream; None keeps the
+        targets.  It moves to its target over ramp_ms of audio at rate_hz at most (hicut_slew); ramp_ms = 0 is a jump.  Returns the slew."""
+        q = None if hicut is None else self._hq15(hicut)
+        slew = hicut_slew(ramp_ms, rate_hz)
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_set_hicut(self._h, q.ctypes.data if q is not None else None, slew), "sdrfm_pcm_stereo_sink_set_hicut")
+        return slew
+
+    def clear_hicut(self):
+        """back to the plain kernels and their bits: hicut = 1"""
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_set_hicut(self._h, None, 0), "sdrfm_pcm_stereo_sink_set_hicut")
+
+    def hicut_state(self):
+        """sdrfm_pcm_stereo_sink_get_hicut: (hicut uint16 [n_streams]: what the next sample starts from, target uint16 [n_streams], slew: 0 on a
+        sink that is not conditioned)"""
+        h, t = np.zeros(self.n_streams, np.uint16), np.zeros(self.n_streams, np.uint16)
+        slew = C.c_uint32()
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_get_hicut(self._h, h.ctypes.data, t.ctypes.data, C.byref(slew)), "sdrfm_pcm_stereo_sink_get_hicut")
+        return h, t, int(slew.value)
+
+    def condition(self, report, status, ramp_ms=50.0, **policy):
+        """set_hicut(scan.hicut_policy(report, status, **policy), ramp_ms): the high-cut the records ask for.  Returns it."""
+        from .scan import hicut_policy
+        hicut = hicut_policy(report, status, **policy)
+        self.set_hicut(hicut, ramp_ms)
+        return hicut
 
     def process_batch(self, left: np.ndarray, right: np.ndarray) -> np.ndarray:
         """host memory: left, right [n_streams, n] float32 -> pcm [n_streams, 2n] int16 (L, R interleaved)"""

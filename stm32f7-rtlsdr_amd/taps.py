@@ -86,6 +86,14 @@ def retune_carry(old_hz, new_hz, T, fs):
     return np.array([c.real, c.imag], dtype=np.float32)
 
 
+def hicut_corner_hz(alpha, hicut_q15, fs):
+    """the -3 dB corner (Hz) of the stereo PCM sink's one-pole de-emphasis with a settled high-cut: the pole of
+    y += a (x - y) with a = alpha hicut_q15 / 32768 lies at -ln(1 - a) fs / (2 pi); a = 1 (no memory at all) gives inf"""
+    a = np.asarray(alpha, np.float64) * np.asarray(hicut_q15, np.float64) / 32768.0
+    with np.errstate(divide="ignore"):
+        return -np.log1p(-a) * float(fs) / (2.0 * np.pi)
+
+
 def pilot_gain(D, fs, f_pilot=19e3):
     """H_D(f_pilot), the gain of the discriminator's D-sample boxcar at the pilot (the H_D of stereo_diff_gain; 0.98982 at D = 10,
     2.4 MS/s): a pilot of deviation v Hz has |q| = 2 pi v D / fs * H_D, which is how sdrfm_scan_report turns pilot_rms_rad into Hz."""
