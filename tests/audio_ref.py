@@ -20,7 +20,12 @@ def ramp(x0, xt, slew, n):
 
 def ramp_outputs(x0, xt, slew, J, count):
     """the values outputs 0 .. count - 1 of a call use that starts J outputs after the set: output j uses n = J + j + 1"""
-    return np.array([ramp(x0, xt, slew, J + j + 1) for j in range(count)], dtype=np.int64)
+    x0, xt, slew, J = int(x0), int(xt), int(slew), int(J)
+    assert 0 <= x0 <= ONE and 0 <= xt <= ONE and 1 <= slew <= ONE and J >= 0
+    n = J + 1 + np.arange(count, dtype=np.int64)                # ramp() on every n at once: the same first form, in int64
+    dist = abs(xt - x0)
+    move = np.minimum(np.minimum(n, -(-dist // slew)) * slew, dist)
+    return x0 + move if xt >= x0 else x0 - move
 
 
 def blend(am, as_, b, v):
