@@ -35,6 +35,7 @@
 #include "sdrfm_math.h"
 #include "sdrfm_q.h"
 #include "sdrfm_fm_call.h"
+#include "sdrfm_fm_route.h"
 #include "sdrfm_fm_plan.h"
 
 #include "sdrfm_b.h"
@@ -914,10 +915,6 @@ static_assert(sizeof(kFastVariants) / sizeof(kFastVariants[0]) == kFmInstanceCou
 // =================================================================================================================
 //  Host side (C-ABI)
 // =================================================================================================================
-#define SDRFM_Q_ADAPT_WINDOW 16u     /* design-Q calls per window of per-stream repair statistics */
-#define SDRFM_Q_ADAPT_SETS 4u        /* counter sets taken in turn: a window's statistics take effect when its set comes round again — at the first design-Q call of the
-                                        window SETS windows later, a FIXED call: the host waits there if the device has not delivered them (a host > (SETS - 1) windows ahead) */
-#define SDRFM_Q_ADAPT_BACKOFF 1024u  /* eligible calls served by the bit-exact kernels after a window of noise-like input */
 struct sdrfm {
   sdrfm_config cfg;
   int device;
@@ -973,28 +970,15 @@ struct sdrfm {
   unsigned int* d_qstat;
   bool yprev_exact, hist_q_valid;
   bool prev_by_q;         // design Q served (some streams of) the previous call: the state it left is what an overlapped call's warm-up reproduces (route_apply leaves this alone)
-  // Which kernel serves a stream is also a matter of what the stream holds: noise-only input sends design Q to its repair path at
-  // almost every audio stage (3 x the time of a carrier's call; the bit-exact kernels: 1.4 x), and a kernel lasts as long as its slowest
-  // wave — so the choice is made PER STREAM (round 5; rounds 3 - 4: per handle).  Design Q's waves add their repair passes into a word per
-  // stream (device memory); a window of SDRFM_Q_ADAPT_WINDOW design-Q calls is read back on a side stream behind the completion events of
-  // the window's last kernels (hipExtLaunchKernelGGL stop events: no marker packets in the compute queues).  A stream more than a quarter of whose audio stages needed a repair
-  // pass is served by the bit-exact kernels for SDRFM_Q_ADAPT_BACKOFF calls (design-B workgroups over the list of such streams INSIDE design
-  // Q's launch over the others — sdrfm_q.hip: k_mix — or, where design B has no instance, a launch ahead of it), then tried on design Q again.
-  // DETERMINISTIC since round 6: a window's statistics take effect at a FIXED call — the first design-Q call of the window
-  // SDRFM_Q_ADAPT_SETS windows later, when the window's counter set comes round again — whenever the read-back arrived; should it not have arrived by then
-  // (a host more than SETS - 1 windows of calls ahead of its device) that call waits for it.  Which kernel serves a stream at which call is therefore a
-  // function of the bytes and the call sequence alone: two runs of one capture give the same bits (tests/test_route_gpu.py).  Every choice is within the
-  // tolerance, a stream's audio is bit-identical to what its kernel gives alone, and SDRFM_CFG_BIT_EXACT pins the kernels.
+  // Per-stream routing between design Q and the bit-exact kernels (sdrfm_fm_route.h has the scheme and the host's bookkeeping: route); here its device resources
+  FmRoute route;
   uint32_t* rt_pass_dev[SDRFM_Q_ADAPT_SETS]; uint32_t* rt_pass_host[SDRFM_Q_ADAPT_SETS]; uint32_t* rt_pass_host_dev[SDRFM_Q_ADAPT_SETS];   // repair passes per stream: the set the open window adds into / pinned read-back
   hipStream_t rt_mon;                                           // side stream of the read-backs
-  hipEvent_t rt_rb_done[SDRFM_Q_ADAPT_SETS]; bool rt_rb_pending[SDRFM_Q_ADAPT_SETS]; uint64_t rt_rb_stages[SDRFM_Q_ADAPT_SETS];   // read-back of set i: its event; audio stages per stream its window covered
+  hipEvent_t rt_rb_done[SDRFM_Q_ADAPT_SETS];                    // read-back of set i is over
   hipEvent_t rt_win_evt[SDRFM_Q_ADAPT_SETS][3];                 // completion events of a window's last kernels: [set][internal stream 0, 1, the handle's stream]
-  bool rt_win_need[3], rt_win_used[3];                          // open window: stream holds kernels no event covers / holds kernels at all
-  uint32_t rt_win_calls, rt_set; uint64_t rt_win_stages;
-  uint8_t* rt_noisy; uint64_t* rt_retry_at; uint32_t rt_n_noisy; uint64_t rt_calls, rt_next_retry;   // host: per stream, served by the bit-exact kernels until call rt_retry_at
-  uint32_t* rt_list_dev[2]; uint32_t* rt_list_host[2]; int rt_list_cur; bool rt_dirty;   // stream lists: the clean streams first, then the noisy ones
-  hipEvent_t rt_applied[2]; bool rt_applied_pending[2];         // list version v is in place (recorded on the handle's stream behind its copy: its host buffer may be rewritten after it)
-  hipEvent_t rt_bx_evt[2]; uint32_t rt_bx_slot; hipStream_t rt_bx_last;   // the bit-exact sub-launches: completion events (stop events), and the stream the latest went to
+  uint32_t* rt_list_dev[2]; uint32_t* rt_list_host[2];          // stream lists: the clean streams first, then the noisy ones
+  hipEvent_t rt_applied[2];                                     // list version v is in place (recorded on the handle's stream behind its copy: its host buffer may be rewritten after it)
+  hipEvent_t rt_bx_evt[2]; hipStream_t rt_bx_last;              // the bit-exact sub-launches: completion events (stop events), and the stream the latest went to
                                                                 // (each takes the state the one before left: on another stream it waits for that one's event)
   bool rt_off;                                                  // (development: design Q whatever the streams hold)
   // SDRFM_F_OVERLAP: two internal streams taken in turn, so that consecutive calls run concurrently on the device (a call's ramp-up
@@ -1033,12 +1017,10 @@ static int route_apply(sdrfm* h);
     }                                                                                                \
   } while (0)
 
-// ---- per-stream routing between design Q and the bit-exact kernels (the handle's comment has the scheme) ------------------------------
+// ---- per-stream routing between design Q and the bit-exact kernels (sdrfm_fm_route.h has the scheme) -----------------------------------
 static int route_create(sdrfm* h) {
   const size_t ns = h->cfg.n_streams;
-  h->rt_noisy = static_cast<uint8_t*>(calloc(ns, 1));
-  h->rt_retry_at = static_cast<uint64_t*>(calloc(ns, sizeof(uint64_t)));
-  if (!h->rt_noisy || !h->rt_retry_at) return SDRFM_ENOMEM;
+  if (!fm_route_alloc(h->route, h->cfg.n_streams)) return SDRFM_ENOMEM;
   for (uint32_t i = 0; i < SDRFM_Q_ADAPT_SETS; ++i) {
     HIP_TRY(hipMalloc(&h->rt_pass_dev[i], ns * sizeof(uint32_t)), SDRFM_ENOMEM);
     HIP_TRY(hipMemset(h->rt_pass_dev[i], 0, ns * sizeof(uint32_t)), SDRFM_FAIL);
@@ -1059,56 +1041,20 @@ static int route_create(sdrfm* h) {
   // on the call's own stream.  hipExtAnyOrderLaunch — the launch behind design Q's without a barrier bit — is ignored on gfx950.  Where both designs have an
   // instance the two kinds of workgroup share ONE launch: sdrfm_q.hip, k_mix.)
   HIP_TRY(hipStreamCreateWithFlags(&h->rt_mon, hipStreamNonBlocking), SDRFM_ENOMEM);
-  h->rt_next_retry = ~0ull;
   return SDRFM_OK;
 }
 
 // Everything the device may still hold for this handle has been synchronised by the caller (sdrfm_reset): every stream back on design Q.
 static int route_reset(sdrfm* h) {
-  if (!h->rt_noisy) return SDRFM_OK;
+  if (!h->route.noisy) return SDRFM_OK;
   const size_t ns = h->cfg.n_streams;
   if (h->rt_mon) HIP_TRY(hipStreamSynchronize(h->rt_mon), SDRFM_FAIL);
   for (int k = 0; k < 2; ++k)
     if (h->ovl_stream[k]) HIP_TRY(hipStreamSynchronize(h->ovl_stream[k]), SDRFM_FAIL);
-  for (uint32_t i = 0; i < SDRFM_Q_ADAPT_SETS; ++i) {
-    HIP_TRY(hipMemset(h->rt_pass_dev[i], 0, ns * sizeof(uint32_t)), SDRFM_FAIL);
-    h->rt_rb_pending[i] = false;
-  }
-  memset(h->rt_noisy, 0, ns);
-  h->rt_n_noisy = 0; h->rt_next_retry = ~0ull; h->rt_dirty = false; h->rt_applied_pending[0] = h->rt_applied_pending[1] = false; h->rt_bx_last = nullptr; h->rt_calls = 0;
-  h->rt_win_calls = 0; h->rt_win_stages = 0; h->rt_set = 0;
-  for (int k = 0; k < 3; ++k) { h->rt_win_need[k] = false; h->rt_win_used[k] = false; }
+  for (uint32_t i = 0; i < SDRFM_Q_ADAPT_SETS; ++i) HIP_TRY(hipMemset(h->rt_pass_dev[i], 0, ns * sizeof(uint32_t)), SDRFM_FAIL);
+  fm_route_reset(h->route);
+  h->rt_bx_last = nullptr;
   return SDRFM_OK;
-}
-
-// The read-back of counter set i is taken in — at a FIXED call: enqueue() calls this at the first design-Q call of the window that will count into set i
-// again, SDRFM_Q_ADAPT_SETS windows after the one the read-back covers.  A stream more than a quarter of whose audio stages needed a repair pass leaves
-// design Q for a while.  The read-back was enqueued (SETS - 1) windows of calls ago; a host that far ahead of its device waits here (the one place a
-// SDRFM_F_DEVICE_PTRS call can wait: include/sdrfm.h) — the price of a kernel assignment that is a function of the bytes and the call sequence alone.
-static int route_take(sdrfm* h, uint32_t i) {
-  if (!h->rt_rb_pending[i]) return SDRFM_OK;
-  HIP_TRY(hipEventSynchronize(h->rt_rb_done[i]), SDRFM_FAIL);
-  h->rt_rb_pending[i] = false;
-  const uint32_t* pass = h->rt_pass_host[i];
-  for (uint32_t s = 0; s < h->cfg.n_streams; ++s)
-    if (!h->rt_noisy[s] && (uint64_t)pass[s] * 4u > h->rt_rb_stages[i]) {
-      h->rt_noisy[s] = 1;
-      h->rt_retry_at[s] = h->rt_calls + SDRFM_Q_ADAPT_BACKOFF;
-      if (h->rt_retry_at[s] < h->rt_next_retry) h->rt_next_retry = h->rt_retry_at[s];
-      h->rt_dirty = true;
-    }
-  return SDRFM_OK;
-}
-
-// streams whose time on the bit-exact kernels is over (counted in calls): design Q is tried again
-static void route_retry(sdrfm* h) {
-  if (h->rt_calls < h->rt_next_retry) return;
-  h->rt_next_retry = ~0ull;
-  for (uint32_t s = 0; s < h->cfg.n_streams; ++s) {
-    if (!h->rt_noisy[s]) continue;
-    if (h->rt_retry_at[s] <= h->rt_calls) { h->rt_noisy[s] = 0; h->rt_dirty = true; }
-    else if (h->rt_retry_at[s] < h->rt_next_retry) h->rt_next_retry = h->rt_retry_at[s];
-  }
 }
 
 static uint32_t max_audio_for(const sdrfm_config& c, uint32_t nbytes) { return fm_max_audio(c.fir_decim, c.audio_decim, nbytes); }
@@ -1142,9 +1088,7 @@ static void q_free(sdrfm* h) {
   }
   if (h->rt_mon) (void)hipStreamDestroy(h->rt_mon);
   h->rt_mon = nullptr;
-  free(h->rt_noisy);
-  free(h->rt_retry_at);
-  h->rt_noisy = nullptr; h->rt_retry_at = nullptr;
+  fm_route_free(h->route);
   if (h->d_qstat) (void)hipFree(h->d_qstat);
   h->d_qstat = nullptr;
   for (int i = 0; i < 2; ++i) {
@@ -1399,6 +1343,12 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
   h->fast = plan.fast >= 0 ? &kFastVariants[plan.fast] : nullptr;
   h->fast_s = plan.fast_s >= 0 ? &kFastVariants[plan.fast_s] : nullptr;
   h->fast_mix = plan.fast_mix >= 0 ? &kFastVariants[plan.fast_mix] : nullptr;
+  // (sdrfm_fm_call.h chooses the bit-exact kernel by the geometry's flags, launch_bx() launches through these pointers: one must not say what the other does not)
+  if (h->geo.has_fast != (h->fast != nullptr) || h->geo.has_s != (h->fast_s != nullptr) || h->geo.has_mix_tile != (h->fast_mix != nullptr)) {
+    fprintf(stderr, "[sdrfm] the plan's tiles and its geometry disagree\n");
+    free_handle(h);
+    return SDRFM_FAIL;
+  }
   h->AB = plan.AB; h->warm_ahead = plan.warm_ahead; h->fast_mode = plan.fast_mode; h->stream_profile = plan.stream_profile ? 1u : 0u;
   h->prio_balance = knobs.prio_balance; h->end_prio = knobs.end_prio;
   if (plan.geo.has_q) { h->q_scale = q_scale; h->q_cst = q_cst; }
@@ -1473,17 +1423,14 @@ static int route_apply(sdrfm* h) {
   const sdrfm_config& c = h->cfg;
   const uint32_t ns = c.n_streams;
   { const int jrc = join_overlap(h); if (jrc != SDRFM_OK) return jrc; }
-  const int v = h->rt_list_cur ^ 1;
-  if (h->rt_applied_pending[v]) {                                // (this version's host buffer feeds a copy enqueued two assignments ago: over, but for a host that far ahead)
-    HIP_TRY(hipEventSynchronize(h->rt_applied[v]), SDRFM_FAIL);
-    h->rt_applied_pending[v] = false;
-  }
+  FmRoute& r = h->route;
+  const FmRouteList l = fm_route_list_begin(r);
+  const int v = l.v;
+  if (l.wait) HIP_TRY(hipEventSynchronize(h->rt_applied[v]), SDRFM_FAIL);   // (this version's host buffer feeds a copy enqueued two assignments ago)
   uint32_t* L = h->rt_list_host[v];
-  uint32_t nc = 0, nn = 0;
-  for (uint32_t s = 0; s < ns; ++s) if (!h->rt_noisy[s]) L[nc++] = s;
-  for (uint32_t s = 0; s < ns; ++s) if (h->rt_noisy[s]) L[nc + nn++] = s;
-  if (!h->yprev_exact && h->hist_q_valid)                        // (design Q served ns - rt_n_noisy streams at the previous call: the clean part of the list in use)
-    HIP_TRY(sdrfm_q_fix_yprev(h->d_hist_q[h->cur], h->d_hpad, h->d_yprev[h->cur], ns - h->rt_n_noisy, h->rt_n_noisy ? h->rt_list_dev[h->rt_list_cur] : nullptr,
+  const uint32_t nn = fm_route_list_fill(r, L).n_noisy;
+  if (!h->yprev_exact && h->hist_q_valid)                        // (design Q served ns - r.n_noisy streams at the previous call: the clean part of the list in use)
+    HIP_TRY(sdrfm_q_fix_yprev(h->d_hist_q[h->cur], h->d_hpad, h->d_yprev[h->cur], ns - r.n_noisy, r.n_noisy ? h->rt_list_dev[r.list_cur] : nullptr,
                               h->stream), SDRFM_FAIL);
   if (c.fir_taps > 1)
     HIP_TRY(hipMemcpy2DAsync(h->d_hist_q[h->cur] + 2 * (SDRFM_Q_TP - (c.fir_taps - 1)), 2 * SDRFM_Q_TP, h->d_hist_b[h->cur], 2 * (size_t)(c.fir_taps - 1),
@@ -1491,10 +1438,9 @@ static int route_apply(sdrfm* h) {
   h->yprev_exact = true; h->hist_q_valid = true;
   HIP_TRY(hipMemcpyAsync(h->rt_list_dev[v], L, (size_t)ns * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream), SDRFM_FAIL);
   HIP_TRY(hipEventRecord(h->rt_applied[v], h->stream), SDRFM_FAIL);
-  h->rt_applied_pending[v] = true;
   for (int k = 0; k < 2; ++k)
     if (h->ovl_stream[k]) HIP_TRY(hipStreamWaitEvent(h->ovl_stream[k], h->rt_applied[v], 0), SDRFM_FAIL);
-  h->rt_list_cur = v; h->rt_n_noisy = nn; h->rt_dirty = false;
+  fm_route_list_commit(r, v, nn);
   return SDRFM_OK;
 }
 
@@ -1554,11 +1500,16 @@ const char* sdrfm_kernel_name(const sdrfm_t* h) { return h ? h->kernel_name : ""
 
 // Which streams design Q serves at this call (the handle's comment: per-stream routing).
 // The first design-Q call of a window: the statistics of the window that last counted into this window's set take effect HERE, at a call the call
-// sequence fixes (route_take waits for a read-back that has not arrived: a host more than SETS - 1 windows ahead of its device).
+// sequence fixes.  The read-back was enqueued (SETS - 1) windows of calls ago; a host that far ahead of its device waits for it here (the one place a
+// SDRFM_F_DEVICE_PTRS call can wait: include/sdrfm.h) — the price of a kernel assignment that is a function of the bytes and the call sequence alone.
 static int route_intake(sdrfm* h) {
-  if (h->rt_win_calls == 0) { const int trc = route_take(h, h->rt_set); if (trc != SDRFM_OK) return trc; }
-  route_retry(h);
-  if (h->rt_dirty) {
+  const int due = fm_route_due(h->route);
+  if (due >= 0) {
+    HIP_TRY(hipEventSynchronize(h->rt_rb_done[due]), SDRFM_FAIL);
+    fm_route_take(h->route, (uint32_t)due, h->rt_pass_host[due]);
+  }
+  fm_route_retry(h->route);
+  if (h->route.dirty) {
     const int arc = route_apply(h);
     if (arc != SDRFM_OK) return arc;
   }
@@ -1604,27 +1555,22 @@ static int ensure_overlap_streams(sdrfm* h) {
 // *halo_bytes is set when the kernel reads its halo as bytes.
 static const char* launch_bx(sdrfm* h, const FmCall& cl, CallParams p, uint32_t bx_waves, bool mixed, hipStream_t bs, hipEvent_t bdone, bool* halo_bytes) {
   const FmGeom& g = h->geo;
-  const uint32_t nsub = p.n_streams;
-  if (fm_stream_ok(g, cl, nsub, mixed)) {
-    p.tiles_per_stream = fm_s_waves(g, cl);
-    p.fold_state = 1;
-    hipExtLaunchKernelGGL(h->fast_s->kernel[0], dim3(nsub * p.tiles_per_stream), dim3(64), h->fast_s->xbytes, bs, nullptr, bdone, 0, p);
-    *halo_bytes = true;
-    return h->fast_s_name;
+  const FmBx b = fm_bx(g, cl, p.n_streams, bx_waves, mixed);
+  p.NA = b.tiles.NA; p.tiles_per_stream = b.tiles.tiles_per_stream; p.fold_state = b.tiles.fold_state;
+  *halo_bytes = *halo_bytes || b.halo_bytes;
+  switch (b.kind) {
+    case 's':
+      hipExtLaunchKernelGGL(h->fast_s->kernel[0], dim3(b.tiles.grid), dim3(64), h->fast_s->xbytes, bs, nullptr, bdone, 0, p);
+      return h->fast_s_name;
+    case 'b': {
+      const FastVariant* fv = b.small_tile ? h->fast_mix : h->fast;
+      hipExtLaunchKernelGGL(fv->kernel[fv == h->fast ? h->fast_mode : 0], dim3(b.tiles.grid), dim3(64), b.small_tile ? g.fast_mix_lds : g.fast_lds, bs, nullptr, bdone, 0, p);
+      return h->fast_name;
+    }
+    default:
+      hipExtLaunchKernelGGL(k_generic, dim3(b.tiles.grid), dim3(256), h->lds_bytes, bs, nullptr, bdone, 0, p);
+      return h->generic_name;
   }
-  if (fm_fast_ok(g, cl)) {
-    const bool small_tile = mixed && h->fast_mix;
-    const FastVariant* fv = small_tile ? h->fast_mix : h->fast;
-    const FmTiles t = fm_b_tiles(g, cl, nsub, bx_waves, small_tile);
-    p.NA = t.NA; p.tiles_per_stream = t.tiles_per_stream; p.fold_state = t.fold_state;
-    hipExtLaunchKernelGGL(fv->kernel[fv == h->fast ? h->fast_mode : 0], dim3(t.grid), dim3(64), small_tile ? g.fast_mix_lds : g.fast_lds, bs, nullptr, bdone, 0, p);
-    *halo_bytes = *halo_bytes || fv->kind == 'b';
-    return h->fast_name;
-  }
-  const FmTiles t = fm_generic_tiles(g, cl, nsub);
-  p.NA = t.NA; p.tiles_per_stream = t.tiles_per_stream;
-  hipExtLaunchKernelGGL(k_generic, dim3(t.grid), dim3(256), h->lds_bytes, bs, nullptr, bdone, 0, p);
-  return h->generic_name;
 }
 
 // A routing window closes: read its statistics back behind its last kernels, on the side stream (nothing here waits, no packet enters a compute queue
@@ -1632,20 +1578,17 @@ static const char* launch_bx(sdrfm* h, const FmCall& cl, CallParams p, uint32_t 
 static int route_window_close(sdrfm* h) {
   const uint32_t ns_all = h->cfg.n_streams;
   hipStream_t wst[3] = {h->ovl_stream[0], h->ovl_stream[1], h->stream};
-  const uint32_t i = h->rt_set;
+  const FmRouteClose cw = fm_route_close(h->route, h->ovl_bound[0], h->ovl_bound[1]);
+  const uint32_t i = cw.set;
   for (int kk = 0; kk < 3; ++kk) {
-    if (!h->rt_win_used[kk]) continue;
-    if (h->rt_win_need[kk]) HIP_TRY(hipEventRecord(h->rt_win_evt[i][kk], wst[kk]), SDRFM_FAIL);
-    // (an internal stream's latest kernel carries ovl_done[kk] — enqueue() —: at or behind the window's last kernel on that stream)
-    HIP_TRY(hipStreamWaitEvent(h->rt_mon, (kk < 2 && h->ovl_bound[kk]) ? h->ovl_done[kk] : h->rt_win_evt[i][kk], 0), SDRFM_FAIL);
-    h->rt_win_used[kk] = false; h->rt_win_need[kk] = false;
+    if (cw.wait[kk] == FM_ROUTE_NO_EVENT) continue;
+    if (cw.record[kk]) HIP_TRY(hipEventRecord(h->rt_win_evt[i][kk], wst[kk]), SDRFM_FAIL);
+    HIP_TRY(hipStreamWaitEvent(h->rt_mon, cw.wait[kk] == FM_ROUTE_OVL_DONE ? h->ovl_done[kk] : h->rt_win_evt[i][kk], 0), SDRFM_FAIL);
   }
   // (one small kernel instead of a copy and a memset: 12 us of host time instead of 40 — a window that closes while the host is only a call ahead
   // of the device, as in a 20-call burst from rest, otherwise leaves the queues dry for the difference)
   hipLaunchKernelGGL(k_route_collect, dim3((ns_all + 255) / 256), dim3(256), 0, h->rt_mon, h->rt_pass_dev[i], h->rt_pass_host_dev[i], ns_all);
   HIP_TRY(hipEventRecord(h->rt_rb_done[i], h->rt_mon), SDRFM_FAIL);
-  h->rt_rb_pending[i] = true; h->rt_rb_stages[i] = h->rt_win_stages;
-  h->rt_set = (h->rt_set + 1u) % SDRFM_Q_ADAPT_SETS; h->rt_win_calls = 0; h->rt_win_stages = 0;
   return SDRFM_OK;
 }
 
@@ -1688,13 +1631,13 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
   // ---- routing intake: which streams design Q serves at this call ------------------------------------------------------------------------------
   const bool q_fit = fm_q_fit(g, cl);
   const uint32_t ns_all = c.n_streams;
-  if (q_fit && h->rt_noisy && !h->rt_off) { const int irc = route_intake(h); if (irc != SDRFM_OK) return irc; }
-  const uint32_t n_noisy = (q_fit && h->rt_noisy) ? h->rt_n_noisy : 0u, n_clean = ns_all - n_noisy;
-  const bool q_ok = fm_q_ok(q_fit, n_noisy, ns_all);
-  const bool bx_all = !q_ok;                                     // the bit-exact kernels serve every stream, on the handle's stream (as every call design Q cannot take)
-  const bool mixed = q_ok && n_noisy > 0;                        // ... or the noisy ones beside design Q: in its launch (k_mix) or ahead of it
-  const bool fuse = fm_fuse(g, cl, mixed);                       // ... in ONE launch of both kinds of workgroup
-  ++h->rt_calls;
+  FmRoute& rt = h->route;
+  const bool counting = rt.noisy && !h->rt_off;                  // the handle keeps per-stream statistics
+  if (q_fit && counting) { const int irc = route_intake(h); if (irc != SDRFM_OK) return irc; }
+  const uint32_t n_noisy = (q_fit && rt.noisy) ? rt.n_noisy : 0u, n_clean = ns_all - n_noisy;
+  const FmServe serve = fm_serve(g, cl, n_noisy);
+  const bool q_ok = serve.q_ok, bx_all = serve.bx_all, mixed = serve.mixed, fuse = serve.fuse;
+  fm_route_count_call(rt);
   // sdrfm_process_batch_pcm: will design Q's launch hold the sink's chain (sdrfm_sink_chain.h)?  Every stream's whole audio row from this launch (no routed stream,
   // no outputs the generic kernel recomputes behind it at the start of a stream), enough quads for runs longer than their predecessor's reach, a sink whose time
   // constant lets runs be sunk independently.  Any other call is followed by the sink's own kernel.
@@ -1734,14 +1677,14 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     // the definition's — its bit-exact kernel wrote it — and design Q left no raw samples for it (a call design Q cannot take behind
     // a mixed call overwrote it from stale rows; tests/test_route_gpu.py::test_a_call_design_q_cannot_take_behind_mixed_calls).
     if (!h->yprev_exact && h->hist_q_valid) {
-      const uint32_t nn = h->rt_noisy ? h->rt_n_noisy : 0u;
-      HIP_TRY(sdrfm_q_fix_yprev(h->d_hist_q[h->cur], h->d_hpad, h->d_yprev[h->cur], c.n_streams - nn, nn ? h->rt_list_dev[h->rt_list_cur] : nullptr, h->stream),
+      const uint32_t nn = rt.noisy ? rt.n_noisy : 0u;
+      HIP_TRY(sdrfm_q_fix_yprev(h->d_hist_q[h->cur], h->d_hpad, h->d_yprev[h->cur], c.n_streams - nn, nn ? h->rt_list_dev[rt.list_cur] : nullptr, h->stream),
               SDRFM_FAIL);
     }
     h->yprev_exact = true; h->hist_q_valid = false; h->prev_by_q = false;
     h->prev_ovl_audio = nullptr;
   }
-  const uint32_t* list_dev = (h->rt_noisy && n_noisy) ? h->rt_list_dev[h->rt_list_cur] : nullptr;   // [clean streams][noisy streams]
+  const uint32_t* list_dev = (rt.noisy && n_noisy) ? h->rt_list_dev[rt.list_cur] : nullptr;   // [clean streams][noisy streams]
   bool behind_in = false;                                        // overlapped call: the handle's stream holds work the launches have to be ordered behind
   if (ovl || mixed) {
     { const int src = ensure_overlap_streams(h); if (src != SDRFM_OK) return src; }
@@ -1778,8 +1721,9 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     // hardware queues — one was seen on the queue of the handle's stream, and every dependence across queues costs ~10 us of a queue's time), no
     // fork and join.  Overlapped calls run it beside the OTHER internal stream's call; it takes the state the previous such launch left, which sits
     // on that other stream then: behind its completion event (launched a whole call earlier: a wait that is over when it is reached).
-    const hipEvent_t bdone = h->rt_bx_evt[h->rt_bx_slot]; h->rt_bx_slot ^= 1u;   // the launch's own completion event (a stop event: no marker packet)
-    if (h->rt_bx_last && h->rt_bx_last != qs) HIP_TRY(hipStreamWaitEvent(qs, h->rt_bx_evt[h->rt_bx_slot], 0), SDRFM_FAIL);   // (the slot just left: the previous launch's event)
+    const uint32_t bslot = fm_route_bx_take(rt);
+    const hipEvent_t bdone = h->rt_bx_evt[bslot];                  // the launch's own completion event (a stop event: no marker packet)
+    if (h->rt_bx_last && h->rt_bx_last != qs) HIP_TRY(hipStreamWaitEvent(qs, h->rt_bx_evt[bslot ^ 1u], 0), SDRFM_FAIL);   // (the other one: the previous launch's event)
     h->rt_bx_last = qs;
     bx_name = launch_bx(h, cl, pb, split.bx_waves, true, qs, bdone, &halo_bytes);
   } else if (bx_all) {
@@ -1808,16 +1752,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     q.guard_r = h->q_guard_r; q.guard_a = h->q_guard_a; q.yprev_exact = h->yprev_exact ? 1u : 0u; q.n_repaired = h->d_qstat;
     const FmRuns r = fm_q_runs(cl, split.q_total, n_clean, with_chain, h->runstate_cap, fm_chain_run_quads(g.Da));
     q.runs = r.runs;
-    // the window of per-stream repair statistics this call adds to (none while the set's previous read-back is still under way), and
-    // whether its kernel's completion carries one of the window's events (the window's last two calls: both internal streams are covered)
-    hipEvent_t done = nullptr;
-    q.stream_pass = nullptr;
-    if (h->rt_noisy && !h->rt_off) {                              // (every window counts: its set was taken in at the window's first call)
-      q.stream_pass = h->rt_pass_dev[h->rt_set];
-      h->rt_win_used[k] = true;
-      if (h->rt_win_calls + 2 >= SDRFM_Q_ADAPT_WINDOW) { done = h->rt_win_evt[h->rt_set][k]; h->rt_win_need[k] = false; }
-      else h->rt_win_need[k] = true;
-    }
+    // The counter set of the routing window this call adds to, and the stop event its kernel carries (fm_route_stop): one of the window's, or the overlap's.
     // For a caller that joins after every call (sdrfm_flush_previous: the consumer loop of INTEGRATION.md) an overlapped call's kernel carries its internal
     // stream's completion event itself (a stop event: the dispatch's own completion signal), so that the join orders the handle's stream behind it WITHOUT a marker
     // packet in that queue: 31 -> 29.4 us per call of that loop.  The kernel is the last thing the call puts on that stream, and a stream completes in order: the
@@ -1825,7 +1760,9 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     // stop event and pays one marker per join: under the kernel tracer a stop event on every kernel shortens the time two kernels are resident (0.96 -> 0.75 of a
     // 100-call burst, +3 % per call; un-profiled within the noise): profiles/r05_q_experiments.txt item 15.
     const bool carry = ovl && h->ovl_join_style;
-    if (carry) { done = h->ovl_done[k]; if (h->rt_win_used[k]) h->rt_win_need[k] = false; }
+    const FmRouteStop stop = fm_route_stop(rt, counting, k, carry);
+    q.stream_pass = counting ? h->rt_pass_dev[stop.set] : nullptr;
+    const hipEvent_t done = stop.evt == FM_ROUTE_OVL_DONE ? h->ovl_done[k] : stop.evt == FM_ROUTE_WINDOW_EVENT ? h->rt_win_evt[stop.set][k] : nullptr;
     with_chain = r.with_chain;
     if (with_chain) {                                             // the sink's chain rides in design Q's workgroups
       chain.pcm = h->pcm_out; chain.pcm_stride = h->pcm_out_stride;
@@ -1849,10 +1786,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     h->prev_ovl_pcm = (ovl && with_chain) ? h->pcm_out : nullptr; h->prev_ovl_pcm_stride = h->pcm_out_stride;
     h->yprev_exact = false; h->hist_q_valid = true; h->prev_by_q = true;
     // ---- the window close ----------------------------------------------------------------------------------------------------------------------
-    if (h->rt_noisy && !h->rt_off) {
-      h->rt_win_stages += fm_win_stages(r.runs, q_steps, c.audio_decim);
-      if (++h->rt_win_calls >= SDRFM_Q_ADAPT_WINDOW) { const int wrc = route_window_close(h); if (wrc != SDRFM_OK) return wrc; }
-    }
+    if (counting && fm_route_count(rt, fm_win_stages(r.runs, q_steps, c.audio_decim))) { const int wrc = route_window_close(h); if (wrc != SDRFM_OK) return wrc; }
     snprintf(q_name, sizeof(q_name), "%s%s%s", h->fast_q_name, ovl ? " overlapped" : "", h->pcm_fused ? " + pcm" : "");
   }
   if (mixed) {
@@ -2193,24 +2127,14 @@ int sdrfm_debug_discriminate(int device, const float* yr, const float* yi, const
 // the next call on and stays there; 0: design Q, until the statistics say otherwise); *n_noisy / noisy_out[s] report the assignment in force after the call.
 int sdrfm_debug_route(sdrfm_t* h, const uint8_t* mask, uint32_t* n_noisy, uint8_t* noisy_out) {
   if (!h) return SDRFM_EINVAL;
-  if (!h->d_qA || !h->rt_noisy) return SDRFM_NOT_SUPPORTED;
+  if (!h->d_qA || !h->route.noisy) return SDRFM_NOT_SUPPORTED;
   HIP_TRY(hipSetDevice(h->device), SDRFM_FAIL);
-  const uint32_t ns = h->cfg.n_streams;
-  if (mask) {
-    h->rt_next_retry = ~0ull;
-    for (uint32_t s = 0; s < ns; ++s) {
-      const uint8_t want = mask[s] ? 1 : 0;
-      if (h->rt_noisy[s] != want) h->rt_dirty = true;
-      h->rt_noisy[s] = want;
-      h->rt_retry_at[s] = ~0ull;
-    }
-    if (h->rt_dirty) {
-      const int arc = route_apply(h);
-      if (arc != SDRFM_OK) return arc;
-    }
+  if (mask && fm_route_set_mask(h->route, mask)) {
+    const int arc = route_apply(h);
+    if (arc != SDRFM_OK) return arc;
   }                                                              // (no mask: the assignment as the last call left it — statistics are taken in by calls only, at fixed ones)
-  if (n_noisy) *n_noisy = h->rt_n_noisy;
-  if (noisy_out) memcpy(noisy_out, h->rt_noisy, ns);
+  if (n_noisy) *n_noisy = h->route.n_noisy;
+  if (noisy_out) memcpy(noisy_out, h->route.noisy, h->cfg.n_streams);
   return SDRFM_OK;
 }
 

@@ -104,6 +104,16 @@ static inline bool fm_q_ok(bool q_fit, uint32_t n_noisy, uint32_t n_streams) {
 static inline bool fm_fuse(const FmGeom& g, const FmCall& c, bool mixed) {
   return mixed && g.mix_lds && fm_fast_ok(g, c) && g.has_mix_tile && c.M >= g.Ta && g.fold_state_ok;
 }
+// Who serves the call, given the n_noisy streams the routing has sent to the bit-exact kernels (sdrfm_fm_route.h; 0 for a call design Q cannot take): design Q
+// some of the streams (q_ok), the bit-exact kernels every stream on the handle's stream (bx_all) or the noisy ones beside design Q (mixed): in its launch
+// (fuse) or ahead of it.
+struct FmServe { bool q_ok, bx_all, mixed, fuse; };
+static inline FmServe fm_serve(const FmGeom& g, const FmCall& c, uint32_t n_noisy) {
+  FmServe s;
+  s.q_ok = fm_q_ok(fm_q_fit(g, c), n_noisy, g.n_streams);
+  s.bx_all = !s.q_ok; s.mixed = s.q_ok && n_noisy > 0; s.fuse = fm_fuse(g, c, s.mixed);
+  return s;
+}
 // Design S.  A lane-segment wave is long (its 64 lanes walk 480 samples each, ~25 us alone on a SIMD): design S pays when
 // the launch fills the machine (>= one wave per SIMD); a single dongle's call is served faster by design B,
 // which cuts its segments as short as the call needs.  Not beside design Q's launch (mixed): design B's small tile serves
@@ -229,6 +239,14 @@ static inline FmTiles fm_generic_tiles(const FmGeom& g, const FmCall& c, uint32_
   t.grid = nsub * t.tiles_per_stream + nsub;
   t.fold_state = 0;
   return t;
+}
+// The bit-exact launch over nsub streams: design S where it pays ('s': tiles_per_stream waves per stream), else design B cut for bx_waves resident waves ('b':
+// on its small tile for the noisy streams of a mixed call where that exists, else on the handle's own), else the generic kernel ('g').
+struct FmBx { char kind; bool small_tile; FmTiles tiles; bool halo_bytes; };   // halo_bytes: the kernel reads its halo as bytes
+static inline FmBx fm_bx(const FmGeom& g, const FmCall& c, uint32_t nsub, uint32_t bx_waves, bool mixed) {
+  if (fm_stream_ok(g, c, nsub, mixed)) { const uint32_t w = fm_s_waves(g, c); return FmBx{'s', false, FmTiles{0u, w, nsub * w, 1u}, true}; }
+  if (fm_fast_ok(g, c)) { const bool small = mixed && g.has_mix_tile; return FmBx{'b', small, fm_b_tiles(g, c, nsub, bx_waves, small), small || g.fast_is_b}; }
+  return FmBx{'g', false, fm_generic_tiles(g, c, nsub), false};
 }
 // Designs Q, B and S read their halo as bytes, which cannot express the zero history at the start of a stream: the few audio
 // outputs that depend on inputs before the first real sample are recomputed by the generic kernel (tile 0..k only), for every stream.

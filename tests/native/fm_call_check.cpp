@@ -3,7 +3,8 @@
  * No parity test sees this arithmetic: the bit-exact designs give the same bits however a stream is segmented, design Q however it is cut into runs.
  * Three kinds of check:
  *   known answers   figures DESIGN.md and the code's comments state for the headline shape (not taken from the functions under test)
- *   properties      over a seeded sweep of shapes, stream counts, call sizes and routed fractions, following enqueue()'s order of decisions
+ *   properties      over a seeded sweep of shapes, stream counts, call sizes and routed fractions; who serves a call and which bit-exact kernel is launched
+ *                   are asked of the functions enqueue() and launch_bx() themselves call (fm_serve, fm_bx)
  *   fm_rows_overlap against a brute-force byte-set intersection
  * Every FmGeom is the one the library plans for the shape (csrc/sdrfm_fm_plan.h) from what an MI355X answers (fm_geom.h), not a hand-written one.
  * Prints "ok" and exits 0, or says what failed and exits 1. */
@@ -77,12 +78,16 @@ static void known_answers() {
     const FmGeom g = geom(sh, 256, true);
     const FmCall c = call_of(0, 0, 480000, g, seen, true, true);
     CHECK(!fm_q_fit(g, c) && fm_stream_ok(g, c, 256, false) && fm_s_waves(g, c) == 8, "%u", fm_s_waves(g, c));
+    const FmBx b = fm_bx(g, c, 256, g.waves_target, false);
+    CHECK(fm_serve(g, c, 0).bx_all && b.kind == 's' && b.tiles.grid == 2048 && b.halo_bytes, "%c %u", b.kind, b.tiles.grid);
   }
   {  // 64 of 256 streams routed, one launch: 16 segments of 6 sub-tiles (1024 design-B workgroups), 2048 design-Q workgroups, 10 runs of 76 quads
      // (profiles/r06_mixed_split.txt)
     const FmGeom g = geom(sh, 256);
     const FmCall c = call_of(0, 0, 480000, g, seen, true, true);
-    CHECK(fm_q_ok(fm_q_fit(g, c), 64, 256) && fm_fuse(g, c, true), "fused");
+    const FmServe sv = fm_serve(g, c, 64);
+    CHECK(sv.q_ok && !sv.bx_all && sv.mixed && sv.fuse, "fused");
+    CHECK(fm_serve(g, c, 128).bx_all && fm_serve(g, c, 127).mixed, "half of the streams routed: the bit-exact kernels take the batch");
     const FmSplit s = fm_split(g, c, true, true, 64);
     const FmTiles t = fm_b_tiles(g, c, 64, s.bx_waves, true);
     const FmRuns r = fm_q_runs(c, s.q_total, 192, false, 0);
@@ -129,11 +134,12 @@ static void one_case(const Shape& sh, int top = 0) {
   const uint32_t phase_x = tidy ? 0u : rnd_in(0, D - 1), phase_d = tidy ? 0u : rnd_in(0, Da - 1);
   const uint64_t n_seen = (rnd() & 7) ? (1u << 20) : rnd_in(0, T);
   const FmCall c = call_of(phase_x, phase_d, 2u * N, g, n_seen, tidy || (rnd() & 1), tidy);
-  // enqueue()'s order of decisions
-  const bool q_fit = fm_q_fit(g, c);
+  // who serves the call (fm_serve), with a drawn share of the streams routed when design Q can take it
   const uint32_t routed_pct = (rnd() & 1) ? 0u : rnd_in(0, 100);
-  const uint32_t n_noisy = q_fit ? (uint32_t)((uint64_t)ns * routed_pct / 100u) : 0u, n_clean = ns - n_noisy;
-  const bool q_ok = fm_q_ok(q_fit, n_noisy, ns), mixed = q_ok && n_noisy > 0, fuse = fm_fuse(g, c, mixed);
+  const uint32_t n_noisy = fm_q_fit(g, c) ? (uint32_t)((uint64_t)ns * routed_pct / 100u) : 0u, n_clean = ns - n_noisy;
+  const FmServe sv = fm_serve(g, c, n_noisy);
+  const bool q_ok = sv.q_ok, mixed = sv.mixed, fuse = sv.fuse;
+  CHECK(sv.bx_all != q_ok && (!mixed || q_ok) && (!fuse || mixed) && (!q_ok || (n_clean > 0 && 2 * n_noisy < ns)), "served by neither or both: %d %d %d %d", q_ok, sv.bx_all, mixed, fuse);
   const FmSplit s = fm_split(g, c, mixed, fuse, n_noisy);
   if (fuse) {
     const uint32_t total = g.mix_waves_per_cu * g.n_cu;
@@ -146,13 +152,14 @@ static void one_case(const Shape& sh, int top = 0) {
   }
   if (mixed || !q_ok) {
     const uint32_t nsub = mixed ? n_noisy : ns;
-    if (fm_stream_ok(g, c, nsub, mixed)) {
-      const uint32_t w = fm_s_waves(g, c);
-      CHECK(w >= 1 && (uint64_t)w * 63 * g.seg >= c.N && (uint64_t)nsub * w <= 0xffffffffull, "design S: %u waves", w);
-    } else if (fm_fast_ok(g, c)) {
-      check_tiles(fm_b_tiles(g, c, nsub, s.bx_waves, mixed && g.has_mix_tile), c, nsub, "design B");
+    const FmBx b = fm_bx(g, c, nsub, s.bx_waves, mixed);          // the kernel launch_bx() launches, and its cut
+    if (b.kind == 's') {
+      const uint32_t w = b.tiles.tiles_per_stream;
+      CHECK(w >= 1 && (uint64_t)w * 63 * g.seg >= c.N && (uint64_t)nsub * w <= 0xffffffffull && b.tiles.grid == nsub * w, "design S: %u waves", w);
+      CHECK(g.has_s && !mixed && b.halo_bytes, "design S without an instance, or beside design Q");
     } else {
-      check_tiles(fm_generic_tiles(g, c, nsub), c, nsub, "generic");
+      check_tiles(b.tiles, c, nsub, b.kind == 'b' ? "design B" : "generic");
+      CHECK(b.kind == 'g' || (b.kind == 'b' && g.has_fast && (!b.small_tile || (mixed && g.has_mix_tile))), "a tile the handle does not have: %c %d", b.kind, b.small_tile);
     }
   }
   if (q_ok) {
