@@ -567,6 +567,53 @@ int  sdrfm_scan_report(const sdrfm_scan_meter* m, double fs, uint32_t D, double 
 /* acc += m, field by field (two's-complement wrap-around, no check); NULL: SDRFM_EINVAL */
 int  sdrfm_scan_meter_add(sdrfm_scan_meter* acc, const sdrfm_scan_meter* m);
 
+/* The deviation HISTOGRAM of a scan stream: the record's dev_q gives an rms deviation and nothing about peaks; modulation
+ * monitoring (ITU-R SM.1268) asks for the peak deviation and how often it passes +-75 kHz.  For every NEW d of a call, index m:
+ *     dq  = (int32) rintf(d * 2^24)          the integer freq_q sums
+ *     bin = floor(dq / 2^18) + 256
+ * |d| <= pi and one ulp more at the most, so dq lies in +-52 707 179 and bin in [54, 457]; the bins outside that range stay 0.  Bin b
+ * spans [(b - 256) / 64, (b - 255) / 64) rad: 1/64 rad, 596.8 Hz at 2.4 MS/s and D = 10.  hist[s][bin] counts the call's new d's of
+ * stream s in uint32 (n <= 2^21 per call: no count wraps); sum_b hist[s][b] == meters[s].n.  COUNTS ARE SUMS OF ONES: a row depends on
+ * nothing but the bytes — not on the workgroup split, the kernel form, the step geometry or the cut of a capture into calls — and the rows
+ * of consecutive calls add up exactly (sdrfm_scan_hist_add, in uint64) to the row of the one call.
+ *
+ * sdrfm_scan_process_batch_hist is sdrfm_scan_process_batch — the same refusals in the same order, the same flags, host buffers staged and
+ * synchronous, SDRFM_F_DEVICE_PTRS only enqueued (hist is then device memory, 4-byte aligned), meters filled with the same integers — and
+ * hist besides: n_streams rows of hist_stride uint32 words.  NULL hist or hist_stride < SDRFM_SCAN_HIST_BINS: SDRFM_EINVAL, with the NULL
+ * handle and NULL meters, before anything else is looked at.  The first SDRFM_SCAN_HIST_BINS words of every row are OVERWRITTEN (zeroed on
+ * the handle's stream before the launch adds to them); the words of a row behind them are not touched.  nbytes == 0 gives zero rows.  A
+ * refused call leaves the state and both outputs alone.  The carried state is the plain call's: the two calls may alternate on a handle.
+ * The device buffer behind host hist calls is allocated at the first one (SDRFM_ENOMEM if that fails).  sdrfm_scan_kernel_name names the
+ * kernel of the last call: it ends in " + hist" after a hist call and not after a plain one. */
+#define SDRFM_SCAN_HIST_BINS 512u
+int  sdrfm_scan_process_batch_hist(sdrfm_scan_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, sdrfm_scan_meter* meters, uint32_t* hist,
+                                   size_t hist_stride, uint32_t flags);
+
+/* Host-only (plain C, no GPU).  acc512[b] += row512[b] for the SDRFM_SCAN_HIST_BINS bins; NULL: SDRFM_EINVAL. */
+int  sdrfm_scan_hist_add(uint64_t* acc512, const uint32_t* row512);
+/* What a histogram says, in double.  hist512 is one stream's accumulated row; m is the record of the same calls (sdrfm_scan_meter_add) or
+ * NULL; fs and D as for sdrfm_scan_report; limit_hz the deviation limit (75e3 for broadcast FM).  With k = fs / (2 pi D) Hz per rad, bin b
+ * spans k (b - 256) / 64 .. k (b - 255) / 64 Hz about the tuned offset (the half step 2^-25 rad of the fixed point is ignored), and
+ *     n               sum hist
+ *     centre_hz       with m: k * freq_q / (2^24 * m->n), sdrfm_scan_report's freq_err_hz; without: k * sum hist[b] (b - 255.5) / 64 / n
+ *     peak_pos_hz     k * (upper edge of the highest non-empty bin) - centre_hz
+ *     peak_neg_hz     k * (lower edge of the lowest non-empty bin) - centre_hz
+ *     peak_hz         max(peak_pos_hz, -peak_neg_hz)
+ *     over_min        the share of n in bins that lie WHOLLY outside centre_hz +- limit_hz
+ *     over_max        the share of n in bins that lie AT LEAST PARTLY outside it
+ *     mpx_power_dbr   with m: 10 log10(2 dev_rms_hz^2 / 19000^2), dev_rms_hz as sdrfm_scan_report's: the modulation power against ITU-R
+ *                     BS.412's reference, a tone of +-19 kHz peak deviation (its 60 s window is the caller's, by sdrfm_scan_meter_add);
+ *                     NaN without m
+ * A deviation is outside iff it is MORE than limit_hz from the centre; a bin holds its lower edge and not its upper one.  So with lo and
+ * hi a bin's edges less centre_hz: wholly outside iff lo > limit or hi <= -limit, partly iff hi > limit or lo < -limit.  over_min and
+ * over_max bracket the truth; nothing is interpolated.  n == 0: every field but n is NaN (SDRFM_OK).  NULL hist512 or out, D == 0, fs not
+ * finite and positive, limit_hz not finite or negative, or m given with m->n != n: SDRFM_EINVAL. */
+typedef struct sdrfm_scan_hist_report_t {
+  uint64_t n;
+  double centre_hz, peak_pos_hz, peak_neg_hz, peak_hz, over_min, over_max, mpx_power_dbr;
+} sdrfm_scan_hist_report_t;
+int  sdrfm_scan_hist_report(const uint64_t* hist512, const sdrfm_scan_meter* m, double fs, uint32_t D, double limit_hz, sdrfm_scan_hist_report_t* out);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Spectrum view of the IQ buffer — the reference's own next task ("Perform some FFT on the samples to check what we are
  * receiving", README.md:29) on the same buffer contract (RTLSDR_CommItfTypedef.buff, usbh_rtlsdr.h:165-173): per stream

@@ -15,7 +15,7 @@ from .demod import FmDemod, FmConfig
 from .wbfm import WbfmDemod, WbfmConfig
 from .stereo import StereoDemod, StereoConfig
 from .bcast import BroadcastDemod, BroadcastConfig
-from .scan import ScanDemod, ScanConfig, METER_DTYPE, meter_add, meter_report, find_stations, stream_status, follow_selection, scan_grid, scan_capture, pilot_snr_db, audio_policy, hicut_policy
+from .scan import ScanDemod, ScanConfig, METER_DTYPE, meter_add, meter_report, find_stations, stream_status, follow_selection, scan_grid, scan_capture, pilot_snr_db, audio_policy, hicut_policy, HIST_BINS, hist_add, hist_edges_hz, hist_report, deviation_quantile, ModulationMonitor
 from .rds import RdsDemod, RdsConfig, RdsSync, RdsGroup, rds_parse, rds_encode_groups, rds_checkword, rds_group_bits
 from .spectrum import SpectrumView, SpectrumConfig, power_db
 from .sink import PcmSink, StereoPcmSink, pcm_deemph_s16_host, pcm_deemph_stereo_s16_host, pcm_deemph_stereo_hicut_s16_host, hicut_slew
@@ -32,4 +32,5 @@ __all__ = [
     "ScanDemod", "ScanConfig", "METER_DTYPE", "meter_add", "meter_report", "find_stations", "stream_status", "scan_grid", "scan_capture", "pilot_gain",
     "retune_carry", "follow_selection", "pilot_snr_db", "audio_policy",
     "pcm_deemph_stereo_hicut_s16_host", "hicut_slew", "hicut_corner_hz", "hicut_policy",
+    "HIST_BINS", "hist_add", "hist_edges_hz", "hist_report", "deviation_quantile", "ModulationMonitor",
 ]

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "sdrfm_scan_synchronize", "sdrfm_scan_kernel_name", "sdrfm_scan_report", "sdrfm_scan_meter_add",
     "sdrfm_bcast_process_batch_metered", "sdrfm_bcast_retune", "sdrfm_bcast_set_audio", "sdrfm_bcast_get_audio",
     "sdrfm_pcm_deemph_stereo_hicut_s16", "sdrfm_pcm_stereo_sink_set_hicut", "sdrfm_pcm_stereo_sink_get_hicut",
+    "sdrfm_scan_process_batch_hist", "sdrfm_scan_hist_add", "sdrfm_scan_hist_report",
 ]
 
 
@@ -132,6 +133,11 @@ class ScanMeter(C.Structure):
 class ScanReport(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("level_dbfs", "freq_err_hz", "dev_rms_hz", "pilot_rms_rad", "pilot_dev_hz", "pilot_frac",
                                           "pilot_steadiness")]
+
+
+class ScanHistReport(C.Structure):
+    _fields_ = [("n", C.c_uint64)] + [(n, C.c_double) for n in ("centre_hz", "peak_pos_hz", "peak_neg_hz", "peak_hz", "over_min", "over_max",
+                                                                  "mpx_power_dbr")]
 
 
 class RdsGroup(C.Structure):
@@ -399,5 +405,11 @@ def load_library(dev=False):
     lib.sdrfm_pcm_stereo_sink_set_hicut.restype = C.c_int
     lib.sdrfm_pcm_stereo_sink_get_hicut.argtypes = [vp, vp, vp, u32p]
     lib.sdrfm_pcm_stereo_sink_get_hicut.restype = C.c_int
+    lib.sdrfm_scan_process_batch_hist.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, C.c_size_t, u32]
+    lib.sdrfm_scan_process_batch_hist.restype = C.c_int
+    lib.sdrfm_scan_hist_add.argtypes = [vp, vp]
+    lib.sdrfm_scan_hist_add.restype = C.c_int
+    lib.sdrfm_scan_hist_report.argtypes = [vp, vp, C.c_double, u32, C.c_double, C.POINTER(ScanHistReport)]
+    lib.sdrfm_scan_hist_report.restype = C.c_int
     _libs[dev] = lib
     return lib

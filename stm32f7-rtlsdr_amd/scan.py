@@ -1,7 +1,8 @@
 """ScanDemod — Python mirror of the sdrfm_scan_* C entry points (the scan handle): one integer record per candidate
 offset of a capture, and on top of it what the records say (meter_report), which candidates are stations (find_stations) and the three
 steps in one (scan_capture), whose result feeds BroadcastDemod.tune.  stream_status reads the same records where they come from a running
-receiver (BroadcastDemod.process_batch_metered): find_stations' policy, per tuned stream."""
+receiver (BroadcastDemod.process_batch_metered): find_stations' policy, per tuned stream.  The hist call
+(process_batch_hist) adds a deviation histogram per stream; hist_report, deviation_quantile and ModulationMonitor read it."""
 import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
@@ -21,6 +22,8 @@ METER_DTYPE = np.dtype([("n", "<u8"), ("n_pilot", "<u8"), ("rf_q", "<i8"), ("fre
                         ("pilot2_q", "<i8"), ("reserved", "<u8")])
 assert METER_DTYPE.itemsize == C.sizeof(_l.ScanMeter) == 64
 REPORT_FIELDS = tuple(n for n, _ in _l.ScanReport._fields_)
+HIST_BINS = 512         # SDRFM_SCAN_HIST_BINS: bin b spans (b - 256) / 64 .. (b - 255) / 64 rad of d
+HIST_REPORT_FIELDS = tuple(n for n, _ in _l.ScanHistReport._fields_)
 
 
 @dataclass
@@ -143,6 +146,31 @@ class ScanDemod:
         self._ck(self._lib.sdrfm_scan_process_batch(self._h, C.c_void_p(iq.data_ptr()), stride, nbytes, C.c_void_p(meters.data_ptr()),
                                                     _l.F_DEVICE_PTRS), "sdrfm_scan_process_batch(device)")
 
+    def process_batch_hist(self, iq: np.ndarray):
+        """host memory: iq as process_batch takes it -> (records, a METER_DTYPE array [n_streams]; the deviation histograms of the call's
+        new d's, uint32 [n_streams, HIST_BINS]).  The records are process_batch's; the two calls may alternate on a handle."""
+        iq = np.ascontiguousarray(iq, dtype=np.uint8)
+        if iq.ndim == 1:
+            iq = iq[None, :]
+        assert iq.shape[0] == (1 if self.cfg.shared_input else self.n_streams), iq.shape
+        nbytes = iq.shape[1]
+        meters = np.zeros(self.n_streams, dtype=METER_DTYPE)
+        hist = np.zeros((self.n_streams, HIST_BINS), dtype=np.uint32)
+        self._ck(self._lib.sdrfm_scan_process_batch_hist(self._h, iq.ctypes.data, nbytes, nbytes, meters.ctypes.data, hist.ctypes.data, HIST_BINS, 0),
+                 "sdrfm_scan_process_batch_hist")
+        return meters, hist
+
+    def process_batch_hist_device(self, iq, meters, hist, nbytes=None):
+        """device tensors: iq and meters as process_batch_device takes them, hist 32-bit integers [n_streams, >= HIST_BINS] with unit stride
+        along a row (a row's first HIST_BINS words are overwritten, the rest is left alone); enqueue only"""
+        assert iq.is_cuda and meters.is_cuda and meters.is_contiguous() and meters.element_size() * meters.numel() >= 64 * self.n_streams
+        assert hist.is_cuda and hist.element_size() == 4 and hist.dim() == 2 and hist.shape[0] >= self.n_streams and hist.stride(1) == 1, hist.shape
+        nbytes = iq.shape[-1] if nbytes is None else int(nbytes)
+        stride = iq.stride(0) if iq.dim() > 1 else nbytes
+        hist_stride = hist.stride(0) if self.n_streams > 1 else max(hist.stride(0), hist.shape[1])
+        self._ck(self._lib.sdrfm_scan_process_batch_hist(self._h, C.c_void_p(iq.data_ptr()), stride, nbytes, C.c_void_p(meters.data_ptr()),
+                                                         C.c_void_p(hist.data_ptr()), hist_stride, _l.F_DEVICE_PTRS), "sdrfm_scan_process_batch_hist(device)")
+
 
 def meter_add(acc, m):
     """acc += m through sdrfm_scan_meter_add, record by record (METER_DTYPE arrays of one shape); returns acc"""
@@ -170,6 +198,114 @@ def meter_report(meters, fs, D):
         for n in REPORT_FIELDS:
             out[n][k] = getattr(r, n)
     return out
+
+
+def hist_add(acc, hist):
+    """acc += hist through sdrfm_scan_hist_add, row by row: acc uint64 [..., HIST_BINS], hist uint32 of the same shape (a hist call's);
+    returns acc"""
+    lib = _l.load_library()
+    assert acc.dtype == np.uint64 and acc.flags.c_contiguous and acc.shape[-1] == HIST_BINS and acc.shape == np.shape(hist), (acc.shape, np.shape(hist))
+    hist = np.ascontiguousarray(hist, dtype=np.uint32)
+    for k in range(acc.size // HIST_BINS):
+        st = lib.sdrfm_scan_hist_add(acc.ctypes.data + 8 * HIST_BINS * k, hist.ctypes.data + 4 * HIST_BINS * k)
+        if st != _l.OK:
+            raise _l.SdrfmError(st, "sdrfm_scan_hist_add")
+    return acc
+
+
+def hist_edges_hz(fs, D):
+    """the HIST_BINS + 1 bin edges in Hz about the tuned offset: bin b spans edges[b] .. edges[b + 1] (596.8 Hz at 2.4 MS/s and D = 10)"""
+    return float(fs) / (2.0 * np.pi * int(D)) * ((np.arange(HIST_BINS + 1, dtype=np.float64) - 256.0) / 64.0)
+
+
+def _hist_rows(hist):
+    hist = np.asarray(hist)
+    assert hist.shape[-1] == HIST_BINS and hist.dtype.kind in "ui", (hist.shape, hist.dtype)
+    return np.ascontiguousarray(hist.reshape(-1, HIST_BINS), dtype=np.uint64)
+
+
+def hist_report(hist, meters, fs, D, limit_hz=75e3):
+    """histograms [n, HIST_BINS] (a call's uint32 rows, or rows summed with hist_add) and the records of the same calls (a METER_DTYPE array
+    [n], or None) -> dict of arrays, one entry per field of sdrfm_scan_hist_report_t, through sdrfm_scan_hist_report"""
+    lib = _l.load_library()
+    rows = _hist_rows(hist)
+    if meters is not None:
+        meters = np.ascontiguousarray(np.atleast_1d(meters), dtype=METER_DTYPE)
+        assert meters.size == rows.shape[0], (meters.size, rows.shape)
+    out = {n: np.empty(rows.shape[0], np.uint64 if n == "n" else np.float64) for n in HIST_REPORT_FIELDS}
+    r = _l.ScanHistReport()
+    for k in range(rows.shape[0]):
+        st = lib.sdrfm_scan_hist_report(rows.ctypes.data + 8 * HIST_BINS * k, None if meters is None else meters.ctypes.data + 64 * k, float(fs), int(D),
+                                        float(limit_hz), C.byref(r))
+        if st != _l.OK:
+            raise _l.SdrfmError(st, "sdrfm_scan_hist_report")
+        for n in HIST_REPORT_FIELDS:
+            out[n][k] = getattr(r, n)
+    return out
+
+
+def deviation_quantile(hist, meters, fs, D, share):
+    """The deviation that the share `share` of the d's exceeds (share 0.01: the deviation passed 1 % of the time), bracketed: returns
+    (lo_hz, hi_hz), float64 arrays [n] with lo <= the true value <= hi.  A d in bin b lies between the bin's nearest and its farthest point
+    from the centre (hist_report's centre_hz); the quantile of the nearest points is lo, that of the farthest is hi — quantiles are monotone
+    in the values.  The quantile of values v with counts c is the smallest v with (count of values above v) <= share * n.  NaN for n = 0."""
+    assert 0.0 <= float(share) <= 1.0, share
+    rows = _hist_rows(hist)
+    centre = hist_report(rows, meters, fs, D)["centre_hz"]
+    edges = hist_edges_hz(fs, D)
+    lo, hi = np.full(rows.shape[0], np.nan), np.full(rows.shape[0], np.nan)
+
+    def quantile(values, counts):
+        order = np.argsort(values, kind="stable")
+        v, c = values[order], counts[order].astype(np.float64)
+        above = c.sum() - np.cumsum(c)                              # the count of values above v[k] (ties in v count as above: conservative)
+        return v[int(np.argmax(above <= share * c.sum()))]
+
+    for k in range(rows.shape[0]):
+        use = np.flatnonzero(rows[k])
+        if use.size == 0:
+            continue
+        a, b = edges[use] - centre[k], edges[use + 1] - centre[k]
+        near = np.where((a <= 0.0) & (b >= 0.0), 0.0, np.minimum(np.abs(a), np.abs(b)))
+        far = np.maximum(np.abs(a), np.abs(b))
+        lo[k], hi[k] = quantile(near, rows[k][use]), quantile(far, rows[k][use])
+    return lo, hi
+
+
+class ModulationMonitor:
+    """Modulation monitoring over the hist calls of a ScanDemod.  push(meters, hist) takes one call's outputs — 50 ms of
+    capture a call is ITU-R SM.1268's observation interval —, keeps the running record (meter_add), the running 64-bit histogram (hist_add)
+    and the call's peak_hz per stream; summary() reads them."""
+
+    def __init__(self, n_streams, fs, D, limit_hz=75e3):
+        self.n_streams, self.fs, self.D, self.limit_hz = int(n_streams), float(fs), int(D), float(limit_hz)
+        self.meters = np.zeros(self.n_streams, dtype=METER_DTYPE)
+        self.hist = np.zeros((self.n_streams, HIST_BINS), dtype=np.uint64)
+        self.peaks = []                                           # one float64 [n_streams] per call
+
+    def push(self, meters, hist):
+        meters = np.ascontiguousarray(np.atleast_1d(meters), dtype=METER_DTYPE)
+        hist = np.ascontiguousarray(hist, dtype=np.uint32).reshape(self.n_streams, HIST_BINS)
+        assert meters.shape == (self.n_streams,), meters.shape
+        peak = hist_report(hist, meters, self.fs, self.D, self.limit_hz)["peak_hz"]
+        meter_add(self.meters, meters)
+        hist_add(self.hist, hist)
+        self.peaks.append(peak)
+        return peak
+
+    def summary(self):
+        """one dict per stream: stream, n, calls (those with any d), peak_hz (the largest of the calls' peaks, each about its own call's
+        centre), calls_over (the share of those calls whose peak passed limit_hz), and centre_hz, over_min, over_max and mpx_power_dbr of
+        the running histogram and record; NaN where there is no d"""
+        rep = hist_report(self.hist, self.meters, self.fs, self.D, self.limit_hz)
+        peaks = np.array(self.peaks, np.float64).reshape(len(self.peaks), self.n_streams)
+        out = []
+        for s in range(self.n_streams):
+            p = peaks[:, s][~np.isnan(peaks[:, s])]
+            out.append(dict(stream=s, n=int(rep["n"][s]), calls=int(p.size), peak_hz=float(p.max()) if p.size else float("nan"),
+                            calls_over=float((p > self.limit_hz).mean()) if p.size else float("nan"), centre_hz=float(rep["centre_hz"][s]),
+                            over_min=float(rep["over_min"][s]), over_max=float(rep["over_max"][s]), mpx_power_dbr=float(rep["mpx_power_dbr"][s])))
+        return out
 
 
 # the thresholds of find_stations and stream_status, and the two rules both apply to entry c of a meter_report
