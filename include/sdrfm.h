@@ -802,6 +802,32 @@ int  sdrfm_bcast_process_batch_metered(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t
                                        float* bb, size_t bb_stride, uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* n_audio,
                                        uint32_t* n_rds, uint32_t flags);
 
+/* The HIST broadcast call: the metered call above and, from the same launch, the scan section's deviation histogram of
+ * every stream — so that a running receiver monitors the modulation of the stations it plays (sdrfm_scan_hist_report, ITU-R SM.1268 /
+ * BS.412) without a scan handle that walks the same bytes again.
+ * Row s counts the call's new d's of stream s — the d's the record's n counts — by bin = floor(dq / 2^18) + 256 of
+ * dq = (int32) rintf(d 2^24), the integer the record's freq_q sums.  It EQUALS, integer for integer, the row sdrfm_scan_process_batch_hist
+ * gives on a scan handle with the same channel taps (an untuned handle: ctaps = (h[k], 0), rot = 0), pilot taps and pilot_min for the same
+ * bytes, for any cut into calls, and depends on nothing else: not on the kernel form, the blend or gain, or a sink.  With the record of
+ * the same call: sum_b hist[b] = n, and sum_b hist[b] (b - 256) 2^18 <= freq_q < sum_b hist[b] (b - 255) 2^18 for n > 0.
+ *   hist          n_streams rows of hist_stride uint32 words, hist_stride >= SDRFM_SCAN_HIST_BINS.  Host memory for a host-buffer call; with
+ *                 SDRFM_F_DEVICE_PTRS device memory, 4-byte aligned (else SDRFM_EINVAL).  The first SDRFM_SCAN_HIST_BINS words of every row
+ *                 are OVERWRITTEN (zeroed on the handle's stream before the launch adds to them); words behind them are left alone;
+ *                 nbytes == 0 gives zero rows.  Rows add up with sdrfm_scan_hist_add and read with sdrfm_scan_hist_report.
+ * NULL h, meters or hist, or hist_stride < SDRFM_SCAN_HIST_BINS: SDRFM_EINVAL, before anything else is looked at.  Every other refusal is
+ * the metered call's, in its order; a refused call writes nothing and leaves the handle and the sink as they were.
+ * Every other output — left, right, bb, pcm, pilot_count, meters, the counts, the carried state — is the metered call's bit for bit:
+ * plain, PCM, metered and hist calls mix freely in one sequence.  The device rows behind host hist calls (n_streams x 2048 bytes) are
+ * allocated at the first one (SDRFM_ENOMEM if that fails): a handle that never makes a hist call allocates and launches what it did.
+ * A hist call launches the hist form of the handle's kernel, which sdrfm_bcast_hist_kernel_name names: sdrfm_bcast_kernel_name's string
+ * and " + hist".  Its bins take 2 KiB of the workgroup's local memory, so at shapes where that memory bounds the step its step is a few
+ * d's shorter than the other calls' (and generic where only the plain form fits the fast kernel's step); no result depends on the step. */
+int  sdrfm_bcast_process_batch_metered_hist(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink /* or NULL */, const uint8_t* iq, size_t iq_stride,
+                                            uint32_t nbytes, float* left, float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride,
+                                            float* bb, size_t bb_stride, uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* hist,
+                                            size_t hist_stride, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags);
+const char* sdrfm_bcast_hist_kernel_name(const sdrfm_bcast_t* h);
+
 /* RE-TUNING a running broadcast receiver: new channel taps and rotations between two calls, the streams kept running.
  * sdrfm_bcast_tune is a restart of every stream; this call is what a drift correction, or the replacement of one station among many, uses.
  *

@@ -2,14 +2,16 @@
 and R and the RDS handle's complex baseband of the same streams from one kernel launch, bit for bit what StereoDemod and RdsDemod give.
 The metered calls add the scan handle's record of every stream from that launch: scan.meter_add, scan.meter_report and
 scan.stream_status read it.  set_audio / clear_audio / audio_state / condition give every stream a stereo blend and an output
-gain, ramped per audio output inside the launch; scan.audio_policy makes them from the records."""
+gain, ramped per audio output inside the launch; scan.audio_policy makes them from the records.  The hist calls add the
+scan handle's deviation histogram of every stream from that launch as well: scan.hist_add, scan.hist_report, scan.deviation_quantile and
+scan.ModulationMonitor read it."""
 import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import lib as _l
-from .scan import METER_DTYPE
+from .scan import HIST_BINS, METER_DTYPE
 from .stereo import _pilot_floats
 
 CFG_FORCE_GENERIC = 1   # SDRFM_BCAST_CFG_FORCE_GENERIC (include/sdrfm.h)
@@ -225,8 +227,12 @@ class BroadcastDemod:
     def synchronize(self):
         self._ck(self._lib.sdrfm_bcast_synchronize(self._h), "sdrfm_bcast_synchronize")
 
-    def _entry(self, name, sink, iq, audio, pcm, bb, pc, meters, flags):
-        """one call of the C entry `name` on addresses: iq (address, row stride, nbytes), audio (left, right, row stride), pcm and bb
+    def hist_kernel_name(self):
+        """the kernel a hist call launches now: kernel_name and " + hist" (its step may be the generic one where the plain call's is fast)"""
+        return self._lib.sdrfm_bcast_hist_kernel_name(self._h).decode()
+
+    def _entry(self, name, sink, iq, audio, pcm, bb, pc, meters, flags, hist=(None, 0)):
+        """one call of the C entry `name` on addresses: iq (address, row stride, nbytes), audio (left, right, row stride), pcm, bb and hist
         (address, row stride).  Raises SdrfmError with the entry's status, returns (n_audio, n_rds)."""
         na, nr = C.c_uint32(), C.c_uint32()
         front, back, counts = (*iq, *audio), (*bb, pc), (C.byref(na), C.byref(nr), flags)
@@ -234,14 +240,17 @@ class BroadcastDemod:
             st = self._lib.sdrfm_bcast_process_batch(self._h, *front, *back, *counts)
         elif name == "sdrfm_bcast_process_batch_pcm":
             st = self._lib.sdrfm_bcast_process_batch_pcm(self._h, sink._h, *front, *pcm, *back, *counts)
-        else:
+        elif name == "sdrfm_bcast_process_batch_metered":
             st = self._lib.sdrfm_bcast_process_batch_metered(self._h, sink._h if sink is not None else None, *front, *pcm, *back, meters, *counts)
+        else:
+            st = self._lib.sdrfm_bcast_process_batch_metered_hist(self._h, sink._h if sink is not None else None, *front, *pcm, *back, meters, *hist,
+                                                                  *counts)
         self._ck(st, name + ("(device)" if flags else ""))
         return na.value, nr.value
 
     def _host_call(self, name, iq, sink=None, with_audio=True):
-        """a host-memory call of the C entry `name`: (L, R, pcm, bb, pilot_count, meters) trimmed to the call's counts, None what the call
-        has not — L and R without with_audio, pcm without a sink, meters of any entry but the metered one"""
+        """a host-memory call of the C entry `name`: (L, R, pcm, bb, pilot_count, meters, hist) trimmed to the call's counts, None what the
+        call has not — L and R without with_audio, pcm without a sink, meters of any entry but the metered ones, hist of any but the hist one"""
         iq = np.ascontiguousarray(iq, dtype=np.uint8)
         if iq.ndim == 1:
             iq = iq[None, :]
@@ -254,26 +263,27 @@ class BroadcastDemod:
         pcm = np.zeros((ns, 2 * ca), dtype=np.int16) if sink is not None else None
         bb = np.zeros((ns, 2 * cr), dtype=np.float32)
         pc = np.zeros(ns, dtype=np.uint32)
-        meters = np.zeros(ns, dtype=METER_DTYPE) if name.endswith("_metered") else None
+        meters = np.zeros(ns, dtype=METER_DTYPE) if "_metered" in name else None
+        hist = np.zeros((ns, HIST_BINS), dtype=np.uint32) if name.endswith("_hist") else None
         adr = lambda a: a.ctypes.data if a is not None else None
         na, nr = self._entry(name, sink, (adr(iq), nbytes, nbytes), (adr(left), adr(right), ca), (adr(pcm), 2 * ca), (adr(bb), 2 * cr), adr(pc),
-                             adr(meters), 0)
+                             adr(meters), 0, (adr(hist), HIST_BINS))
         trim = lambda a, n: a[:, :n] if a is not None else None
-        return trim(left, na), trim(right, na), trim(pcm, 2 * na), np.ascontiguousarray(bb[:, : 2 * nr]).view(np.complex64), pc, meters
+        return trim(left, na), trim(right, na), trim(pcm, 2 * na), np.ascontiguousarray(bb[:, : 2 * nr]).view(np.complex64), pc, meters, hist
 
-    def _device_call(self, name, iq, left, right, bb, pilot_count, nbytes, sink=None, pcm=None, meters=None):
+    def _device_call(self, name, iq, left, right, bb, pilot_count, nbytes, sink=None, pcm=None, meters=None, hist=(None, 0)):
         """a device-tensor call of the C entry `name`, enqueue only: (n_audio, n_rds).  A tensor that is None goes as NULL with stride 0;
-        meters is an address"""
+        meters is an address, hist an (address, row stride)"""
         adr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
         row = lambda t: t.stride(0) if t is not None else 0
         nbytes = iq.shape[1] if nbytes is None else int(nbytes)
         return self._entry(name, sink, (adr(iq), iq.stride(0), nbytes), (adr(left), adr(right), row(left)), (adr(pcm), row(pcm)),
-                           (adr(bb), bb.stride(0)), adr(pilot_count), meters, _l.F_DEVICE_PTRS)
+                           (adr(bb), bb.stride(0)), adr(pilot_count), meters, _l.F_DEVICE_PTRS, hist)
 
     def process_batch(self, iq: np.ndarray):
         """host memory: iq [n_streams, nbytes] uint8 -> (L, R [n_streams, n_audio] float32, bb [n_streams, n_rds] complex64,
         pilot_count [n_streams] uint32)"""
-        left, right, _, bb, pc, _ = self._host_call("sdrfm_bcast_process_batch", iq)
+        left, right, _, bb, pc, _, _ = self._host_call("sdrfm_bcast_process_batch", iq)
         return left, right, bb, pc
 
     def process_batch_device(self, iq, left, right, bb, pilot_count=None, nbytes=None):
@@ -300,13 +310,11 @@ class BroadcastDemod:
         """sdrfm_bcast_process_batch_metered on host memory: what process_batch (sink=None) or process_batch_pcm(sink, iq, with_audio)
         returns and, behind it, the streams' records of the same launch: a scan.METER_DTYPE array [n_streams]."""
         assert with_audio or sink is not None, "without a sink the audio rows are all the audio there is"
-        out = self._host_call("sdrfm_bcast_process_batch_metered", iq, sink, with_audio)
+        out = self._host_call("sdrfm_bcast_process_batch_metered", iq, sink, with_audio)[:6]
         return out if sink is not None else out[:2] + out[3:]
 
-    def process_batch_metered_device(self, iq, left, right, bb, meters, pilot_count=None, nbytes=None, sink=None, pcm=None):
-        """device tensors as process_batch_device (sink=None: left and right given, no pcm) or process_batch_pcm_device (sink and pcm given;
-        left = right = None: the sink reads the handle's own rows) takes them, and meters: int64 [n_streams, 8] (sdrfm_scan_meter's eight
-        words) or the address of n_streams records in device memory, 8-byte aligned.  Enqueue only.  Returns (n_audio, n_rds)."""
+    def _metered_device_args(self, iq, left, right, bb, meters, sink, pcm):
+        """the checks of a metered device call's tensors; returns the address of the records"""
         assert iq.is_cuda and bb.is_cuda and bb.stride(1) == 1 and (left is None) == (right is None)
         assert (sink is None) == (pcm is None) and (sink is not None or left is not None)
         if left is not None:
@@ -318,4 +326,29 @@ class BroadcastDemod:
             mp = C.c_void_p(meters.data_ptr())
         else:
             mp = C.c_void_p(int(meters)) if meters else None
+        return mp
+
+    def process_batch_metered_device(self, iq, left, right, bb, meters, pilot_count=None, nbytes=None, sink=None, pcm=None):
+        """device tensors as process_batch_device (sink=None: left and right given, no pcm) or process_batch_pcm_device (sink and pcm given;
+        left = right = None: the sink reads the handle's own rows) takes them, and meters: int64 [n_streams, 8] (sdrfm_scan_meter's eight
+        words) or the address of n_streams records in device memory, 8-byte aligned.  Enqueue only.  Returns (n_audio, n_rds)."""
+        mp = self._metered_device_args(iq, left, right, bb, meters, sink, pcm)
         return self._device_call("sdrfm_bcast_process_batch_metered", iq, left, right, bb, pilot_count, nbytes, sink, pcm, mp)
+
+    def process_batch_metered_hist(self, iq: np.ndarray, sink=None, with_audio=True):
+        """sdrfm_bcast_process_batch_metered_hist on host memory: process_batch_metered's tuple and, behind it, the streams' deviation
+        histograms of the same launch: uint32 [n_streams, scan.HIST_BINS], what ScanDemod.process_batch_hist gives of the same bytes and
+        tuning."""
+        assert with_audio or sink is not None, "without a sink the audio rows are all the audio there is"
+        out = self._host_call("sdrfm_bcast_process_batch_metered_hist", iq, sink, with_audio)
+        return out if sink is not None else out[:2] + out[3:]
+
+    def process_batch_metered_hist_device(self, iq, left, right, bb, meters, hist, pilot_count=None, nbytes=None, sink=None, pcm=None):
+        """process_batch_metered_device's tensors and hist: 32-bit integers [n_streams, >= scan.HIST_BINS] with unit stride along a row (a
+        row's first HIST_BINS words are overwritten, the rest is left alone).  Enqueue only.  Returns (n_audio, n_rds)."""
+        mp = self._metered_device_args(iq, left, right, bb, meters, sink, pcm)
+        ns = self.cfg.n_streams
+        assert hist.is_cuda and hist.element_size() == 4 and hist.dim() == 2 and hist.shape[0] >= ns and hist.stride(1) == 1, hist.shape
+        hist_stride = hist.stride(0) if ns > 1 else max(hist.stride(0), hist.shape[1])
+        return self._device_call("sdrfm_bcast_process_batch_metered_hist", iq, left, right, bb, pilot_count, nbytes, sink, pcm, mp,
+                                 (C.c_void_p(hist.data_ptr()), hist_stride))

@@ -30,10 +30,15 @@
  * A conditioned handle (sdrfm_bcast_set_audio) launches the sixth template argument's form of any of those: the same walk,
  * carriers and chains, and where L and R are formed the stream's stereo blend and output gain, both ramped per audio output by
  * sdrfm_audio_ctl.h's closed form from one small record per stream — values, not carried state, so nothing new is handed over.
+ *
+ * A hist call (sdrfm_bcast_process_batch_metered_hist) launches the seventh template argument's form of a metered kernel:
+ * beside meter_take every new d counted in sdrfm_hist.h's 512 bins, which lie in LDS behind the plain layout — the scan handle's histogram
+ * row of the stream, from the launch that receives it.  The bins shorten the step at the LDS-limited shapes; no result depends on the step.
  */
 #include <new>
 
 #include "sdrfm_carrier.h"
+#include "sdrfm_hist.h"
 #include "sdrfm_meter.h"
 #include "sdrfm_out_stages.h"
 #include "sdrfm_pilot_front.h"
@@ -59,6 +64,8 @@ struct BcastParams : FrontParams {
   unsigned long long* meters;  // metered: [ns][8], sdrfm_scan_meter as eight 64-bit words, zeroed before the launch
   const AudioCtlRec* actl;     // blended: [ns], the streams' ramps
   uint32_t slew, J;            // blended: the ramps' units per audio output, the audio outputs between the set and this call
+  uint32_t* hist;              // hist: [ns][hist_stride], a row's first SDRFM_SCAN_HIST_BINS words, zeroed before the launch
+  size_t hist_stride;          // words
 };
 
 // how many of a workgroup's nw waves take a step's nc RDS chains (of Tr links), the others taking its na audio outputs (of 2 Ta links):
@@ -72,8 +79,9 @@ __device__ __forceinline__ int bcast_rds_waves(int nw, int nc, int Tr, int na, i
   return wr;
 }
 
-template <int FT, int FD, int FP, bool TU, bool ME = false, bool BL = false>
+template <int FT, int FD, int FP, bool TU, bool ME = false, bool BL = false, bool HI = false>
 __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
+  static_assert(ME || !HI, "the histogram counts the d's the meter stage takes");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t T = FT > 0 ? FT : p.T, P = FT > 0 ? FP : p.P;
   const uint32_t Ta = p.Ta, Da = p.Da, Tr = p.Tr, Dr = p.Dr, H = p.H, Dl = p.Dl, NY = p.NY, NDT = p.NDT, ZP = p.zplane;
@@ -81,7 +89,8 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   // LDS: region (x as f16 pairs | d's, s's, zr's, zi's) | ys[NY] | hb[H] | tps[P] | grs[Tr] | gas[Ta] | hs[T; tuned: 2T] | zb[2 (Tr - 1)] | sb[Ta - 1];
   // hb and tps padded so that grs starts on 16 bytes.  grs holds the RDS taps oldest first (grs[k] = gr[Tr - 1 - k]): the output chains
   // read them four at a time
-  // (a metered kernel adds nothing to it: y, d and q of a new d are there already)
+  // (a metered kernel adds nothing to it: y, d and q of a new d are there already; a hist kernel adds bins[SDRFM_SCAN_HIST_BINS] on the next
+  // 16 bytes behind sb)
   FrontWg<FT, FD, FP, TU> w;
   w.xs = reinterpret_cast<h2_t*>(smem);
   w.ds = reinterpret_cast<float*>(smem);
@@ -95,6 +104,8 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   w.hs = gas + Ta;
   float* zb = w.hs + (TU ? 2 * T : T);                                        // the last Tr - 1 (zr, zi), plane by plane, for the next step
   float* sb = zb + 2 * (Tr - 1);                                // the last Ta - 1 s's
+  uint32_t* bins = nullptr;                                     // hist: the workgroup's counts
+  if constexpr (HI) bins = reinterpret_cast<uint32_t*>(smem + hist_bins_offset((size_t)(reinterpret_cast<unsigned char*>(sb + (Ta - 1)) - smem)));
   if constexpr (TU) {
     const uint32_t st = blockIdx.x / p.blocks_per_stream;
     w.ctaps = p.ctaps + (size_t)st * 2 * T;
@@ -114,6 +125,10 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   }
   uint32_t cnt = 0;
   MeterAcc acc;                                                 // metered: the lane's sums, and the gate's count in place of cnt
+  if constexpr (HI) {
+    hist_zero(bins, tid);
+    __syncthreads();
+  }
 
   front_walk(p, w, [&](int a, int b, bool full) {
     front_d_stage(p, w, a, b);
@@ -145,6 +160,7 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
           if (o >= Tm - 1) {
             const int j = o - (Tm - 1);
             meter_take(acc, w.ys[j + yo], ds[H + j], q, p.pmin2);
+            if constexpr (HI) hist_take(bins, ds[H + j]);
           }
         } else {
           cnt += (on && o >= Tm - 1) ? 1u : 0u;
@@ -170,6 +186,10 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast(BcastParams p) {
   if constexpr (ME) {
     front_count(p, s, tid, acc.on);                             // the same comparison on the same pw as the carriers' gate
     meter_flush(acc, p.meters + 8 * (size_t)s, tid);
+    if constexpr (HI) {
+      __syncthreads();
+      hist_flush(bins, p.hist + (size_t)s * p.hist_stride, tid);
+    }
   } else {
     front_count(p, s, tid, cnt);
   }
@@ -212,8 +232,8 @@ __global__ void __launch_bounds__(PF_THREADS) k_bcast_retune(const RetuneOp* ops
 
 // =================================================================================================================
 //  Host side: handle, argument checks (all before any device work), launch geometry.  The walk's state is the header's PilotFront.
-//  bcast_kernel names the sixteen instantiations, once; a BcastForm for the untuned and one for the tuned kernels holds what a launch
-//  looks up (step, slots, name); the three process_batch entries are one call path (bcast_batch), tune and retune one installation.
+//  bcast_kernel names the twenty-four instantiations, once; a BcastForm for the untuned and one for the tuned kernels holds what a launch
+//  looks up (step, slots, name); the four process_batch entries are one call path (bcast_batch), tune and retune one installation.
 // =================================================================================================================
 typedef void (*bcast_kernel_fn)(BcastParams);
 
@@ -223,6 +243,11 @@ struct BcastForm {
   bool fast = false;
   uint32_t slots[2][2] = {{1, 1}, {1, 1}};     // [metered][blend]: workgroups the device runs at a time (compute units x workgroups per unit)
   char name[2][120];                           // [blend]
+  // the hist kernels' own: the bins take LDS from the step at the LDS-limited shapes
+  FrontStep hist_step;
+  bool hist_fast = false;
+  uint32_t hist_slots[2] = {1, 1};             // [blend]
+  char hist_name[2][128];                      // [blend]
 };
 
 struct sdrfm_bcast {
@@ -247,6 +272,7 @@ struct sdrfm_bcast {
   // channel taps looked at at create, the tuned ones at tune
   bool meter_ok = false, meter_ok_tuned = false;
   sdrfm_scan_meter* d_meters = nullptr;        // host-buffer calls: the records [ns]
+  uint32_t* d_hist = nullptr;                  // host-buffer hist calls: the rows [ns][512], allocated at the first such call
   // the conditioned form (sdrfm_bcast_set_audio): the streams' ramps on the host and, from the first set on, on the device; the handle's
   // slew and the audio outputs since the last set (saturated)
   bool blend = false;
@@ -275,8 +301,23 @@ size_t bcast_lds_tuned(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t
   return bcast_lds(T, D, P, Tg, H, NY, NDT, region_words) + 4 * (size_t)T;
 }
 
-// the sixteen kernels
-bcast_kernel_fn bcast_kernel(bool fast, bool tuned, bool metered, bool blend) {
+// the hist kernels' LDS: the plain layout (rounded up to 16) and the bins
+size_t bcast_hist_lds(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t H, uint32_t NY, uint32_t NDT, uint32_t* region_words) {
+  return hist_bins_offset(bcast_lds(T, D, P, Tg, H, NY, NDT, region_words)) + HIST_LDS_BYTES;
+}
+
+size_t bcast_hist_lds_tuned(uint32_t T, uint32_t D, uint32_t P, uint32_t Tg, uint32_t H, uint32_t NY, uint32_t NDT, uint32_t* region_words) {
+  return hist_bins_offset(bcast_lds_tuned(T, D, P, Tg, H, NY, NDT, region_words)) + HIST_LDS_BYTES;
+}
+
+// the twenty-four kernels: the sixteen of the plain and the metered calls, the eight of the hist call (all metered)
+bcast_kernel_fn bcast_kernel(bool fast, bool tuned, bool metered, bool blend, bool hist = false) {
+  static const bcast_kernel_fn kh[2][2][2] = {                   // [tuned][blend][fast]
+      {{k_bcast<0, 0, 0, false, true, false, true>, k_bcast<64, 10, 101, false, true, false, true>},
+       {k_bcast<0, 0, 0, false, true, true, true>, k_bcast<64, 10, 101, false, true, true, true>}},
+      {{k_bcast<0, 0, 0, true, true, false, true>, k_bcast<64, 10, 101, true, true, false, true>},
+       {k_bcast<0, 0, 0, true, true, true, true>, k_bcast<64, 10, 101, true, true, true, true>}}};
+  if (hist) return kh[tuned][blend][fast];
   static const bcast_kernel_fn k[2][2][2][2] = {                 // [tuned][metered][blend][fast]
       {{{k_bcast<0, 0, 0, false, false, false>, k_bcast<64, 10, 101, false, false, false>},
         {k_bcast<0, 0, 0, false, false, true>, k_bcast<64, 10, 101, false, false, true>}},
@@ -298,6 +339,7 @@ void bcast_free(sdrfm_bcast* h) {
   decim_free(h->au); decim_free(h->rd);
   (void)hipFree(h->d_left); (void)hipFree(h->d_right); (void)hipFree(h->d_bb);
   (void)hipFree(h->d_ctaps); (void)hipFree(h->d_rot); (void)hipFree(h->d_meters); (void)hipFree(h->d_ops); (void)hipFree(h->d_actl);
+  (void)hipFree(h->d_hist);
   free(h->rot_host); free(h->ops_host); free(h->actl_host);
   delete h;
 }
@@ -359,6 +401,15 @@ int sdrfm_bcast_create(const sdrfm_bcast_config* cfg, sdrfm_bcast_t** out) {
     snprintf(f.name[1], sizeof f.name[1], "%s blend", f.name[0]);
     for (int me = 0; me < 2; ++me)
       for (int bl = 0; bl < 2; ++bl) f.slots[me][bl] = front_slots(bcast_kernel(f.fast, tu, me, bl), f.step.lds, prop);
+    const front_lds_fn hlds = tu ? bcast_hist_lds_tuned : bcast_hist_lds;
+    f.hist_step = front_step(hlds, 64, 10, 101, bcast_tg(Ta, Tr), H, PF_FAST_NY, PF_FAST_NY - 1);
+    f.hist_fast = f.fast && f.hist_step.lds <= PF_LDS_BUDGET;
+    if (!f.hist_fast) f.hist_step = front_step_generic(hlds, T, D, P, bcast_tg(Ta, Tr), H);
+    snprintf(f.hist_name[0], sizeof f.hist_name[0], "bcast-%s%s T%u D%u P%u Ta%u Da%u Tr%u Dr%u + hist", f.hist_fast ? "fast" : "generic",
+             tu ? "-tuned" : "", T, D, P, Ta, Da, Tr, Dr);
+    snprintf(f.hist_name[1], sizeof f.hist_name[1], "bcast-%s%s T%u D%u P%u Ta%u Da%u Tr%u Dr%u blend + hist", f.hist_fast ? "fast" : "generic",
+             tu ? "-tuned" : "", T, D, P, Ta, Da, Tr, Dr);
+    for (int bl = 0; bl < 2; ++bl) f.hist_slots[bl] = front_slots(bcast_kernel(f.hist_fast, tu, true, bl, true), f.hist_step.lds, prop);
   }
   h->meter_ok = meter_taps_ok(h->f.hc, 1, T, METER_MAX_CTAP_SUM) && meter_taps_ok(h->f.bc, 1, 2 * P, METER_MAX_PTAP_SUM);
   rc = sdrfm_bcast_reset(h);
@@ -401,12 +452,15 @@ static int bcast_stage_in(const sdrfm_bcast* h, const uint8_t* iq, size_t iq_str
   return hipMemcpyAsync(h->f.d_iq, iq, nbytes, hipMemcpyHostToDevice, h->f.stream) == hipSuccess ? SDRFM_OK : SDRFM_FAIL;
 }
 
-// one call on device buffers, enqueued on the handle's stream; d_meters: a metered call's records, nullptr for a plain call
+// one call on device buffers, enqueued on the handle's stream; d_meters: a metered call's records, nullptr for a plain call; d_hist: a hist
+// call's rows, nullptr for any other
 static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, float* d_left, float* d_right, size_t audio_stride,
-                         float* d_bb, size_t bb_stride, uint32_t* d_pc, sdrfm_scan_meter* d_meters, uint32_t* n_audio, uint32_t* n_rds) {
+                         float* d_bb, size_t bb_stride, uint32_t* d_pc, sdrfm_scan_meter* d_meters, uint32_t* d_hist, size_t hist_stride,
+                         uint32_t* n_audio, uint32_t* n_rds) {
   const uint32_t ns = h->cfg.n_streams;
   const BcastForm& form = h->form[h->tuned];
-  const FrontStep& step = form.step;
+  const bool hist = d_hist != nullptr;
+  const FrontStep& step = hist ? form.hist_step : form.step;
   if (step.lds > PF_LDS_BUDGET) return SDRFM_FAIL;               // (no shape within the header's limits gets here: NY = 2 fits them all)
   BcastParams p;
   memset(&p, 0, sizeof p);
@@ -426,13 +480,15 @@ static int bcast_enqueue(sdrfm_bcast* h, const uint8_t* d_iq, size_t iq_stride, 
   p.zplane = rds_zplane(p.Tr, p.NDT);
   p.meters = reinterpret_cast<unsigned long long*>(d_meters);
   p.actl = h->d_actl; p.slew = h->slew; p.J = h->J;
+  p.hist = d_hist; p.hist_stride = hist_stride;
   const bool metered = d_meters != nullptr;
-  p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, form.slots[metered][h->blend]);   // as the RDS handle chooses them
+  p.blocks_per_stream = front_split(M, p.NDT, p.H, ns, hist ? form.hist_slots[h->blend] : form.slots[metered][h->blend]);   // as the RDS handle chooses them
   p.span = M ? (M + p.blocks_per_stream - 1) / p.blocks_per_stream : 0;
   if (front_zero_count(h->f, d_pc, true) != SDRFM_OK) return SDRFM_FAIL;
   if (d_meters && hipMemsetAsync(d_meters, 0, sizeof(sdrfm_scan_meter) * ns, h->f.stream) != hipSuccess) return SDRFM_FAIL;
+  if (hist && hipMemset2DAsync(d_hist, sizeof(uint32_t) * hist_stride, 0, HIST_LDS_BYTES, ns, h->f.stream) != hipSuccess) return SDRFM_FAIL;
   const dim3 grid(ns * p.blocks_per_stream), block(PF_THREADS);
-  const bcast_kernel_fn kernel = bcast_kernel(form.fast, h->tuned, metered, h->blend);
+  const bcast_kernel_fn kernel = bcast_kernel(hist ? form.hist_fast : form.fast, h->tuned, metered, h->blend, hist);
   kernel<<<grid, block, step.lds, h->f.stream>>>(p);
   if (hipGetLastError() != hipSuccess) return SDRFM_FAIL;
   front_advance(h->f, p.N);
@@ -449,12 +505,17 @@ static uint32_t bcast_max_bytes(const sdrfm_bcast* h, bool metered) {
   return metered && h->f.max_bytes > METER_MAX_BYTES ? METER_MAX_BYTES : h->f.max_bytes;
 }
 
-// a call of no bytes: no launch, no outputs, the counts and a metered call's records are 0
-static int bcast_empty_call(const sdrfm_bcast* h, uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t flags) {
-  const size_t bytes = sizeof(sdrfm_scan_meter) * h->cfg.n_streams;
+// a call of no bytes: no launch, no outputs, the counts, a metered call's records and a hist call's rows are 0
+static int bcast_empty_call(const sdrfm_bcast* h, uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* hist, size_t hist_stride, uint32_t flags) {
+  const uint32_t ns = h->cfg.n_streams;
+  const size_t bytes = sizeof(sdrfm_scan_meter) * ns;
   if (meters && !(flags & SDRFM_F_DEVICE_PTRS)) memset(meters, 0, bytes);
   if (meters && (flags & SDRFM_F_DEVICE_PTRS) &&
       (hipSetDevice(h->f.device) != hipSuccess || hipMemsetAsync(meters, 0, bytes, h->f.stream) != hipSuccess))
+    return SDRFM_FAIL;
+  for (uint32_t s = 0; hist && !(flags & SDRFM_F_DEVICE_PTRS) && s < ns; ++s) memset(hist + (size_t)s * hist_stride, 0, HIST_LDS_BYTES);
+  if (hist && (flags & SDRFM_F_DEVICE_PTRS) &&
+      hipMemset2DAsync(hist, sizeof(uint32_t) * hist_stride, 0, HIST_LDS_BYTES, ns, h->f.stream) != hipSuccess)
     return SDRFM_FAIL;
   return front_empty_call(h->f, pilot_count, flags);
 }
@@ -466,12 +527,21 @@ static int bcast_meters_back(const sdrfm_bcast* h, sdrfm_scan_meter* meters) {
   return e == hipSuccess ? SDRFM_OK : SDRFM_FAIL;
 }
 
-// the three process_batch entries.  sink == nullptr: the plain call.  With a sink, behind the launch on the handle's stream the stereo sink's
+// a host-buffer hist call's rows back, likewise
+static int bcast_hist_back(const sdrfm_bcast* h, uint32_t* hist, size_t hist_stride) {
+  if (!hist) return SDRFM_OK;
+  const hipError_t e = hipMemcpy2DAsync(hist, sizeof(uint32_t) * hist_stride, h->d_hist, HIST_LDS_BYTES, HIST_LDS_BYTES, h->cfg.n_streams,
+                                        hipMemcpyDeviceToHost, h->f.stream);
+  return e == hipSuccess ? SDRFM_OK : SDRFM_FAIL;
+}
+
+// the four process_batch entries.  sink == nullptr: the plain call.  With a sink, behind the launch on the handle's stream the stereo sink's
 // default kernel over this call's L and R rows, which are the handle's own where the caller gives none.  With `meters` the
-// metered call of either form: the same checks in the same order, the same launch geometry
+// metered call of either form: the same checks in the same order, the same launch geometry.  With `hist` besides the hist call of either:
+// the same checks again, the hist kernels' step
 static int bcast_batch(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left,
                        float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride, uint32_t* pilot_count,
-                       sdrfm_scan_meter* meters, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
+                       sdrfm_scan_meter* meters, uint32_t* hist, size_t hist_stride, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
   if (!h || !n_audio || !n_rds) return SDRFM_EINVAL;
   if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;       // SDRFM_F_OVERLAP: not for this handle
   if (sink && !left != !right) return SDRFM_EINVAL;            // both, or neither: the sink then reads the handle's own rows
@@ -486,7 +556,7 @@ static int bcast_batch(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const ui
   if (nbytes == 0) {
     *n_audio = 0;
     *n_rds = 0;
-    return bcast_empty_call(h, pilot_count, meters, flags);
+    return bcast_empty_call(h, pilot_count, meters, hist, hist_stride, flags);
   }
   if (!iq) return SDRFM_EINVAL;
   if (ns > 1 && !bcast_shared(h) && iq_stride < nbytes) return SDRFM_ECAPACITY;
@@ -499,18 +569,19 @@ static int bcast_batch(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const ui
     float* const l = own ? h->d_left : left;
     float* const r = own ? h->d_right : right;
     const size_t as = own ? h->d_audio_stride : audio_stride;
-    rc = bcast_enqueue(h, iq, iq_stride, nbytes, l, r, as, bb, bb_stride, pilot_count, meters, n_audio, n_rds);
+    rc = bcast_enqueue(h, iq, iq_stride, nbytes, l, r, as, bb, bb_stride, pilot_count, meters, hist, hist_stride, n_audio, n_rds);
     if (rc != SDRFM_OK || !sink) return rc;
     return sdrfm_stereo_sink_launch_on(sink, l, r, as, Aa, pcm, pcm_stride, h->f.stream);
   }
 
+  if (hist && !h->d_hist && hipMalloc(&h->d_hist, (size_t)HIST_LDS_BYTES * ns) != hipSuccess) { h->d_hist = nullptr; return SDRFM_ENOMEM; }
   int16_t* d_pcm = nullptr;
   size_t d_pcm_stride = 0;
   if (sink) rc = sdrfm_stereo_sink_reserve(sink, Aa, &d_pcm, &d_pcm_stride);   // (before anything is enqueued: a refusal leaves both handles alone)
   if (rc != SDRFM_OK) return rc;
   if (bcast_stage_in(h, iq, iq_stride, nbytes) != SDRFM_OK) return SDRFM_FAIL;
   rc = bcast_enqueue(h, h->f.d_iq, h->f.d_iq_stride, nbytes, h->d_left, h->d_right, h->d_audio_stride, h->d_bb, h->d_bb_stride, h->f.d_pc,
-                     meters ? h->d_meters : nullptr, n_audio, n_rds);
+                     meters ? h->d_meters : nullptr, hist ? h->d_hist : nullptr, HIST_BINS, n_audio, n_rds);
   if (rc != SDRFM_OK) return rc;
   if (sink) rc = sdrfm_stereo_sink_launch_on(sink, h->d_left, h->d_right, h->d_audio_stride, Aa, d_pcm, d_pcm_stride, h->f.stream);
   if (rc != SDRFM_OK) return rc;
@@ -519,35 +590,55 @@ static int bcast_batch(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const ui
   if (front_copy_back(h->f, bb, bb_stride, h->d_bb, h->d_bb_stride, 2 * (size_t)Ar) != SDRFM_OK) return SDRFM_FAIL;
   if (sink && sdrfm_stereo_sink_copy_back(sink, pcm, pcm_stride, Aa, h->f.stream) != SDRFM_OK) return SDRFM_FAIL;
   if (bcast_meters_back(h, meters) != SDRFM_OK) return SDRFM_FAIL;
+  if (bcast_hist_back(h, hist, hist_stride) != SDRFM_OK) return SDRFM_FAIL;
   return front_finish(h->f, pilot_count);
 }
 
 int sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left, float* right,
                               size_t audio_stride, float* bb, size_t bb_stride, uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds,
                               uint32_t flags) {
-  return bcast_batch(h, nullptr, iq, iq_stride, nbytes, left, right, audio_stride, nullptr, 0, bb, bb_stride, pilot_count, nullptr, n_audio, n_rds,
-                     flags);
+  return bcast_batch(h, nullptr, iq, iq_stride, nbytes, left, right, audio_stride, nullptr, 0, bb, bb_stride, pilot_count, nullptr, nullptr, 0, n_audio,
+                     n_rds, flags);
 }
 
 int sdrfm_bcast_process_batch_pcm(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left,
                                   float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride,
                                   uint32_t* pilot_count, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
   if (!sink) return SDRFM_EINVAL;                                // (this entry has no plain form)
-  return bcast_batch(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, nullptr, n_audio, n_rds,
-                     flags);
+  return bcast_batch(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, nullptr, nullptr, 0, n_audio,
+                     n_rds, flags);
 }
 
 // either call above with the streams' records from the same launch.  What is the metered call's own is refused first:
-// no records to write, PCM without a sink, taps whose sums could leave int64; the form's own checks follow in its own order
+// no records to write, PCM without a sink, taps whose sums could leave int64; the form's own checks follow in its own order.  hist: the
+// hist call's rows (checked by its entry), nullptr for the metered call
+static int bcast_metered(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left,
+                         float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride, uint32_t* pilot_count,
+                         sdrfm_scan_meter* meters, uint32_t* hist, size_t hist_stride, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
+  if (!h || !meters || !n_audio || !n_rds) return SDRFM_EINVAL;
+  if (!sink && pcm) return SDRFM_EINVAL;
+  if ((uintptr_t)meters % 8 || (uintptr_t)hist % 4) return SDRFM_EINVAL;
+  if (!(h->tuned ? h->meter_ok_tuned : h->meter_ok)) return SDRFM_EINVAL;
+  return bcast_batch(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, meters, hist, hist_stride,
+                     n_audio, n_rds, flags);
+}
+
 int sdrfm_bcast_process_batch_metered(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes,
                                       float* left, float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb, size_t bb_stride,
                                       uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
-  if (!h || !meters || !n_audio || !n_rds) return SDRFM_EINVAL;
-  if (!sink && pcm) return SDRFM_EINVAL;
-  if ((uintptr_t)meters % 8) return SDRFM_EINVAL;
-  if (!(h->tuned ? h->meter_ok_tuned : h->meter_ok)) return SDRFM_EINVAL;
-  return bcast_batch(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, meters, n_audio, n_rds,
-                     flags);
+  return bcast_metered(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, meters, nullptr, 0,
+                       n_audio, n_rds, flags);
+}
+
+// the metered call with the streams' deviation histograms from the same launch.  What is the hist call's own is refused
+// first, before the handle is read; everything else is the metered call's code
+int sdrfm_bcast_process_batch_metered_hist(sdrfm_bcast_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes,
+                                           float* left, float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride, float* bb,
+                                           size_t bb_stride, uint32_t* pilot_count, sdrfm_scan_meter* meters, uint32_t* hist, size_t hist_stride,
+                                           uint32_t* n_audio, uint32_t* n_rds, uint32_t flags) {
+  if (!h || !meters || !hist || hist_stride < HIST_BINS) return SDRFM_EINVAL;
+  return bcast_metered(h, sink, iq, iq_stride, nbytes, left, right, audio_stride, pcm, pcm_stride, bb, bb_stride, pilot_count, meters, hist, hist_stride,
+                       n_audio, n_rds, flags);
 }
 
 int sdrfm_bcast_set_stream(sdrfm_bcast_t* h, void* hip_stream) {
@@ -564,6 +655,11 @@ int sdrfm_bcast_synchronize(sdrfm_bcast_t* h) {
 
 const char* sdrfm_bcast_kernel_name(const sdrfm_bcast_t* h) {
   return h ? h->form[h->tuned].name[h->blend] : "";
+}
+
+// the kernel a hist call launches now
+const char* sdrfm_bcast_hist_kernel_name(const sdrfm_bcast_t* h) {
+  return h ? h->form[h->tuned].hist_name[h->blend] : "";
 }
 
 // sdrfm_bcast_tune's and sdrfm_bcast_retune's taps and rotations: all finite, every rotation within [-pi, pi]

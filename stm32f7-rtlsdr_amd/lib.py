@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "sdrfm_bcast_process_batch_metered", "sdrfm_bcast_retune", "sdrfm_bcast_set_audio", "sdrfm_bcast_get_audio",
     "sdrfm_pcm_deemph_stereo_hicut_s16", "sdrfm_pcm_stereo_sink_set_hicut", "sdrfm_pcm_stereo_sink_get_hicut",
     "sdrfm_scan_process_batch_hist", "sdrfm_scan_hist_add", "sdrfm_scan_hist_report",
+    "sdrfm_bcast_process_batch_metered_hist", "sdrfm_bcast_hist_kernel_name",
 ]
 
 
@@ -411,5 +412,10 @@ def load_library(dev=False):
     lib.sdrfm_scan_hist_add.restype = C.c_int
     lib.sdrfm_scan_hist_report.argtypes = [vp, vp, C.c_double, u32, C.c_double, C.POINTER(ScanHistReport)]
     lib.sdrfm_scan_hist_report.restype = C.c_int
+    lib.sdrfm_bcast_process_batch_metered_hist.argtypes = [vp, vp, vp, C.c_size_t, u32, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp,
+                                                           C.c_size_t, u32p, u32p, u32]
+    lib.sdrfm_bcast_process_batch_metered_hist.restype = C.c_int
+    lib.sdrfm_bcast_hist_kernel_name.argtypes = [vp]
+    lib.sdrfm_bcast_hist_kernel_name.restype = C.c_char_p
     _libs[dev] = lib
     return lib
