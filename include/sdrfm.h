@@ -958,6 +958,78 @@ int  sdrfm_pcm_deemph_stereo_hicut_s16(const float* left, const float* right, ui
 int  sdrfm_pcm_stereo_sink_set_hicut(sdrfm_pcm_stereo_sink_t* k, const uint16_t* hicut_q15 /* n_streams, or NULL: targets kept */, uint32_t slew_q15);
 int  sdrfm_pcm_stereo_sink_get_hicut(const sdrfm_pcm_stereo_sink_t* k, uint16_t* hicut_q15, uint16_t* target_q15, uint32_t* slew_q15);
 
+/* A per-stream AUDIO METER on the stereo PCM sink: what the receiver plays, for the silence, dead-channel, anti-phase and
+ * clipping alarms.  One integer record per stream, defined on the int16 stereo PCM rows the sink wrote — pcm[2i] = L, pcm[2i + 1] = R, i < n —
+ * and on nothing else.  The input is int16, so every field is an exact integer and there is no rounding rule.
+ *
+ * Definition.  n counts sample pairs; sum_l, sum_r, sq_l, sq_r and cross are the sums of L, R, L^2, R^2 and L R; peak_* is the largest |x|
+ * (0 .. 32768); clip_* counts the samples equal to -32768 or 32767.  The three sdrfm_audio_runs describe the predicates |L| <= quiet_lsb,
+ * |R| <= quiet_lsb and both at once over the n pairs in their order: count = the pairs that satisfy it, lead = the length of the longest
+ * prefix that satisfies it throughout, trail = that of the longest such suffix, longest = the longest run of consecutive pairs that satisfy
+ * it.  A silence alarm needs the runs and not the count: programme audio passes through zero all the time.  All four are 0 for n = 0.
+ *
+ * The JOIN of a record a and the record b of the pairs that FOLLOW, sdrfm_audio_meter_add(acc = a, m = b): n, the sums, the rail counts and
+ * every runs' count add, the peaks take the maximum, and per predicate
+ *     lead    = a.lead + (a.lead == a.n ? b.lead : 0)
+ *     trail   = b.trail + (b.trail == b.n ? a.trail : 0)
+ *     longest = max(a.longest, b.longest, a.trail + b.lead)
+ * The zero record is the identity on either side.  THE JOIN IS ASSOCIATIVE AND NOT COMMUTATIVE: acc comes before m.  Any cut of the pairs
+ * into pieces joined in their order gives the same record — which is how the device computes it and how reads are accumulated.
+ * EVERY FIELD IS EXACT WHILE THE ACCUMULATED n <= 2^32 (24.8 h at 48 kHz: sq <= 2^32 2^30 and |cross| <= 2^62).  Beyond that the unsigned
+ * fields wrap and the signed ones are computed in unsigned arithmetic: nothing is undefined behaviour, and nothing is claimed.
+ *
+ * Host side, plain C with no GPU behind it (csrc/audio_meter.c):
+ *   sdrfm_pcm_audio_meter_s16   joins the record of these n pairs onto *acc: the definition as code, and the routine a board-side host uses.
+ *                               SDRFM_EINVAL for acc NULL, pcm_interleaved NULL with n > 0, quiet_lsb > 32767.
+ *   sdrfm_audio_meter_add       the ordered join above; SDRFM_EINVAL for a NULL pointer.
+ *   sdrfm_audio_meter_report    the record in physical units, computed in double.  *_dbfs are 20 log10(x / 32768), -inf for zero power; dc_*
+ *                               are the means in LSB; rail_* and quiet_* are shares of n; longest_*_s and trail_*_s are seconds at fs_audio;
+ *                               correlation = cross / sqrt(sq_l sq_r), NaN when a channel has no power; mid and side are the powers of
+ *                               (L + R) / 2 and (L - R) / 2, (sq_l + sq_r +- 2 cross) / 4 / n, in dBFS, side_mid_db their ratio (NaN when
+ *                               both are zero).  n = 0: every field NaN.  SDRFM_EINVAL for a NULL pointer or an fs_audio that is not
+ *                               finite and positive.
+ *
+ * On the sink (csrc/sdrfm_sink_stereo.hip, the kernel's body in csrc/sdrfm_audio_meter.h).  A sink is created without a meter and then
+ * allocates and launches exactly what it did before.
+ *   _meter_enable   quiet_lsb > 32767 or a NULL sink: SDRFM_EINVAL before any device work.  Allocates n_streams records on the device
+ *                   (SDRFM_ENOMEM), zeroed.  Enabling an enabled sink waits for the sink's stream, zeroes the records and takes the new threshold.
+ *   _meter_disable  waits for the sink's stream and stops the metering; the records are gone.
+ *   _meter_read     flags is a subset of SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET, out is 8-byte aligned and holds n_streams records, the sink
+ *                   is enabled: else SDRFM_EINVAL.  Host out: synchronises the sink's stream, copies and, with SDRFM_AMETER_F_RESET, zeroes the
+ *                   records.  Device out: the copy, and the zeroing, are enqueued on the sink's stream and nowhere else.
+ *   sdrfm_pcm_stereo_sink_reset also zeroes the records of an enabled sink.
+ * While enabled, EVERY launch of the sink — the default, exact, high-cut default and high-cut exact forms; sdrfm_pcm_stereo_sink_process_batch
+ * and the sink's launch behind sdrfm_stereo_process_batch_pcm, sdrfm_bcast_process_batch_pcm, sdrfm_bcast_process_batch_metered and
+ * sdrfm_bcast_process_batch_metered_hist; host and device buffers — is followed on the same stream by one launch of the meter kernel, which reads
+ * the PCM rows just written and joins the call's record onto each stream's.  The sink kernels are the same kernels with the same arguments:
+ * PCM, states and high-cut ramps keep their bits.  What lies in a row behind 2n is the caller's: it is neither read nor written.
+ * Around the one-call forms, which launch on the HANDLE's stream, call enable, disable and read only after the handle's _synchronize — the
+ * rule of sdrfm_pcm_stereo_sink_get_state. */
+typedef struct sdrfm_audio_runs { uint64_t count, lead, trail, longest; } sdrfm_audio_runs;   /* 32 bytes */
+typedef struct sdrfm_audio_meter {                 /* 192 bytes, 8-byte aligned */
+  uint64_t n;                                       /* sample pairs */
+  int64_t  sum_l, sum_r;                            /* sum L, sum R */
+  uint64_t sq_l, sq_r;                              /* sum L^2, sum R^2 */
+  int64_t  cross;                                   /* sum L R */
+  uint32_t peak_l, peak_r;                          /* max |x|, 0 .. 32768 */
+  uint64_t clip_l, clip_r;                          /* samples equal to -32768 or 32767 */
+  sdrfm_audio_runs quiet_l, quiet_r, quiet_both;    /* predicate |x| <= quiet_lsb on L, on R, on both */
+  uint64_t reserved[3];                             /* 0 */
+} sdrfm_audio_meter;
+typedef struct sdrfm_audio_report_t {
+  double rms_l_dbfs, rms_r_dbfs, peak_l_dbfs, peak_r_dbfs, dc_l, dc_r, rail_l, rail_r;
+  double quiet_l, quiet_r, quiet_both;
+  double longest_l_s, longest_r_s, longest_both_s, trail_l_s, trail_r_s, trail_both_s;
+  double correlation, mid_dbfs, side_dbfs, side_mid_db;
+} sdrfm_audio_report_t;
+#define SDRFM_AMETER_F_RESET 8u   /* flag for sdrfm_pcm_stereo_sink_meter_read (beside SDRFM_F_DEVICE_PTRS): zero the records behind the copy */
+int  sdrfm_pcm_audio_meter_s16(const int16_t* pcm_interleaved, uint32_t n, uint32_t quiet_lsb, sdrfm_audio_meter* acc);
+int  sdrfm_audio_meter_add(sdrfm_audio_meter* acc, const sdrfm_audio_meter* m);
+int  sdrfm_audio_meter_report(const sdrfm_audio_meter* m, double fs_audio, sdrfm_audio_report_t* out);
+int  sdrfm_pcm_stereo_sink_meter_enable(sdrfm_pcm_stereo_sink_t* k, uint32_t quiet_lsb);
+int  sdrfm_pcm_stereo_sink_meter_disable(sdrfm_pcm_stereo_sink_t* k);
+int  sdrfm_pcm_stereo_sink_meter_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_audio_meter* out /* n_streams records */, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ from .bcast import BroadcastDemod, BroadcastConfig
 from .scan import ScanDemod, ScanConfig, METER_DTYPE, meter_add, meter_report, find_stations, stream_status, follow_selection, scan_grid, scan_capture, pilot_snr_db, audio_policy, hicut_policy, HIST_BINS, hist_add, hist_edges_hz, hist_report, deviation_quantile, ModulationMonitor
 from .rds import RdsDemod, RdsConfig, RdsSync, RdsGroup, rds_parse, rds_encode_groups, rds_checkword, rds_group_bits
 from .spectrum import SpectrumView, SpectrumConfig, power_db
-from .sink import PcmSink, StereoPcmSink, pcm_deemph_s16_host, pcm_deemph_stereo_s16_host, pcm_deemph_stereo_hicut_s16_host, hicut_slew
+from .sink import PcmSink, StereoPcmSink, pcm_deemph_s16_host, pcm_deemph_stereo_s16_host, pcm_deemph_stereo_hicut_s16_host, hicut_slew, AUDIO_METER_DTYPE, pcm_audio_meter_host, audio_meter_add, audio_meter_report, audio_alarms, AudioMonitor
 from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain, rds_gain, rds_lowpass_taps, tuned_channel_taps, tuned_rotation, retune_carry, pilot_gain, hicut_corner_hz
 from .siggen import make_iq, make_iq_stereo, make_iq_rds, make_iq_stations, MODES
 from .frontend import ReplayFrontEnd, XferState
@@ -33,4 +33,5 @@ __all__ = [
     "retune_carry", "follow_selection", "pilot_snr_db", "audio_policy",
     "pcm_deemph_stereo_hicut_s16_host", "hicut_slew", "hicut_corner_hz", "hicut_policy",
     "HIST_BINS", "hist_add", "hist_edges_hz", "hist_report", "deviation_quantile", "ModulationMonitor",
+    "AUDIO_METER_DTYPE", "pcm_audio_meter_host", "audio_meter_add", "audio_meter_report", "audio_alarms", "AudioMonitor",
 ]

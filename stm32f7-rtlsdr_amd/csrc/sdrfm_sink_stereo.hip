@@ -24,6 +24,9 @@
  * What this sink leaves out on purpose: it takes no part in the in-launch chain protocol (sdrfm_sink_chain.h) — no tagged state slots, no waits on the
  * device, no atomics.  The state is a plain float[n_streams][2]; a stream's workgroup (its lane, in the exact form) reads it at the start and writes
  * it at the end, and calls on one HIP stream are ordered.
+ * A METERED sink (sdrfm_pcm_stereo_sink_meter_enable) follows every launch of any of the four with one launch of
+ *   k_pcm_audio_meter       one workgroup of 256 lanes per stream over the PCM row just written (sdrfm_audio_meter.h): the call's integer record
+ *                           joined onto the stream's.  A kernel of its own for the reason the sink is one: the four above keep their bits.
  */
 #include <hip/hip_runtime.h>
 
@@ -36,6 +39,7 @@
 
 #include "../../include/sdrfm.h"
 #include "sdrfm_audio_ctl.h"
+#include "sdrfm_audio_meter.h"
 #include "sdrfm_sink_hicut.h"
 #include "sdrfm_sink_kernels.h"
 #include "sdrfm_sink_stereo.h"
@@ -111,6 +115,12 @@ __global__ void __launch_bounds__(256) k_pcm_stereo_sink_hicut_scan(StereoSinkPa
   }
 }
 
+// ---- the audio meter: reads what any of the four wrote ----------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(SDRFM_AM_NT) k_pcm_audio_meter(AudioMeterParams p) {
+  __shared__ sdrfm_audio_meter part[SDRFM_AM_NT / 64];
+  audio_meter_stream(part, p);
+}
+
 }  // namespace
 
 struct sdrfm_pcm_stereo_sink {
@@ -129,6 +139,11 @@ struct sdrfm_pcm_stereo_sink {
   HicutRec* d_hc;
   uint32_t slew, J;
   bool hicut;
+  // the audio meter (sdrfm_pcm_stereo_sink_meter_enable): the streams' records on the device, from the first enable on; meter: the sink is
+  // metered and every launch is followed by the meter kernel
+  sdrfm_audio_meter* d_meter;   // [n_streams]
+  uint32_t quiet_lsb;
+  bool meter;
 };
 
 static const HicutRec HICUT_FLAT = {(uint16_t)SDRFM_ACTL_ONE, (uint16_t)SDRFM_ACTL_ONE};
@@ -141,6 +156,7 @@ static void stereo_sink_free(sdrfm_pcm_stereo_sink* k) {
   if (k->d_right) (void)hipFree(k->d_right);
   if (k->d_pcm) (void)hipFree(k->d_pcm);
   if (k->d_hc) (void)hipFree(k->d_hc);
+  if (k->d_meter) (void)hipFree(k->d_meter);
   free(k->hc_host);
   if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
   delete k;
@@ -200,6 +216,11 @@ static int stereo_sink_launch(sdrfm_pcm_stereo_sink* k, const float* left, const
   else hipLaunchKernelGGL(k_pcm_stereo_sink_scan, dim3(k->n_streams), dim3(SINK_NT), 0, stream, p, sink_carry_factor(k->alpha));
   STRY(hipGetLastError(), SDRFM_FAIL);
   k->J = audio_ctl_advance(k->J, n);                            // the samples since the last set: the next call's ramps go on from here
+  if (k->meter) {                                               // behind the rows just written, on the same stream
+    const AudioMeterParams mp = {pcm, pcm_stride, k->d_meter, n, k->quiet_lsb};
+    hipLaunchKernelGGL(k_pcm_audio_meter, dim3(k->n_streams), dim3(SDRFM_AM_NT), 0, stream, mp);
+    STRY(hipGetLastError(), SDRFM_FAIL);
+  }
   return SDRFM_OK;
 }
 
@@ -258,6 +279,7 @@ int sdrfm_pcm_stereo_sink_reset(sdrfm_pcm_stereo_sink_t* k) {
   if (!k) return SDRFM_EINVAL;
   STRY(hipSetDevice(k->device), SDRFM_FAIL);
   STRY(hipMemsetAsync(k->d_state, 0, sizeof(float) * 2 * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
+  if (k->meter) STRY(hipMemsetAsync(k->d_meter, 0, sizeof(sdrfm_audio_meter) * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
   STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
   k->J = SDRFM_ACTL_J_MAX;                                      // the high-cut's settings stay, its ramps are complete
   return SDRFM_OK;
@@ -359,6 +381,48 @@ int sdrfm_pcm_stereo_sink_get_hicut(const sdrfm_pcm_stereo_sink_t* k, uint16_t* 
     if (target_q15) target_q15[s] = r.ht;
   }
   if (slew_q15) *slew_q15 = k->hicut ? k->slew : 0u;
+  return SDRFM_OK;
+}
+
+// the audio meter.  Every check comes before any device work; enable and disable wait for the sink's stream before they change
+// what a launch may still use
+int sdrfm_pcm_stereo_sink_meter_enable(sdrfm_pcm_stereo_sink_t* k, uint32_t quiet_lsb) {
+  if (!k || quiet_lsb > SDRFM_AM_QUIET_MAX) return SDRFM_EINVAL;
+  if (hipSetDevice(k->device) != hipSuccess) return SDRFM_FAIL;
+  const size_t bytes = sizeof(sdrfm_audio_meter) * (size_t)k->n_streams;
+  if (!k->d_meter && hipMalloc(&k->d_meter, bytes) != hipSuccess) { k->d_meter = nullptr; return SDRFM_ENOMEM; }
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipMemsetAsync(k->d_meter, 0, bytes, k->stream), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  k->quiet_lsb = quiet_lsb;
+  k->meter = true;
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_stereo_sink_meter_disable(sdrfm_pcm_stereo_sink_t* k) {
+  if (!k) return SDRFM_EINVAL;
+  if (!k->meter) return SDRFM_OK;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  k->meter = false;
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_stereo_sink_meter_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_audio_meter* out, uint32_t flags) {
+  if (!k || !out || (flags & ~(SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET)) || (uintptr_t)out % 8 != 0 || !k->meter) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  const size_t bytes = sizeof(sdrfm_audio_meter) * (size_t)k->n_streams;
+  if (flags & SDRFM_F_DEVICE_PTRS) {                            // enqueued on the sink's stream, and nowhere else
+    STRY(hipMemcpyAsync(out, k->d_meter, bytes, hipMemcpyDeviceToDevice, k->stream), SDRFM_FAIL);
+    if (flags & SDRFM_AMETER_F_RESET) STRY(hipMemsetAsync(k->d_meter, 0, bytes, k->stream), SDRFM_FAIL);
+    return SDRFM_OK;
+  }
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipMemcpy(out, k->d_meter, bytes, hipMemcpyDeviceToHost), SDRFM_FAIL);
+  if (flags & SDRFM_AMETER_F_RESET) {
+    STRY(hipMemsetAsync(k->d_meter, 0, bytes, k->stream), SDRFM_FAIL);
+    STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  }
   return SDRFM_OK;
 }
 

@@ -2,6 +2,8 @@
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 STATUS = {
@@ -42,6 +44,8 @@ ABI_SYMBOLS = [
     "sdrfm_pcm_deemph_stereo_hicut_s16", "sdrfm_pcm_stereo_sink_set_hicut", "sdrfm_pcm_stereo_sink_get_hicut",
     "sdrfm_scan_process_batch_hist", "sdrfm_scan_hist_add", "sdrfm_scan_hist_report",
     "sdrfm_bcast_process_batch_metered_hist", "sdrfm_bcast_hist_kernel_name",
+    "sdrfm_pcm_audio_meter_s16", "sdrfm_audio_meter_add", "sdrfm_audio_meter_report",
+    "sdrfm_pcm_stereo_sink_meter_enable", "sdrfm_pcm_stereo_sink_meter_disable", "sdrfm_pcm_stereo_sink_meter_read",
 ]
 
 
@@ -139,6 +143,31 @@ class ScanReport(C.Structure):
 class ScanHistReport(C.Structure):
     _fields_ = [("n", C.c_uint64)] + [(n, C.c_double) for n in ("centre_hz", "peak_pos_hz", "peak_neg_hz", "peak_hz", "over_min", "over_max",
                                                                   "mpx_power_dbr")]
+
+
+class AudioRuns(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("lead", C.c_uint64), ("trail", C.c_uint64), ("longest", C.c_uint64)]
+
+
+class AudioMeter(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("sum_l", C.c_int64), ("sum_r", C.c_int64), ("sq_l", C.c_uint64), ("sq_r", C.c_uint64), ("cross", C.c_int64),
+                ("peak_l", C.c_uint32), ("peak_r", C.c_uint32), ("clip_l", C.c_uint64), ("clip_r", C.c_uint64),
+                ("quiet_l", AudioRuns), ("quiet_r", AudioRuns), ("quiet_both", AudioRuns), ("reserved", C.c_uint64 * 3)]
+
+
+# sdrfm_audio_meter as a structured dtype: StereoPcmSink.read_meters returns an array of these
+AUDIO_RUNS_DTYPE = np.dtype([("count", "<u8"), ("lead", "<u8"), ("trail", "<u8"), ("longest", "<u8")])
+AUDIO_METER_DTYPE = np.dtype([("n", "<u8"), ("sum_l", "<i8"), ("sum_r", "<i8"), ("sq_l", "<u8"), ("sq_r", "<u8"), ("cross", "<i8"),
+                              ("peak_l", "<u4"), ("peak_r", "<u4"), ("clip_l", "<u8"), ("clip_r", "<u8"), ("quiet_l", AUDIO_RUNS_DTYPE),
+                              ("quiet_r", AUDIO_RUNS_DTYPE), ("quiet_both", AUDIO_RUNS_DTYPE), ("reserved", "<u8", (3,))])
+assert AUDIO_METER_DTYPE.itemsize == C.sizeof(AudioMeter) == 192
+AMETER_F_RESET = 8      # SDRFM_AMETER_F_RESET
+
+
+class AudioReport(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("rms_l_dbfs", "rms_r_dbfs", "peak_l_dbfs", "peak_r_dbfs", "dc_l", "dc_r", "rail_l", "rail_r",
+                                          "quiet_l", "quiet_r", "quiet_both", "longest_l_s", "longest_r_s", "longest_both_s",
+                                          "trail_l_s", "trail_r_s", "trail_both_s", "correlation", "mid_dbfs", "side_dbfs", "side_mid_db")]
 
 
 class RdsGroup(C.Structure):
@@ -417,5 +446,17 @@ def load_library(dev=False):
     lib.sdrfm_bcast_process_batch_metered_hist.restype = C.c_int
     lib.sdrfm_bcast_hist_kernel_name.argtypes = [vp]
     lib.sdrfm_bcast_hist_kernel_name.restype = C.c_char_p
+    lib.sdrfm_pcm_audio_meter_s16.argtypes = [vp, u32, u32, vp]
+    lib.sdrfm_pcm_audio_meter_s16.restype = C.c_int
+    lib.sdrfm_audio_meter_add.argtypes = [vp, vp]
+    lib.sdrfm_audio_meter_add.restype = C.c_int
+    lib.sdrfm_audio_meter_report.argtypes = [vp, C.c_double, C.POINTER(AudioReport)]
+    lib.sdrfm_audio_meter_report.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_meter_enable.argtypes = [vp, u32]
+    lib.sdrfm_pcm_stereo_sink_meter_enable.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_meter_disable.argtypes = [vp]
+    lib.sdrfm_pcm_stereo_sink_meter_disable.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_meter_read.argtypes = [vp, vp, u32]
+    lib.sdrfm_pcm_stereo_sink_meter_read.restype = C.c_int
     _libs[dev] = lib
     return lib

@@ -251,3 +251,125 @@ class StereoPcmSink:
         self._ck(self._lib.sdrfm_pcm_stereo_sink_process_batch(self._h, C.c_void_p(left.data_ptr()), C.c_void_p(right.data_ptr()), left.stride(0), n,
                                                                C.c_void_p(pcm.data_ptr()), pcm.stride(0), _l.F_DEVICE_PTRS | self._xf),
                  "sdrfm_pcm_stereo_sink_process_batch(device)")
+
+    # ---- the audio meter ----
+    def enable_meter(self, quiet_lsb=0):
+        """sdrfm_pcm_stereo_sink_meter_enable: from the next call on every launch of this sink is followed by the meter kernel, which joins the
+        call's record onto each stream's; a sample is quiet when |x| <= quiet_lsb (0 .. 32767).  Enabling again zeroes the records."""
+        if not 0 <= int(quiet_lsb) <= 0xFFFFFFFF:
+            raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_stereo_sink_meter_enable: quiet_lsb")
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_meter_enable(self._h, int(quiet_lsb)), "sdrfm_pcm_stereo_sink_meter_enable")
+
+    def disable_meter(self):
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_meter_disable(self._h), "sdrfm_pcm_stereo_sink_meter_disable")
+
+    def read_meters(self, reset=True):
+        """sdrfm_pcm_stereo_sink_meter_read into host memory: an AUDIO_METER_DTYPE array [n_streams], what the sink has written since the records
+        were last zeroed; reset=True zeroes them behind the copy, so that successive reads join with audio_meter_add (AudioMonitor does)."""
+        out = np.zeros(self.n_streams, dtype=AUDIO_METER_DTYPE)
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_meter_read(self._h, out.ctypes.data, _l.AMETER_F_RESET if reset else 0), "sdrfm_pcm_stereo_sink_meter_read")
+        return out
+
+    def read_meters_device(self, out, reset=True):
+        """the same into a torch tensor on the device of at least 192 * n_streams bytes (8-byte aligned); only enqueues on the sink's stream"""
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 192 * self.n_streams
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_meter_read(self._h, C.c_void_p(out.data_ptr()), _l.F_DEVICE_PTRS | (_l.AMETER_F_RESET if reset else 0)),
+                 "sdrfm_pcm_stereo_sink_meter_read(device)")
+
+
+AUDIO_METER_DTYPE = _l.AUDIO_METER_DTYPE
+AUDIO_REPORT_FIELDS = tuple(n for n, _ in _l.AudioReport._fields_)
+
+
+def pcm_audio_meter_host(pcm, quiet_lsb=0, acc=None):
+    """sdrfm_pcm_audio_meter_s16 (the host-side C routine, the definition of the record): pcm int16 [2n] or [streams, 2n], L and R interleaved
+    -> an AUDIO_METER_DTYPE array, one record per row, joined onto acc (records of the pairs before) when that is given."""
+    lib = _l.load_library()
+    rows = np.ascontiguousarray(np.atleast_2d(pcm), dtype=np.int16)
+    assert rows.ndim == 2 and rows.shape[1] % 2 == 0, rows.shape
+    if not 0 <= int(quiet_lsb) <= 0xFFFFFFFF:
+        raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_audio_meter_s16: quiet_lsb")
+    out = np.zeros(rows.shape[0], dtype=AUDIO_METER_DTYPE) if acc is None else np.ascontiguousarray(np.atleast_1d(acc), dtype=AUDIO_METER_DTYPE).copy()
+    assert out.shape == (rows.shape[0],), out.shape
+    for k in range(rows.shape[0]):
+        st = lib.sdrfm_pcm_audio_meter_s16(rows[k].ctypes.data if rows.shape[1] else None, rows.shape[1] // 2, int(quiet_lsb), out.ctypes.data + 192 * k)
+        if st != _l.OK:
+            raise _l.SdrfmError(st, "sdrfm_pcm_audio_meter_s16")
+    return out
+
+
+def audio_meter_add(acc, m):
+    """acc = acc then m through sdrfm_audio_meter_add, record by record (AUDIO_METER_DTYPE arrays of one shape).  The join is ordered: m holds
+    the pairs that FOLLOW acc's.  Returns acc."""
+    lib = _l.load_library()
+    assert acc.dtype == AUDIO_METER_DTYPE and m.dtype == AUDIO_METER_DTYPE and acc.shape == m.shape and acc.flags.c_contiguous
+    m = np.ascontiguousarray(m)
+    for k in range(acc.size):
+        st = lib.sdrfm_audio_meter_add(acc.ctypes.data + 192 * k, m.ctypes.data + 192 * k)
+        if st != _l.OK:
+            raise _l.SdrfmError(st, "sdrfm_audio_meter_add")
+    return acc
+
+
+def audio_meter_report(meters, fs_audio=48000.0):
+    """records -> dict of float64 arrays, one entry per field of sdrfm_audio_report_t, through sdrfm_audio_meter_report"""
+    lib = _l.load_library()
+    meters = np.ascontiguousarray(np.atleast_1d(meters), dtype=AUDIO_METER_DTYPE)
+    out = {n: np.empty(meters.size, np.float64) for n in AUDIO_REPORT_FIELDS}
+    r = _l.AudioReport()
+    for k in range(meters.size):
+        st = lib.sdrfm_audio_meter_report(meters.ctypes.data + 192 * k, float(fs_audio), C.byref(r))
+        if st != _l.OK:
+            raise _l.SdrfmError(st, "sdrfm_audio_meter_report")
+        for n in AUDIO_REPORT_FIELDS:
+            out[n][k] = getattr(r, n)
+    return out
+
+
+# audio_alarms' thresholds: a silence of two seconds; L and R at a correlation of -0.5 or below; a side signal 40 dB below the mid; one sample in
+# ten thousand at a rail
+SILENCE_S, PHASE_CORR, MONO_SIDE_DB, CLIP_SHARE = 2.0, -0.5, -40.0, 1e-4
+
+
+def audio_alarms(report, silence_s=SILENCE_S, phase_corr=PHASE_CORR, mono_side_db=MONO_SIDE_DB, clip_share=CLIP_SHARE):
+    """What an audio_meter_report says about the programme, one dict per stream:
+      silent        both channels have been quiet for the last silence_s seconds or more (trail_both_s: the run is still going on)
+      left_dead     L has been quiet that long and R has not;  right_dead likewise
+      out_of_phase  the correlation of L and R is phase_corr or below
+      mono          the side signal lies mono_side_db or more below the mid signal
+      clipping      a share of clip_share or more of either channel's samples sits at a rail
+    A NaN (no samples, a channel without power) raises nothing."""
+    out = []
+    with np.errstate(invalid="ignore"):
+        for s in range(len(report["trail_both_s"])):
+            tl, tr, tb = (float(report[k][s]) for k in ("trail_l_s", "trail_r_s", "trail_both_s"))
+            silent = tb >= silence_s
+            out.append(dict(silent=bool(silent), left_dead=bool(tl >= silence_s and not tr >= silence_s), right_dead=bool(tr >= silence_s and not tl >= silence_s),
+                            out_of_phase=bool(report["correlation"][s] <= phase_corr), mono=bool(report["side_mid_db"][s] <= mono_side_db),
+                            clipping=bool(max(report["rail_l"][s], report["rail_r"][s]) >= clip_share)))
+    return out
+
+
+class AudioMonitor:
+    """Audio monitoring over the reads of a metered StereoPcmSink.  push(records) takes one read_meters(reset=True) and joins
+    it BEHIND the running records (audio_meter_add), so a silence that spans many reads is one run; summary() reads them."""
+
+    def __init__(self, n_streams, fs_audio=48000.0):
+        self.n_streams, self.fs_audio = int(n_streams), float(fs_audio)
+        self.meters = np.zeros(self.n_streams, dtype=AUDIO_METER_DTYPE)
+        self.reads = 0
+
+    def push(self, records):
+        """returns the report of this read alone"""
+        records = np.ascontiguousarray(np.atleast_1d(records), dtype=AUDIO_METER_DTYPE)
+        assert records.shape == (self.n_streams,), records.shape
+        audio_meter_add(self.meters, records)
+        self.reads += 1
+        return audio_meter_report(records, self.fs_audio)
+
+    def summary(self, **thresholds):
+        """one dict per stream: stream, n, reads, every field of the running record's report, and alarms (audio_alarms(report, **thresholds))"""
+        rep = audio_meter_report(self.meters, self.fs_audio)
+        alarms = audio_alarms(rep, **thresholds)
+        return [dict(stream=s, n=int(self.meters["n"][s]), reads=self.reads, alarms=alarms[s], **{k: float(rep[k][s]) for k in AUDIO_REPORT_FIELDS})
+                for s in range(self.n_streams)]
