@@ -2043,7 +2043,9 @@ int sdrfm_ring_submit(sdrfm_ring_t* r, const uint8_t* iq, uint32_t nbytes) {
   HIP_TRY(hipMemcpyAsync(r->dev_iq[s], r->host_iq[s], nbytes, hipMemcpyHostToDevice, r->s_h2d), SDRFM_FAIL);
   HIP_TRY(hipEventRecord(r->ev_h2d[s], r->s_h2d), SDRFM_FAIL);
   HIP_TRY(hipStreamWaitEvent(h->stream, r->ev_h2d[s], 0), SDRFM_FAIL);
-  const int rc = enqueue(h, r->dev_iq[s], nbytes, nbytes, r->dev_audio[s], r->audio_cap, &r->n_audio[s]);
+  // (the stride of the one row is the slot's allocated size, as the staging rows' is: enqueue() takes the rows' alignment class from (pointer, stride), and
+  // with the chunk's own length a submit of 4 k + 2 bytes ran on the generic kernel where the same bytes through sdrfm_process run on design B)
+  const int rc = enqueue(h, r->dev_iq[s], ((size_t)r->slot_bytes + 255) & ~(size_t)255, nbytes, r->dev_audio[s], r->audio_cap, &r->n_audio[s]);
   if (rc != SDRFM_OK) return rc;
   HIP_TRY(hipEventRecord(r->ev_kernel[s], h->stream), SDRFM_FAIL);
   HIP_TRY(hipStreamWaitEvent(r->s_d2h, r->ev_kernel[s], 0), SDRFM_FAIL);
