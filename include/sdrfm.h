@@ -1030,6 +1030,71 @@ int  sdrfm_pcm_stereo_sink_meter_enable(sdrfm_pcm_stereo_sink_t* k, uint32_t qui
 int  sdrfm_pcm_stereo_sink_meter_disable(sdrfm_pcm_stereo_sink_t* k);
 int  sdrfm_pcm_stereo_sink_meter_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_audio_meter* out /* n_streams records */, uint32_t flags);
 
+/* A per-stream PCM RATE MATCHER behind the sinks: the int16 stereo rows either PCM sink leaves, at the DONGLE's 48 kHz, resampled
+ * per stream by an arbitrary ratio — a few ppm to lock onto the consumer's clock, or 48/44.1 — on the device.  All arithmetic is integer and
+ * exact: the device and the host routine agree bit for bit, and any cut of a stream into calls gives the same outputs.
+ *
+ * Rows.  in[s * in_stride + 2i] = L, [... + 2i + 1] = R, i < n: what both sinks write (the mono sink's L = R rows as well); out likewise.
+ * Per-stream state.  step, 32.32 fixed point: input pairs per output pair, 2^30 <= step <= 2^34, 2^32 after create.  pos, 32.32, measured against
+ * the call's first new pair, and hist, the last n_taps - 1 input pairs: both 0 after create and reset.
+ * Table, given at create: coef[(NPH + 1)][n_taps] int16 in Q15, NPH = 2^log2_phases, 4 <= log2_phases <= 8, n_taps a multiple of 4 in 4 .. 64.
+ * Row p serves the fraction p / NPH; row NPH is there so that the interpolation never wraps.  A table is taken only if in every row the sum of
+ * |coef| over the taps [0, n_taps / 2) is <= 65535 and likewise over [n_taps / 2, n_taps) (sdrfm_pcm_rate_check_coef): a half-row dot product
+ * with any int16 input then fits an int32, which is what lets the kernel use 32-bit packed dot products and stay exact.
+ *
+ * One call of n <= 2^20 pairs, x[i] the new pairs for i >= 0 and hist for i < 0:
+ *     cnt  = pos >= n 2^32 ? 0 : ceil((n 2^32 - pos) / step)
+ *     for j < cnt:  P = pos + j step,  i = P >> 32,  f = P & 0xffffffff,  p = f >> (32 - log2_phases),  mu = (f >> (24 - log2_phases)) & 255
+ *         per channel  A0 = sum_k coef[p][k] x[i - n_taps + 1 + k],  A1 the same with row p + 1
+ *         y[j] = sat16((A0 (256 - mu) + A1 mu + 2^22) >> 23)         64-bit, arithmetic shift
+ *     pos <- pos + cnt step - n 2^32;  hist <- the last n_taps - 1 pairs of (hist, the n new pairs), also for n < n_taps - 1
+ * A new step takes effect at the next call's first output.  Output j sits at input time (i - n_taps / 2) + f / 2^32: the latency is n_taps / 2
+ * input pairs.
+ *
+ * Host side, plain C with no GPU behind it (csrc/pcm_rate.c):
+ *   sdrfm_pcm_rate_s16         one stream's call, the definition as code; the caller carries *pos and hist (2 (n_taps - 1) int16, zero at the start).
+ *                              SDRFM_EINVAL: coef, pos, hist or n_out NULL, in NULL with n > 0, out NULL with outputs to write, a table shape, a
+ *                              step or an n outside the ranges above.  SDRFM_ECAPACITY: the call yields more than out_cap_pairs — nothing is
+ *                              written and *pos and hist stay.  It accumulates in 64 bits and so does not ask for the half-row bound.
+ *   sdrfm_pcm_rate_check_coef  SDRFM_OK for a table the device takes, SDRFM_EINVAL otherwise.
+ *
+ * The handle follows sdrfm_pcm_stereo_sink_*'s contract:
+ *   create    config or out NULL, n_streams == 0, flags != 0, a table shape outside the ranges or a table over the bound: SDRFM_EINVAL before any
+ *             device is looked for; a missing or non-gfx950 device: SDRFM_NO_DEVICE.  The table is copied.
+ *   set_step  one step per stream; any outside [2^30, 2^34]: SDRFM_EINVAL and every step stays.  Waits for the handle's stream.
+ *   count     what the NEXT call of n pairs yields: n_out[s] per stream (or NULL) and *max_out, their maximum (or NULL); n > 2^20: SDRFM_EINVAL.
+ *   process_batch   Every refusal is made before anything is enqueued and leaves the handle as it was: flags outside SDRFM_F_DEVICE_PTRS, n > 2^20,
+ *             an odd in_stride or out_stride (int16 elements): SDRFM_EINVAL; then n == 0 is a no-op; then in or out NULL, or device rows that are
+ *             not 4-byte aligned: SDRFM_EINVAL; with more than one stream in_stride < 2n or out_stride < 2 max cnt: SDRFM_ECAPACITY.  n_out (host
+ *             memory, n_streams, or NULL) is filled at return even when the call only enqueues: cnt and pos are closed forms of (pos, step, n)
+ *             and the handle keeps a host mirror of them.  Exactly 2 cnt[s] int16 are written per row; what lies behind them is the caller's.
+ *             With SDRFM_F_DEVICE_PTRS the rows are device memory and the call only enqueues on the handle's stream: give it the sink's or the
+ *             demodulator's stream (or synchronise) so that it runs after the PCM exists.  With host buffers the call stages, runs, copies back and
+ *             is synchronous.
+ *   get_state synchronises the handle's stream and gives the steps and the DEVICE's pos (either may be NULL); SDRFM_FAIL should the device's pos
+ *             differ from the host mirror.
+ *   reset     pos and hist to 0, the steps stay.
+ *   NULL handles answer SDRFM_EINVAL (destroy: nothing; kernel_name: NULL).
+ * The kernel (csrc/sdrfm_pcm_rate.hip, its body and the launch geometry in csrc/sdrfm_pcm_rate.h): one workgroup per stream and span of
+ * consecutive outputs, the table and the span's input window in LDS.  pos and hist live on the device in two sets; a call reads one and writes the
+ * other, and calls are ordered by the HIP stream they are enqueued on.  kernel name: "pcm-rate". */
+typedef struct sdrfm_pcm_rate sdrfm_pcm_rate_t;
+typedef struct sdrfm_pcm_rate_config { uint32_t n_streams, n_taps, log2_phases, flags; const int16_t* coef; int32_t device; } sdrfm_pcm_rate_config;
+int  sdrfm_pcm_rate_create(const sdrfm_pcm_rate_config* config, sdrfm_pcm_rate_t** out);   /* every step starts at 2^32 */
+void sdrfm_pcm_rate_destroy(sdrfm_pcm_rate_t* k);
+int  sdrfm_pcm_rate_reset(sdrfm_pcm_rate_t* k);                                             /* pos, hist = 0; steps kept */
+int  sdrfm_pcm_rate_set_step(sdrfm_pcm_rate_t* k, const uint64_t* step /* n_streams */);
+int  sdrfm_pcm_rate_count(const sdrfm_pcm_rate_t* k, uint32_t n, uint32_t* n_out /* n_streams, or NULL */, uint32_t* max_out);
+int  sdrfm_pcm_rate_process_batch(sdrfm_pcm_rate_t* k, const int16_t* in, size_t in_stride, uint32_t n, int16_t* out, size_t out_stride,
+                                  uint32_t* n_out /* host, n_streams, or NULL */, uint32_t flags);
+int  sdrfm_pcm_rate_get_state(sdrfm_pcm_rate_t* k, uint64_t* step, uint64_t* pos);          /* synchronises; the DEVICE's pos */
+int  sdrfm_pcm_rate_set_stream(sdrfm_pcm_rate_t* k, void* hip_stream);
+int  sdrfm_pcm_rate_synchronize(sdrfm_pcm_rate_t* k);
+const char* sdrfm_pcm_rate_kernel_name(const sdrfm_pcm_rate_t* k);
+int  sdrfm_pcm_rate_s16(const int16_t* in, uint32_t n, const int16_t* coef, uint32_t n_taps, uint32_t log2_phases, uint64_t step, uint64_t* pos,
+                        int16_t* hist /* 2 * (n_taps - 1) */, int16_t* out, uint32_t out_cap_pairs, uint32_t* n_out);
+int  sdrfm_pcm_rate_check_coef(const int16_t* coef, uint32_t n_taps, uint32_t log2_phases);
+
 #ifdef __cplusplus
 }
 #endif

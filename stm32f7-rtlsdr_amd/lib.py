@@ -46,6 +46,9 @@ ABI_SYMBOLS = [
     "sdrfm_bcast_process_batch_metered_hist", "sdrfm_bcast_hist_kernel_name",
     "sdrfm_pcm_audio_meter_s16", "sdrfm_audio_meter_add", "sdrfm_audio_meter_report",
     "sdrfm_pcm_stereo_sink_meter_enable", "sdrfm_pcm_stereo_sink_meter_disable", "sdrfm_pcm_stereo_sink_meter_read",
+    "sdrfm_pcm_rate_create", "sdrfm_pcm_rate_destroy", "sdrfm_pcm_rate_reset", "sdrfm_pcm_rate_set_step", "sdrfm_pcm_rate_count",
+    "sdrfm_pcm_rate_process_batch", "sdrfm_pcm_rate_get_state", "sdrfm_pcm_rate_set_stream", "sdrfm_pcm_rate_synchronize",
+    "sdrfm_pcm_rate_kernel_name", "sdrfm_pcm_rate_s16", "sdrfm_pcm_rate_check_coef",
 ]
 
 
@@ -168,6 +171,11 @@ class AudioReport(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("rms_l_dbfs", "rms_r_dbfs", "peak_l_dbfs", "peak_r_dbfs", "dc_l", "dc_r", "rail_l", "rail_r",
                                           "quiet_l", "quiet_r", "quiet_both", "longest_l_s", "longest_r_s", "longest_both_s",
                                           "trail_l_s", "trail_r_s", "trail_both_s", "correlation", "mid_dbfs", "side_dbfs", "side_mid_db")]
+
+
+class PcmRateConfig(C.Structure):
+    _fields_ = [("n_streams", C.c_uint32), ("n_taps", C.c_uint32), ("log2_phases", C.c_uint32), ("flags", C.c_uint32),
+                ("coef", C.POINTER(C.c_int16)), ("device", C.c_int32)]
 
 
 class RdsGroup(C.Structure):
@@ -458,5 +466,30 @@ def load_library(dev=False):
     lib.sdrfm_pcm_stereo_sink_meter_disable.restype = C.c_int
     lib.sdrfm_pcm_stereo_sink_meter_read.argtypes = [vp, vp, u32]
     lib.sdrfm_pcm_stereo_sink_meter_read.restype = C.c_int
+    u64p = C.POINTER(C.c_uint64)
+    lib.sdrfm_pcm_rate_create.argtypes = [C.POINTER(PcmRateConfig), C.POINTER(vp)]
+    lib.sdrfm_pcm_rate_create.restype = C.c_int
+    lib.sdrfm_pcm_rate_destroy.argtypes = [vp]
+    lib.sdrfm_pcm_rate_destroy.restype = None
+    lib.sdrfm_pcm_rate_reset.argtypes = [vp]
+    lib.sdrfm_pcm_rate_reset.restype = C.c_int
+    lib.sdrfm_pcm_rate_set_step.argtypes = [vp, vp]
+    lib.sdrfm_pcm_rate_set_step.restype = C.c_int
+    lib.sdrfm_pcm_rate_count.argtypes = [vp, u32, vp, u32p]
+    lib.sdrfm_pcm_rate_count.restype = C.c_int
+    lib.sdrfm_pcm_rate_process_batch.argtypes = [vp, vp, C.c_size_t, u32, vp, C.c_size_t, vp, u32]
+    lib.sdrfm_pcm_rate_process_batch.restype = C.c_int
+    lib.sdrfm_pcm_rate_get_state.argtypes = [vp, vp, vp]
+    lib.sdrfm_pcm_rate_get_state.restype = C.c_int
+    lib.sdrfm_pcm_rate_set_stream.argtypes = [vp, vp]
+    lib.sdrfm_pcm_rate_set_stream.restype = C.c_int
+    lib.sdrfm_pcm_rate_synchronize.argtypes = [vp]
+    lib.sdrfm_pcm_rate_synchronize.restype = C.c_int
+    lib.sdrfm_pcm_rate_kernel_name.argtypes = [vp]
+    lib.sdrfm_pcm_rate_kernel_name.restype = C.c_char_p
+    lib.sdrfm_pcm_rate_s16.argtypes = [vp, u32, vp, u32, u32, C.c_uint64, u64p, vp, vp, u32, u32p]
+    lib.sdrfm_pcm_rate_s16.restype = C.c_int
+    lib.sdrfm_pcm_rate_check_coef.argtypes = [vp, u32, u32]
+    lib.sdrfm_pcm_rate_check_coef.restype = C.c_int
     _libs[dev] = lib
     return lib

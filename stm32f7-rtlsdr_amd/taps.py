@@ -99,3 +99,24 @@ def pilot_gain(D, fs, f_pilot=19e3):
     2.4 MS/s): a pilot of deviation v Hz has |q| = 2 pi v D / fs * H_D, which is how sdrfm_scan_report turns pilot_rms_rad into Hz."""
     x = np.pi * f_pilot / fs
     return float(np.sin(x * D) / (D * np.sin(x)))
+
+
+def rate_coef(NT=32, LOGPH=8, cutoff=None, beta=9.0, step=1 << 32):
+    """the coefficient table of the PCM rate matcher: int16 [(2^LOGPH + 1), NT] in Q15,
+    coef[p][k] = Q15(h(k - NT/2 + 1 - p / 2^LOGPH)) with h(t) = cutoff sinc(cutoff t) Kaiser(beta) over |t| <= NT/2 — row p interpolates at the
+    fraction p / 2^LOGPH, row 2^LOGPH is the next pair's row 0 moved by one tap.  cutoff is in units of the INPUT's Nyquist frequency; the
+    default, 0.9 min(1, 2^32 / step), keeps the images of a step above one pair per output below the output's Nyquist frequency.  Each row is
+    normalised to sum 1, rounded, and its largest tap adjusted so that the row sums to exactly 32768: a constant input comes out as itself."""
+    NT, LOGPH = int(NT), int(LOGPH)
+    if cutoff is None:
+        cutoff = 0.9 * min(1.0, float(1 << 32) / float(step))
+    nph = 1 << LOGPH
+    t = np.arange(NT, dtype=np.float64)[None, :] - NT / 2 + 1 - np.arange(nph + 1, dtype=np.float64)[:, None] / nph
+    u = np.clip(1.0 - (2.0 * t / NT) ** 2, 0.0, None)
+    h = float(cutoff) * np.sinc(float(cutoff) * t) * np.i0(float(beta) * np.sqrt(u)) / np.i0(float(beta)) * (np.abs(t) <= NT / 2)
+    q = np.rint(h / h.sum(axis=1, keepdims=True) * 32768.0).astype(np.int64)
+    rows = np.arange(nph + 1)
+    q[rows, np.argmax(q, axis=1)] += 32768 - q.sum(axis=1)
+    if q.max() > 32767 or q.min() < -32768:
+        raise ValueError("rate_coef: a tap does not fit Q15 (cutoff %g at %d taps)" % (cutoff, NT))
+    return q.astype(np.int16)
