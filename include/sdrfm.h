@@ -1095,6 +1095,97 @@ int  sdrfm_pcm_rate_s16(const int16_t* in, uint32_t n, const int16_t* coef, uint
                         int16_t* hist /* 2 * (n_taps - 1) */, int16_t* out, uint32_t out_cap_pairs, uint32_t* n_out);
 int  sdrfm_pcm_rate_check_coef(const int16_t* coef, uint32_t n_taps, uint32_t log2_phases);
 
+/* A per-stream K-WEIGHTED LOUDNESS METER on the stereo PCM sink: ITU-R BS.1770-4 / EBU R 128 momentary, short-term and
+ * integrated loudness in LUFS and loudness range (EBU Tech 3342) of what the receiver plays.  The device filters the int16 stereo PCM rows the
+ * sink wrote and leaves sub-block energies; a small host object turns those into M, S, I and LRA.  No PCM is copied to the host.
+ *
+ * Coefficients.  sdrfm_loudness_coef holds 10 doubles, two biquads with a0 = 1: c[0 .. 4] = b0 b1 b2 a1 a2 of the high shelf, c[5 .. 9] those of
+ * the 38 Hz high-pass.  sdrfm_loudness_default_coef fills in the 48 kHz values printed in BS.1770-4; coefficients for another rate are the
+ * caller's business.  sdrfm_loudness_check_coef: SDRFM_EINVAL for NULL, a non-finite value, or poles not strictly inside the unit circle
+ * (|a2| < 1 and |a1| < 1 + a2 for either biquad).
+ *
+ * State, per stream (sdrfm_loudness_state, 88 bytes): pos, the pairs consumed since enable or reset; z[channel][4], both biquads in TRANSPOSED
+ * DIRECT FORM II, z = {shelf s1, shelf s2, high-pass s1, high-pass s2}; e[channel], the running energy of the open sub-block.
+ *
+ * Definition, one pair after the other, x in int16 LSB units with no scaling by 32768, every product and sum rounded on its own in double:
+ *     y1 = b0 x + s1;   s1 = (b1 x - a1 y1) + s2;   s2 = b2 x - a2 y1        (shelf), then the same with x = y1 and the high-pass: y2
+ *     e[ch] += y2 y2;   ++pos;   when pos is a multiple of block_len: emit {e[0], e[1]} and zero e
+ * Sub-block k is pairs [k block_len, (k + 1) block_len) of the stream, counted from enable or reset; its record is sdrfm_loudness_block
+ * {e_l, e_r} = the sums of y_L^2 and y_R^2 of the K-weighted samples, in LSB^2.
+ *
+ * Host side, plain C with no GPU behind it (csrc/loudness.c):
+ *   sdrfm_pcm_loudness_s16   walks n pairs as above from *state: the definition as code, and the routine a board-side host runs.  SDRFM_EINVAL:
+ *                            state, coef or n_blocks NULL, pcm_interleaved NULL with n > 0, coefficients sdrfm_loudness_check_coef refuses,
+ *                            block_len outside 64 .. 2^20, out_blocks NULL when the call completes a sub-block.  SDRFM_ECAPACITY: the call
+ *                            completes more than out_cap sub-blocks — nothing is written and *state stays.
+ *   sdrfm_loudness_gate_*    one stream's gate.  _push takes CONSECUTIVE sub-block energies.  With z[k] = (e_l + e_r) / (block_len 32768^2):
+ *                            momentary loudness M = -0.691 + 10 log10 of the mean of the last 4 z, short-term S the same over the last 30 z;
+ *                            a gating block is every window of 4 consecutive sub-blocks (75 % overlap, one per sub-block from the fourth on);
+ *                            integrated loudness I keeps the gating blocks above the absolute gate (> -70 LUFS), then those above the relative
+ *                            gate (> 10 LU below the mean of the absolute-gated), and takes the mean of z over what remains; loudness range LRA
+ *                            keeps the short-term values, one per sub-block from the thirtieth on, above the absolute gate and above 20 LU below
+ *                            their absolute-gated power mean, and is their 95th minus their 10th percentile.  THE COUNTS 4 AND 30 MEAN 400 ms AND
+ *                            3 s ONLY WHEN block_len IS A TENTH OF A SECOND (4800 at 48 kHz).  Memory is bounded: two histograms of 0.1 LU bins
+ *                            over -70 .. +10 LUFS (louder values go into the last bin) with a count and a sum of z per bin; the relative gates
+ *                            are applied at bin edges — the bin that holds the gate is kept whole — and a percentile is the mean loudness of
+ *                            the bin that holds the element of rank round((n - 1) p).  _report: m, s, i, lra, max_m, max_s; NaN where there are
+ *                            too few sub-blocks (fewer than 4 for m, max_m and i, fewer than 30 for s, max_s and lra; lra also when no
+ *                            short-term value passed the absolute gate), -inf for zero power (i: no gating block passed the gates); n_blocks
+ *                            pushed, n_gating gating blocks, n_abs and n_rel of them past either gate, n_short, n_short_abs, n_short_rel
+ *                            likewise for the short-term values.  create: block_len outside 64 .. 2^20 or out NULL: SDRFM_EINVAL.  push: a
+ *                            NULL gate, blocks NULL with n > 0, or an energy that is negative or not finite (nothing of the push is taken):
+ *                            SDRFM_EINVAL.  _reset empties it, _free releases it (NULL: nothing).
+ *
+ * On the sink (csrc/sdrfm_sink_stereo.hip, the kernel's body in csrc/sdrfm_loudness.h).  A sink that never enables loudness allocates and
+ * launches exactly what it did before.
+ *   _loudness_enable   coef NULL means the default coefficients.  A NULL sink, refused coefficients, block_len outside 64 .. 2^20, cap_blocks
+ *                      outside 1 .. 4096: SDRFM_EINVAL before any device work.  Allocates per stream the state and a ring of cap_blocks
+ *                      sdrfm_loudness_block, zeroed (SDRFM_ENOMEM), and computes in double on the host the powers of the per-channel 4 x 4
+ *                      transition matrix the kernel's scan uses.  Enabling an enabled sink waits for its stream and starts over.
+ *   _loudness_disable  waits for the sink's stream, stops the metering and frees the state and the ring.
+ *   _loudness_read     flags must be 0, out is host memory, first_block and n_blocks are not NULL, the sink is enabled: else SDRFM_EINVAL.
+ *                      Synchronises the sink's stream and copies, per stream, the sub-blocks completed and not yet read, laid out
+ *                      out[s * (*n_blocks) + j]; *first_block is the stream-global index of the first one.  More than out_cap_blocks of them:
+ *                      SDRFM_ECAPACITY and nothing is consumed.  out may be NULL when there is nothing to return.
+ *   _loudness_get_state  synchronises the sink's stream and copies the n_streams device states.
+ *   sdrfm_pcm_stereo_sink_reset also zeroes an enabled sink's loudness states and ring; sub-block indices start at 0 again.
+ * Every stream of a sink receives the same n in every call, so sub-block boundaries coincide across streams and the host mirrors pos: it knows at
+ * return how many sub-blocks a call completed.  The ring keeps the newest cap_blocks; a gap shows in *first_block; a single call that completes
+ * more than cap_blocks stores exactly the newest cap_blocks, each slot written once.
+ * While enabled, EVERY launch of the sink — its four forms; sdrfm_pcm_stereo_sink_process_batch with host or device buffers; the sink's launch
+ * behind sdrfm_stereo_process_batch_pcm, sdrfm_bcast_process_batch_pcm, sdrfm_bcast_process_batch_metered and
+ * sdrfm_bcast_process_batch_metered_hist — is followed on the same stream by one launch of k_pcm_loudness over the rows just written, behind the
+ * audio meter's kernel if that is enabled too.  The sink's and the meter's kernels are the same kernels with the same arguments: PCM, states,
+ * high-cut ramps and audio-meter records keep their bits.  What lies in a row behind 2n is the caller's: it is neither read nor written.
+ * The kernel: one workgroup of 256 lanes per stream, a tile of 4864 pairs cut into 256 chunks of 19; each chunk filtered from zero state in
+ * double, a scan over lanes with the matrix powers for the true incoming states, a second pass that sums y^2, and one lane per sub-block and
+ * channel adding the chunks' pieces in lane order — no atomics, so the same call sequence gives the same bits.  Its energies differ from the
+ * definition's by rounding only (DESIGN.md §4.22 gives the measured bound the tests hold it to); pos and the block bookkeeping are exact.
+ * Around the one-call forms, which launch on the HANDLE's stream, call enable, disable, read and get_state only after the handle's _synchronize
+ * — the rule of sdrfm_pcm_stereo_sink_get_state. */
+typedef struct sdrfm_loudness_coef { double c[10]; } sdrfm_loudness_coef;                              /* shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 */
+typedef struct sdrfm_loudness_state { uint64_t pos; double z[2][4]; double e[2]; } sdrfm_loudness_state;   /* 88 bytes */
+typedef struct sdrfm_loudness_block { double e_l, e_r; } sdrfm_loudness_block;                         /* 16 bytes */
+typedef struct sdrfm_loudness_report_t {
+  double m, s, i, lra, max_m, max_s;                                                                   /* LUFS; lra in LU */
+  uint64_t n_blocks, n_gating, n_abs, n_rel, n_short, n_short_abs, n_short_rel;
+} sdrfm_loudness_report_t;
+typedef struct sdrfm_loudness_gate sdrfm_loudness_gate_t;
+int  sdrfm_loudness_default_coef(sdrfm_loudness_coef* out);
+int  sdrfm_loudness_check_coef(const sdrfm_loudness_coef* coef);
+int  sdrfm_pcm_loudness_s16(const int16_t* pcm_interleaved, uint32_t n, const sdrfm_loudness_coef* coef, uint32_t block_len,
+                            sdrfm_loudness_state* state, sdrfm_loudness_block* out_blocks, uint32_t out_cap, uint32_t* n_blocks);
+int  sdrfm_loudness_gate_create(uint32_t block_len, sdrfm_loudness_gate_t** out);
+int  sdrfm_loudness_gate_push(sdrfm_loudness_gate_t* g, const sdrfm_loudness_block* blocks, uint32_t n);
+int  sdrfm_loudness_gate_report(const sdrfm_loudness_gate_t* g, sdrfm_loudness_report_t* out);
+int  sdrfm_loudness_gate_reset(sdrfm_loudness_gate_t* g);
+void sdrfm_loudness_gate_free(sdrfm_loudness_gate_t* g);
+int  sdrfm_pcm_stereo_sink_loudness_enable(sdrfm_pcm_stereo_sink_t* k, const sdrfm_loudness_coef* coef /* or NULL */, uint32_t block_len, uint32_t cap_blocks);
+int  sdrfm_pcm_stereo_sink_loudness_disable(sdrfm_pcm_stereo_sink_t* k);
+int  sdrfm_pcm_stereo_sink_loudness_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_loudness_block* out /* [n_streams][*n_blocks] */, uint32_t out_cap_blocks,
+                                         uint64_t* first_block, uint32_t* n_blocks, uint32_t flags);
+int  sdrfm_pcm_stereo_sink_loudness_get_state(sdrfm_pcm_stereo_sink_t* k, sdrfm_loudness_state* out /* n_streams */);
+
 #ifdef __cplusplus
 }
 #endif

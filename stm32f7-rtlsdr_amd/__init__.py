@@ -23,6 +23,7 @@ from .rate import PcmRateMatcher, pcm_rate_host, step_for, ClockServo
 from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain, rds_gain, rds_lowpass_taps, tuned_channel_taps, tuned_rotation, retune_carry, pilot_gain, hicut_corner_hz, rate_coef
 from .siggen import make_iq, make_iq_stereo, make_iq_rds, make_iq_stations, MODES
 from .frontend import ReplayFrontEnd, XferState
+from .loudness import LOUDNESS_STATE_DTYPE, loudness_default_coef, pcm_loudness_host, LoudnessGate, LoudnessMonitor, loudness_alarms
 from . import fanout
 from . import rate
 from . import lib
@@ -36,5 +37,6 @@ __all__ = [
     "pcm_deemph_stereo_hicut_s16_host", "hicut_slew", "hicut_corner_hz", "hicut_policy",
     "HIST_BINS", "hist_add", "hist_edges_hz", "hist_report", "deviation_quantile", "ModulationMonitor",
     "AUDIO_METER_DTYPE", "pcm_audio_meter_host", "audio_meter_add", "audio_meter_report", "audio_alarms", "AudioMonitor",
+    "LOUDNESS_STATE_DTYPE", "loudness_default_coef", "pcm_loudness_host", "LoudnessGate", "LoudnessMonitor", "loudness_alarms",
     "PcmRateMatcher", "pcm_rate_host", "rate_coef", "step_for", "ClockServo", "rate",
 ]

@@ -27,6 +27,9 @@
  * A METERED sink (sdrfm_pcm_stereo_sink_meter_enable) follows every launch of any of the four with one launch of
  *   k_pcm_audio_meter       one workgroup of 256 lanes per stream over the PCM row just written (sdrfm_audio_meter.h): the call's integer record
  *                           joined onto the stream's.  A kernel of its own for the reason the sink is one: the four above keep their bits.
+ * A sink with LOUDNESS enabled (sdrfm_pcm_stereo_sink_loudness_enable) follows every launch, and the meter's if there is one, with
+ *   k_pcm_loudness          one workgroup of 256 lanes per stream over the same PCM row (sdrfm_loudness.h): K-weighting in double by a two-pass
+ *                           blocked scan, the sub-block energies into the stream's ring.
  */
 #include <hip/hip_runtime.h>
 
@@ -40,6 +43,7 @@
 #include "../../include/sdrfm.h"
 #include "sdrfm_audio_ctl.h"
 #include "sdrfm_audio_meter.h"
+#include "sdrfm_loudness.h"
 #include "sdrfm_sink_hicut.h"
 #include "sdrfm_sink_kernels.h"
 #include "sdrfm_sink_stereo.h"
@@ -121,6 +125,12 @@ __global__ void __launch_bounds__(SDRFM_AM_NT) k_pcm_audio_meter(AudioMeterParam
   audio_meter_stream(part, p);
 }
 
+// ---- the loudness meter: reads the same rows ----------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(SDRFM_LD_NT) k_pcm_loudness(LoudnessParams p) {
+  __shared__ LoudnessShared sh;
+  loudness_stream(sh, p);
+}
+
 }  // namespace
 
 struct sdrfm_pcm_stereo_sink {
@@ -144,6 +154,15 @@ struct sdrfm_pcm_stereo_sink {
   sdrfm_audio_meter* d_meter;   // [n_streams]
   uint32_t quiet_lsb;
   bool meter;
+  // the loudness meter (sdrfm_pcm_stereo_sink_loudness_enable): states, ring and matrix powers on the device while enabled; lpos mirrors the
+  // streams' pos (every stream receives the same n), lread = the sub-blocks already handed out
+  sdrfm_loudness_state* d_lstate;   // [n_streams]
+  sdrfm_loudness_block* d_lring;    // [n_streams][lcap]
+  double* d_lpw;                    // [SDRFM_LD_TABLE]
+  sdrfm_loudness_coef lcoef;
+  uint32_t lblock, lcap;
+  uint64_t lpos, lread;
+  bool loud;
 };
 
 static const HicutRec HICUT_FLAT = {(uint16_t)SDRFM_ACTL_ONE, (uint16_t)SDRFM_ACTL_ONE};
@@ -157,6 +176,9 @@ static void stereo_sink_free(sdrfm_pcm_stereo_sink* k) {
   if (k->d_pcm) (void)hipFree(k->d_pcm);
   if (k->d_hc) (void)hipFree(k->d_hc);
   if (k->d_meter) (void)hipFree(k->d_meter);
+  if (k->d_lstate) (void)hipFree(k->d_lstate);
+  if (k->d_lring) (void)hipFree(k->d_lring);
+  if (k->d_lpw) (void)hipFree(k->d_lpw);
   free(k->hc_host);
   if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
   delete k;
@@ -221,6 +243,16 @@ static int stereo_sink_launch(sdrfm_pcm_stereo_sink* k, const float* left, const
     hipLaunchKernelGGL(k_pcm_audio_meter, dim3(k->n_streams), dim3(SDRFM_AM_NT), 0, stream, mp);
     STRY(hipGetLastError(), SDRFM_FAIL);
   }
+  if (k->loud) {                                                // behind the meter, over the same rows
+    LoudnessParams lp;
+    lp.pcm = pcm; lp.pcm_stride = pcm_stride; lp.state = k->d_lstate; lp.ring = k->d_lring; lp.pw = k->d_lpw; lp.coef = k->lcoef;
+    lp.blk0 = k->lpos / k->lblock;
+    lp.keep_from = ld_keep_from((k->lpos + n) / k->lblock, k->lcap);
+    lp.n = n; lp.block_len = k->lblock; lp.cap_blocks = k->lcap; lp.off0 = (uint32_t)(k->lpos % k->lblock);
+    hipLaunchKernelGGL(k_pcm_loudness, dim3(k->n_streams), dim3(SDRFM_LD_NT), 0, stream, lp);
+    STRY(hipGetLastError(), SDRFM_FAIL);
+    k->lpos += n;                                               // the host's mirror of every stream's pos
+  }
   return SDRFM_OK;
 }
 
@@ -280,6 +312,11 @@ int sdrfm_pcm_stereo_sink_reset(sdrfm_pcm_stereo_sink_t* k) {
   STRY(hipSetDevice(k->device), SDRFM_FAIL);
   STRY(hipMemsetAsync(k->d_state, 0, sizeof(float) * 2 * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
   if (k->meter) STRY(hipMemsetAsync(k->d_meter, 0, sizeof(sdrfm_audio_meter) * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
+  if (k->loud) {
+    STRY(hipMemsetAsync(k->d_lstate, 0, sizeof(sdrfm_loudness_state) * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
+    STRY(hipMemsetAsync(k->d_lring, 0, sizeof(sdrfm_loudness_block) * (size_t)k->n_streams * k->lcap, k->stream), SDRFM_FAIL);
+    k->lpos = k->lread = 0;
+  }
   STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
   k->J = SDRFM_ACTL_J_MAX;                                      // the high-cut's settings stay, its ramps are complete
   return SDRFM_OK;
@@ -423,6 +460,84 @@ int sdrfm_pcm_stereo_sink_meter_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_audio_met
     STRY(hipMemsetAsync(k->d_meter, 0, bytes, k->stream), SDRFM_FAIL);
     STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
   }
+  return SDRFM_OK;
+}
+
+// the loudness meter.  Every check comes before any device work; enable and disable wait for the sink's stream before they
+// change or free what a launch may still use
+static void loudness_release(sdrfm_pcm_stereo_sink* k) {
+  if (k->d_lstate) (void)hipFree(k->d_lstate);
+  if (k->d_lring) (void)hipFree(k->d_lring);
+  if (k->d_lpw) (void)hipFree(k->d_lpw);
+  k->d_lstate = nullptr; k->d_lring = nullptr; k->d_lpw = nullptr;
+  k->loud = false;
+  k->lpos = k->lread = 0;
+}
+
+int sdrfm_pcm_stereo_sink_loudness_enable(sdrfm_pcm_stereo_sink_t* k, const sdrfm_loudness_coef* coef, uint32_t block_len, uint32_t cap_blocks) {
+  if (!k) return SDRFM_EINVAL;
+  sdrfm_loudness_coef c;
+  if (coef) c = *coef;
+  else (void)sdrfm_loudness_default_coef(&c);
+  if (sdrfm_loudness_check_coef(&c) != SDRFM_OK) return SDRFM_EINVAL;
+  if (block_len < SDRFM_LD_BLOCK_MIN || block_len > SDRFM_LD_BLOCK_MAX || cap_blocks < 1u || cap_blocks > SDRFM_LD_CAP_MAX) return SDRFM_EINVAL;
+  double pw[SDRFM_LD_TABLE];
+  ld_matrix_powers(c.c, pw);                                    // on the host, here: the scan's A^(L 2^i) in its balanced coordinates
+  if (hipSetDevice(k->device) != hipSuccess) return SDRFM_FAIL;
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  loudness_release(k);                                          // an enabled sink starts over
+  const size_t sb = sizeof(sdrfm_loudness_state) * (size_t)k->n_streams, rb = sizeof(sdrfm_loudness_block) * (size_t)k->n_streams * cap_blocks;
+  if (hipMalloc(&k->d_lstate, sb) != hipSuccess || hipMalloc(&k->d_lring, rb) != hipSuccess || hipMalloc(&k->d_lpw, sizeof(pw)) != hipSuccess) {
+    loudness_release(k);
+    return SDRFM_ENOMEM;
+  }
+  if (hipMemsetAsync(k->d_lstate, 0, sb, k->stream) != hipSuccess || hipMemsetAsync(k->d_lring, 0, rb, k->stream) != hipSuccess ||
+      hipMemcpyAsync(k->d_lpw, pw, sizeof(pw), hipMemcpyHostToDevice, k->stream) != hipSuccess || hipStreamSynchronize(k->stream) != hipSuccess) {
+    loudness_release(k);
+    return SDRFM_FAIL;
+  }
+  k->lcoef = c; k->lblock = block_len; k->lcap = cap_blocks;
+  k->loud = true;
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_stereo_sink_loudness_disable(sdrfm_pcm_stereo_sink_t* k) {
+  if (!k) return SDRFM_EINVAL;
+  if (!k->loud) return SDRFM_OK;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  loudness_release(k);
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_stereo_sink_loudness_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_loudness_block* out, uint32_t out_cap_blocks, uint64_t* first_block,
+                                        uint32_t* n_blocks, uint32_t flags) {
+  if (!k || !first_block || !n_blocks || flags || !k->loud) return SDRFM_EINVAL;
+  const uint64_t done = k->lpos / k->lblock, kept = ld_keep_from(done, k->lcap);
+  const uint64_t first = k->lread > kept ? k->lread : kept;
+  const uint32_t nb = (uint32_t)(done - first);                 // <= lcap
+  if (nb > out_cap_blocks) return SDRFM_ECAPACITY;
+  if (nb && !out) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (nb) {                                                     // the ring wraps at most once inside [first, done)
+    const uint32_t s0 = ld_ring_slot(first, k->lcap);
+    const uint32_t a = nb < k->lcap - s0 ? nb : k->lcap - s0, b = nb - a;
+    const size_t rec = sizeof(sdrfm_loudness_block);
+    STRY(hipMemcpy2D(out, rec * nb, k->d_lring + s0, rec * k->lcap, rec * a, k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
+    if (b) STRY(hipMemcpy2D(out + a, rec * nb, k->d_lring, rec * k->lcap, rec * b, k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
+  }
+  k->lread = done;
+  *first_block = first;
+  *n_blocks = nb;
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_stereo_sink_loudness_get_state(sdrfm_pcm_stereo_sink_t* k, sdrfm_loudness_state* out) {
+  if (!k || !out || !k->loud) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipMemcpy(out, k->d_lstate, sizeof(sdrfm_loudness_state) * (size_t)k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
   return SDRFM_OK;
 }
 

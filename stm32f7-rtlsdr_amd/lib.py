@@ -46,6 +46,9 @@ ABI_SYMBOLS = [
     "sdrfm_bcast_process_batch_metered_hist", "sdrfm_bcast_hist_kernel_name",
     "sdrfm_pcm_audio_meter_s16", "sdrfm_audio_meter_add", "sdrfm_audio_meter_report",
     "sdrfm_pcm_stereo_sink_meter_enable", "sdrfm_pcm_stereo_sink_meter_disable", "sdrfm_pcm_stereo_sink_meter_read",
+    "sdrfm_loudness_default_coef", "sdrfm_loudness_check_coef", "sdrfm_pcm_loudness_s16", "sdrfm_loudness_gate_create", "sdrfm_loudness_gate_push",
+    "sdrfm_loudness_gate_report", "sdrfm_loudness_gate_reset", "sdrfm_loudness_gate_free", "sdrfm_pcm_stereo_sink_loudness_enable",
+    "sdrfm_pcm_stereo_sink_loudness_disable", "sdrfm_pcm_stereo_sink_loudness_read", "sdrfm_pcm_stereo_sink_loudness_get_state",
     "sdrfm_pcm_rate_create", "sdrfm_pcm_rate_destroy", "sdrfm_pcm_rate_reset", "sdrfm_pcm_rate_set_step", "sdrfm_pcm_rate_count",
     "sdrfm_pcm_rate_process_batch", "sdrfm_pcm_rate_get_state", "sdrfm_pcm_rate_set_stream", "sdrfm_pcm_rate_synchronize",
     "sdrfm_pcm_rate_kernel_name", "sdrfm_pcm_rate_s16", "sdrfm_pcm_rate_check_coef",
@@ -171,6 +174,29 @@ class AudioReport(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("rms_l_dbfs", "rms_r_dbfs", "peak_l_dbfs", "peak_r_dbfs", "dc_l", "dc_r", "rail_l", "rail_r",
                                           "quiet_l", "quiet_r", "quiet_both", "longest_l_s", "longest_r_s", "longest_both_s",
                                           "trail_l_s", "trail_r_s", "trail_both_s", "correlation", "mid_dbfs", "side_dbfs", "side_mid_db")]
+
+
+class LoudnessCoef(C.Structure):
+    _fields_ = [("c", C.c_double * 10)]
+
+
+class LoudnessState(C.Structure):
+    _fields_ = [("pos", C.c_uint64), ("z", (C.c_double * 4) * 2), ("e", C.c_double * 2)]
+
+
+class LoudnessBlock(C.Structure):
+    _fields_ = [("e_l", C.c_double), ("e_r", C.c_double)]
+
+
+class LoudnessReport(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("m", "s", "i", "lra", "max_m", "max_s")] + [
+        (n, C.c_uint64) for n in ("n_blocks", "n_gating", "n_abs", "n_rel", "n_short", "n_short_abs", "n_short_rel")]
+
+
+# sdrfm_loudness_state and sdrfm_loudness_block as structured dtypes
+LOUDNESS_STATE_DTYPE = np.dtype([("pos", "<u8"), ("z", "<f8", (2, 4)), ("e", "<f8", (2,))])
+LOUDNESS_BLOCK_DTYPE = np.dtype([("e_l", "<f8"), ("e_r", "<f8")])
+assert LOUDNESS_STATE_DTYPE.itemsize == C.sizeof(LoudnessState) == 88 and LOUDNESS_BLOCK_DTYPE.itemsize == C.sizeof(LoudnessBlock) == 16
 
 
 class PcmRateConfig(C.Structure):
@@ -491,5 +517,29 @@ def load_library(dev=False):
     lib.sdrfm_pcm_rate_s16.restype = C.c_int
     lib.sdrfm_pcm_rate_check_coef.argtypes = [vp, u32, u32]
     lib.sdrfm_pcm_rate_check_coef.restype = C.c_int
+    lib.sdrfm_loudness_default_coef.argtypes = [vp]
+    lib.sdrfm_loudness_default_coef.restype = C.c_int
+    lib.sdrfm_loudness_check_coef.argtypes = [vp]
+    lib.sdrfm_loudness_check_coef.restype = C.c_int
+    lib.sdrfm_pcm_loudness_s16.argtypes = [vp, u32, vp, u32, vp, vp, u32, u32p]
+    lib.sdrfm_pcm_loudness_s16.restype = C.c_int
+    lib.sdrfm_loudness_gate_create.argtypes = [u32, C.POINTER(vp)]
+    lib.sdrfm_loudness_gate_create.restype = C.c_int
+    lib.sdrfm_loudness_gate_push.argtypes = [vp, vp, u32]
+    lib.sdrfm_loudness_gate_push.restype = C.c_int
+    lib.sdrfm_loudness_gate_report.argtypes = [vp, C.POINTER(LoudnessReport)]
+    lib.sdrfm_loudness_gate_report.restype = C.c_int
+    lib.sdrfm_loudness_gate_reset.argtypes = [vp]
+    lib.sdrfm_loudness_gate_reset.restype = C.c_int
+    lib.sdrfm_loudness_gate_free.argtypes = [vp]
+    lib.sdrfm_loudness_gate_free.restype = None
+    lib.sdrfm_pcm_stereo_sink_loudness_enable.argtypes = [vp, vp, u32, u32]
+    lib.sdrfm_pcm_stereo_sink_loudness_enable.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_loudness_disable.argtypes = [vp]
+    lib.sdrfm_pcm_stereo_sink_loudness_disable.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_loudness_read.argtypes = [vp, vp, u32, u64p, u32p, u32]
+    lib.sdrfm_pcm_stereo_sink_loudness_read.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_loudness_get_state.argtypes = [vp, vp]
+    lib.sdrfm_pcm_stereo_sink_loudness_get_state.restype = C.c_int
     _libs[dev] = lib
     return lib

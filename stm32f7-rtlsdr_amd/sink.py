@@ -276,6 +276,41 @@ class StereoPcmSink:
         self._ck(self._lib.sdrfm_pcm_stereo_sink_meter_read(self._h, C.c_void_p(out.data_ptr()), _l.F_DEVICE_PTRS | (_l.AMETER_F_RESET if reset else 0)),
                  "sdrfm_pcm_stereo_sink_meter_read(device)")
 
+    # ---- the loudness meter ----
+    def enable_loudness(self, block_len=4800, cap_blocks=64, coef=None):
+        """sdrfm_pcm_stereo_sink_loudness_enable: from the next call on every launch of this sink is followed by the loudness kernel, which leaves
+        the K-weighted energies of every completed sub-block of block_len pairs in a ring of cap_blocks per stream.  coef: 10 doubles
+        (loudness_default_coef() when None).  Enabling again starts over."""
+        for v, what in ((block_len, "block_len"), (cap_blocks, "cap_blocks")):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_stereo_sink_loudness_enable: " + what)
+        c = None
+        if coef is not None:
+            c = np.ascontiguousarray(coef, dtype=np.float64)
+            if c.shape != (10,):
+                raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_stereo_sink_loudness_enable: coef")
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_loudness_enable(self._h, None if c is None else c.ctypes.data, int(block_len), int(cap_blocks)),
+                 "sdrfm_pcm_stereo_sink_loudness_enable")
+        self._loud_cap = int(cap_blocks)
+
+    def disable_loudness(self):
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_loudness_disable(self._h), "sdrfm_pcm_stereo_sink_loudness_disable")
+
+    def read_loudness(self, out_cap_blocks=None):
+        """sdrfm_pcm_stereo_sink_loudness_read: (first_block, energies float64 [n_streams, n_blocks, 2]) — the sub-blocks completed and not yet
+        read, (e_l, e_r) in LSB^2; first_block is the stream-global index of the first.  Synchronises the sink's stream."""
+        cap = getattr(self, "_loud_cap", 0) if out_cap_blocks is None else int(out_cap_blocks)
+        buf = np.zeros((self.n_streams, max(cap, 1), 2), np.float64)
+        first, nb = C.c_uint64(0), C.c_uint32(0)
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_loudness_read(self._h, buf.ctypes.data, cap, C.byref(first), C.byref(nb), 0), "sdrfm_pcm_stereo_sink_loudness_read")
+        return int(first.value), buf.reshape(-1)[:self.n_streams * nb.value * 2].reshape(self.n_streams, nb.value, 2).copy()
+
+    def loudness_state(self):
+        """sdrfm_pcm_stereo_sink_loudness_get_state: a LOUDNESS_STATE_DTYPE array [n_streams] (pos, z, e) from the device"""
+        out = np.zeros(self.n_streams, dtype=_l.LOUDNESS_STATE_DTYPE)
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_loudness_get_state(self._h, out.ctypes.data), "sdrfm_pcm_stereo_sink_loudness_get_state")
+        return out
+
 
 AUDIO_METER_DTYPE = _l.AUDIO_METER_DTYPE
 AUDIO_REPORT_FIELDS = tuple(n for n, _ in _l.AudioReport._fields_)
