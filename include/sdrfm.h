@@ -1102,7 +1102,17 @@ int  sdrfm_pcm_rate_check_coef(const int16_t* coef, uint32_t n_taps, uint32_t lo
  * Coefficients.  sdrfm_loudness_coef holds 10 doubles, two biquads with a0 = 1: c[0 .. 4] = b0 b1 b2 a1 a2 of the high shelf, c[5 .. 9] those of
  * the 38 Hz high-pass.  sdrfm_loudness_default_coef fills in the 48 kHz values printed in BS.1770-4; coefficients for another rate are the
  * caller's business.  sdrfm_loudness_check_coef: SDRFM_EINVAL for NULL, a non-finite value, or poles not strictly inside the unit circle
- * (|a2| < 1 and |a1| < 1 + a2 for either biquad).
+ * (|a2| < 1 and |a1| < 1 + a2 for either biquad).  The host routine is exact by definition for every set that check accepts.
+ * sdrfm_loudness_check_domain says whether the DEVICE may be enabled with a set: SDRFM_OK, or SDRFM_EINVAL for a set check_coef refuses and
+ * for a stable set outside the device's domain.  The device's scan over lanes loses to rounding an amount that depends on the coefficients, and
+ * no simple function of them bounds it, so the call measures: it runs the kernel's order of operations in plain C on the host against the
+ * definition over the rows on which the difference peaks (DC at the rail, a full-range burst followed by silence, full-range noise; sub-blocks
+ * of 64 and 4800 pairs) and writes, where rel and abs_per_sample are not NULL, the worst |d| / e over the sub-blocks whose mean square is at
+ * least 1e6 LSB^2 and the worst |d| / block_len over the others.  In domain: rel <= 6.25e-11 and abs_per_sample <= 6.25e-5, a sixteenth of
+ * what one lost sample of a full-range row amounts to.  The default set and the K-weighting re-derived for 32, 44.1 and 96 kHz are in; the
+ * one for 192 kHz, high-pass poles within a few milliradians of z = 1 at radius 0.999 or more, poles of either biquad within a hundredth of
+ * a radian of z = -1 and a shelf with poles of radius 0.99 near z = 1 are out (tests/loudness_cases.py lists the sets measured and their
+ * figures).  Pure host arithmetic, some 10 ms.
  *
  * State, per stream (sdrfm_loudness_state, 88 bytes): pos, the pairs consumed since enable or reset; z[channel][4], both biquads in TRANSPOSED
  * DIRECT FORM II, z = {shelf s1, shelf s2, high-pass s1, high-pass s2}; e[channel], the running energy of the open sub-block.
@@ -1138,10 +1148,12 @@ int  sdrfm_pcm_rate_check_coef(const int16_t* coef, uint32_t n_taps, uint32_t lo
  *
  * On the sink (csrc/sdrfm_sink_stereo.hip, the kernel's body in csrc/sdrfm_loudness.h).  A sink that never enables loudness allocates and
  * launches exactly what it did before.
- *   _loudness_enable   coef NULL means the default coefficients.  A NULL sink, refused coefficients, block_len outside 64 .. 2^20, cap_blocks
- *                      outside 1 .. 4096: SDRFM_EINVAL before any device work.  Allocates per stream the state and a ring of cap_blocks
- *                      sdrfm_loudness_block, zeroed (SDRFM_ENOMEM), and computes in double on the host the powers of the per-channel 4 x 4
- *                      transition matrix the kernel's scan uses.  Enabling an enabled sink waits for its stream and starts over.
+ *   _loudness_enable   coef NULL means the default coefficients.  A NULL sink, coefficients sdrfm_loudness_check_coef refuses, a stable set that
+ *                      sdrfm_loudness_check_domain refuses, block_len outside 64 .. 2^20, cap_blocks outside 1 .. 4096: SDRFM_EINVAL before
+ *                      any device work, and an enabled sink goes on as it was.  Allocates per stream the state and a ring of cap_blocks
+ *                      sdrfm_loudness_block, zeroed (SDRFM_ENOMEM), and computes on the host, in long double rounded to double, the powers of
+ *                      the per-channel 4 x 4 transition matrix the kernel's scan uses.  Enabling an enabled sink waits for its stream and
+ *                      starts over.
  *   _loudness_disable  waits for the sink's stream, stops the metering and frees the state and the ring.
  *   _loudness_read     flags must be 0, out is host memory, first_block and n_blocks are not NULL, the sink is enabled: else SDRFM_EINVAL.
  *                      Synchronises the sink's stream and copies, per stream, the sub-blocks completed and not yet read, laid out
@@ -1159,8 +1171,12 @@ int  sdrfm_pcm_rate_check_coef(const int16_t* coef, uint32_t n_taps, uint32_t lo
  * high-cut ramps and audio-meter records keep their bits.  What lies in a row behind 2n is the caller's: it is neither read nor written.
  * The kernel: one workgroup of 256 lanes per stream, a tile of 4864 pairs cut into 256 chunks of 19; each chunk filtered from zero state in
  * double, a scan over lanes with the matrix powers for the true incoming states, a second pass that sums y^2, and one lane per sub-block and
- * channel adding the chunks' pieces in lane order — no atomics, so the same call sequence gives the same bits.  Its energies differ from the
- * definition's by rounding only (DESIGN.md §4.22 gives the measured bound the tests hold it to); pos and the block bookkeeping are exact.
+ * channel adding the chunks' pieces in lane order — no atomics, so the same call sequence gives the same bits.  Its energies differ
+ * from the definition's by rounding, and how much depends on the coefficients: only the sets of the domain can be enabled, for which the
+ * kernel's arithmetic restated on the host stays a factor of sixteen inside 1e-9 of a loud sub-block's energy and 1e-3 LSB^2 per sample of a
+ * quiet one.  What is MEASURED on the device is the default set and the in-domain sets tests/loudness_cases.py lists, each held to 8 x its
+ * own figures; for other sets of the domain the predicate's margin is the only statement.  pos and the block bookkeeping
+ * are exact.
  * Around the one-call forms, which launch on the HANDLE's stream, call enable, disable, read and get_state only after the handle's _synchronize
  * — the rule of sdrfm_pcm_stereo_sink_get_state. */
 typedef struct sdrfm_loudness_coef { double c[10]; } sdrfm_loudness_coef;                              /* shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 */
@@ -1173,6 +1189,7 @@ typedef struct sdrfm_loudness_report_t {
 typedef struct sdrfm_loudness_gate sdrfm_loudness_gate_t;
 int  sdrfm_loudness_default_coef(sdrfm_loudness_coef* out);
 int  sdrfm_loudness_check_coef(const sdrfm_loudness_coef* coef);
+int  sdrfm_loudness_check_domain(const sdrfm_loudness_coef* coef, double* rel /* or NULL */, double* abs_per_sample /* or NULL */);
 int  sdrfm_pcm_loudness_s16(const int16_t* pcm_interleaved, uint32_t n, const sdrfm_loudness_coef* coef, uint32_t block_len,
                             sdrfm_loudness_state* state, sdrfm_loudness_block* out_blocks, uint32_t out_cap, uint32_t* n_blocks);
 int  sdrfm_loudness_gate_create(uint32_t block_len, sdrfm_loudness_gate_t** out);

@@ -32,6 +32,15 @@ int sdrfm_loudness_check_coef(const sdrfm_loudness_coef* coef) {
   return SDRFM_OK;
 }
 
+/* the sets the DEVICE may be enabled with (sdrfm_loudness.h: ld_probe).  This object, built with -ffp-contract=off, holds the one compiled copy of
+ * the probe: the sink's enable calls it */
+int sdrfm_loudness_check_domain(const sdrfm_loudness_coef* coef, double* rel, double* abs_per_sample) {
+  if (sdrfm_loudness_check_coef(coef) != SDRFM_OK) return SDRFM_EINVAL;
+  double pw[SDRFM_LD_TABLE];
+  ld_matrix_powers(coef->c, pw);
+  return ld_in_domain(coef->c, pw, rel, abs_per_sample) ? SDRFM_OK : SDRFM_EINVAL;
+}
+
 int sdrfm_pcm_loudness_s16(const int16_t* pcm_interleaved, uint32_t n, const sdrfm_loudness_coef* coef, uint32_t block_len,
                            sdrfm_loudness_state* state, sdrfm_loudness_block* out_blocks, uint32_t out_cap, uint32_t* n_blocks) {
   if (!state || !coef || !n_blocks || (!pcm_interleaved && n)) return SDRFM_EINVAL;

@@ -178,6 +178,156 @@ SDRFM_LD_FN uint64_t ld_blocks_done(uint64_t pos, uint32_t n, uint32_t block_len
 SDRFM_LD_FN uint32_t ld_ring_slot(uint64_t b, uint32_t cap) { return (uint32_t)(b % cap); }
 SDRFM_LD_FN uint64_t ld_keep_from(uint64_t total, uint32_t cap) { return total > cap ? total - cap : 0u; }
 
+/* ---- the domain: the coefficient sets the device may be enabled with.  Host only ------------------------------------------------------------
+ * The scan is exact in exact arithmetic for every stable set; what it loses to rounding depends on the set, and neither kappa, nor the largest
+ * entry of the table, nor the pole radii bound it: the 96 kHz K-weighting and the 48 kHz shelf over a high-pass with the same poles lie a
+ * factor of nine apart.  So the predicate measures.  ld_emulate_channel is the kernel's order of operations for one channel
+ * in plain C — what tools/loudness_emulate.py restates in numpy —, ld_reference_channel the definition, and ld_probe runs both over the rows on
+ * which the difference peaks: DC at the positive rail in calls of 4800 and 4800 pairs and in one of 2 TILE + 17, DC and a full-range burst of
+ * 4800 pairs each followed by three calls of zeros, a full-range row of TILE + 1; at block_len 64 and 4800.  A sub-block whose mean square
+ * is at least SDRFM_LD_LOUD LSB^2 counts towards the relative figure |d| / e, any other towards the absolute one |d| / block_len, as in
+ * tests/loudness_cases.py.  There a set is IN DOMAIN when both figures, measured over more rows than these, are at most an eighth of what
+ * would hide a lost sample (1e-9 and 1e-3 LSB^2 per sample): the device's evaluation order then has a factor of eight to itself.  The
+ * predicate asks for half of that, a sixteenth, because the figure behind a burst moves with the burst's samples — by 1.3 on the one set of
+ * the tests' grid where it decides — and the probe tries one burst.  About 4e5 filter steps: some 8 ms per call. */
+#define SDRFM_LD_LOUD 1e6
+#define SDRFM_LD_ACCEPT_REL (1.25e-10 / 2.0)
+#define SDRFM_LD_ACCEPT_ABS (1.25e-4 / 2.0)
+#define SDRFM_LD_PROBE_CALL 4800u
+#define SDRFM_LD_PROBE_LONG (2u * SDRFM_LD_TILE + 17u)
+#define SDRFM_LD_PROBE_MAX (SDRFM_LD_PROBE_LONG > SDRFM_LD_PROBE_CALL ? SDRFM_LD_PROBE_LONG : SDRFM_LD_PROBE_CALL)   /* the longest call of the probe */
+
+/* one call of the kernel on one channel: x[n] from the state (z[4], *e, *pos) -> the energies of the sub-blocks it completes, in out; returns
+ * how many.  Every sum in the kernel's order: pass 1, the scan's combine, pass 2's two pieces, the pieces in lane order */
+static inline uint32_t ld_emulate_channel(const double* c, const double* pw, const int16_t* x, uint32_t n, uint32_t B, double* z, double* e,
+                                          uint64_t* pos, double* out) {
+  double zz[2][SDRFM_LD_NT][4], piece[2][SDRFM_LD_NT];
+  const double kappa = pw[16u * SDRFM_LD_STEPS], rkappa = pw[16u * SDRFM_LD_STEPS + 1u];
+  uint32_t off = (uint32_t)(*pos % B), done = 0;
+  for (uint32_t t = 0; t < ld_tiles(n); ++t) {
+    const int16_t* xt = x + (size_t)t * SDRFM_LD_TILE;
+    const uint32_t m = ld_tile_len(n, t), nact = ld_active_lanes(m);
+    uint32_t cb, len, cur = 0;
+    for (uint32_t j = 0; j < nact; ++j) {                        /* pass 1 */
+      double* q = zz[0][j];
+      ld_chunk(m, j, &cb, &len);
+      for (int k = 0; k < 4; ++k) q[k] = j == 0 ? z[k] : 0.0;
+      for (uint32_t i = 0; i < len; ++i) (void)ld_kw_step(c, q, (double)xt[cb + i]);
+      q[3] = kappa * (q[2] + q[3]);
+    }
+    for (uint32_t s = 0; (1u << s) < nact; ++s) {                /* the scan */
+      const uint32_t d = 1u << s;
+      for (uint32_t j = 0; j < nact; ++j) {
+        for (int k = 0; k < 4; ++k) zz[cur ^ 1u][j][k] = zz[cur][j][k];
+        if (j >= d) ld_matvec_add(pw + 16u * s, zz[cur][j - d], zz[cur ^ 1u][j]);
+      }
+      cur ^= 1u;
+    }
+    double zn[4] = {0.0, 0.0, 0.0, 0.0};
+    for (uint32_t j = 0; j < nact; ++j) {                        /* pass 2 */
+      double q[4], e0 = 0.0, e1 = 0.0;
+      ld_chunk(m, j, &cb, &len);
+      for (int k = 0; k < 4; ++k) q[k] = j == 0 ? z[k] : zz[cur][j - 1u][k];
+      if (j) q[3] = q[3] * rkappa - q[2];
+      const uint32_t split = ld_split((off + cb) % B, B, len);
+      for (uint32_t i = 0; i < len; ++i) {
+        const double y = ld_kw_step(c, q, (double)xt[cb + i]);
+        const double sq = y * y;
+        if (i < split) e0 = e0 + sq;
+        else e1 = e1 + sq;
+      }
+      piece[0][j] = e0;
+      piece[1][j] = e1;
+      if (j + 1u == nact)
+        for (int k = 0; k < 4; ++k) zn[k] = q[k];
+    }
+    for (int k = 0; k < 4; ++k) z[k] = zn[k];
+    const uint32_t nb = ld_tile_blocks(off, m, B);
+    for (uint32_t k = 0; k <= nb; ++k) {                         /* the sub-blocks */
+      int64_t start;
+      uint32_t lo, hi;
+      ld_block_span(off, m, B, k, &start, &lo, &hi);
+      double acc = k == 0 ? *e : 0.0;
+      if (hi > lo)
+        for (uint32_t j = lo / SDRFM_LD_L; j <= (hi - 1u) / SDRFM_LD_L; ++j) acc = acc + piece[ld_piece(j, start)][j];
+      if (k < nb) out[done++] = acc;
+      else *e = acc;
+    }
+    off = ld_tile_next_off(off, m, B);
+  }
+  *pos += n;
+  return done;
+}
+
+/* the same call by the definition, one sample after the other (sdrfm_pcm_loudness_s16's loop for one channel) */
+static inline uint32_t ld_reference_channel(const double* c, const int16_t* x, uint32_t n, uint32_t B, double* z, double* e, uint64_t* pos,
+                                            double* out) {
+  uint32_t left = B - (uint32_t)(*pos % B), done = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const double y = ld_kw_step(c, z, (double)x[i]);
+    *e = *e + y * y;
+    if (--left == 0) {
+      out[done++] = *e;
+      *e = 0.0;
+      left = B;
+    }
+  }
+  *pos += n;
+  return done;
+}
+
+/* the two figures of a set over the probe's rows.  pw = ld_matrix_powers(c) */
+enum { LD_P_END = 0, LD_P_ZERO, LD_P_DC, LD_P_NOISE };
+typedef struct ld_probe_call { uint32_t what, n; } ld_probe_call;
+#define SDRFM_LD_PROBE_ROWS 5
+
+static inline void ld_probe(const double* c, const double* pw, double* rel, double* ab) {
+  static const ld_probe_call rows[SDRFM_LD_PROBE_ROWS][4] = {
+      {{LD_P_DC, SDRFM_LD_PROBE_CALL}, {LD_P_DC, SDRFM_LD_PROBE_CALL}, {LD_P_END, 0u}, {LD_P_END, 0u}},
+      {{LD_P_DC, SDRFM_LD_PROBE_LONG}, {LD_P_END, 0u}, {LD_P_END, 0u}, {LD_P_END, 0u}},
+      {{LD_P_DC, SDRFM_LD_PROBE_CALL}, {LD_P_ZERO, SDRFM_LD_PROBE_CALL}, {LD_P_ZERO, SDRFM_LD_PROBE_CALL}, {LD_P_ZERO, SDRFM_LD_PROBE_CALL}},
+      {{LD_P_NOISE, SDRFM_LD_PROBE_CALL}, {LD_P_ZERO, SDRFM_LD_PROBE_CALL}, {LD_P_ZERO, SDRFM_LD_PROBE_CALL}, {LD_P_ZERO, SDRFM_LD_PROBE_CALL}},
+      {{LD_P_NOISE, SDRFM_LD_TILE + 1u}, {LD_P_END, 0u}, {LD_P_END, 0u}, {LD_P_END, 0u}}};
+  static const uint32_t block_lens[2] = {SDRFM_LD_BLOCK_MIN, 4800u};
+  int16_t x[SDRFM_LD_PROBE_MAX];
+  double got[SDRFM_LD_PROBE_MAX / SDRFM_LD_BLOCK_MIN + 1u], want[SDRFM_LD_PROBE_MAX / SDRFM_LD_BLOCK_MIN + 1u];
+  *rel = *ab = 0.0;
+  for (int b = 0; b < 2; ++b)
+    for (int row = 0; row < SDRFM_LD_PROBE_ROWS; ++row) {
+      const uint32_t B = block_lens[b];
+      double zg[4] = {0.0, 0.0, 0.0, 0.0}, zw[4] = {0.0, 0.0, 0.0, 0.0}, eg = 0.0, ew = 0.0;
+      uint64_t pos_g = 0, pos_w = 0, lcg = 0x9E3779B97F4A7C15ull + (uint64_t)row;
+      for (int call = 0; call < 4 && rows[row][call].what != LD_P_END; ++call) {
+        const uint32_t what = rows[row][call].what, n = rows[row][call].n;
+        for (uint32_t i = 0; i < n; ++i) {
+          if (what == LD_P_ZERO) x[i] = 0;
+          else if (what == LD_P_DC) x[i] = 32767;
+          else {
+            lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+            x[i] = (int16_t)(uint16_t)(lcg >> 48);                           /* full range: the top 16 bits as a two's-complement int16 */
+          }
+        }
+        const uint32_t k = ld_emulate_channel(c, pw, x, n, B, zg, &eg, &pos_g, got);
+        (void)ld_reference_channel(c, x, n, B, zw, &ew, &pos_w, want);
+        for (uint32_t i = 0; i < k; ++i) {
+          const double d = got[i] > want[i] ? got[i] - want[i] : want[i] - got[i];
+          if (!(d == d)) { *rel = *ab = 1.0; return; }                       /* NaN: a set whose sums overflow is in no domain */
+          if (want[i] >= SDRFM_LD_LOUD * (double)B) { if (d / want[i] > *rel) *rel = d / want[i]; }
+          else if (d / (double)B > *ab) *ab = d / (double)B;
+        }
+      }
+    }
+}
+
+/* the predicate; the two figures go to rel and ab where those are not NULL */
+static inline int ld_in_domain(const double* c, const double* pw, double* rel, double* ab) {
+  double r, a;
+  ld_probe(c, pw, &r, &a);
+  if (rel) *rel = r;
+  if (ab) *ab = a;
+  return r <= SDRFM_LD_ACCEPT_REL && a <= SDRFM_LD_ACCEPT_ABS;
+}
+
 #if defined(__HIPCC__)
 
 struct LoudnessParams {

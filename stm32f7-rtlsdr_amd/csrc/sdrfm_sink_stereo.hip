@@ -481,6 +481,9 @@ int sdrfm_pcm_stereo_sink_loudness_enable(sdrfm_pcm_stereo_sink_t* k, const sdrf
   else (void)sdrfm_loudness_default_coef(&c);
   if (sdrfm_loudness_check_coef(&c) != SDRFM_OK) return SDRFM_EINVAL;
   if (block_len < SDRFM_LD_BLOCK_MIN || block_len > SDRFM_LD_BLOCK_MAX || cap_blocks < 1u || cap_blocks > SDRFM_LD_CAP_MAX) return SDRFM_EINVAL;
+  // a stable set the scan is not good for is refused: the host routine serves it.  The library's own default is in the domain (the CPU tests hold
+  // that) and is not probed again at every enable
+  if (coef && sdrfm_loudness_check_domain(&c, nullptr, nullptr) != SDRFM_OK) return SDRFM_EINVAL;
   double pw[SDRFM_LD_TABLE];
   ld_matrix_powers(c.c, pw);                                    // on the host, here: the scan's A^(L 2^i) in its balanced coordinates
   if (hipSetDevice(k->device) != hipSuccess) return SDRFM_FAIL;

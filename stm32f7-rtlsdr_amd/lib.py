@@ -46,7 +46,7 @@ ABI_SYMBOLS = [
     "sdrfm_bcast_process_batch_metered_hist", "sdrfm_bcast_hist_kernel_name",
     "sdrfm_pcm_audio_meter_s16", "sdrfm_audio_meter_add", "sdrfm_audio_meter_report",
     "sdrfm_pcm_stereo_sink_meter_enable", "sdrfm_pcm_stereo_sink_meter_disable", "sdrfm_pcm_stereo_sink_meter_read",
-    "sdrfm_loudness_default_coef", "sdrfm_loudness_check_coef", "sdrfm_pcm_loudness_s16", "sdrfm_loudness_gate_create", "sdrfm_loudness_gate_push",
+    "sdrfm_loudness_default_coef", "sdrfm_loudness_check_coef", "sdrfm_loudness_check_domain", "sdrfm_pcm_loudness_s16", "sdrfm_loudness_gate_create", "sdrfm_loudness_gate_push",
     "sdrfm_loudness_gate_report", "sdrfm_loudness_gate_reset", "sdrfm_loudness_gate_free", "sdrfm_pcm_stereo_sink_loudness_enable",
     "sdrfm_pcm_stereo_sink_loudness_disable", "sdrfm_pcm_stereo_sink_loudness_read", "sdrfm_pcm_stereo_sink_loudness_get_state",
     "sdrfm_pcm_rate_create", "sdrfm_pcm_rate_destroy", "sdrfm_pcm_rate_reset", "sdrfm_pcm_rate_set_step", "sdrfm_pcm_rate_count",
@@ -521,6 +521,8 @@ def load_library(dev=False):
     lib.sdrfm_loudness_default_coef.restype = C.c_int
     lib.sdrfm_loudness_check_coef.argtypes = [vp]
     lib.sdrfm_loudness_check_coef.restype = C.c_int
+    lib.sdrfm_loudness_check_domain.argtypes = [vp, vp, vp]
+    lib.sdrfm_loudness_check_domain.restype = C.c_int
     lib.sdrfm_pcm_loudness_s16.argtypes = [vp, u32, vp, u32, vp, vp, u32, u32p]
     lib.sdrfm_pcm_loudness_s16.restype = C.c_int
     lib.sdrfm_loudness_gate_create.argtypes = [u32, C.POINTER(vp)]

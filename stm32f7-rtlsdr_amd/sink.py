@@ -280,7 +280,8 @@ class StereoPcmSink:
     def enable_loudness(self, block_len=4800, cap_blocks=64, coef=None):
         """sdrfm_pcm_stereo_sink_loudness_enable: from the next call on every launch of this sink is followed by the loudness kernel, which leaves
         the K-weighted energies of every completed sub-block of block_len pairs in a ring of cap_blocks per stream.  coef: 10 doubles
-        (loudness_default_coef() when None).  Enabling again starts over."""
+        (loudness_default_coef() when None); a stable set outside the device's domain (sdrfm_loudness_check_domain) is refused with SDRFM_EINVAL
+        and pcm_loudness_host serves it.  Enabling again starts over."""
         for v, what in ((block_len, "block_len"), (cap_blocks, "cap_blocks")):
             if not 0 <= int(v) <= 0xFFFFFFFF:
                 raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_stereo_sink_loudness_enable: " + what)

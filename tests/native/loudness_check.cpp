@@ -168,7 +168,47 @@ static void table() {
   }
 }
 
+// the plain-C restatement of the kernel (ld_emulate_channel) against the definition over ragged calls, and the predicate built on it
+static void domain() {
+  const double k48[10] = {1.53512485958697, -2.69169618940638, 1.19839281085285, -1.69065929318241, 0.73248077421585,
+                          1.0, -2.0, 1.0, -1.99004745483398, 0.99007225036621};
+  double pw[SDRFM_LD_TABLE], rel = -1, ab = -1;
+  ld_matrix_powers(k48, pw);
+  const uint32_t cuts[] = {1, 0, 2, SDRFM_LD_L, SDRFM_LD_TILE - 1, SDRFM_LD_TILE + 1, 257, 64, 2 * SDRFM_LD_TILE + 17};
+  for (uint32_t B : {64u, 100u}) {
+    double zg[4] = {0, 0, 0, 0}, zw[4] = {0, 0, 0, 0}, eg = 0, ew = 0;
+    uint64_t pg = 0, pw_ = 0, seed = 12345;
+    for (uint32_t n : cuts) {
+      std::vector<int16_t> x(n);
+      for (auto& v : x) {
+        seed = seed * 6364136223846793005ull + 1442695040888963407ull;
+        v = (int16_t)(uint16_t)(seed >> 48);
+      }
+      std::vector<double> got(n / B + 2, -1.0), want(n / B + 2, -2.0);
+      const uint32_t k = ld_emulate_channel(k48, pw, x.data(), n, B, zg, &eg, &pg, got.data());
+      CHECK(k == ld_reference_channel(k48, x.data(), n, B, zw, &ew, &pw_, want.data()) && k == ld_blocks_done(pg - n, n, B));
+      CHECK(pg == pw_ && got[k] == -1.0 && want[k] == -2.0);                      // nothing behind the sub-blocks the call completes
+      for (uint32_t i = 0; i < k; ++i) CHECK(std::fabs(got[i] - want[i]) <= 1e-9 * want[i] + 1e-3 * B);
+      CHECK(std::fabs(eg - ew) <= 1e-9 * ew + 1e-3 * B);
+      for (int r = 0; r < 4; ++r) CHECK(std::fabs(zg[r] - zw[r]) <= 1e-6);
+    }
+  }
+  const int in = ld_in_domain(k48, pw, &rel, &ab);
+  CHECK(rel >= 0 && ab >= 0 && in == (rel <= SDRFM_LD_ACCEPT_REL && ab <= SDRFM_LD_ACCEPT_ABS));
+#ifndef LOUDNESS_CHECK_REDUCED
+  CHECK(in && rel > 1e-11 && ab > 1e-5);                                         // the default set: 3.17e-11 and 3.41e-5 (tests/loudness_cases.py)
+  double near_minus_one[10];
+  for (int k = 0; k < 10; ++k) near_minus_one[k] = k48[k];
+  near_minus_one[8] = 2.0 * 0.999 * std::cos(1e-3);                              // high-pass poles at 0.999 e^(+-i (pi - 1e-3))
+  near_minus_one[9] = 0.999 * 0.999;
+  ld_matrix_powers(near_minus_one, pw);
+  CHECK(!ld_in_domain(near_minus_one, pw, &rel, &ab) && rel > 1e-7);
+  CHECK(!ld_in_domain(near_minus_one, pw, nullptr, nullptr));
+#endif
+}
+
 int main() {
+  domain();
 #ifdef LOUDNESS_CHECK_REDUCED
   static_assert(SDRFM_LD_TILE == 12, "the reduced tile");
   for (uint32_t B = 64; B <= 70; ++B)

@@ -41,6 +41,28 @@ def process(x, coef, step, pos=0, hist=None):
     return out.reshape(-1), pos + cnt * step - n * ONE, ext[ext.shape[0] - (nt - 1):].astype(np.int16).reshape(-1)
 
 
+def process_fast(x, coef, step, pos=0, hist=None, chunk=1 << 16):
+    """process() for calls of up to 2^20 pairs: the phases as one uint64 numpy progression (pos + cnt step < 2^32 (n + 4) <= 2^53, no wrap) and the
+    sums `chunk` outputs at a time.  tests/test_pcm_rate_cpu.py holds it to process()"""
+    nt, logph = shape_of(coef)
+    x = np.asarray(x, np.int16).reshape(-1, 2)
+    n = x.shape[0]
+    hist = np.zeros((nt - 1, 2), np.int16) if hist is None else np.asarray(hist, np.int16).reshape(nt - 1, 2)
+    ext = np.concatenate([hist, x]).astype(np.int64)
+    cnt = count(pos, step, n)
+    assert 0 <= pos < 1 << 53 and pos + cnt * step < 1 << 53
+    c = coef.astype(np.int64)
+    out = np.zeros((cnt, 2), np.int16)
+    for a in range(0, cnt, chunk):
+        P = np.uint64(pos) + np.arange(a, min(a + chunk, cnt), dtype=np.uint64) * np.uint64(step)
+        i, f = (P >> np.uint64(32)).astype(np.int64), (P & np.uint64(0xFFFFFFFF)).astype(np.int64)
+        p, mu = f >> (32 - logph), (f >> (24 - logph)) & 255
+        taps = ext[i[:, None] + np.arange(nt)[None, :]]
+        acc = np.einsum("jk,jkc->jc", c[p], taps) * (256 - mu)[:, None] + np.einsum("jk,jkc->jc", c[p + 1], taps) * mu[:, None]
+        out[a:a + P.size] = np.clip((acc + (1 << 22)) >> 23, -32768, 32767)
+    return out.reshape(-1), pos + cnt * step - n * ONE, ext[ext.shape[0] - (nt - 1):].astype(np.int16).reshape(-1)
+
+
 def run(x, coef, step, cuts, pos=0, hist=None):
     """the row cut into calls of the given lengths (pairs): (the outputs of every call, pos after every call, final hist)"""
     outs, poss, at = [], [], 0
@@ -59,6 +81,29 @@ def random_full_range(rng, shape):
     if flat.size >= 4:
         flat[:2], flat[-2:] = -32768, 32767
     return x
+
+
+def bound_table(nt, logph, rng=None):
+    """a legal table with the sum of |coef| EXACTLY 65535 in both halves of every row, at any tap count (small_table's clip to int16 can leave a
+    half row of two or four taps short of it): random magnitudes of at most 32767 with random signs; a half row of two taps is -32768 beside
+    +-32767, the only way two int16 reach 65535"""
+    rng = np.random.default_rng(nt * 32 + logph) if rng is None else rng
+    rows, half = (1 << logph) + 1, nt // 2
+    c = np.zeros((rows, nt), np.int64)
+    for p in range(rows):
+        for h in range(2):
+            if half == 2:
+                seg = np.array([-32768, 32767 * int(rng.choice((-1, 1)))])[:: int(rng.choice((-1, 1)))]
+            else:
+                w = rng.random(half) + 0.05
+                mag = np.minimum(np.floor(w * (65535 / w.sum())).astype(np.int64), 32767)
+                while mag.sum() < 65535:                                   # hand the remainder to the taps that have room, largest first
+                    k = int(np.argmax(np.where(mag < 32767, mag, -1)))
+                    mag[k] += min(65535 - int(mag.sum()), 32767 - int(mag[k]))
+                seg = mag * rng.choice((-1, 1), half)
+            c[p, h * half:(h + 1) * half] = seg
+    assert (np.abs(c[:, :half]).sum(axis=1) == 65535).all() and (np.abs(c[:, half:]).sum(axis=1) == 65535).all()
+    return c.astype(np.int16)
 
 
 def small_table(nt, logph, rng=None, overshoot=False):

@@ -7,7 +7,7 @@ import re
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ["sdrfm_loudness_default_coef", "sdrfm_loudness_check_coef", "sdrfm_pcm_loudness_s16", "sdrfm_loudness_gate_create", "sdrfm_loudness_gate_push",
+SYMBOLS = ["sdrfm_loudness_default_coef", "sdrfm_loudness_check_coef", "sdrfm_loudness_check_domain", "sdrfm_pcm_loudness_s16", "sdrfm_loudness_gate_create", "sdrfm_loudness_gate_push",
            "sdrfm_loudness_gate_report", "sdrfm_loudness_gate_reset", "sdrfm_loudness_gate_free", "sdrfm_pcm_stereo_sink_loudness_enable",
            "sdrfm_pcm_stereo_sink_loudness_disable", "sdrfm_pcm_stereo_sink_loudness_read", "sdrfm_pcm_stereo_sink_loudness_get_state"]
 
@@ -53,6 +53,31 @@ def test_coefficients_and_their_check(pkg):
     edge = c.copy()
     edge[3] = np.nextafter(1.0 + c[4], 0.0)
     assert lib.sdrfm_loudness_check_coef(edge.ctypes.data) == 0
+
+
+def test_the_device_domain_is_refused_without_a_device(pkg):
+    """sdrfm_loudness_check_domain is what _loudness_enable asks before any device work: a stable set outside the domain answers SDRFM_EINVAL,
+    with the two figures that say why; sdrfm_loudness_check_coef and the host routine go on accepting it"""
+    import loudness_cases as lc
+    lib, E = pkg.load_library(), pkg.lib.EINVAL
+    sets = lc.coef_sets()
+    rel, ab = C.c_double(-1.0), C.c_double(-1.0)
+    assert lib.sdrfm_loudness_check_domain(None, C.byref(rel), C.byref(ab)) == E and (rel.value, ab.value) == (-1.0, -1.0)
+    unstable = pkg.loudness_default_coef()
+    unstable[9] = 1.0
+    assert lib.sdrfm_loudness_check_domain(unstable.ctypes.data, C.byref(rel), C.byref(ab)) == E and (rel.value, ab.value) == (-1.0, -1.0)
+    c = pkg.loudness_default_coef()
+    assert lib.sdrfm_loudness_check_domain(c.ctypes.data, None, None) == 0
+    assert lib.sdrfm_loudness_check_domain(c.ctypes.data, C.byref(rel), C.byref(ab)) == 0
+    assert 0.0 < rel.value <= lc.MEASURED_REL and 0.0 < ab.value <= lc.MEASURED_ABS          # the default's figures peak on the probe's own DC rows
+    pcm = lc.interleave(*lc.random_rows(300, 1))
+    for name in ("k192000", "hp r=0.99 th=pi-1e-3", "hp r=0.999 th=1e-3", "shelf r=0.999 th=0.01"):
+        bad = sets[name]
+        assert lib.sdrfm_loudness_check_coef(bad.ctypes.data) == 0, name
+        assert lib.sdrfm_loudness_check_domain(bad.ctypes.data, C.byref(rel), C.byref(ab)) == E, name
+        assert rel.value > 1e-9 / 16 or ab.value > 1e-3 / 16, (name, rel.value, ab.value)
+        assert lib.sdrfm_pcm_stereo_sink_loudness_enable(None, bad.ctypes.data, 4800, 64) == E
+        assert pkg.pcm_loudness_host(pcm, 64, bad)[0].shape == (1, 4, 2), name               # exact by definition: the host routine serves it
 
 
 def test_host_routine_refusals_change_nothing(pkg):

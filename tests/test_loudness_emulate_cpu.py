@@ -2,6 +2,7 @@
 operations in numpy: same L, same tile, same matrix powers — against the C routine sdrfm_pcm_loudness_s16 on the GPU tests' own inputs
 (tests/loudness_cases.py).  The two terms of |e - e_host| <= RTOL e_host + ATOL block_len are measured separately and printed; RTOL and ATOL
 are 8 x the recorded figures, and the hard conditions RTOL <= 1e-9 and ATOL <= 1e-3 LSB^2 per sample are asserted as such."""
+import ctypes as C
 import os
 import sys
 
@@ -58,6 +59,100 @@ def test_measured_tolerance_and_the_hard_caps(pkg):
     assert rel >= lc.MEASURED_REL / 2 and ab >= lc.MEASURED_ABS / 2, (rel, ab)               # and are measurements, not guesses
     assert lc.RTOL == 8 * lc.MEASURED_REL and lc.ATOL == 8 * lc.MEASURED_ABS
     assert lc.RTOL <= 1e-9 and lc.ATOL <= 1e-3                                               # the hard conditions
+
+
+def _calls(pkg, coef, calls, bl, with_open):
+    """stream 0 of a row's calls (L, R) through the emulation and the C routine, states carried: (energies [blocks, 2]) x 2.  with_open: behind
+    every call's sub-blocks also the open sub-block's running energy, which the device tests hold to the same bound"""
+    st, pos, z, e, got, want, done = None, 0, None, None, [], [], 0
+    for Li, Ri in calls:
+        pcm = lc.interleave(Li, Ri)[0]
+        w, st = pkg.pcm_loudness_host(pcm, bl, coef, state=st)
+        b, pos, z, e = em.emulate(pcm, bl, coef, pos, z, e)
+        assert [k for k, _, _ in b] == list(range(done, done + w.shape[1]))
+        done += w.shape[1]
+        got += [[el, er] for _, el, er in b] + ([e.tolist()] if with_open else [])
+        want += w[0].tolist() + ([st["e"][0].tolist()] if with_open else [])
+    assert pos == int(st["pos"][0])
+    return np.array(got).reshape(-1, 2), np.array(want).reshape(-1, 2)
+
+
+def _figures(pkg, coef, rows, with_open=True):
+    rel = ab = 0.0
+    for calls in rows:
+        for bl in lc.COEF_BLOCK_LENS:
+            r, a = lc.measure(*_calls(pkg, coef, calls, bl, with_open), bl)
+            rel, ab = max(rel, r), max(ab, a)
+    return rel, ab
+
+
+def test_k_weighting_rederived_at_48000_is_the_default(pkg):
+    c = pkg.loudness_default_coef()
+    assert c.tolist() == list(lc.DEFAULT_COEF)
+    assert float(np.abs(lc.k_weighting(48000) - c).max()) <= 1e-15
+    lib = pkg.load_library()
+    for name, coef in lc.coef_sets().items():
+        assert lib.sdrfm_loudness_check_coef(coef.ctypes.data) == 0, name                    # every set of the grid is one the library's check accepts
+    assert len(lc.STRESS) == 27 and len(lc.coef_sets()) == 32
+
+
+def test_every_set_against_its_recorded_figures(pkg):
+    """the emulation against the C routine for every coefficient set: the fresh figures do not exceed the recorded ones and are no guesses"""
+    assert sorted(lc.COEF_MEASURED) == sorted(lc.coef_sets())
+    for name, coef in lc.coef_sets().items():
+        rel, ab = _figures(pkg, coef, lc.coef_rows(name in lc.STRESS).values())
+        print('    "%s": (%.3g, %.3g),' % (name, rel, ab))
+        want_rel, want_ab = lc.COEF_MEASURED[name]
+        assert rel <= want_rel and ab <= want_ab, (name, rel, ab)
+        assert rel >= want_rel / 2 and ab >= want_ab / 2, (name, rel, ab)
+    # the default's row here is what the module's RTOL and ATOL already rest on
+    assert lc.COEF_MEASURED["default"][0] <= lc.MEASURED_REL and lc.COEF_MEASURED["default"][1] <= lc.MEASURED_ABS
+    for name in lc.coef_sets():
+        if lc.in_domain(name):
+            rtol, atol = lc.coef_tolerance(name)
+            assert rtol <= 1e-9 and atol <= 1e-3, name                                       # the hard conditions, for every set the device is held to
+
+
+def test_the_predicate_against_the_grid(pkg):
+    """sdrfm_loudness_check_domain, the predicate behind _loudness_enable, held to the measurement: every set it accepts is in domain by the
+    recorded figures, the default and the 32, 44.1 and 96 kHz K-weightings are accepted, and so every listed set outside the domain is refused.
+    Its own figures are the emulation's over the probe's rows bit for bit: the plain-C restatement of the kernel in csrc/sdrfm_loudness.h and
+    tools/loudness_emulate.py are the same arithmetic"""
+    lib = pkg.load_library()
+    accepted = []
+    for name, coef in lc.coef_sets().items():
+        rel, ab = C.c_double(), C.c_double()
+        rc = lib.sdrfm_loudness_check_domain(coef.ctypes.data, C.byref(rel), C.byref(ab))
+        assert rc in (0, pkg.lib.EINVAL), (name, rc)
+        assert (rel.value, ab.value) == _figures(pkg, coef, lc.probe_rows(), with_open=False), name   # (the probe looks at completed sub-blocks)
+        assert (rc == 0) == (rel.value <= lc.DOMAIN_REL / 2 and ab.value <= lc.DOMAIN_ABS / 2), name   # it asks for half the domain's figures
+        if rc == 0:
+            accepted.append(name)
+            assert lc.in_domain(name), (name, lc.COEF_MEASURED[name])
+        print("%-28s recorded %.3g %.3g, the probe's %.3g %.3g: %s" % ((name,) + lc.COEF_MEASURED[name] + (rel.value, ab.value, "accepted" if rc == 0 else "refused")))
+    assert {"default", "k32000", "k44100", "k96000"} <= set(accepted)
+    assert "k192000" not in accepted and not [n for n in accepted if "pi-1e-" in n or n.startswith("shelf ")]
+    assert len(accepted) >= 12                                                               # conservative, not empty
+    # why the predicate measures: the 96 kHz set is in, and its own high-pass behind the default shelf — the same kappa, a smaller table — is out
+    assert lc.in_domain("k96000") and not lc.in_domain("hp of k96000") and "hp of k96000" not in accepted
+    assert em.balance(lc.coef_sets()["k96000"]) == em.balance(lc.coef_sets()["hp of k96000"]) == 512.0
+    assert np.abs(em.matrix_powers(lc.coef_sets()["hp of k96000"])).max() <= 1.0 < np.abs(em.matrix_powers(lc.coef_sets()["k96000"])).max()
+
+
+def test_a_table_built_in_double_is_outside_the_room_the_device_gets(pkg, monkeypatch):
+    """what tests/test_pcm_loudness_coef_gpu.py must not pass: a power table built in double instead of long double.  At the default set that
+    changes nothing one could see (3.16e-11 against 3.17e-11) — only with other sets does the table decide: with high-pass poles at
+    0.9999 e^(+-i (pi - 0.3)) every row the device test runs lies beyond the room that set gets, 8 x its recorded figures"""
+    monkeypatch.setattr(em, "TABLE_DTYPE", np.float64)
+    name = "hp r=0.9999 th=pi-0.3"
+    assert lc.in_domain(name)
+    rtol, atol = lc.coef_tolerance(name)
+    for row, calls in lc.coef_rows(False).items():
+        rel, ab = _figures(pkg, lc.coef_sets()[name], [calls])
+        print("double table, %s: %.3g %.3g against %.3g %.3g" % (row, rel, ab, rtol, atol))
+        assert rel > 4 * rtol and ab <= atol, (row, rel, ab)                                 # (measured: 12 x, 22 x and 43 x)
+    rel, ab = _figures(pkg, pkg.loudness_default_coef(), [lc.coef_rows(False)["dc_pos"]])
+    assert rel <= lc.MEASURED_REL and ab <= lc.MEASURED_ABS
 
 
 def test_a_displaced_sample_is_far_outside_the_bound(pkg):

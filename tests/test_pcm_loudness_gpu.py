@@ -351,7 +351,10 @@ def test_lifecycle_and_refusals_on_a_live_sink(pkg):
         nan[0] = np.nan
         unstable = pkg.loudness_default_coef()
         unstable[9] = 1.0
-        for coef, b_, cap in ((None, 63, 16), (None, (1 << 20) + 1, 16), (None, bl, 0), (None, bl, 4097), (nan, bl, 16), (unstable, bl, 16)):
+        outside = [lc.coef_sets()[k] for k in ("k192000", "hp r=0.999 th=pi-1e-3", "shelf r=0.999 th=0.01")]   # stable, but not in the device's domain
+        assert all(lib.sdrfm_loudness_check_coef(c.ctypes.data) == 0 and lib.sdrfm_loudness_check_domain(c.ctypes.data, None, None) == E for c in outside)
+        for coef, b_, cap in [(None, 63, 16), (None, (1 << 20) + 1, 16), (None, bl, 0), (None, bl, 4097), (nan, bl, 16), (unstable, bl, 16)] + [
+                (c, bl, 16) for c in outside]:
             assert lib.sdrfm_pcm_stereo_sink_loudness_enable(sink._h, None if coef is None else coef.ctypes.data, b_, cap) == E
         for flags in (1, 2, 8, 0x80000000):
             assert read(buf.ctypes.data, 16, C.byref(first), C.byref(nb), flags) == E

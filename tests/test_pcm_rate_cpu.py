@@ -80,6 +80,24 @@ def test_cut_invariance_over_ragged_cuts(pkg):
     assert rails == 2 * len(ref.STEPS)                                 # full-range noise overshoots: both rails at every step
 
 
+def test_the_vectorised_reference_is_the_reference(pkg):
+    """ref.process_fast — what tests/test_pcm_rate_tables_gpu.py holds calls of 2^20 pairs to — against ref.process, at every step, from reset and
+    from a carried state, with chunks smaller than a call so that their seams are crossed; and once against the C routine on a call of 2^17 pairs"""
+    rng = np.random.default_rng(25)
+    x = ref.random_full_range(rng, 2 * 1500)
+    for nt, logph in ((4, 4), (12, 5), (64, 8)):
+        coef = ref.small_table(nt, logph, overshoot=True)
+        for step in ref.STEPS:
+            a, b = ref.process(x[:2000], coef, step), ref.process_fast(x[:2000], coef, step, chunk=97)
+            assert _same(a, b), (nt, step)
+            assert _same(ref.process(x[2000:], coef, step, a[1], a[2]), ref.process_fast(x[2000:], coef, step, b[1], b[2], chunk=64)), (nt, step)
+            assert _same(ref.process(x[:2], coef, step, a[1], a[2]), ref.process_fast(x[:2], coef, step, b[1], b[2])), (nt, step)   # often no output at all
+    coef = ref.small_table(4, 4, overshoot=True)
+    big = ref.random_full_range(rng, 2 * (1 << 17))
+    for step in (1 << 30, (1 << 34) - 1):
+        assert _same(pkg.pcm_rate_host(big, coef, step), ref.process_fast(big, coef, step)), step
+
+
 def test_a_constant_comes_out_as_itself(pkg):
     for step in ref.STEPS:
         for nt, logph, cutoff in ((32, 8, None), (48, 8, 0.9), (16, 4, 0.5)):

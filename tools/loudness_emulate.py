@@ -15,6 +15,7 @@ import numpy as np
 
 L, NT, STEPS = 19, 256, 8
 TILE = L * NT
+TABLE_DTYPE = np.longdouble          # the precision the table is built in (ld_matrix_powers: long double); a test sets float64 to show what that costs
 
 
 def transition(c):
@@ -52,12 +53,12 @@ def balance(c):
 def matrix_powers(c):
     """ld_matrix_powers: [STEPS, 4, 4], pw[i] = (T A T^-1)^(L 2^i) in long double, rounded to double at the end; T maps z to the scan's
     coordinates (z0, z1, z2, kappa (z2 + z3))"""
-    kap = np.longdouble(balance(c))
-    T = np.eye(4, dtype=np.longdouble)
+    kap = TABLE_DTYPE(balance(c))
+    T = np.eye(4, dtype=TABLE_DTYPE)
     T[3, 2] = T[3, 3] = kap
-    Ti = np.eye(4, dtype=np.longdouble)
+    Ti = np.eye(4, dtype=TABLE_DTYPE)
     Ti[3, 2], Ti[3, 3] = -1.0, 1.0 / kap
-    A = matmul(matmul(T, transition(c).astype(np.longdouble)), Ti)
+    A = matmul(matmul(T, transition(c).astype(TABLE_DTYPE)), Ti)
     P = A.copy()
     for _ in range(1, L):
         P = matmul(A, P)
