@@ -1203,6 +1203,82 @@ int  sdrfm_pcm_stereo_sink_loudness_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_loudn
                                          uint64_t* first_block, uint32_t* n_blocks, uint32_t flags);
 int  sdrfm_pcm_stereo_sink_loudness_get_state(sdrfm_pcm_stereo_sink_t* k, sdrfm_loudness_state* out /* n_streams */);
 
+/* A per-stream TRUE-PEAK METER on the stereo PCM sink: the maximum true peak of ITU-R BS.1770-4 Annex 2 / EBU R 128, in
+ * dBTP, of what the receiver plays — the peak of the waveform an interpolator (the rate matcher, the consumer's DAC) reconstructs from the int16
+ * samples, which a sample peak can understate by several dB.  A fixed polyphase FIR on int16 with int16 taps, all-integer and EXACT: the device
+ * equals the host routine bit for bit, and any cut of a stream into calls gives the same record.  No PCM is copied to the host.
+ *
+ * Table.  coef[P][NT] int16 in Q15, given at enable: P = n_phases is 2, 4 or 8, NT = n_taps a multiple of 4 in 4 .. 64.  A table is taken only
+ * if in every row the sum of |coef| over taps [0, NT/2) is <= 65535, and likewise over [NT/2, NT) — the rate matcher's half-row bound
+ * (sdrfm_truepeak_check_coef: SDRFM_EINVAL for NULL, a shape outside the ranges or a half-row over the bound): half a row's dot product with any
+ * int16 input then fits an int32.  sdrfm_truepeak_default_coef gives P = 4, NT = 12, the 48 coefficients of BS.1770-4 Annex 2 (multiples of
+ * 2^-13, exact in Q15); out holds 48 int16, n_phases and n_taps may be NULL.
+ *
+ * One call is n pairs of one stream.  x[i] is the new pairs for i >= 0, hist for i < 0 — the last NT - 1 pairs before the call, zero after
+ * enable and reset — and zero further back.  Per channel, for 0 <= i < n and 0 <= p < P:   A[i][p] = sum over k of coef[p][k] x[i - k],   taken
+ * exactly; the bound gives |A| <= 2 * 65535 * 32768 < 2^32.  hist becomes the last NT - 1 pairs of (hist, new pairs), also for n < NT - 1.
+ *
+ * Record (sdrfm_truepeak, 64 bytes): n, the pairs covered; peak_*, the maximum over i and p of |A| in units of 2^-15 LSB, so 0 dBTP = 2^30;
+ * at_*, the smallest i at which some phase attains peak_*, counted from the record's first pair, 0 when peak_* is 0; over_*, the number of
+ * (i, p) with |A| > limit (strict); reserved, 0.
+ * The JOIN of a record a and the record b of the pairs that FOLLOW, sdrfm_truepeak_add(acc = a, m = b): n and over_* add; where b.peak > a.peak
+ * (strict) the peak is b's and at = a.n + b.at, otherwise a's stay.  The join is associative and the zero record is its identity, so any cut
+ * of a stream into calls, joined in order, gives the stream's record.
+ * limit is in the record's units, 0 .. 2^32 - 1.  sdrfm_truepeak_limit(dbtp) = floor(2^30 10^(dbtp / 20)) clamped to that range, 0 for a NaN;
+ * -1 dBTP is the R 128 production limit.
+ *
+ * Host side, plain C with no GPU behind it (csrc/truepeak.c):
+ *   sdrfm_pcm_truepeak_s16   the definition as code, accumulating in 64 bits (it does not need the bound): joins the call's record onto *acc
+ *                            and advances hist.  SDRFM_EINVAL, with nothing written: acc, coef or hist NULL, pcm_interleaved NULL with n > 0,
+ *                            a shape outside the ranges, limit > 2^32 - 1.
+ *   sdrfm_truepeak_add       the ordered join above; SDRFM_EINVAL for a NULL pointer.
+ *   sdrfm_truepeak_report    in double: dbtp_l, dbtp_r and dbtp (their maximum) = 20 log10(peak / 2^30), -inf for a zero peak; over_frac_* =
+ *                            over / (n P); at_seconds_* = at / fs_audio.  Every field is NaN for a record of no pairs.  SDRFM_EINVAL: a NULL
+ *                            pointer, n_phases not 2, 4 or 8, fs_audio not finite and positive.
+ *
+ * On the sink (csrc/sdrfm_sink_stereo.hip, the kernel's body in csrc/sdrfm_truepeak.h).  A sink that never enables true peak allocates and
+ * launches exactly what it did before.
+ *   _truepeak_enable   coef NULL means the default table, and n_phases and n_taps are then not looked at.  A NULL sink, a table
+ *                      sdrfm_truepeak_check_coef refuses, limit > 2^32 - 1: SDRFM_EINVAL before any device work, and an enabled sink goes on
+ *                      as it was.  Allocates per stream the record and the history, and the packed table, zeroed (SDRFM_ENOMEM).  Enabling an
+ *                      enabled sink waits for its stream and starts over.
+ *   _truepeak_disable  waits for the sink's stream, stops the metering and frees what enable allocated.
+ *   _truepeak_read     flags is a subset of SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET, out is 8-byte aligned and holds n_streams records, the
+ *                      sink is enabled: else SDRFM_EINVAL.  The semantics are _meter_read's.  SDRFM_AMETER_F_RESET zeroes the records behind
+ *                      the copy and KEEPS THE HISTORY: the stream continues, and the reads' records join to the stream's.
+ *   sdrfm_pcm_stereo_sink_reset also zeroes an enabled sink's records and history.
+ * While enabled, EVERY launch of the sink — its four forms, host or device buffers, and its launch behind sdrfm_stereo_process_batch_pcm,
+ * sdrfm_bcast_process_batch_pcm, sdrfm_bcast_process_batch_metered and sdrfm_bcast_process_batch_metered_hist — is followed on the same stream
+ * by one launch of k_pcm_truepeak over the rows just written, behind the audio meter's and the loudness kernels if those are enabled.  Those
+ * kernels, their arguments and their bits are untouched.  The kernel: one workgroup of 1024 lanes per stream, the row in tiles of 4864 pairs
+ * staged in LDS as an L and an R plane of packed sample pairs behind their NT - 1 predecessors, the table in LDS tap-reversed and packed; a
+ * lane takes a pair's P phases of both channels as packed 16-bit dot products, each half-row into an int32 and the two halves summed in 64
+ * bits; per channel one 64-bit key (peak << 32 | ~index) reduced by max over lanes, waves and the workgroup — no atomics.
+ * Around the one-call forms, which launch on the HANDLE's stream, call enable, disable and read only after the handle's _synchronize — the rule
+ * of sdrfm_pcm_stereo_sink_get_state. */
+typedef struct sdrfm_truepeak {                    /* 64 bytes, 8-byte aligned */
+  uint64_t n;
+  uint64_t peak_l, peak_r;
+  uint64_t at_l, at_r;
+  uint64_t over_l, over_r;
+  uint64_t reserved;
+} sdrfm_truepeak;
+typedef struct sdrfm_truepeak_report_t {
+  double dbtp_l, dbtp_r, dbtp;
+  double over_frac_l, over_frac_r;
+  double at_seconds_l, at_seconds_r;
+} sdrfm_truepeak_report_t;
+int  sdrfm_truepeak_default_coef(int16_t* out /* 48 */, uint32_t* n_phases, uint32_t* n_taps);
+int  sdrfm_truepeak_check_coef(const int16_t* coef, uint32_t n_phases, uint32_t n_taps);
+uint64_t sdrfm_truepeak_limit(double dbtp);
+int  sdrfm_pcm_truepeak_s16(const int16_t* pcm_interleaved, uint32_t n, const int16_t* coef, uint32_t n_phases, uint32_t n_taps, uint64_t limit,
+                            int16_t* hist /* 2 * (n_taps - 1) */, sdrfm_truepeak* acc);
+int  sdrfm_truepeak_add(sdrfm_truepeak* acc, const sdrfm_truepeak* m);
+int  sdrfm_truepeak_report(const sdrfm_truepeak* m, uint32_t n_phases, double fs_audio, sdrfm_truepeak_report_t* out);
+int  sdrfm_pcm_stereo_sink_truepeak_enable(sdrfm_pcm_stereo_sink_t* k, const int16_t* coef /* or NULL */, uint32_t n_phases, uint32_t n_taps, uint64_t limit);
+int  sdrfm_pcm_stereo_sink_truepeak_disable(sdrfm_pcm_stereo_sink_t* k);
+int  sdrfm_pcm_stereo_sink_truepeak_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_truepeak* out /* n_streams records */, uint32_t flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,10 +20,11 @@ from .rds import RdsDemod, RdsConfig, RdsSync, RdsGroup, rds_parse, rds_encode_g
 from .spectrum import SpectrumView, SpectrumConfig, power_db
 from .sink import PcmSink, StereoPcmSink, pcm_deemph_s16_host, pcm_deemph_stereo_s16_host, pcm_deemph_stereo_hicut_s16_host, hicut_slew, AUDIO_METER_DTYPE, pcm_audio_meter_host, audio_meter_add, audio_meter_report, audio_alarms, AudioMonitor
 from .rate import PcmRateMatcher, pcm_rate_host, step_for, ClockServo
-from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain, rds_gain, rds_lowpass_taps, tuned_channel_taps, tuned_rotation, retune_carry, pilot_gain, hicut_corner_hz, rate_coef
+from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain, rds_gain, rds_lowpass_taps, tuned_channel_taps, tuned_rotation, retune_carry, pilot_gain, hicut_corner_hz, rate_coef, truepeak_coef
 from .siggen import make_iq, make_iq_stereo, make_iq_rds, make_iq_stations, MODES
 from .frontend import ReplayFrontEnd, XferState
 from .loudness import LOUDNESS_STATE_DTYPE, loudness_default_coef, pcm_loudness_host, LoudnessGate, LoudnessMonitor, loudness_alarms
+from .truepeak import TRUEPEAK_DTYPE, truepeak_default_coef, truepeak_limit, pcm_truepeak_host, truepeak_add, truepeak_report, truepeak_alarms, headroom_gain_q15
 from . import fanout
 from . import rate
 from . import lib
@@ -38,5 +39,7 @@ __all__ = [
     "HIST_BINS", "hist_add", "hist_edges_hz", "hist_report", "deviation_quantile", "ModulationMonitor",
     "AUDIO_METER_DTYPE", "pcm_audio_meter_host", "audio_meter_add", "audio_meter_report", "audio_alarms", "AudioMonitor",
     "LOUDNESS_STATE_DTYPE", "loudness_default_coef", "pcm_loudness_host", "LoudnessGate", "LoudnessMonitor", "loudness_alarms",
+    "TRUEPEAK_DTYPE", "truepeak_default_coef", "truepeak_limit", "pcm_truepeak_host", "truepeak_add", "truepeak_report", "truepeak_alarms",
+    "headroom_gain_q15", "truepeak_coef",
     "PcmRateMatcher", "pcm_rate_host", "rate_coef", "step_for", "ClockServo", "rate",
 ]

@@ -30,6 +30,9 @@
  * A sink with LOUDNESS enabled (sdrfm_pcm_stereo_sink_loudness_enable) follows every launch, and the meter's if there is one, with
  *   k_pcm_loudness          one workgroup of 256 lanes per stream over the same PCM row (sdrfm_loudness.h): K-weighting in double by a two-pass
  *                           blocked scan, the sub-block energies into the stream's ring.
+ * A sink with TRUE PEAK enabled (sdrfm_pcm_stereo_sink_truepeak_enable) follows every launch, and those two if there are any, with
+ *   k_pcm_truepeak          one workgroup of 1024 lanes per stream over the same PCM row (sdrfm_truepeak.h): a polyphase FIR in packed 16-bit dot
+ *                           products over LDS-staged planes, the peak and its place by a max over 64-bit keys.
  */
 #include <hip/hip_runtime.h>
 
@@ -47,6 +50,7 @@
 #include "sdrfm_sink_hicut.h"
 #include "sdrfm_sink_kernels.h"
 #include "sdrfm_sink_stereo.h"
+#include "sdrfm_truepeak.h"
 
 namespace {
 
@@ -131,6 +135,12 @@ __global__ void __launch_bounds__(SDRFM_LD_NT) k_pcm_loudness(LoudnessParams p) 
   loudness_stream(sh, p);
 }
 
+// ---- the true-peak meter: reads the same rows ---------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(SDRFM_TP_NT) k_pcm_truepeak(TruePeakParams p) {
+  __shared__ TruePeakShared sh;
+  truepeak_stream(sh, p);
+}
+
 }  // namespace
 
 struct sdrfm_pcm_stereo_sink {
@@ -163,6 +173,13 @@ struct sdrfm_pcm_stereo_sink {
   uint32_t lblock, lcap;
   uint64_t lpos, lread;
   bool loud;
+  // the true-peak meter (sdrfm_pcm_stereo_sink_truepeak_enable): records, histories and the packed table on the device while enabled
+  sdrfm_truepeak* d_tprec;          // [n_streams]
+  unsigned* d_tphist;               // [n_streams][tp_nt - 1] pairs
+  unsigned* d_tptab;                // [tp_P][tp_nt / 2]
+  uint64_t tp_limit;
+  uint32_t tp_P, tp_nt;
+  bool tpeak;
 };
 
 static const HicutRec HICUT_FLAT = {(uint16_t)SDRFM_ACTL_ONE, (uint16_t)SDRFM_ACTL_ONE};
@@ -179,6 +196,9 @@ static void stereo_sink_free(sdrfm_pcm_stereo_sink* k) {
   if (k->d_lstate) (void)hipFree(k->d_lstate);
   if (k->d_lring) (void)hipFree(k->d_lring);
   if (k->d_lpw) (void)hipFree(k->d_lpw);
+  if (k->d_tprec) (void)hipFree(k->d_tprec);
+  if (k->d_tphist) (void)hipFree(k->d_tphist);
+  if (k->d_tptab) (void)hipFree(k->d_tptab);
   free(k->hc_host);
   if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
   delete k;
@@ -253,6 +273,11 @@ static int stereo_sink_launch(sdrfm_pcm_stereo_sink* k, const float* left, const
     STRY(hipGetLastError(), SDRFM_FAIL);
     k->lpos += n;                                               // the host's mirror of every stream's pos
   }
+  if (k->tpeak) {                                               // behind both, over the same rows
+    const TruePeakParams tp = {pcm, pcm_stride, k->d_tprec, k->d_tphist, k->d_tptab, k->tp_limit, n, k->tp_nt, k->tp_P};
+    hipLaunchKernelGGL(k_pcm_truepeak, dim3(k->n_streams), dim3(SDRFM_TP_NT), 0, stream, tp);
+    STRY(hipGetLastError(), SDRFM_FAIL);
+  }
   return SDRFM_OK;
 }
 
@@ -316,6 +341,10 @@ int sdrfm_pcm_stereo_sink_reset(sdrfm_pcm_stereo_sink_t* k) {
     STRY(hipMemsetAsync(k->d_lstate, 0, sizeof(sdrfm_loudness_state) * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
     STRY(hipMemsetAsync(k->d_lring, 0, sizeof(sdrfm_loudness_block) * (size_t)k->n_streams * k->lcap, k->stream), SDRFM_FAIL);
     k->lpos = k->lread = 0;
+  }
+  if (k->tpeak) {
+    STRY(hipMemsetAsync(k->d_tprec, 0, sizeof(sdrfm_truepeak) * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
+    STRY(hipMemsetAsync(k->d_tphist, 0, sizeof(unsigned) * (size_t)k->n_streams * (k->tp_nt - 1u), k->stream), SDRFM_FAIL);
   }
   STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
   k->J = SDRFM_ACTL_J_MAX;                                      // the high-cut's settings stay, its ramps are complete
@@ -541,6 +570,72 @@ int sdrfm_pcm_stereo_sink_loudness_get_state(sdrfm_pcm_stereo_sink_t* k, sdrfm_l
   STRY(hipSetDevice(k->device), SDRFM_FAIL);
   STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
   STRY(hipMemcpy(out, k->d_lstate, sizeof(sdrfm_loudness_state) * (size_t)k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+// the true-peak meter.  Every check comes before any device work; enable and disable wait for the sink's stream before they
+// change or free what a launch may still use
+static void truepeak_release(sdrfm_pcm_stereo_sink* k) {
+  if (k->d_tprec) (void)hipFree(k->d_tprec);
+  if (k->d_tphist) (void)hipFree(k->d_tphist);
+  if (k->d_tptab) (void)hipFree(k->d_tptab);
+  k->d_tprec = nullptr; k->d_tphist = nullptr; k->d_tptab = nullptr;
+  k->tpeak = false;
+}
+
+int sdrfm_pcm_stereo_sink_truepeak_enable(sdrfm_pcm_stereo_sink_t* k, const int16_t* coef, uint32_t n_phases, uint32_t n_taps, uint64_t limit) {
+  if (!k || limit > SDRFM_TP_LIMIT_MAX) return SDRFM_EINVAL;
+  int16_t dflt[48];
+  if (!coef) {
+    (void)sdrfm_truepeak_default_coef(dflt, &n_phases, &n_taps);
+    coef = dflt;
+  }
+  if (sdrfm_truepeak_check_coef(coef, n_phases, n_taps) != SDRFM_OK) return SDRFM_EINVAL;
+  uint32_t tab[SDRFM_TP_TABLE_DWORDS];
+  tp_pack_table(coef, n_phases, n_taps, tab);
+  if (hipSetDevice(k->device) != hipSuccess) return SDRFM_FAIL;
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  truepeak_release(k);                                          // an enabled sink starts over
+  const size_t rb = sizeof(sdrfm_truepeak) * (size_t)k->n_streams, hb = sizeof(unsigned) * (size_t)k->n_streams * (n_taps - 1u);
+  const size_t tb = sizeof(uint32_t) * n_phases * (n_taps / 2u);
+  if (hipMalloc(&k->d_tprec, rb) != hipSuccess || hipMalloc(&k->d_tphist, hb) != hipSuccess || hipMalloc(&k->d_tptab, tb) != hipSuccess) {
+    truepeak_release(k);
+    return SDRFM_ENOMEM;
+  }
+  if (hipMemsetAsync(k->d_tprec, 0, rb, k->stream) != hipSuccess || hipMemsetAsync(k->d_tphist, 0, hb, k->stream) != hipSuccess ||
+      hipMemcpyAsync(k->d_tptab, tab, tb, hipMemcpyHostToDevice, k->stream) != hipSuccess || hipStreamSynchronize(k->stream) != hipSuccess) {
+    truepeak_release(k);
+    return SDRFM_FAIL;
+  }
+  k->tp_limit = limit; k->tp_P = n_phases; k->tp_nt = n_taps;
+  k->tpeak = true;
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_stereo_sink_truepeak_disable(sdrfm_pcm_stereo_sink_t* k) {
+  if (!k) return SDRFM_EINVAL;
+  if (!k->tpeak) return SDRFM_OK;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  truepeak_release(k);
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_stereo_sink_truepeak_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_truepeak* out, uint32_t flags) {
+  if (!k || !out || (flags & ~(SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET)) || (uintptr_t)out % 8 != 0 || !k->tpeak) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  const size_t bytes = sizeof(sdrfm_truepeak) * (size_t)k->n_streams;
+  if (flags & SDRFM_F_DEVICE_PTRS) {                            // enqueued on the sink's stream, and nowhere else
+    STRY(hipMemcpyAsync(out, k->d_tprec, bytes, hipMemcpyDeviceToDevice, k->stream), SDRFM_FAIL);
+    if (flags & SDRFM_AMETER_F_RESET) STRY(hipMemsetAsync(k->d_tprec, 0, bytes, k->stream), SDRFM_FAIL);
+    return SDRFM_OK;
+  }
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipMemcpy(out, k->d_tprec, bytes, hipMemcpyDeviceToHost), SDRFM_FAIL);
+  if (flags & SDRFM_AMETER_F_RESET) {                           // the records only: the history stays and the stream continues
+    STRY(hipMemsetAsync(k->d_tprec, 0, bytes, k->stream), SDRFM_FAIL);
+    STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  }
   return SDRFM_OK;
 }
 

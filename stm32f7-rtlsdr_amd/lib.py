@@ -49,6 +49,9 @@ ABI_SYMBOLS = [
     "sdrfm_loudness_default_coef", "sdrfm_loudness_check_coef", "sdrfm_loudness_check_domain", "sdrfm_pcm_loudness_s16", "sdrfm_loudness_gate_create", "sdrfm_loudness_gate_push",
     "sdrfm_loudness_gate_report", "sdrfm_loudness_gate_reset", "sdrfm_loudness_gate_free", "sdrfm_pcm_stereo_sink_loudness_enable",
     "sdrfm_pcm_stereo_sink_loudness_disable", "sdrfm_pcm_stereo_sink_loudness_read", "sdrfm_pcm_stereo_sink_loudness_get_state",
+    "sdrfm_truepeak_default_coef", "sdrfm_truepeak_check_coef", "sdrfm_truepeak_limit", "sdrfm_pcm_truepeak_s16", "sdrfm_truepeak_add",
+    "sdrfm_truepeak_report", "sdrfm_pcm_stereo_sink_truepeak_enable", "sdrfm_pcm_stereo_sink_truepeak_disable",
+    "sdrfm_pcm_stereo_sink_truepeak_read",
     "sdrfm_pcm_rate_create", "sdrfm_pcm_rate_destroy", "sdrfm_pcm_rate_reset", "sdrfm_pcm_rate_set_step", "sdrfm_pcm_rate_count",
     "sdrfm_pcm_rate_process_batch", "sdrfm_pcm_rate_get_state", "sdrfm_pcm_rate_set_stream", "sdrfm_pcm_rate_synchronize",
     "sdrfm_pcm_rate_kernel_name", "sdrfm_pcm_rate_s16", "sdrfm_pcm_rate_check_coef",
@@ -197,6 +200,19 @@ class LoudnessReport(C.Structure):
 LOUDNESS_STATE_DTYPE = np.dtype([("pos", "<u8"), ("z", "<f8", (2, 4)), ("e", "<f8", (2,))])
 LOUDNESS_BLOCK_DTYPE = np.dtype([("e_l", "<f8"), ("e_r", "<f8")])
 assert LOUDNESS_STATE_DTYPE.itemsize == C.sizeof(LoudnessState) == 88 and LOUDNESS_BLOCK_DTYPE.itemsize == C.sizeof(LoudnessBlock) == 16
+
+
+class TruePeak(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n", "peak_l", "peak_r", "at_l", "at_r", "over_l", "over_r", "reserved")]
+
+
+class TruePeakReport(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("dbtp_l", "dbtp_r", "dbtp", "over_frac_l", "over_frac_r", "at_seconds_l", "at_seconds_r")]
+
+
+# sdrfm_truepeak as a structured dtype
+TRUEPEAK_DTYPE = np.dtype([(n, "<u8") for n, _ in TruePeak._fields_])
+assert TRUEPEAK_DTYPE.itemsize == C.sizeof(TruePeak) == 64
 
 
 class PcmRateConfig(C.Structure):
@@ -543,5 +559,24 @@ def load_library(dev=False):
     lib.sdrfm_pcm_stereo_sink_loudness_read.restype = C.c_int
     lib.sdrfm_pcm_stereo_sink_loudness_get_state.argtypes = [vp, vp]
     lib.sdrfm_pcm_stereo_sink_loudness_get_state.restype = C.c_int
+    u64 = C.c_uint64
+    lib.sdrfm_truepeak_default_coef.argtypes = [vp, u32p, u32p]
+    lib.sdrfm_truepeak_default_coef.restype = C.c_int
+    lib.sdrfm_truepeak_check_coef.argtypes = [vp, u32, u32]
+    lib.sdrfm_truepeak_check_coef.restype = C.c_int
+    lib.sdrfm_truepeak_limit.argtypes = [C.c_double]
+    lib.sdrfm_truepeak_limit.restype = u64
+    lib.sdrfm_pcm_truepeak_s16.argtypes = [vp, u32, vp, u32, u32, u64, vp, vp]
+    lib.sdrfm_pcm_truepeak_s16.restype = C.c_int
+    lib.sdrfm_truepeak_add.argtypes = [vp, vp]
+    lib.sdrfm_truepeak_add.restype = C.c_int
+    lib.sdrfm_truepeak_report.argtypes = [vp, u32, C.c_double, C.POINTER(TruePeakReport)]
+    lib.sdrfm_truepeak_report.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_truepeak_enable.argtypes = [vp, vp, u32, u32, u64]
+    lib.sdrfm_pcm_stereo_sink_truepeak_enable.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_truepeak_disable.argtypes = [vp]
+    lib.sdrfm_pcm_stereo_sink_truepeak_disable.restype = C.c_int
+    lib.sdrfm_pcm_stereo_sink_truepeak_read.argtypes = [vp, vp, u32]
+    lib.sdrfm_pcm_stereo_sink_truepeak_read.restype = C.c_int
     _libs[dev] = lib
     return lib

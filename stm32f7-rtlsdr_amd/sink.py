@@ -312,6 +312,42 @@ class StereoPcmSink:
         self._ck(self._lib.sdrfm_pcm_stereo_sink_loudness_get_state(self._h, out.ctypes.data), "sdrfm_pcm_stereo_sink_loudness_get_state")
         return out
 
+    # ---- the true-peak meter ----
+    def enable_truepeak(self, limit_dbtp=-1.0, coef=None, limit=None):
+        """sdrfm_pcm_stereo_sink_truepeak_enable: from the next call on every launch of this sink is followed by the true-peak kernel, which joins
+        the call's record (peak of the 4 x oversampled waveform, where it is, and how many values lie over limit_dbtp) onto each stream's.  coef:
+        int16 [n_phases, n_taps] in Q15 (the BS.1770-4 Annex 2 table when None; taps.truepeak_coef designs others).  limit, when given, is the limit in the record's units
+        (0 dBTP = 2^30) and limit_dbtp is not looked at.  Enabling again starts over."""
+        from .truepeak import truepeak_limit
+        c, P, NT = None, 0, 0
+        if coef is not None:
+            c = np.ascontiguousarray(coef, dtype=np.int16)
+            if c.ndim != 2 or not np.array_equal(c, np.asarray(coef)):
+                raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_stereo_sink_truepeak_enable: coef")
+            P, NT = c.shape
+        lim = truepeak_limit(limit_dbtp) if limit is None else int(limit)
+        if not 0 <= lim <= 0xFFFFFFFFFFFFFFFF:
+            raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_stereo_sink_truepeak_enable: limit")
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_truepeak_enable(self._h, None if c is None else c.ctypes.data, P, NT, lim),
+                 "sdrfm_pcm_stereo_sink_truepeak_enable")
+        self.truepeak_phases = 4 if c is None else int(P)
+
+    def disable_truepeak(self):
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_truepeak_disable(self._h), "sdrfm_pcm_stereo_sink_truepeak_disable")
+
+    def read_truepeak(self, reset=True):
+        """sdrfm_pcm_stereo_sink_truepeak_read into host memory: a TRUEPEAK_DTYPE array [n_streams], what the sink has written since the records
+        were last zeroed; reset=True zeroes them behind the copy and keeps the history, so that successive reads join with truepeak_add."""
+        out = np.zeros(self.n_streams, dtype=_l.TRUEPEAK_DTYPE)
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_truepeak_read(self._h, out.ctypes.data, _l.AMETER_F_RESET if reset else 0), "sdrfm_pcm_stereo_sink_truepeak_read")
+        return out
+
+    def read_truepeak_device(self, out, reset=True):
+        """the same into a torch tensor on the device of at least 64 * n_streams bytes (8-byte aligned); only enqueues on the sink's stream"""
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 64 * self.n_streams
+        self._ck(self._lib.sdrfm_pcm_stereo_sink_truepeak_read(self._h, C.c_void_p(out.data_ptr()), _l.F_DEVICE_PTRS | (_l.AMETER_F_RESET if reset else 0)),
+                 "sdrfm_pcm_stereo_sink_truepeak_read(device)")
+
 
 AUDIO_METER_DTYPE = _l.AUDIO_METER_DTYPE
 AUDIO_REPORT_FIELDS = tuple(n for n, _ in _l.AudioReport._fields_)

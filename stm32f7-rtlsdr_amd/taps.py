@@ -120,3 +120,25 @@ def rate_coef(NT=32, LOGPH=8, cutoff=None, beta=9.0, step=1 << 32):
     if q.max() > 32767 or q.min() < -32768:
         raise ValueError("rate_coef: a tap does not fit Q15 (cutoff %g at %d taps)" % (cutoff, NT))
     return q.astype(np.int16)
+
+
+def truepeak_coef(n_phases=4, n_taps=12, cutoff=0.9, beta=6.0):
+    """a coefficient table for the true-peak meter: int16 [n_phases, n_taps] in Q15, a windowed-sinc interpolator laid out as
+    the BS.1770-4 Annex 2 table is — coef[p][k] = Q15(h(k - (n_taps - 1) / 2 + (p - (n_phases - 1) / 2) / n_phases)) with h(t) = cutoff
+    sinc(cutoff t) Kaiser(beta) over |t| <= n_taps / 2, so the phases lie symmetrically about the middle of the row and row n_phases - 1 - p
+    is row p reversed.  cutoff is in units of the input's Nyquist frequency.  Each row is normalised to sum 1, rounded, and its largest tap
+    adjusted so that the row sums to exactly 32768: a constant input reads its own level.  ValueError where a tap does not fit Q15 or half a
+    row passes the bound of sdrfm_truepeak_check_coef (sum of |coef| <= 65535)."""
+    P, NT = int(n_phases), int(n_taps)
+    if P not in (2, 4, 8) or NT % 4 or not 4 <= NT <= 64:
+        raise ValueError("truepeak_coef: %d phases of %d taps" % (P, NT))
+    t = np.arange(NT, dtype=np.float64)[None, :] - (NT - 1) / 2 + (np.arange(P, dtype=np.float64)[:, None] - (P - 1) / 2) / P
+    u = np.clip(1.0 - (2.0 * t / NT) ** 2, 0.0, None)
+    h = float(cutoff) * np.sinc(float(cutoff) * t) * np.i0(float(beta) * np.sqrt(u)) / np.i0(float(beta)) * (np.abs(t) <= NT / 2)
+    q = np.rint(h / h.sum(axis=1, keepdims=True) * 32768.0).astype(np.int64)
+    q[np.arange(P), np.argmax(q, axis=1)] += 32768 - q.sum(axis=1)
+    if q.max() > 32767 or q.min() < -32768:
+        raise ValueError("truepeak_coef: a tap does not fit Q15 (cutoff %g at %d taps)" % (cutoff, NT))
+    if max(np.abs(q[:, :NT // 2]).sum(axis=1).max(), np.abs(q[:, NT // 2:]).sum(axis=1).max()) > 65535:
+        raise ValueError("truepeak_coef: half a row passes the bound (cutoff %g at %d taps)" % (cutoff, NT))
+    return q.astype(np.int16)
