@@ -7,6 +7,7 @@
  *     sdrfm_host_atan2f, sdrfm_host_discriminate   HOST evaluation of the device's K3 arithmetic (same source, same rounding)
  *     sdrfm_debug_discriminate                     K3 evaluated ON THE DEVICE for n operand sets, both code forms
  *     sdrfm_q_build                                design Q: the channel taps as i8 matrix-pipe operand tables (csrc/qtaps.c)
+ *     sdrfm_q_seed                                 design Q: the constant term in tap units, the S0 accumulator's starting value (csrc/qtaps.c; no GPU)
  *     sdrfm_q_guard                                design Q: the conditioning guard's thresholds for a tap set (csrc/qtaps.c; no GPU)
  *     sdrfm_debug_q_guard                          design Q: a handle's guard thresholds and how often its repair path ran
  *     sdrfm_debug_read_ceiling                     what a read-only stream with design Q's access pattern gets out of the memory system
@@ -38,6 +39,10 @@ int sdrfm_debug_discriminate(int device, const float* yr, const float* yi, const
 /* Design Q (csrc/qtaps.c): h[0..T) -> A[D/2][3][64][16] (K-chunk, digit, lane, byte) i8 operand tables, the fp32 scale q with
  * y = q (S0 + 256 S1 + 65536 S2) + cst, cst = 0.5 sum(h), and the first K-chunk holding a non-zero tap.  0 on success. */
 int sdrfm_q_build(const float* h, uint32_t T, uint32_t D, int8_t* A, float* q, float* cst, uint32_t* first_chunk);
+
+/* Design Q (csrc/qtaps.c): the constant term 0.5 sum(H) of the same taps in tap units, as the integer the scale-free recombination starts its S0 accumulator
+ * from (an odd sum: the nearer neighbour); -1 for taps sdrfm_q_build refuses or a seed that could leave i32 with the largest S0 + (S1 << 8).  0 on success. */
+int sdrfm_q_seed(const float* h, uint32_t T, uint32_t D, int32_t* seed);
 
 /* Design Q (csrc/qtaps.c): the conditioning guard's thresholds for channel taps h[0..T) and audio taps g[0..Ta).  0 on success. */
 int sdrfm_q_guard(const float* h, uint32_t T, const float* g, uint32_t Ta, float* guard_r, float* guard_a);

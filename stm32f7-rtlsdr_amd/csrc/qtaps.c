@@ -24,6 +24,7 @@
  */
 #include <math.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "sdrfm_q_host.h"
@@ -73,6 +74,44 @@ int sdrfm_q_build(const float* h, uint32_t T, uint32_t D, int8_t* A, float* q_ou
   *q_out = qf;
   *cst_out = (float)(0.5 * hsum);
   *first_chunk = c0;
+  return 0;
+}
+
+/* The constant term in TAP UNITS, for the scale-free recombination (sdrfm_q.hip, SDRFM_Q_SCALEFREE): the kernel forms Y = y / q = S0 + 2^8 S1 + 2^16 S2 + seed with
+ * the seed as the S0 accumulator's starting value, so that the constant costs no instruction.  With H[k] the integers of sdrfm_q_build, seed = sum(H) / 2 makes
+ * q Y = q sum H[k] (byte - 127.5): the taps' fixed-point image against the spec's own x, every tap's error q / 2 against |x| <= 127.5 — inside the 64 T q the
+ * worst-case guard radius allows for it (below) with T q / 4 to spare.  An odd sum(H) has no integer half: the seed is then the neighbour of sum(H) / 2 nearer
+ * to the fp32 constant 0.5 sum(h) / q of the scaled form, one more q / 2 — within that spare for T >= 2, and for T = 1 the one tap is H = +-SDRFM_Q_HMAX with an
+ * error of one fp32 rounding of q, not q / 2.  (The exact half would cost an instruction per value)
+ * The seed plus the largest |S0 + (S1 << 8)| any bytes can produce must stay inside i32: checked here, -1 otherwise (never for T <= 9 D <= 144: 2^30.2 at most). */
+int sdrfm_q_seed(const float* h, uint32_t T, uint32_t D, int32_t* seed_out) {
+  if (!h || !seed_out || D < 2 || (D & 1u) || D > SDRFM_Q_MAX_D || T < 1 || T > 9 * D) return -1;
+  double hmax = 0.0, hsum = 0.0;
+  for (uint32_t k = 0; k < T; ++k) {
+    if (!isfinite(h[k])) return -1;
+    if (fabs((double)h[k]) > hmax) hmax = fabs((double)h[k]);
+    hsum += (double)h[k];
+  }
+  if (hmax == 0.0) return -1;
+  const float qf = (float)(hmax / (double)SDRFM_Q_HMAX);
+  if (!(qf > 0.0f) || !isfinite(65536.0f * qf)) return -1;
+  long long sumH = 0, reach = 0;                                    /* reach: the largest |S0 + 256 S1| over all bytes (|byte - 128| <= 128) */
+  for (uint32_t k = 0; k < T; ++k) {
+    long long H = llround((double)h[k] / (double)qf);               /* as sdrfm_q_build has them */
+    if (H > SDRFM_Q_HMAX) H = SDRFM_Q_HMAX;
+    if (H < -SDRFM_Q_HMAX) H = -SDRFM_Q_HMAX;
+    sumH += H;
+    const long long d0 = ((H + 128) % 256 + 256) % 256 - 128, H1 = (H - d0) / 256, d1 = ((H1 + 128) % 256 + 256) % 256 - 128;
+    reach += 128 * (llabs(d0) + 256 * llabs(d1));
+  }
+  long long seed = sumH / 2;                                        /* (C division: towards zero) */
+  if (sumH & 1) {
+    const double want = 0.5 * hsum / (double)qf;
+    const long long lo = (sumH - 1) / 2;                            /* sumH - 1 is even: exact; the two neighbours are lo, lo + 1 */
+    seed = fabs((double)lo - want) <= fabs((double)(lo + 1) - want) ? lo : lo + 1;
+  }
+  if (llabs(seed) + reach > 2147483647LL) return -1;
+  *seed_out = (int32_t)seed;
   return 0;
 }
 

@@ -959,6 +959,7 @@ struct sdrfm {
   // design Q (matrix-pipe FIR, sdrfm_q.hip): operand tables on the device, scale / offset, first K-chunk that holds taps
   int8_t* d_qA;
   float q_scale, q_cst;
+  int32_t q_seed;                    // the constant term in tap units (sdrfm_q_seed): design Q's scale-free recombination
   uint32_t q_c0, q_nslot;
   char fast_q_name[64];
   // design Q's conditioning guard: thresholds, the zero-padded taps of the repair path's chain, the last 64 raw samples of
@@ -1299,9 +1300,10 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
   const size_t q_tab_bytes = (size_t)SDRFM_Q_SPARSE_CHUNKS(in.D) * SDRFM_Q_DIGITS * 64 * 16;
   int8_t* q_tab = nullptr;
   float q_scale = 0.f, q_cst = 0.f;
+  int32_t q_seed = 0;
   if (fm_plan_offers_q(in, knobs)) {
     q_tab = (int8_t*)malloc(q_tab_bytes);
-    in.q_built = q_tab && sdrfm_q_build(hc, in.T, in.D, q_tab, &q_scale, &q_cst, &in.q_c0) == 0;   // (false: taps the tables cannot hold)
+    in.q_built = q_tab && sdrfm_q_build(hc, in.T, in.D, q_tab, &q_scale, &q_cst, &in.q_c0) == 0 && sdrfm_q_seed(hc, in.T, in.D, &q_seed) == 0;   // (false: taps the tables cannot hold)
     const uint32_t nslot = fm_plan_q_nslot(in, knobs);
     in.q_lds = sdrfm_q_lds_bytes(nslot, in.D, in.Da);
     in.q_symbol = sdrfm_q_kernel_symbol(in.q_c0, nslot, in.D, in.Da);
@@ -1351,7 +1353,7 @@ int sdrfm_create(const sdrfm_config* cfg, sdrfm_t** out) {
   }
   h->AB = plan.AB; h->warm_ahead = plan.warm_ahead; h->fast_mode = plan.fast_mode; h->stream_profile = plan.stream_profile ? 1u : 0u;
   h->prio_balance = knobs.prio_balance; h->end_prio = knobs.end_prio;
-  if (plan.geo.has_q) { h->q_scale = q_scale; h->q_cst = q_cst; }
+  if (plan.geo.has_q) { h->q_scale = q_scale; h->q_cst = q_cst; h->q_seed = q_seed; }
   h->q_c0 = plan.q_c0; h->q_nslot = plan.q_nslot; h->q_guard_r = plan.q_guard_r; h->q_guard_a = plan.q_guard_a;
   h->rt_off = knobs.q_no_adapt;
   snprintf(h->generic_name, sizeof(h->generic_name), "%s", plan.generic_name);
@@ -1749,7 +1751,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
       HIP_TRY(hipMemcpy2DAsync(h->d_hist_q[h->cur] + 2 * (SDRFM_Q_TP - (c.fir_taps - 1)), 2 * SDRFM_Q_TP, p.hist_b_in, 2 * (size_t)(c.fir_taps - 1),
                                2 * (size_t)(c.fir_taps - 1), c.n_streams, hipMemcpyDeviceToDevice, h->stream), SDRFM_FAIL);
     q.hpad = h->d_hpad; q.hist_q_in = h->d_hist_q[h->cur]; q.hist_q_out = h->d_hist_q[h->cur ^ 1];
-    q.guard_r = h->q_guard_r; q.guard_a = h->q_guard_a; q.yprev_exact = h->yprev_exact ? 1u : 0u; q.n_repaired = h->d_qstat;
+    q.guard_r = h->q_guard_r; q.guard_a = h->q_guard_a; q.seed = h->q_seed; q.guard_rq = h->q_guard_r / h->q_scale; q.yprev_exact = h->yprev_exact ? 1u : 0u; q.n_repaired = h->d_qstat;
     const FmRuns r = fm_q_runs(cl, split.q_total, n_clean, with_chain, h->runstate_cap, fm_chain_run_quads(g.Da));
     q.runs = r.runs;
     // The counter set of the routing window this call adds to, and the stop event its kernel carries (fm_route_stop): one of the window's, or the overlap's.

@@ -42,6 +42,9 @@ struct SdrfmQParams {
   uint8_t* hist_q_out;
   float guard_r;                // a lane is repaired when max(|re|, |im|) of one of its three y's is below this ...
   float guard_a;                // ... or one of its two |d|'s is above this (the branch cut); guard_r = 0 and guard_a = 4 switch the guard off
+  int32_t seed;                 // scale-free recombination (SDRFM_Q_SCALEFREE): the constant term in tap units, the S0 accumulator's starting value (sdrfm_q_seed) ...
+  float guard_rq;               // ... and guard_r / q0: the radius Y = y / q0 is compared against, in the step loop and for a carried y[-1] design Q left (yprev_exact = 0: yprev_out
+                                // of the scale-free form is Y, in tap units; nothing but the next design-Q call reads it — a bit-exact kernel that takes over recomputes y[-1])
   uint32_t yprev_exact;         // yprev_in holds the definition's y[-1] (reset, or the previous call ran on a bit-exact kernel): hist_q_in[0] is not valid then
   unsigned int* n_repaired;     // statistics (device, two words: repaired lanes, repair passes) or nullptr
   unsigned int* stream_pass;    // [n_streams of the handle] or nullptr: repair passes per stream, added up by the waves that ran any (the host routes a stream
@@ -71,6 +74,8 @@ bool sdrfm_q_has_pcm_chain(uint32_t first_chunk, uint32_t nslot, uint32_t d, uin
 hipError_t sdrfm_q_launch_pcm(const SdrfmQParams& p, const SdrfmSinkChain& t, uint32_t first_chunk, uint32_t nslot, uint32_t d, uint32_t da, hipStream_t stream,
                               hipEvent_t done = nullptr);
 const char* sdrfm_q_kernel_symbol(uint32_t first_chunk, uint32_t nslot, uint32_t d, uint32_t da);
+// what a y[-1] these kernels hand over (yprev_out) is multiplied by to be at true scale: q0 for the scale-free recombination (tap units), else 1 (tools/qbench)
+double sdrfm_q_yprev_scale(float q0);
 // ---- one launch for a mixed batch (sdrfm_q.hip: k_mix): b_blocks design-B workgroups (tile R = b_R; b as k_fastb takes it, fold_state = 1) over the
 // streams of b.slist, then q.n_streams * q.runs design-Q workgroups.  An instance exists for every shape both designs have one for (LDS bytes of one workgroup; 0 = none).
 struct CallParams;   // sdrfm_b.h

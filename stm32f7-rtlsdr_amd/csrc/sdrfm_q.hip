@@ -28,7 +28,8 @@
  *       B operand as the MFMA wants it (conflict-free: lane stride 160 B)--> v_xor 0x80808080
  *   3 K-chunks of 128 bytes x 3 digits v_smfmac_i32_16x16x128_i8 (A = tap tables, exactly 2:4 sparse: I rows hold taps at even
  *   bytes, Q rows at odd ones; wave-constant, 36 VGPRs + one index word) --> S0, S1, S2 exact in i32
- *   --> y = fma(f32(S0 + (S1 << 8)), q, fma(f32(S2), 65536 q, 0.5 sum h)): lane (n, g) holds (I, Q) of outputs 8 n + 2 g, +1
+ *   --> Y = y / q = fma(f32(S2), 65536, f32(S0 + (S1 << 8))), S0 started at the constant term in tap units (SDRFM_Q_SCALEFREE: the angle needs no scale; the
+ *       scaled form: y = fma(f32(S0 + (S1 << 8)), q, fma(f32(S2), 65536 q, 0.5 sum h))): lane (n, g) holds (I, Q) of outputs 8 n + 2 g, +1
  *   --> y[m-1] of the lane's first output from lane - 16 (ds_bpermute) --> K3 twice (scalar code: packed f32 instructions stall
  *       the matrix pipe, profiles/ubench_r03) --> d's into an LDS buffer
  *   every DA = 5 steps (640 d's = 128 audio outputs): K4, two consecutive outputs per lane from 20 aligned 8-byte reads --> parked in LDS
@@ -106,8 +107,31 @@ struct QGeo {
 #ifndef SDRFM_Q_MICRO
 #define SDRFM_Q_MICRO 1     // 1 (round 6): the carried angle enters lane 0 through v_writelane (one instruction instead of a move and a select); the d write's address
 #endif                      // is one shift-add on a pointer kept in a VGPR (the compiler re-added the buffer's offset every step)
+#ifndef SDRFM_Q_SCALEFREE
+#define SDRFM_Q_SCALEFREE 1 // 1: the recombination leaves the scale out.  K3 is a difference of angles and the arctangent uses only mn / mx, so the common factor q0 of the four y
+#endif                      // is dead work: Y = y / q0 = fma(f32(S2), 65536, f32(S0 + (S1 << 8))) with the constant term (SdrfmQParams::seed, tap units) as the S0 accumulator's
+                            // starting value — one fused multiply-add less per value, and the three scalar factors leave the loop.  The guard compares the arctangent's own
+                            // larger magnitude against guard_r / q0 (guard_rq).  yprev_out carries Y as it is: the next design-Q call (yprev_exact = 0) tests it against guard_rq too
+                            // and takes its angle bit for bit as this call would; a y[-1] from a reset or a bit-exact kernel (yprev_exact = 1) is at true scale and meets guard_r.
+                            // The repair path, the hand-over of input bytes and d's and the PCM chain work at true scale as before.  0: the scaled form.
+                            // With SDRFM_Q_NOB6: 98 -> 94 vector instructions in the step block, 26 -> 18 with a scalar-register operand (the slow kind: tools/ubench/ubench15.hip);
+                            // two streams, steady, every run below every run of the parent commit's binary: 21.59 -> 21.37 us (the recombination alone, an earlier build: 21.49
+                            // against 21.56, overlapping the parent's runs); the consumer loop no slower: profiles/q_scalefree_experiments.txt item 1
+#ifndef SDRFM_Q_NOB6
+#define SDRFM_Q_NOB6 1      // 1: D / 2 odd (D = 10): the sixth 64-byte piece of a lane's window lies beyond the window — the tables hold no tap there, and an integer product
+#endif                      // with a zero tap is zero whatever the byte is — so it is not read (one ds_read_b128 per step, 4 VGPRs): the last issue's upper half is left undefined
+#ifndef SDRFM_Q_CVGPR
+#define SDRFM_Q_CVGPR 0     // the step's constants kept in VGPRs instead of literals (a bit mask; tools/ubench/ubench15.hip prices the operand forms): 1 = the recombination's 65536,
+#endif                      // 2 = the arctangent's six coefficients, 4 = the wrap's three constants, 8 = pi / 2 and pi, 16 = the byte - 128 mask.  Not kept: a literal costs a full-rate
+                            // instruction nothing (ubench15: v_fmaak 1.13 ns against 1.14 with registers; only a scalar REGISTER operand is slow, 1.80), and 15 (128 VGPRs, no spill;
+                            // 31 spills) measured 21.40 us against 21.31 without: q_scalefree_experiments.txt item 2
+#ifndef SDRFM_Q_W3
+#define SDRFM_Q_W3 0        // 1: the D = 10 instances budget three waves per SIMD (168 VGPRs, 12 waves per CU, as the D = 16 instance runs): room for every constant of SDRFM_Q_CVGPR
+#endif                      // (154 VGPRs used).  Not kept: serial calls the same, overlapped calls 21.79 (CVGPR = 15) / 21.96 (31) against 21.31 us — the three spare wave slots per CU
+                            // are what lets the next call's waves start under the previous call's tail: q_scalefree_experiments.txt item 3
+static_assert(!SDRFM_Q_SCALEFREE || SDRFM_Q_K3, "the scale-free recombination rests on K3 as a difference of angles");
 #ifndef SDRFM_Q_AUX
-#define SDRFM_Q_AUX 2   // cache policy of the ring's fetches: 2 = nt (streamed once; measured 0.4-1 us per launch better than the default policy)
+#define SDRFM_Q_AUX 2  // cache policy of the ring's fetches: 2 = nt (streamed once; measured 0.4-1 us per launch better than the default policy)
 #endif
 #ifndef SDRFM_Q_WQB
 #define SDRFM_Q_WQB 4   // blocks of a warm-up = the unit runs are cut in (>= 4: QTA - 1 d's and the y before them)
@@ -145,29 +169,38 @@ __device__ __forceinline__ float q_discriminate(float yr, float yi, float pr, fl
 // conditioning guard tests, so the guard's three v_max and its v_min3 go too (sdrfm_q.hip: "the conditioning guard").  The price is
 // one more rounding of the arctangent in every d (both angles carry the polynomial's 3.9e-7) and the wrap: |d - definition's d| <= 1.1e-6
 // worst case where the phase is well conditioned (the guard's business where it is not), measured 7e-7 (tools/q_emulate.py k3="diff").
-__device__ __forceinline__ float q_angle(float yr, float yi, float& mx_out) {
+// The step's constants (SDRFM_Q_CVGPR): literals by default — the compiler folds them into v_fmaak / v_fmamk / v_sub with a 32-bit literal —, or, per group, values held
+// in VGPRs across the step loop (made opaque once before it).
+struct QK {
+  float c[6] = {0x1.e34882p-8f, -0x1.22fc74p-5f, 0x1.509024p-4f, -0x1.12688cp-3f, 0x1.96c562p-3f, -0x1.554086p-2f};   // the arctangent's polynomial in s = v^2
+  float w[3] = {0x1.45f306p-3f, 0x1.8p+23f, -0x1.921fb6p+2f};                                                       // the wrap: 1 / 2 pi, 1.5 * 2^23, -2 pi
+  float hpi = 0x1.921fb6p+0f, pi = 0x1.921fb6p+1f;
+  float k16 = 65536.0f;
+  int xm = (int)0x80808080;
+};
+__device__ __forceinline__ float q_angle(float yr, float yi, float& mx_out, const QK& K = QK{}) {
   const float ax = __builtin_fabsf(yr), ay = __builtin_fabsf(yi);
   const float mx = __builtin_fmaxf(__builtin_fmaxf(ax, ay), 0x1p-120f), mn = __builtin_fminf(ax, ay);   // v_max3_f32, v_min_f32
   mx_out = mx;
   const float v = mn * __builtin_amdgcn_rcpf(mx);
   const float s2 = v * v;
-  float q = 0x1.e34882p-8f;
-  q = __builtin_fmaf(q, s2, -0x1.22fc74p-5f);
-  q = __builtin_fmaf(q, s2, 0x1.509024p-4f);
-  q = __builtin_fmaf(q, s2, -0x1.12688cp-3f);
-  q = __builtin_fmaf(q, s2, 0x1.96c562p-3f);
-  q = __builtin_fmaf(q, s2, -0x1.554086p-2f);
+  float q = K.c[0];
+  q = __builtin_fmaf(q, s2, K.c[1]);
+  q = __builtin_fmaf(q, s2, K.c[2]);
+  q = __builtin_fmaf(q, s2, K.c[3]);
+  q = __builtin_fmaf(q, s2, K.c[4]);
+  q = __builtin_fmaf(q, s2, K.c[5]);
   float a = __builtin_fmaf(v, s2 * q, v);
-  if (ay > ax) a = 0x1.921fb6p+0f - a;
-  if (yr < 0.0f) a = 0x1.921fb6p+1f - a;
+  if (ay > ax) a = K.hpi - a;
+  if (yr < 0.0f) a = K.pi - a;
   return __builtin_copysignf(a, yi);                            // (the two reflections as sign transfers — v_bfi around pi / 4 and pi / 2, no compare + select — measured
 }                                                               // 0.8 % slower and cost two more roundings: profiles/r06_q_experiments.txt item 4)
 // x in (-2 pi, 2 pi) -> x - 2 pi rint(x / 2 pi): three full-rate instructions (the rounding through the 1.5 * 2^23 constant; v_rndne_f32 is a quarter-rate one)
-__device__ __forceinline__ float q_wrap(float x) {
-  float t = __builtin_fmaf(x, 0x1.45f306p-3f, 0x1.8p+23f);
+__device__ __forceinline__ float q_wrap(float x, const QK& K = QK{}) {
+  float t = __builtin_fmaf(x, K.w[0], K.w[1]);
   asm volatile("" : "+v"(t));                                   // (keeps the two roundings apart)
-  const float k = t - 0x1.8p+23f;
-  return __builtin_fmaf(k, -0x1.921fb6p+2f, x);
+  const float k = t - K.w[1];
+  return __builtin_fmaf(k, K.w[2], x);
 }
 
 // v -> (int16) rint(clamp(v, -32768, 32767)) in both halves of a word, as the host routine has it (csrc/pcm_sink.c): one v_med3 (v is never a NaN for finite
@@ -379,7 +412,11 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
     float mxp;
     const float tp = q_angle(cr, ci, mxp);
     cth = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tp)));
+#if SDRFM_Q_SCALEFREE
+    cfl = __builtin_amdgcn_ballot_w64(mxp < (p.yprev_exact ? p.guard_r : p.guard_rq)) & 1ull;   // (a y[-1] the previous design-Q call left is in tap units: see yprev_out below)
+#else
     cfl = __builtin_amdgcn_ballot_w64(mxp < p.guard_r) & 1ull;
+#endif
   }
 #endif
   db[lane] = hz0;
@@ -451,7 +488,7 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
     } else {
       const unsigned char* wb = smem + baddr + ringoff;
 #pragma unroll
-      for (int c = 2 * C0; c < 2 * NSC; ++c) dst[c - 2 * C0] = *reinterpret_cast<const qi4_t*>(wb + 64 * c);
+      for (int c = 2 * C0; c < 2 * NSC - ((SDRFM_Q_NOB6 && (NCH & 1)) ? 1 : 0); ++c) dst[c - 2 * C0] = *reinterpret_cast<const qi4_t*>(wb + 64 * c);
       if (ringoff + STEPB == RINGB) {                           // the next step starts the ring over: its pre-halo = the ring's last block
         if (lane < BLKB / 16) {
           const qi4_t hcp = *reinterpret_cast<const qi4_t*>(smem + PRE + RINGB - BLKB + 16 * lane);
@@ -743,15 +780,29 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
   // remaining steps (a wave that is behind outranks one that is ahead), alone or on top of the rank: no better (25.9 - 26.4 us).
 #ifdef SDRFM_Q_GUARD_L1
   float guard_r = 2.0f * p.guard_r, guard_a = p.guard_a;
+#elif SDRFM_Q_SCALEFREE
+  float guard_r = p.guard_rq, guard_a = p.guard_a;            // (the loop's norms are those of Y = y / q0)
 #else
   float guard_r = p.guard_r, guard_a = p.guard_a;             // (in VGPRs: the loop's scalar registers are all taken)
 #endif
   asm volatile("" : "+v"(guard_r), "+v"(guard_a));
+  QK K;
+  if constexpr ((SDRFM_Q_CVGPR & 1) != 0) asm volatile("" : "+v"(K.k16));
+  if constexpr ((SDRFM_Q_CVGPR & 2) != 0) asm volatile("" : "+v"(K.c[0]), "+v"(K.c[1]), "+v"(K.c[2]), "+v"(K.c[3]), "+v"(K.c[4]), "+v"(K.c[5]));
+  if constexpr ((SDRFM_Q_CVGPR & 4) != 0) asm volatile("" : "+v"(K.w[0]), "+v"(K.w[1]), "+v"(K.w[2]));
+  if constexpr ((SDRFM_Q_CVGPR & 8) != 0) asm volatile("" : "+v"(K.hpi), "+v"(K.pi));
+  if constexpr ((SDRFM_Q_CVGPR & 16) != 0) asm volatile("" : "+v"(K.xm));
+#if SDRFM_Q_SCALEFREE
+  // the seed twice in one 64-bit scalar: an accumulator's four words start from it with two 64-bit moves, as they start from zero
+  const int seed1 = __builtin_amdgcn_readfirstlane(p.seed);
+  unsigned long long seed2 = (unsigned long long)(unsigned)seed1 * 0x100000001ull;
+  asm volatile("" : "+v"(seed2));                               // (one VGPR pair across the loop)
+#endif
 #ifdef SDRFM_Q_SCALE_VGPR   // experiment (round 5): the recombination's factors in VGPRs (an FMA with an SGPR operand issues at half rate) — measured 0.2 us
   float q0v = p.q0, q2v = p.q2, cstv = p.cst;                  // per call SLOWER than leaving them in SGPRs (the kernel sits at its 128 VGPRs): profiles/r05_q_experiments.txt
   asm volatile("" : "+v"(q0v), "+v"(q2v), "+v"(cstv));
 #else
-  const float q0v = p.q0, q2v = p.q2, cstv = p.cst;
+  [[maybe_unused]] const float q0v = p.q0, q2v = p.q2, cstv = p.cst;
 #endif
 #if SDRFM_Q_MICRO && SDRFM_Q_K3
   int doff = (PRE + RINGB) + 4 * (DB0 + sigma + dlane);          // LDS byte offset of the lane's two d's of the stage's first step (opaque: an offset, not a
@@ -810,7 +861,21 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
     qi4_t acc[SDRFM_Q_DIGITS];
 #pragma unroll
     for (int t = 0; t < SDRFM_Q_DIGITS; ++t) acc[t] = qi4_t{0, 0, 0, 0};   // (zeroed by the matrix pipe itself — a dense issue with a zero A operand — measured slower: r06_q_experiments.txt item 3)
-    [[maybe_unused]] constexpr int XM = (int)0x80808080;
+#if SDRFM_Q_SCALEFREE
+    {
+      // S0 starts from the constant term (tap units), S1 and S2 from zero: six v_mov_b64 written out, the zeros as inline constants and the seed from ONE register
+      // pair.  (Left to the compiler, a quad of zeros and a quad of seeds are kept in eight VGPRs across the loop — four more than the scaled form's quad of zeros,
+      // which at the 128-register cap sent k_mfir_pcm's scalar spills to scratch.)
+      typedef unsigned long long ql2_t __attribute__((ext_vector_type(2)));
+      unsigned long long a0, a1, z0, z1, z2, z3;
+      asm volatile("v_mov_b64 %0, %6\n\tv_mov_b64 %1, %6\n\tv_mov_b64 %2, 0\n\tv_mov_b64 %3, 0\n\tv_mov_b64 %4, 0\n\tv_mov_b64 %5, 0"
+                   : "=&v"(a0), "=&v"(a1), "=&v"(z0), "=&v"(z1), "=&v"(z2), "=&v"(z3) : "v"(seed2));
+      acc[0] = __builtin_bit_cast(qi4_t, ql2_t{a0, a1});
+      acc[1] = __builtin_bit_cast(qi4_t, ql2_t{z0, z1});
+      acc[2] = __builtin_bit_cast(qi4_t, ql2_t{z2, z3});
+    }
+#endif
+    [[maybe_unused]] const int XM = K.xm;
 #ifndef SDRFM_Q_LDSXOR
 #pragma unroll
     for (int c = 0; c < NB - 1 + (NCH & 1 ? 0 : 1); ++c)                                      // byte - 128 as i8 (not the piece beyond the window)
@@ -819,7 +884,11 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
 #pragma unroll
     for (int c = C0; c < NSC; ++c) {
       // 128 window bytes per issue: the lane's two 16-byte pieces 64 bytes apart
-      const qi4_t lo = B[2 * c - 2 * C0], hi = B[2 * c + 1 - 2 * C0];
+      const qi4_t lo = B[2 * c - 2 * C0];
+      qi4_t hi = B[2 * c + 1 - 2 * C0];
+      if constexpr (SDRFM_Q_NOB6 && (NCH & 1)) {
+        if (c == NSC - 1) asm volatile("" : "=v"(hi));            // beyond the window: zero taps only — any bytes do, none are read (whatever the four registers hold)
+      }
       const qi8_t b = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
       for (int t = 0; t < SDRFM_Q_DIGITS; ++t) {
@@ -837,7 +906,11 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
       // (The digit sums as exact floats — accumulators started at the bit pattern of 1.5 * 2^23, a full-rate subtraction instead of the conversions and the
       // shift-add, three fused multiply-adds — measured no faster with the factors in SGPRs and slower with them in VGPRs: r06_q_experiments.txt item 2.)
       const int s01 = acc[0][r] + acc[1][r] * 256;              // exact: |S0| <= 2^20, |S1 << 8| <= 2^28
+#if SDRFM_Q_SCALEFREE
+      y[r] = __builtin_fmaf((float)acc[2][r], K.k16, (float)s01);   // Y = y / q0 (the constant term came in through S0)
+#else
       y[r] = __builtin_fmaf((float)s01, q0v, __builtin_fmaf((float)acc[2][r], q2v, cstv));
+#endif
     }
 #ifdef SDRFM_Q_PHASES
     asm volatile("" : "+v"(y[0]), "+v"(y[1]), "+v"(y[2]), "+v"(y[3]));
@@ -847,9 +920,9 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
 #if SDRFM_Q_K3
     // (round 6) angles, not products: the lane's second angle first — it is what the neighbour needs —, the exchange in flight under the first one's chain
     float mx0, mx1;
-    const float th1 = q_angle(y[2], y[3], mx1);
+    const float th1 = q_angle(y[2], y[3], mx1, K);
     float thp = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(srcaddr, __builtin_bit_cast(int, th1)));
-    const float th0 = q_angle(y[0], y[1], mx0);
+    const float th0 = q_angle(y[0], y[1], mx0, K);
 #if SDRFM_Q_MICRO
     asm("v_writelane_b32 %0, %1, 0" : "+v"(thp) : "s"(cth));    // lane 0: the carried angle
 #else
@@ -860,8 +933,8 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
 #endif
     Q_PHASE(4);                                                 // neighbour exchange
     cth = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, th1), 63));
-    const float d1 = q_wrap(th1 - th0);
-    const float d0 = q_wrap(th0 - thp);
+    const float d1 = q_wrap(th1 - th0, K);
+    const float d0 = q_wrap(th0 - thp, K);
 #else
     float pr = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(srcaddr, __builtin_bit_cast(int, y[2])));
     float pi = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(srcaddr, __builtin_bit_cast(int, y[3])));
@@ -888,7 +961,10 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
       dst[0] = d0;
       dst[1] = d1;
     }
-    if (LAST && last_run && lane == ylast_lane) kargs()->yprev_out[stream] = make_float2(y[2], y[3]);   // (the call's last output lies in the last run's last step)
+    // (the call's last output lies in the last run's last step.  Scale-free: Y as it is, in tap units — the next design-Q call takes the angle of the same two words and gets
+    // the same bits as a call that holds both outputs, which no rescaled copy would give; nothing else reads a y[-1] design Q wrote: a bit-exact kernel that takes
+    // over recomputes it from hist_q, sdrfm_q_fix_yprev)
+    if (LAST && last_run && lane == ylast_lane) kargs()->yprev_out[stream] = make_float2(y[2], y[3]);
 #if !(defined(SDRFM_Q_ABLATE) && (SDRFM_Q_ABLATE & 512))
     // ---- the conditioning guard: design Q's y is within E ~ 1e-4 (absolute) of the definition's fmaf chain, so its d is within
     // E / |y| + E / |p| of the definition's — fine while both magnitudes are large, not at a deep fade, and near d = +-pi the two may land
@@ -1108,14 +1184,14 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
 
 
 template <int C0, int NSLOT, int D, int DA>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D == 16 ? 3 : 4))) k_mfir(SdrfmQParams p) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((D == 16 || (SDRFM_Q_W3 && D == 10)) ? 3 : 4))) k_mfir(SdrfmQParams p) {
   mfir_body<C0, NSLOT, D, DA>(p, blockIdx.x);
 }
 
 // The same launch with the PCM sink's chain in it (round 6, sdrfm_sink_chain.h): every run sinks its own audio outputs.  A kernel of its own, so that the
 // instruction stream of k_mfir does not change by a byte.
 template <int C0, int NSLOT, int D, int DA>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D == 16 ? 3 : 4))) k_mfir_pcm(QPcmArgs a) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((D == 16 || (SDRFM_Q_W3 && D == 10)) ? 3 : 4))) k_mfir_pcm(QPcmArgs a) {
   mfir_body<C0, NSLOT, D, DA, true>(a.p, blockIdx.x);
 }
 
@@ -1273,6 +1349,8 @@ const char* sdrfm_q_kernel_symbol(uint32_t first_chunk, uint32_t nslot, uint32_t
   const QVariant* v = q_find(first_chunk, nslot, d, da);
   return v ? v->name : "";
 }
+
+double sdrfm_q_yprev_scale(float q0) { return SDRFM_Q_SCALEFREE ? (double)q0 : 1.0; }
 
 int sdrfm_q_blocks_per_cu(uint32_t first_chunk, uint32_t nslot, uint32_t d, uint32_t da) {
   const QVariant* v = q_find(first_chunk, nslot, d, da);

@@ -59,7 +59,7 @@ ABI_SYMBOLS = [
 
 
 # include/sdrfm_dev.h: test hooks the product library also exports / development-library-only aids (not the drop-in boundary)
-TEST_HOOK_SYMBOLS = ["sdrfm_host_atan2f", "sdrfm_host_discriminate", "sdrfm_debug_discriminate", "sdrfm_q_build", "sdrfm_q_guard", "sdrfm_q_guard2", "sdrfm_debug_q_guard", "sdrfm_debug_read_ceiling", "sdrfm_debug_route", "sdrfm_sink_chain_tables"]
+TEST_HOOK_SYMBOLS = ["sdrfm_host_atan2f", "sdrfm_host_discriminate", "sdrfm_debug_discriminate", "sdrfm_q_build", "sdrfm_q_seed", "sdrfm_q_guard", "sdrfm_q_guard2", "sdrfm_debug_q_guard", "sdrfm_debug_read_ceiling", "sdrfm_debug_route", "sdrfm_sink_chain_tables"]
 DEV_ONLY_SYMBOLS = ["sdrfm_debug_phase_cycles", "sdrfm_debug_raw", "sdrfm_dev_read_debug"]
 
 
@@ -292,6 +292,8 @@ def load_library(dev=False):
         lib.sdrfm_debug_raw.restype = C.c_int
     lib.sdrfm_q_build.argtypes = [vp, u32, u32, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u32p]
     lib.sdrfm_q_build.restype = C.c_int
+    lib.sdrfm_q_seed.argtypes = [vp, u32, u32, C.POINTER(C.c_int32)]
+    lib.sdrfm_q_seed.restype = C.c_int
     lib.sdrfm_debug_discriminate.argtypes = [C.c_int] + [vp] * 6 + [u32]
     lib.sdrfm_debug_discriminate.restype = C.c_int
     lib.sdrfm_q_guard.argtypes = [vp, u32, vp, u32, C.POINTER(C.c_float), C.POINTER(C.c_float)]

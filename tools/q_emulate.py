@@ -104,8 +104,10 @@ def design_q_audio(iq, h, g, ndig=3, D=10, Da=5, guard=None, stats=None, device_
     round 4 took them from the oracle, which checked the flagging rule but not the repair arithmetic).  device_atan: the unflagged d's use design Q's
     own 6-coefficient arctangent (q_atan2_dev), not libm's.  stats (a dict) receives the number of repaired pairs.
     k3: "diff" (round 6, the kernel's default) — d[m] = wrap(theta[m] - theta[m-1]), theta = the device's arctangent of y itself (q_angle / q_wrap) —
-    or "product" (rounds 3 - 5: the arctangent of the conjugate product).  recomb: "cvt" (S0 + 256 S1 in i32, two conversions, two fmas) or "magic"
-    (each digit sum as an exact float, three fmas: the SDRFM_Q_MAGIC experiment)."""
+    or "product" (rounds 3 - 5: the arctangent of the conjugate product).  recomb: "cvt" (S0 + 256 S1 in i32, two conversions, two fmas), "magic"
+    (each digit sum as an exact float, three fmas: the SDRFM_Q_MAGIC experiment) or "scalefree" (SDRFM_Q_SCALEFREE: the S0 accumulator started at the constant
+    term in tap units — csrc/qtaps.c sdrfm_q_seed —, Y = y / q = fma(f32(S2), 65536, f32(S0 + 256 S1)): K3 and the guard work on Y, the guard's radius divided
+    by q; needs k3 = "diff")."""
     T, Ta = len(h), len(g)
     b = iq.astype(np.int64)
     xi8 = np.stack([b[0::2] - 128, b[1::2] - 128], axis=1)          # [N, 2]
@@ -121,7 +123,19 @@ def design_q_audio(iq, h, g, ndig=3, D=10, Da=5, guard=None, stats=None, device_
     assert np.abs(S).max() < 2 ** 31
     qf = np.float32(q)
     cst = np.float32(0.5 * np.sum(np.asarray(h, dtype=np.float64)))
-    if ndig == 3 and recomb == "magic":
+    scale = np.float32(1.0)                                          # what the guard's radius is divided by: y below is Y = y / q for the scale-free form
+    if ndig == 3 and recomb == "scalefree":
+        assert k3 == "diff" and device_atan
+        sumH = int((digs[0] + 256 * digs[1] + 65536 * digs[2]).sum())
+        seed = sumH // 2
+        if sumH & 1:                                                 # no integer half: the neighbour nearer to 0.5 sum(h) / q (csrc/qtaps.c)
+            w = 0.5 * float(np.sum(np.asarray(h, dtype=np.float64))) / float(qf)
+            seed = seed if abs(seed - w) <= abs(seed + 1 - w) else seed + 1
+        s01 = S[0] + seed + 256 * S[1]
+        assert np.abs(s01).max() < 2 ** 31 and np.abs(S[0] + seed).max() < 2 ** 31
+        y = fma32(f32(S[2]), np.float32(65536.0), f32(s01))
+        scale = qf
+    elif ndig == 3 and recomb == "magic":
         assert np.abs(S).max() < 2 ** 22
         y = fma32(f32(S[0]), qf, fma32(f32(S[1]), np.float32(256.0) * qf, fma32(f32(S[2]), np.float32(65536.0) * qf, cst)))
     elif ndig == 3:
@@ -140,7 +154,7 @@ def design_q_audio(iq, h, g, ndig=3, D=10, Da=5, guard=None, stats=None, device_
     orc = Oracle(h, g, D, Da)
     want = orc.process(iq)
     yo, _ = orc.last_stage()
-    y[~ok] = yo[~ok]
+    y[~ok] = f32(yo[~ok] / scale)
     # K3 (spec arithmetic, fp32)
     prev = np.vstack([np.zeros((1, 2), np.float32), y[:-1]])
     yr, yi, pr, pi = y[:, 0], y[:, 1], prev[:, 0], prev[:, 1]
@@ -153,7 +167,7 @@ def design_q_audio(iq, h, g, ndig=3, D=10, Da=5, guard=None, stats=None, device_
     else:
         d = q_atan2_dev(im, re) if device_atan else np.where((re == 0) & (im == 0), np.float32(0), np.arctan2(im, re).astype(np.float32))
     if guard is not None:
-        gr_, ga_ = np.float32(guard[0]), np.float32(guard[1])
+        gr_, ga_ = np.float32(np.float32(guard[0]) / scale), np.float32(guard[1])
         linf = np.maximum(np.abs(y[:, 0]), np.abs(y[:, 1]))
         linf_p = np.maximum(np.abs(prev[:, 0]), np.abs(prev[:, 1]))
         Mp = (M // 2) * 2
@@ -188,13 +202,14 @@ def design_q_audio(iq, h, g, ndig=3, D=10, Da=5, guard=None, stats=None, device_
     j = np.arange(A)
     for k in range(Ta):                                             # window element k (oldest first) times g[Ta-1-k]
         acc = fma32(np.float32(g[Ta - 1 - k]), dd[(j + 1) * Da - 1 + k], acc)
-    ymax_err = float(np.max(np.abs(y[ok].astype(np.float64) - yo[ok].astype(np.float64))))
+    ymax_err = float(np.max(np.abs(y[ok].astype(np.float64) * float(scale) - yo[ok].astype(np.float64))))
     return acc, want, ymax_err
 
 
 def main():
     nstreams = int(os.environ.get("QEMU_STREAMS", "8"))
     nsamp = int(os.environ.get("QEMU_SAMPLES", "240000"))
+    recomb = os.environ.get("QEMU_RECOMB", "cvt")                   # "scalefree": the three-digit rows through the scale-free recombination
     rows = []
     for T in (16, 32, 64):
         h, g = pkg.default_config(T)
@@ -203,12 +218,12 @@ def main():
                 iq = pkg.make_iq(nstreams, nsamp, mode=mode, first_id=40)
                 worst, over, yerr = 0.0, 0, 0.0
                 for s in range(nstreams):
-                    got, want, ye = design_q_audio(iq[s], h, g, ndig)
+                    got, want, ye = design_q_audio(iq[s], h, g, ndig, recomb=recomb if ndig == 3 else "cvt")
                     e = np.abs(got.astype(np.float64) - want) / np.maximum(np.abs(want), 1.0)
                     worst = max(worst, float(e.max()))
                     over += int((e > 1e-5).sum())
                     yerr = max(yerr, ye)
-                rows.append({"T": T, "digits": ndig, "mode": mode, "streams": nstreams, "samples": nsamp,
+                rows.append({"T": T, "digits": ndig, "recomb": recomb if ndig == 3 else "cvt", "mode": mode, "streams": nstreams, "samples": nsamp,
                              "max_scaled_err": worst, "n_over_1e-5": over, "max_abs_y_err": yerr})
                 print(json.dumps(rows[-1]), flush=True)
     return rows

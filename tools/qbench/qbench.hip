@@ -106,6 +106,7 @@ int main(int argc, char** argv) {
   p.iq = d_iq; p.iq_stride = stride; p.audio = d_audio; p.audio_stride = astride;
   p.yprev_in = d_ypi; p.yprev_out = d_ypo; p.hist_d_in = d_hdi; p.hist_d_out = d_hdo; p.hist_b_in = d_hbi; p.hist_b_out = d_hbo; p.hist_x_out = d_hxo;
   p.A = d_A; p.g = d_g; p.q0 = q; p.q2 = 65536.0f * q; p.cst = cst;
+  if (sdrfm_q_seed(h.data(), T, D, &p.seed)) { fprintf(stderr, "sdrfm_q_seed failed\n"); return 2; }
   p.T = T; p.N = nsamp; p.M = M; p.A_out = A; p.steps_total = (M + 127) / 128; p.runs = runs; p.n_streams = ns; p.dbg = nullptr; p.prio_by_age = getenv("QBENCH_NOPRIO") ? 0u : 1u;
   unsigned int* d_st = nullptr;
   // the conditioning guard (csrc/sdrfm_fm_plan.h, fm_tap_verdict): thresholds as the library derives them; QBENCH_GUARD=0 switches it off.
@@ -119,6 +120,7 @@ int main(int argc, char** argv) {
     p.guard_r = (float)(2.0 * gmax * E / 5e-6); p.guard_a = (float)(M_PI - 2.0 * 5e-6 / gmax);
     if (getenv("QBENCH_GUARD") && !atoi(getenv("QBENCH_GUARD"))) { p.guard_r = 0.0f; p.guard_a = 4.0f; }
     if (getenv("QBENCH_GUARD_R")) p.guard_r = (float)atof(getenv("QBENCH_GUARD_R"));
+    p.guard_rq = p.guard_r / q;
     float* d_hp; uint8_t *d_hqi, *d_hqo;
     CK(hipMalloc(&d_hp, SDRFM_Q_TP * 4)); CK(hipMemcpy(d_hp, hp.data(), SDRFM_Q_TP * 4, hipMemcpyHostToDevice));
     CK(hipMalloc(&d_hqi, (size_t)ns * 2 * SDRFM_Q_TP)); CK(hipMalloc(&d_hqo, (size_t)ns * 2 * SDRFM_Q_TP));
@@ -165,7 +167,8 @@ int main(int argc, char** argv) {
       if (e > 1e-5) ++bad;
     }
     for (int k = 0; k < 31; ++k) worst_state = fmax(worst_state, fabs(ohd[s * 31 + k] - dd[31 + M - 31 + k]));
-    worst_state = fmax(worst_state, fmax(fabs(oyp[2 * s] - pr), fabs(oyp[2 * s + 1] - pi)) / fmax(1.0, hypot(pr, pi)));
+    const double ys = sdrfm_q_yprev_scale(q);   // (the scale-free recombination hands y[-1] over in tap units)
+    worst_state = fmax(worst_state, fmax(fabs(oyp[2 * s] * ys - pr), fabs(oyp[2 * s + 1] * ys - pi)) / fmax(1.0, hypot(pr, pi)));
     for (int k = 0; k < HT; ++k)
       if (ohb[((size_t)s * HT + k) * 2] != row[2 * (nsamp - HT + k)] || ohb[((size_t)s * HT + k) * 2 + 1] != row[2 * (nsamp - HT + k) + 1]) worst_state = 1e9;
   }
