@@ -1279,6 +1279,103 @@ int  sdrfm_pcm_stereo_sink_truepeak_enable(sdrfm_pcm_stereo_sink_t* k, const int
 int  sdrfm_pcm_stereo_sink_truepeak_disable(sdrfm_pcm_stereo_sink_t* k);
 int  sdrfm_pcm_stereo_sink_truepeak_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_truepeak* out /* n_streams records */, uint32_t flags);
 
+/* A per-stream LOOK-AHEAD PCM LIMITER with a ramped make-up gain, behind the sinks: the int16 stereo rows either PCM sink
+ * leaves, raised by up to x 16 and held under a sample ceiling, on the device — the actuator for what the loudness and true-peak meters read.  A
+ * handle of its own beside the rate matcher.  All arithmetic is integer and exact: the device and the host routine agree bit for bit, and any
+ * cut of a stream into calls gives the same outputs, state and (joined) records.
+ *
+ * Rows.  in[s * in_stride + 2i] = L, [... + 2i + 1] = R, i < n; out likewise, and a call of n pairs writes exactly n pairs per stream.  out may
+ * be in (same pointer and stride): a sink's rows limited in place.
+ * Handle-wide, at create: log2_window LW in 2 .. 8, W = 2^LW pairs, D = W - 1 the latency in pairs; gain_slew in 1 .. 32768, Q12 units per pair.
+ * Per stream: the ceiling C in 1 .. 32767 LSB; the release delta in 1 .. 2^23; the make-up gain, a ramp (gain0, gain_t) in Q12 in [0, 65536]
+ * (4096 = unity, 65536 = x 16).  After create C = 29204 (-1 dBFS, floored), delta = 874 (0 -> 1 in about 0.2 s at 48 kHz), gain0 = gain_t = 4096.
+ *
+ * Pair u of a stream, counted from reset; J the pairs since the last set_gain (saturating at 65536) and i the pair's index in the call:
+ *   1  G = ramp(gain0, gain_t, gain_slew, J + i + 1): towards gain_t by at most gain_slew per pair (the closed form of the broadcast receiver's
+ *      audio ramps);  x'_c[u] = (x_c[u] G + 2^11) >> 12 per channel, arithmetic shift, |x'| <= 2^19
+ *   2  a[u] = max(|x'_L|, |x'_R|);  g[u] = 32768 where a <= C, else floor(C 32768 / a)                    (Q15, 32-bit unsigned division)
+ *   3  m[u] = min over k = 0 .. D of g[u - k]
+ *   4  r[u] = min(256 m[u], r[u - 1] + delta)                                                             (Q23)
+ *   5  S[u] = sum over k = 0 .. D of r[u - k] <= 2^31;  s[u] = S >> (LW + 8)                              (Q15)
+ *   6  y_c[u] = (x'_c[u - D] s[u] + 2^14) >> 15, 64-bit product, arithmetic shift, stored as int16 with no saturation
+ * Before the start x' = 0, g = 32768, r = 2^23.
+ *   The ceiling holds: every r in S[u] is <= 256 g[u - D], so s[u] <= g[u - D] and, with the rounding, |y| <= C for every pair.
+ *   Transparency: with G = 4096 and no |x| over C, y[u] = x[u - D] bit for bit.
+ *   Cut invariance: any cut into calls, of 0 pairs and of fewer than D pairs as well, gives the stream's output and state.
+ * State per stream, 4 D int32 words, oldest first: x'_L and x'_R of the last D pairs interleaved, then g of the last D pairs, then r of the last
+ * D pairs; r[u - 1] is the last word.  Parameter changes apply to the pairs that enter from the next call on; state words already held keep
+ * the values they were computed with.
+ * Record (sdrfm_pcm_limit_rec, 32 bytes): n, the pairs covered; limited, the pairs with s < 32768; min_gain, the smallest s (32768 for none);
+ * at, the smallest u at which it was attained, counted from the record's first pair (0 for none).  The JOIN of a record a and the record b of
+ * the pairs that FOLLOW, sdrfm_pcm_limit_add(acc = a, m = b): n and limited add; where b.min_gain < a.min_gain (strict) the minimum is b's and
+ * at = a.n + b.at.  The join is associative and (0, 0, 32768, 0) is its identity.
+ *
+ * Host side, plain C with no GPU behind it (csrc/limit.c):
+ *   sdrfm_pcm_limit_s16          one stream's call, the definition as code: limits n pairs, advances state (sdrfm_pcm_limit_state_words int32;
+ *                                sdrfm_pcm_limit_state_init gives the state before the start) and joins the call's record onto *acc.  out may be
+ *                                in.  SDRFM_EINVAL, with nothing touched: p, state or acc NULL, in or out NULL with n > 0, n > 2^20, J > 65536,
+ *                                or anything sdrfm_pcm_limit_check_params refuses.
+ *   sdrfm_pcm_limit_state_words  4 D for a log2_window in 2 .. 8, else 0.
+ *   sdrfm_pcm_limit_check_params SDRFM_OK for parameters the device takes, SDRFM_EINVAL for NULL or any value outside the ranges above.
+ *   sdrfm_pcm_limit_add          the ordered join above; SDRFM_EINVAL for a NULL pointer.
+ *   sdrfm_pcm_limit_report       in double: reduction_db = -20 log10(min_gain / 32768) (0 for none, +inf for a gain of 0), limited_frac =
+ *                                limited / n, at_seconds = at / fs_audio; every field NaN for a record of no pairs.  SDRFM_EINVAL: a NULL
+ *                                pointer, fs_audio not finite and positive.
+ *   sdrfm_pcm_limit_ceiling      floor(32768 10^(dbfs / 20)) clamped to 1 .. 32767; 1 for a NaN.
+ *
+ * The handle follows sdrfm_pcm_rate_*'s contract:
+ *   create     config or out NULL, n_streams == 0, flags != 0, log2_window or gain_slew outside the ranges: SDRFM_EINVAL before any device is
+ *              looked for; a missing or non-gfx950 device: SDRFM_NO_DEVICE.
+ *   set_params one ceiling and one release per stream, either array may be NULL (those stay), not both; any value outside its range:
+ *              SDRFM_EINVAL and every parameter stays.  Waits for the handle's stream.
+ *   set_gain   one target per stream in Q12; any above 65536 or a jump other than 0 and 1: SDRFM_EINVAL and every ramp stays.  Every stream's
+ *              ramp restarts at the value it has reached (jump = 0) or at the target itself (jump = 1), towards its new target, and J becomes 0.
+ *              Waits for the handle's stream.
+ *   get_params the parameters as the next call uses them (out, n_streams, or NULL) and J (or NULL).
+ *   process_batch   Every refusal is made before anything is enqueued and leaves the handle as it was: flags outside SDRFM_F_DEVICE_PTRS,
+ *              n > 2^20, an odd in_stride or out_stride (int16 elements): SDRFM_EINVAL; then n == 0 is a no-op; then in or out NULL, or device rows
+ *              that are not 4-byte aligned: SDRFM_EINVAL; with more than one stream in_stride < 2n or out_stride < 2n: SDRFM_ECAPACITY.  Exactly
+ *              2n int16 are written per row.  With SDRFM_F_DEVICE_PTRS the rows are device memory and the call only enqueues on the handle's
+ *              stream: give it the sink's stream (or synchronise) so that it runs after the PCM exists.  With host buffers the call stages,
+ *              runs, copies back and is synchronous.
+ *   read       flags is a subset of SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET and out is 8-byte aligned and holds n_streams records: else
+ *              SDRFM_EINVAL.  Host out: synchronises, copies and, with SDRFM_AMETER_F_RESET, sets the records to the identity behind the copy;
+ *              device out: the same, enqueued on the handle's stream.  The state is KEPT: the stream continues and the reads' records join
+ *              to the stream's.
+ *   get_state  synchronises the handle's stream and gives the device's state, n_streams x 4 D int32.
+ *   reset      the state to the one before the start and the records to the identity; the parameters, the ramps and J stay.
+ *   NULL handles answer SDRFM_EINVAL (destroy: nothing; kernel_name: NULL).
+ * The kernel (csrc/sdrfm_pcm_limit.hip, its body and the launch geometry in csrc/sdrfm_limit.h): one workgroup of 1024 lanes per stream, the row
+ * in tiles of SDRFM_PCM_LIMIT_TILE pairs staged whole in LDS behind their D pairs of lead-in before any output of the tile is stored; the window
+ * minimum and the window sum by LW doubling steps, the release as a scan over (min, +) maps — a lane's five consecutive pairs, the wave by
+ * shuffles, the sixteen waves through LDS — with its carry in a register between tiles; no atomics.  kernel name: "pcm-limit". */
+#define SDRFM_PCM_LIMIT_TILE 5120u                 /* pairs of a tile of k_pcm_limit: the tests place their shapes around it */
+typedef struct sdrfm_pcm_limit sdrfm_pcm_limit_t;
+typedef struct sdrfm_pcm_limit_config { uint32_t n_streams, log2_window, gain_slew, flags; int32_t device; } sdrfm_pcm_limit_config;
+typedef struct sdrfm_pcm_limit_params { uint32_t ceiling, release, gain0, gain_t; } sdrfm_pcm_limit_params;      /* 16 bytes */
+typedef struct sdrfm_pcm_limit_rec { uint64_t n, limited, min_gain, at; } sdrfm_pcm_limit_rec;                     /* 32 bytes, 8-byte aligned */
+typedef struct sdrfm_pcm_limit_report_t { double reduction_db, limited_frac, at_seconds; } sdrfm_pcm_limit_report_t;
+int  sdrfm_pcm_limit_create(const sdrfm_pcm_limit_config* config, sdrfm_pcm_limit_t** out);
+void sdrfm_pcm_limit_destroy(sdrfm_pcm_limit_t* k);
+int  sdrfm_pcm_limit_reset(sdrfm_pcm_limit_t* k);
+int  sdrfm_pcm_limit_set_params(sdrfm_pcm_limit_t* k, const uint32_t* ceiling /* n_streams, or NULL */, const uint32_t* release /* likewise */);
+int  sdrfm_pcm_limit_set_gain(sdrfm_pcm_limit_t* k, const uint32_t* gain_q12 /* n_streams */, uint32_t jump /* 0 or 1 */);
+int  sdrfm_pcm_limit_get_params(const sdrfm_pcm_limit_t* k, sdrfm_pcm_limit_params* out /* n_streams, or NULL */, uint32_t* J);
+int  sdrfm_pcm_limit_process_batch(sdrfm_pcm_limit_t* k, const int16_t* in, size_t in_stride, uint32_t n, int16_t* out, size_t out_stride, uint32_t flags);
+int  sdrfm_pcm_limit_read(sdrfm_pcm_limit_t* k, sdrfm_pcm_limit_rec* out /* n_streams records */, uint32_t flags);
+int  sdrfm_pcm_limit_get_state(sdrfm_pcm_limit_t* k, int32_t* state /* n_streams x 4 D */);
+int  sdrfm_pcm_limit_set_stream(sdrfm_pcm_limit_t* k, void* hip_stream);
+int  sdrfm_pcm_limit_synchronize(sdrfm_pcm_limit_t* k);
+const char* sdrfm_pcm_limit_kernel_name(const sdrfm_pcm_limit_t* k);
+int  sdrfm_pcm_limit_s16(const int16_t* in, uint32_t n, uint32_t log2_window, uint32_t gain_slew, uint32_t J, const sdrfm_pcm_limit_params* p,
+                         int32_t* state /* 4 D */, int16_t* out, sdrfm_pcm_limit_rec* acc);
+uint32_t sdrfm_pcm_limit_state_words(uint32_t log2_window);
+int  sdrfm_pcm_limit_state_init(uint32_t log2_window, int32_t* state /* 4 D */);
+int  sdrfm_pcm_limit_check_params(const sdrfm_pcm_limit_params* p, uint32_t log2_window, uint32_t gain_slew);
+int  sdrfm_pcm_limit_add(sdrfm_pcm_limit_rec* acc, const sdrfm_pcm_limit_rec* m);
+int  sdrfm_pcm_limit_report(const sdrfm_pcm_limit_rec* m, double fs_audio, sdrfm_pcm_limit_report_t* out);
+uint32_t sdrfm_pcm_limit_ceiling(double dbfs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,264 @@
+/*
+ * sdrfm_pcm_limit.hip — the per-stream look-ahead PCM limiter behind the sdrfm_pcm_limit_* C-ABI (include/sdrfm.h): the int16
+ * stereo rows the PCM sinks leave, under a ramped make-up gain and a look-ahead peak limiter, on the device.  The arithmetic is the host
+ * routine sdrfm_pcm_limit_s16's (csrc/limit.c) and all-integer, so the outputs, the state and the records are that routine's bit for bit.
+ *
+ *   k_pcm_limit   one workgroup of 1024 lanes per stream, grid (streams); the row in tiles of SDRFM_PCM_LIMIT_TILE pairs staged in LDS behind
+ *                 their lead-in.  The body, the arithmetic and the geometry are in csrc/sdrfm_limit.h.
+ *
+ * State: 4 D int32 per stream on the device, one set.  The kernel reads a stream's state into registers before its first barrier and writes it
+ * behind its last, and calls are ordered by the HIP stream they are enqueued on.  The gain ramp is a closed form of (gain0, gain_t, slew, J):
+ * the handle keeps J on the host and passes it by value.
+ */
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "../../include/sdrfm.h"
+#include "sdrfm_limit.h"
+
+#define STRY(expr, code)                                                                                       \
+  do {                                                                                                         \
+    hipError_t e__ = (expr);                                                                                   \
+    if (e__ != hipSuccess) {                                                                                   \
+      fprintf(stderr, "[sdrfm] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__);  \
+      return (code);                                                                                           \
+    }                                                                                                          \
+  } while (0)
+
+namespace {
+
+__global__ void __launch_bounds__(SDRFM_LIMIT_NT) k_pcm_limit(LimitParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned limit_lds[];
+  limit_stream(limit_lds, p);
+}
+
+}  // namespace
+
+struct sdrfm_pcm_limit {
+  uint32_t n_streams, lw, slew, J;
+  int device;
+  hipStream_t own_stream, stream;
+  sdrfm_pcm_limit_params* d_par;   // [n_streams]
+  int32_t* d_state;                // [n_streams][4 D]
+  sdrfm_pcm_limit_rec* d_rec;      // [n_streams]
+  sdrfm_pcm_limit_params* par;     // host: the parameters as the device holds them
+  int32_t* state0;                 // host: the state after reset, and the records' identity
+  sdrfm_pcm_limit_rec* rec0;
+  int16_t* d_buf;                  // staging for host-pointer calls: limited in place
+  int16_t* h_buf;
+  uint32_t cap;                    // pairs per stream the staging holds
+};
+
+static void limit_free(sdrfm_pcm_limit* k) {
+  if (!k) return;
+  (void)hipSetDevice(k->device);
+  if (k->d_par) (void)hipFree(k->d_par);
+  if (k->d_state) (void)hipFree(k->d_state);
+  if (k->d_rec) (void)hipFree(k->d_rec);
+  if (k->d_buf) (void)hipFree(k->d_buf);
+  free(k->h_buf);
+  free(k->par);
+  free(k->state0);
+  free(k->rec0);
+  if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
+  delete k;
+}
+
+// one call over device buffers on the handle's stream; J moves with it
+static int limit_launch(sdrfm_pcm_limit* k, const int16_t* in, size_t in_stride, uint32_t n, int16_t* out, size_t out_stride) {
+  LimitParams p;
+  p.in = in; p.in_stride = in_stride; p.out = out; p.out_stride = out_stride;
+  p.par = k->d_par; p.state = k->d_state; p.rec = k->d_rec;
+  p.n = n; p.lw = k->lw; p.slew = k->slew; p.J = k->J;
+  hipLaunchKernelGGL(k_pcm_limit, dim3(k->n_streams), dim3(SDRFM_LIMIT_NT), limit_lds_bytes(), k->stream, p);
+  STRY(hipGetLastError(), SDRFM_FAIL);
+  k->J = audio_ctl_advance(k->J, n);
+  return SDRFM_OK;
+}
+
+static int limit_reserve(sdrfm_pcm_limit* k, uint32_t n) {
+  if (n <= k->cap) return SDRFM_OK;
+  if (k->d_buf) (void)hipFree(k->d_buf);
+  free(k->h_buf);
+  k->d_buf = nullptr; k->h_buf = nullptr; k->cap = 0;
+  const uint32_t cap = (n + 1023u) & ~1023u;
+  k->h_buf = (int16_t*)malloc(sizeof(int16_t) * 2 * (size_t)cap * k->n_streams);
+  if (!k->h_buf || hipMalloc(&k->d_buf, sizeof(int16_t) * 2 * (size_t)cap * k->n_streams) != hipSuccess) return SDRFM_ENOMEM;
+  k->cap = cap;
+  return SDRFM_OK;
+}
+
+// the parameters to the device, behind whatever launch may still read them
+static int limit_upload(sdrfm_pcm_limit* k) {
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipMemcpy(k->d_par, k->par, sizeof(sdrfm_pcm_limit_params) * (size_t)k->n_streams, hipMemcpyHostToDevice), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+extern "C" {
+
+int sdrfm_pcm_limit_create(const sdrfm_pcm_limit_config* cfg, sdrfm_pcm_limit_t** out) {
+  if (!out) return SDRFM_EINVAL;
+  *out = nullptr;
+  if (!cfg || !cfg->n_streams || cfg->flags || !limit_shape_ok(cfg->log2_window, cfg->gain_slew)) return SDRFM_EINVAL;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return SDRFM_NO_DEVICE;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SDRFM_NO_DEVICE;
+  STRY(hipSetDevice(cfg->device), SDRFM_NO_DEVICE);
+  sdrfm_pcm_limit* k = new (std::nothrow) sdrfm_pcm_limit();
+  if (!k) return SDRFM_ENOMEM;
+  memset(static_cast<void*>(k), 0, sizeof(*k));
+  const uint32_t ns = cfg->n_streams, words = limit_state_words(cfg->log2_window);
+  k->n_streams = ns; k->lw = cfg->log2_window; k->slew = cfg->gain_slew; k->device = cfg->device;
+  k->par = (sdrfm_pcm_limit_params*)malloc(sizeof(sdrfm_pcm_limit_params) * ns);
+  k->state0 = (int32_t*)malloc(sizeof(int32_t) * (size_t)words * ns);
+  k->rec0 = (sdrfm_pcm_limit_rec*)malloc(sizeof(sdrfm_pcm_limit_rec) * ns);
+  if (!k->par || !k->state0 || !k->rec0) { limit_free(k); return SDRFM_ENOMEM; }
+  for (uint32_t s = 0; s < ns; ++s) {
+    k->par[s].ceiling = SDRFM_LIMIT_CEILING_DEFAULT; k->par[s].release = SDRFM_LIMIT_RELEASE_DEFAULT;
+    k->par[s].gain0 = k->par[s].gain_t = SDRFM_LIMIT_GAIN_UNITY;
+    (void)sdrfm_pcm_limit_state_init(k->lw, k->state0 + (size_t)s * words);
+    k->rec0[s].n = 0; k->rec0[s].limited = 0; k->rec0[s].min_gain = SDRFM_LIMIT_ONE; k->rec0[s].at = 0;
+  }
+  const bool ok = hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking) == hipSuccess &&
+                  hipMalloc(&k->d_par, sizeof(sdrfm_pcm_limit_params) * ns) == hipSuccess &&
+                  hipMalloc(&k->d_state, sizeof(int32_t) * (size_t)words * ns) == hipSuccess &&
+                  hipMalloc(&k->d_rec, sizeof(sdrfm_pcm_limit_rec) * ns) == hipSuccess;
+  if (!ok) { limit_free(k); return SDRFM_ENOMEM; }
+  k->stream = k->own_stream;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_pcm_limit), hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit_lds_bytes()) != hipSuccess ||
+      hipMemcpy(k->d_par, k->par, sizeof(sdrfm_pcm_limit_params) * ns, hipMemcpyHostToDevice) != hipSuccess) {
+    limit_free(k);
+    return SDRFM_FAIL;
+  }
+  const int rc = sdrfm_pcm_limit_reset(k);
+  if (rc != SDRFM_OK) { limit_free(k); return rc; }
+  *out = k;
+  return SDRFM_OK;
+}
+
+void sdrfm_pcm_limit_destroy(sdrfm_pcm_limit_t* k) {
+  if (!k) return;
+  (void)hipSetDevice(k->device);
+  (void)hipStreamSynchronize(k->stream);
+  limit_free(k);
+}
+
+int sdrfm_pcm_limit_reset(sdrfm_pcm_limit_t* k) {
+  if (!k) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipMemcpy(k->d_state, k->state0, sizeof(int32_t) * (size_t)limit_state_words(k->lw) * k->n_streams, hipMemcpyHostToDevice), SDRFM_FAIL);
+  STRY(hipMemcpy(k->d_rec, k->rec0, sizeof(sdrfm_pcm_limit_rec) * (size_t)k->n_streams, hipMemcpyHostToDevice), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+// every check comes before any device work; the calls wait for the handle's stream before they replace what a launch may still read
+int sdrfm_pcm_limit_set_params(sdrfm_pcm_limit_t* k, const uint32_t* ceiling, const uint32_t* release) {
+  if (!k || (!ceiling && !release)) return SDRFM_EINVAL;
+  for (uint32_t s = 0; s < k->n_streams; ++s) {
+    if (ceiling && (ceiling[s] < 1u || ceiling[s] > SDRFM_LIMIT_CEILING_MAX)) return SDRFM_EINVAL;
+    if (release && (release[s] < 1u || release[s] > SDRFM_LIMIT_R_ONE)) return SDRFM_EINVAL;
+  }
+  for (uint32_t s = 0; s < k->n_streams; ++s) {
+    if (ceiling) k->par[s].ceiling = ceiling[s];
+    if (release) k->par[s].release = release[s];
+  }
+  return limit_upload(k);
+}
+
+int sdrfm_pcm_limit_set_gain(sdrfm_pcm_limit_t* k, const uint32_t* gain_q12, uint32_t jump) {
+  if (!k || !gain_q12 || jump > 1u) return SDRFM_EINVAL;
+  for (uint32_t s = 0; s < k->n_streams; ++s)
+    if (gain_q12[s] > SDRFM_LIMIT_GAIN_MAX) return SDRFM_EINVAL;
+  for (uint32_t s = 0; s < k->n_streams; ++s) {                   // the ramps restart where they have got to
+    k->par[s].gain0 = jump ? gain_q12[s] : audio_ctl_ramp(k->par[s].gain0, k->par[s].gain_t, k->slew, k->J);
+    k->par[s].gain_t = gain_q12[s];
+  }
+  k->J = 0;
+  return limit_upload(k);
+}
+
+int sdrfm_pcm_limit_get_params(const sdrfm_pcm_limit_t* k, sdrfm_pcm_limit_params* out, uint32_t* J) {
+  if (!k) return SDRFM_EINVAL;
+  if (out) memcpy(out, k->par, sizeof(sdrfm_pcm_limit_params) * (size_t)k->n_streams);
+  if (J) *J = k->J;
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_limit_process_batch(sdrfm_pcm_limit_t* k, const int16_t* in, size_t in_stride, uint32_t n, int16_t* out, size_t out_stride, uint32_t flags) {
+  if (!k) return SDRFM_EINVAL;
+  if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;
+  if (n > SDRFM_LIMIT_N_MAX) return SDRFM_EINVAL;
+  if ((in_stride | out_stride) & 1u) return SDRFM_EINVAL;           // rows are read and written as (L, R) dwords
+  if (n == 0) return SDRFM_OK;
+  if (!in || !out) return SDRFM_EINVAL;
+  const bool device_ptrs = (flags & SDRFM_F_DEVICE_PTRS) != 0;
+  if (device_ptrs && ((uintptr_t)in % 4 != 0 || (uintptr_t)out % 4 != 0)) return SDRFM_EINVAL;
+  if (k->n_streams > 1 && (in_stride < 2 * (size_t)n || out_stride < 2 * (size_t)n)) return SDRFM_ECAPACITY;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  if (device_ptrs) return limit_launch(k, in, in_stride, n, out, out_stride);
+  // host buffers: stage, limit in place, copy back, synchronous
+  int rc = limit_reserve(k, n);
+  if (rc != SDRFM_OK) return rc;
+  const size_t is = (k->n_streams > 1) ? in_stride : 2 * (size_t)n, os = (k->n_streams > 1) ? out_stride : 2 * (size_t)n;
+  STRY(hipMemcpy2DAsync(k->d_buf, sizeof(int16_t) * 2 * k->cap, in, sizeof(int16_t) * is, sizeof(int16_t) * 2 * n, k->n_streams, hipMemcpyHostToDevice,
+                        k->stream), SDRFM_FAIL);
+  rc = limit_launch(k, k->d_buf, 2 * (size_t)k->cap, n, k->d_buf, 2 * (size_t)k->cap);
+  if (rc != SDRFM_OK) return rc;
+  STRY(hipMemcpy2DAsync(k->h_buf, sizeof(int16_t) * 2 * k->cap, k->d_buf, sizeof(int16_t) * 2 * k->cap, sizeof(int16_t) * 2 * n, k->n_streams,
+                        hipMemcpyDeviceToHost, k->stream), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  for (uint32_t s = 0; s < k->n_streams; ++s) memcpy(out + s * os, k->h_buf + (size_t)s * 2 * k->cap, sizeof(int16_t) * 2 * n);   // exactly 2n int16 per row
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_limit_read(sdrfm_pcm_limit_t* k, sdrfm_pcm_limit_rec* out, uint32_t flags) {
+  if (!k || !out || (flags & ~(SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET)) || (uintptr_t)out % 8 != 0) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  const size_t bytes = sizeof(sdrfm_pcm_limit_rec) * (size_t)k->n_streams;
+  if (flags & SDRFM_F_DEVICE_PTRS) {                            // enqueued on the handle's stream, and nowhere else
+    STRY(hipMemcpyAsync(out, k->d_rec, bytes, hipMemcpyDeviceToDevice, k->stream), SDRFM_FAIL);
+    if (flags & SDRFM_AMETER_F_RESET) STRY(hipMemcpyAsync(k->d_rec, k->rec0, bytes, hipMemcpyHostToDevice, k->stream), SDRFM_FAIL);
+    return SDRFM_OK;
+  }
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipMemcpy(out, k->d_rec, bytes, hipMemcpyDeviceToHost), SDRFM_FAIL);
+  if (flags & SDRFM_AMETER_F_RESET)                             // the records only: the state stays and the stream continues
+    STRY(hipMemcpy(k->d_rec, k->rec0, bytes, hipMemcpyHostToDevice), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_limit_get_state(sdrfm_pcm_limit_t* k, int32_t* state) {
+  if (!k || !state) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipMemcpy(state, k->d_state, sizeof(int32_t) * (size_t)limit_state_words(k->lw) * k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_limit_set_stream(sdrfm_pcm_limit_t* k, void* hip_stream) {
+  if (!k) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  k->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : k->own_stream;
+  return SDRFM_OK;
+}
+
+int sdrfm_pcm_limit_synchronize(sdrfm_pcm_limit_t* k) {
+  if (!k) return SDRFM_EINVAL;
+  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  return SDRFM_OK;
+}
+
+const char* sdrfm_pcm_limit_kernel_name(const sdrfm_pcm_limit_t* k) { return k ? "pcm-limit" : nullptr; }
+
+}  // extern "C"

@@ -55,6 +55,11 @@ ABI_SYMBOLS = [
     "sdrfm_pcm_rate_create", "sdrfm_pcm_rate_destroy", "sdrfm_pcm_rate_reset", "sdrfm_pcm_rate_set_step", "sdrfm_pcm_rate_count",
     "sdrfm_pcm_rate_process_batch", "sdrfm_pcm_rate_get_state", "sdrfm_pcm_rate_set_stream", "sdrfm_pcm_rate_synchronize",
     "sdrfm_pcm_rate_kernel_name", "sdrfm_pcm_rate_s16", "sdrfm_pcm_rate_check_coef",
+    "sdrfm_pcm_limit_create", "sdrfm_pcm_limit_destroy", "sdrfm_pcm_limit_reset", "sdrfm_pcm_limit_set_params", "sdrfm_pcm_limit_set_gain",
+    "sdrfm_pcm_limit_get_params", "sdrfm_pcm_limit_process_batch", "sdrfm_pcm_limit_read", "sdrfm_pcm_limit_get_state",
+    "sdrfm_pcm_limit_set_stream", "sdrfm_pcm_limit_synchronize", "sdrfm_pcm_limit_kernel_name", "sdrfm_pcm_limit_s16",
+    "sdrfm_pcm_limit_state_words", "sdrfm_pcm_limit_state_init", "sdrfm_pcm_limit_check_params", "sdrfm_pcm_limit_add",
+    "sdrfm_pcm_limit_report", "sdrfm_pcm_limit_ceiling",
 ]
 
 
@@ -218,6 +223,28 @@ assert TRUEPEAK_DTYPE.itemsize == C.sizeof(TruePeak) == 64
 class PcmRateConfig(C.Structure):
     _fields_ = [("n_streams", C.c_uint32), ("n_taps", C.c_uint32), ("log2_phases", C.c_uint32), ("flags", C.c_uint32),
                 ("coef", C.POINTER(C.c_int16)), ("device", C.c_int32)]
+
+
+class PcmLimitConfig(C.Structure):
+    _fields_ = [("n_streams", C.c_uint32), ("log2_window", C.c_uint32), ("gain_slew", C.c_uint32), ("flags", C.c_uint32), ("device", C.c_int32)]
+
+
+class PcmLimitParams(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("ceiling", "release", "gain0", "gain_t")]
+
+
+class PcmLimitRec(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n", "limited", "min_gain", "at")]
+
+
+class PcmLimitReport(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("reduction_db", "limited_frac", "at_seconds")]
+
+
+# sdrfm_pcm_limit_rec and sdrfm_pcm_limit_params as structured dtypes
+LIMIT_DTYPE = np.dtype([(n, "<u8") for n, _ in PcmLimitRec._fields_])
+LIMIT_PARAMS_DTYPE = np.dtype([(n, "<u4") for n, _ in PcmLimitParams._fields_])
+assert LIMIT_DTYPE.itemsize == C.sizeof(PcmLimitRec) == 32 and LIMIT_PARAMS_DTYPE.itemsize == C.sizeof(PcmLimitParams) == 16
 
 
 class RdsGroup(C.Structure):
@@ -535,6 +562,44 @@ def load_library(dev=False):
     lib.sdrfm_pcm_rate_s16.restype = C.c_int
     lib.sdrfm_pcm_rate_check_coef.argtypes = [vp, u32, u32]
     lib.sdrfm_pcm_rate_check_coef.restype = C.c_int
+    lib.sdrfm_pcm_limit_create.argtypes = [C.POINTER(PcmLimitConfig), C.POINTER(vp)]
+    lib.sdrfm_pcm_limit_create.restype = C.c_int
+    lib.sdrfm_pcm_limit_destroy.argtypes = [vp]
+    lib.sdrfm_pcm_limit_destroy.restype = None
+    lib.sdrfm_pcm_limit_reset.argtypes = [vp]
+    lib.sdrfm_pcm_limit_reset.restype = C.c_int
+    lib.sdrfm_pcm_limit_set_params.argtypes = [vp, vp, vp]
+    lib.sdrfm_pcm_limit_set_params.restype = C.c_int
+    lib.sdrfm_pcm_limit_set_gain.argtypes = [vp, vp, u32]
+    lib.sdrfm_pcm_limit_set_gain.restype = C.c_int
+    lib.sdrfm_pcm_limit_get_params.argtypes = [vp, vp, u32p]
+    lib.sdrfm_pcm_limit_get_params.restype = C.c_int
+    lib.sdrfm_pcm_limit_process_batch.argtypes = [vp, vp, C.c_size_t, u32, vp, C.c_size_t, u32]
+    lib.sdrfm_pcm_limit_process_batch.restype = C.c_int
+    lib.sdrfm_pcm_limit_read.argtypes = [vp, vp, u32]
+    lib.sdrfm_pcm_limit_read.restype = C.c_int
+    lib.sdrfm_pcm_limit_get_state.argtypes = [vp, vp]
+    lib.sdrfm_pcm_limit_get_state.restype = C.c_int
+    lib.sdrfm_pcm_limit_set_stream.argtypes = [vp, vp]
+    lib.sdrfm_pcm_limit_set_stream.restype = C.c_int
+    lib.sdrfm_pcm_limit_synchronize.argtypes = [vp]
+    lib.sdrfm_pcm_limit_synchronize.restype = C.c_int
+    lib.sdrfm_pcm_limit_kernel_name.argtypes = [vp]
+    lib.sdrfm_pcm_limit_kernel_name.restype = C.c_char_p
+    lib.sdrfm_pcm_limit_s16.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp]
+    lib.sdrfm_pcm_limit_s16.restype = C.c_int
+    lib.sdrfm_pcm_limit_state_words.argtypes = [u32]
+    lib.sdrfm_pcm_limit_state_words.restype = u32
+    lib.sdrfm_pcm_limit_state_init.argtypes = [u32, vp]
+    lib.sdrfm_pcm_limit_state_init.restype = C.c_int
+    lib.sdrfm_pcm_limit_check_params.argtypes = [vp, u32, u32]
+    lib.sdrfm_pcm_limit_check_params.restype = C.c_int
+    lib.sdrfm_pcm_limit_add.argtypes = [vp, vp]
+    lib.sdrfm_pcm_limit_add.restype = C.c_int
+    lib.sdrfm_pcm_limit_report.argtypes = [vp, C.c_double, C.POINTER(PcmLimitReport)]
+    lib.sdrfm_pcm_limit_report.restype = C.c_int
+    lib.sdrfm_pcm_limit_ceiling.argtypes = [C.c_double]
+    lib.sdrfm_pcm_limit_ceiling.restype = u32
     lib.sdrfm_loudness_default_coef.argtypes = [vp]
     lib.sdrfm_loudness_default_coef.restype = C.c_int
     lib.sdrfm_loudness_check_coef.argtypes = [vp]
