@@ -1376,6 +1376,58 @@ int  sdrfm_pcm_limit_add(sdrfm_pcm_limit_rec* acc, const sdrfm_pcm_limit_rec* m)
 int  sdrfm_pcm_limit_report(const sdrfm_pcm_limit_rec* m, double fs_audio, sdrfm_pcm_limit_report_t* out);
 uint32_t sdrfm_pcm_limit_ceiling(double dbfs);
 
+/* The limiter's TRUE-PEAK FORM: the same handle, parameters, records and calls, with a detector that sees the waveform BETWEEN
+ * the samples — the true-peak meter's interpolator over x' — so that the ceiling reads as dBTP.  It is a second constructor, host routine and
+ * kernel instance; a handle made by sdrfm_pcm_limit_create, sdrfm_pcm_limit_s16 and k_pcm_limit are what they were, bit for bit.
+ *
+ * Handle-wide, besides LW and gain_slew: a table coef[P][NT] under exactly sdrfm_truepeak_check_coef's rules (NULL: sdrfm_truepeak_default_coef's,
+ * and n_phases and n_taps are then not looked at); H = NT / 2.  The window has to hold half a row, 2^LW >= NT / 2: then D + H >= NT - 1 and the x'
+ * delay line is the interpolator's history as well.  The latency is D + H pairs.
+ *
+ * Pair u of a stream; steps 1 and 3 - 5 are the sample form's:
+ *   1   G and x'[u] as above, |x'| <= 2^19
+ *   1b  per channel c and phase p   A_c[u][p] = sum over k of coef[p][k] x'_c[u - k],   exactly, x' = 0 before the start; the table's bound gives
+ *       |A| <= 2 * 65535 * 2^19 < 2^36.  T[u] = the maximum of |A| over c and p.  With the table's layout (taps.truepeak_coef) these are the
+ *       waveform's values between pairs u - H and u - H + 1.
+ *   2'  v = u - H, the DETECTOR PAIR;  a[v] = max(|x'_L[v]|, |x'_R[v]|, (T[u] + 32767) >> 15) — the oversampled peak rounded UP to an LSB, a < 2^22;
+ *       g[v] = 32768 where a <= C, else floor(C 32768 / a), the same 32-bit unsigned division.  x'[v] = 0 for v < 0, and g = 32768 for v < -H.
+ *   3 - 5  on index v: m[v], r[v], S[v], s[v] as above
+ *   6'  y_c[u] = (x'_c[v - D] s[v] + 2^14) >> 15, stored as int16 with no saturation
+ * The start-up is part of the definition: for -H <= v < 0 the rule 2' applies with x'[v] = 0, so what the interpolator rings AHEAD of a stream's
+ * first pairs is held under the ceiling like any other value.  (The state carries no count of pairs; zeros before the start and zeros in the
+ * stream are the same state, and cut invariance needs them to be.)
+ *   The sample ceiling still holds, |y| <= C: a[v] >= the pair's sample magnitude.
+ *   Transparency: with G = 4096, every |x| <= C and every T <= C 2^15, y[u] = x[u - D - H] bit for bit.
+ *   Cut invariance: any cut into calls, of 0 pairs and of fewer than D + H pairs as well, gives the stream's output, state and joined records.
+ *   At constant gain: where s is one value over an interpolated value's support, that value of the OUTPUT is at most
+ *   C 2^15 + floor(max over p of sum over k of |coef[p][k]| / 2) in the true-peak record's units; the second term is the rounding of y.
+ * State per stream, 4 D + 2 H = 4 D + NT int32 words, oldest first: x'_L and x'_R of the last D + H pairs interleaved, then g of the last D detector
+ * pairs, then r of the last D detector pairs; before the start 0, 32768 and 2^23.  The record and its join are the sample form's: s of the call's
+ * output pairs.
+ *
+ *   sdrfm_pcm_tplimit_s16          one stream's call, the definition as code with 64-bit accumulation; out may be in.  SDRFM_EINVAL, with nothing
+ *                                  touched: whatever sdrfm_pcm_limit_s16 refuses, a table sdrfm_truepeak_check_coef refuses, 2^LW < NT / 2.  coef NULL
+ *                                  means the default table here as well.
+ *   sdrfm_pcm_tplimit_state_words  4 D + NT for a log2_window in 2 .. 8 and an n_taps the table rules and the window take, else 0.
+ *   sdrfm_pcm_tplimit_state_init   the state before the start; SDRFM_EINVAL for NULL or where _state_words answers 0.
+ *   sdrfm_pcm_tplimit_latency      D + NT / 2, 0 where _state_words answers 0.
+ *   sdrfm_pcm_limit_add, _report, _check_params and _ceiling serve both forms; a ceiling here reads as dBTP.
+ *   sdrfm_pcm_tplimit_create       sdrfm_pcm_limit_create's rules for config, flags == 0 included; then a table sdrfm_truepeak_check_coef refuses or
+ *                                  2^LW < NT / 2: SDRFM_EINVAL — all before any device is looked for.  Every sdrfm_pcm_limit_* call works on such a
+ *                                  handle under the same contract; get_state gives n_streams x (4 D + NT) words; kernel name: "pcm-limit-tp".
+ *   sdrfm_pcm_tplimit_get_detector n_phases, n_taps and the latency in pairs (each may be NULL): P, NT and D + H, or 0, 0 and D for a handle made
+ *                                  by sdrfm_pcm_limit_create.  SDRFM_EINVAL for a NULL handle.
+ * (The names keep clear of the prefix sdrfm_pcm_limit_, whose set of declarations is the sample form's ABI.)
+ * The kernel k_pcm_limit_tp is a second instance of k_pcm_limit's body: the x' planes behind D + H pairs of lead-in, the packed table in LDS
+ * tap-reversed, and per pair the P phases of both channels as 64-bit multiply-adds (x' has 20 bits); no atomics. */
+int  sdrfm_pcm_tplimit_create(const sdrfm_pcm_limit_config* config, const int16_t* coef /* or NULL */, uint32_t n_phases, uint32_t n_taps, sdrfm_pcm_limit_t** out);
+int  sdrfm_pcm_tplimit_get_detector(const sdrfm_pcm_limit_t* k, uint32_t* n_phases, uint32_t* n_taps, uint32_t* latency);
+int  sdrfm_pcm_tplimit_s16(const int16_t* in, uint32_t n, uint32_t log2_window, uint32_t gain_slew, uint32_t J, const sdrfm_pcm_limit_params* p,
+                           const int16_t* coef, uint32_t n_phases, uint32_t n_taps, int32_t* state /* 4 D + NT */, int16_t* out, sdrfm_pcm_limit_rec* acc);
+uint32_t sdrfm_pcm_tplimit_state_words(uint32_t log2_window, uint32_t n_taps);
+int  sdrfm_pcm_tplimit_state_init(uint32_t log2_window, uint32_t n_taps, int32_t* state /* 4 D + NT */);
+uint32_t sdrfm_pcm_tplimit_latency(uint32_t log2_window, uint32_t n_taps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ from .siggen import make_iq, make_iq_stereo, make_iq_rds, make_iq_stations, MODE
 from .frontend import ReplayFrontEnd, XferState
 from .loudness import LOUDNESS_STATE_DTYPE, loudness_default_coef, pcm_loudness_host, LoudnessGate, LoudnessMonitor, loudness_alarms
 from .truepeak import TRUEPEAK_DTYPE, truepeak_default_coef, truepeak_limit, pcm_truepeak_host, truepeak_add, truepeak_report, truepeak_alarms, headroom_gain_q15
-from .limit import PcmLimiter, LIMIT_DTYPE, pcm_limit_host, limit_add, limit_report, limit_ceiling, limit_release, normalise_gain_q12
+from .limit import PcmLimiter, LIMIT_DTYPE, pcm_limit_host, pcm_limit_tp_host, limit_add, limit_report, limit_ceiling, limit_release, normalise_gain_q12
 from . import fanout
 from . import rate
 from . import lib
@@ -43,5 +43,5 @@ __all__ = [
     "TRUEPEAK_DTYPE", "truepeak_default_coef", "truepeak_limit", "pcm_truepeak_host", "truepeak_add", "truepeak_report", "truepeak_alarms",
     "headroom_gain_q15", "truepeak_coef",
     "PcmRateMatcher", "pcm_rate_host", "rate_coef", "step_for", "ClockServo", "rate",
-    "PcmLimiter", "LIMIT_DTYPE", "pcm_limit_host", "limit_add", "limit_report", "limit_ceiling", "limit_release", "normalise_gain_q12",
+    "PcmLimiter", "LIMIT_DTYPE", "pcm_limit_host", "pcm_limit_tp_host", "limit_add", "limit_report", "limit_ceiling", "limit_release", "normalise_gain_q12",
 ]

@@ -3,10 +3,12 @@
  * stereo rows the PCM sinks leave, under a ramped make-up gain and a look-ahead peak limiter, on the device.  The arithmetic is the host
  * routine sdrfm_pcm_limit_s16's (csrc/limit.c) and all-integer, so the outputs, the state and the records are that routine's bit for bit.
  *
- *   k_pcm_limit   one workgroup of 1024 lanes per stream, grid (streams); the row in tiles of SDRFM_PCM_LIMIT_TILE pairs staged in LDS behind
- *                 their lead-in.  The body, the arithmetic and the geometry are in csrc/sdrfm_limit.h.
+ *   k_pcm_limit      one workgroup of 1024 lanes per stream, grid (streams); the row in tiles of SDRFM_PCM_LIMIT_TILE pairs staged in LDS behind
+ *                    their lead-in.  The body, the arithmetic and the geometry are in csrc/sdrfm_limit.h.
+ *   k_pcm_limit_tp   the same body's true-peak form for a handle made by sdrfm_pcm_tplimit_create: the detector sees the P
+ *                    phases of the oversampled waveform, as 64-bit multiply-adds over the x' planes.
  *
- * State: 4 D int32 per stream on the device, one set.  The kernel reads a stream's state into registers before its first barrier and writes it
+ * State: 4 D int32 per stream (4 D + NT in the true-peak form) on the device, one set.  The kernel reads a stream's state into registers before its first barrier and writes it
  * behind its last, and calls are ordered by the HIP stream they are enqueued on.  The gain ramp is a closed form of (gain0, gain_t, slew, J):
  * the handle keeps J on the host and passes it by value.
  */
@@ -34,13 +36,20 @@ namespace {
 
 __global__ void __launch_bounds__(SDRFM_LIMIT_NT) k_pcm_limit(LimitParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned limit_lds[];
-  limit_stream(limit_lds, p);
+  limit_stream<false>(limit_lds, p);
+}
+
+__global__ void __launch_bounds__(SDRFM_LIMIT_NT) k_pcm_limit_tp(LimitTpParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned limit_lds[];
+  limit_stream<true>(limit_lds, p);
 }
 
 }  // namespace
 
 struct sdrfm_pcm_limit {
   uint32_t n_streams, lw, slew, J;
+  uint32_t P, nt, words;           // the detector's table (0, 0 for the sample form) and the state's words per stream
+  unsigned* d_table;               // the packed table, true-peak form only
   int device;
   hipStream_t own_stream, stream;
   sdrfm_pcm_limit_params* d_par;   // [n_streams]
@@ -60,6 +69,7 @@ static void limit_free(sdrfm_pcm_limit* k) {
   if (k->d_par) (void)hipFree(k->d_par);
   if (k->d_state) (void)hipFree(k->d_state);
   if (k->d_rec) (void)hipFree(k->d_rec);
+  if (k->d_table) (void)hipFree(k->d_table);
   if (k->d_buf) (void)hipFree(k->d_buf);
   free(k->h_buf);
   free(k->par);
@@ -71,11 +81,13 @@ static void limit_free(sdrfm_pcm_limit* k) {
 
 // one call over device buffers on the handle's stream; J moves with it
 static int limit_launch(sdrfm_pcm_limit* k, const int16_t* in, size_t in_stride, uint32_t n, int16_t* out, size_t out_stride) {
-  LimitParams p;
+  LimitTpParams p;
   p.in = in; p.in_stride = in_stride; p.out = out; p.out_stride = out_stride;
   p.par = k->d_par; p.state = k->d_state; p.rec = k->d_rec;
   p.n = n; p.lw = k->lw; p.slew = k->slew; p.J = k->J;
-  hipLaunchKernelGGL(k_pcm_limit, dim3(k->n_streams), dim3(SDRFM_LIMIT_NT), limit_lds_bytes(), k->stream, p);
+  p.table = k->d_table; p.nt = k->nt; p.P = k->P;
+  if (k->nt) hipLaunchKernelGGL(k_pcm_limit_tp, dim3(k->n_streams), dim3(SDRFM_LIMIT_NT), limit_tp_lds_bytes(), k->stream, p);
+  else hipLaunchKernelGGL(k_pcm_limit, dim3(k->n_streams), dim3(SDRFM_LIMIT_NT), limit_lds_bytes(), k->stream, static_cast<const LimitParams&>(p));
   STRY(hipGetLastError(), SDRFM_FAIL);
   k->J = audio_ctl_advance(k->J, n);
   return SDRFM_OK;
@@ -101,12 +113,8 @@ static int limit_upload(sdrfm_pcm_limit* k) {
   return SDRFM_OK;
 }
 
-extern "C" {
-
-int sdrfm_pcm_limit_create(const sdrfm_pcm_limit_config* cfg, sdrfm_pcm_limit_t** out) {
-  if (!out) return SDRFM_EINVAL;
-  *out = nullptr;
-  if (!cfg || !cfg->n_streams || cfg->flags || !limit_shape_ok(cfg->log2_window, cfg->gain_slew)) return SDRFM_EINVAL;
+// the two constructors behind their refusals: coef NULL is the sample form, else a table sdrfm_truepeak_check_coef has taken
+static int limit_create(const sdrfm_pcm_limit_config* cfg, const int16_t* coef, uint32_t n_phases, uint32_t n_taps, sdrfm_pcm_limit_t** out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return SDRFM_NO_DEVICE;
   hipDeviceProp_t prop;
@@ -115,7 +123,9 @@ int sdrfm_pcm_limit_create(const sdrfm_pcm_limit_config* cfg, sdrfm_pcm_limit_t*
   sdrfm_pcm_limit* k = new (std::nothrow) sdrfm_pcm_limit();
   if (!k) return SDRFM_ENOMEM;
   memset(static_cast<void*>(k), 0, sizeof(*k));
-  const uint32_t ns = cfg->n_streams, words = limit_state_words(cfg->log2_window);
+  const uint32_t ns = cfg->n_streams, words = coef ? limit_tp_state_words(cfg->log2_window, n_taps) : limit_state_words(cfg->log2_window);
+  if (coef) { k->P = n_phases; k->nt = n_taps; }
+  k->words = words;
   k->n_streams = ns; k->lw = cfg->log2_window; k->slew = cfg->gain_slew; k->device = cfg->device;
   k->par = (sdrfm_pcm_limit_params*)malloc(sizeof(sdrfm_pcm_limit_params) * ns);
   k->state0 = (int32_t*)malloc(sizeof(int32_t) * (size_t)words * ns);
@@ -124,7 +134,8 @@ int sdrfm_pcm_limit_create(const sdrfm_pcm_limit_config* cfg, sdrfm_pcm_limit_t*
   for (uint32_t s = 0; s < ns; ++s) {
     k->par[s].ceiling = SDRFM_LIMIT_CEILING_DEFAULT; k->par[s].release = SDRFM_LIMIT_RELEASE_DEFAULT;
     k->par[s].gain0 = k->par[s].gain_t = SDRFM_LIMIT_GAIN_UNITY;
-    (void)sdrfm_pcm_limit_state_init(k->lw, k->state0 + (size_t)s * words);
+    if (coef) (void)sdrfm_pcm_tplimit_state_init(k->lw, n_taps, k->state0 + (size_t)s * words);
+    else (void)sdrfm_pcm_limit_state_init(k->lw, k->state0 + (size_t)s * words);
     k->rec0[s].n = 0; k->rec0[s].limited = 0; k->rec0[s].min_gain = SDRFM_LIMIT_ONE; k->rec0[s].at = 0;
   }
   const bool ok = hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking) == hipSuccess &&
@@ -133,7 +144,15 @@ int sdrfm_pcm_limit_create(const sdrfm_pcm_limit_config* cfg, sdrfm_pcm_limit_t*
                   hipMalloc(&k->d_rec, sizeof(sdrfm_pcm_limit_rec) * ns) == hipSuccess;
   if (!ok) { limit_free(k); return SDRFM_ENOMEM; }
   k->stream = k->own_stream;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_pcm_limit), hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit_lds_bytes()) != hipSuccess ||
+  if (coef) {
+    unsigned packed[SDRFM_TP_TABLE_DWORDS];
+    tp_pack_table(coef, n_phases, n_taps, packed);
+    const size_t bytes = sizeof(unsigned) * n_phases * (n_taps / 2u);
+    if (hipMalloc(&k->d_table, bytes) != hipSuccess) { limit_free(k); return SDRFM_ENOMEM; }
+    if (hipMemcpy(k->d_table, packed, bytes, hipMemcpyHostToDevice) != hipSuccess) { limit_free(k); return SDRFM_FAIL; }
+  }
+  const void* const kernel = coef ? reinterpret_cast<const void*>(k_pcm_limit_tp) : reinterpret_cast<const void*>(k_pcm_limit);
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(coef ? limit_tp_lds_bytes() : limit_lds_bytes())) != hipSuccess ||
       hipMemcpy(k->d_par, k->par, sizeof(sdrfm_pcm_limit_params) * ns, hipMemcpyHostToDevice) != hipSuccess) {
     limit_free(k);
     return SDRFM_FAIL;
@@ -141,6 +160,33 @@ int sdrfm_pcm_limit_create(const sdrfm_pcm_limit_config* cfg, sdrfm_pcm_limit_t*
   const int rc = sdrfm_pcm_limit_reset(k);
   if (rc != SDRFM_OK) { limit_free(k); return rc; }
   *out = k;
+  return SDRFM_OK;
+}
+
+extern "C" {
+
+int sdrfm_pcm_limit_create(const sdrfm_pcm_limit_config* cfg, sdrfm_pcm_limit_t** out) {
+  if (!out) return SDRFM_EINVAL;
+  *out = nullptr;
+  if (!cfg || !cfg->n_streams || cfg->flags || !limit_shape_ok(cfg->log2_window, cfg->gain_slew)) return SDRFM_EINVAL;
+  return limit_create(cfg, nullptr, 0, 0, out);
+}
+
+int sdrfm_pcm_tplimit_create(const sdrfm_pcm_limit_config* cfg, const int16_t* coef, uint32_t n_phases, uint32_t n_taps, sdrfm_pcm_limit_t** out) {
+  if (!out) return SDRFM_EINVAL;
+  *out = nullptr;
+  if (!cfg || !cfg->n_streams || cfg->flags || !limit_shape_ok(cfg->log2_window, cfg->gain_slew)) return SDRFM_EINVAL;
+  int16_t def[48];
+  if (!coef) { (void)sdrfm_truepeak_default_coef(def, &n_phases, &n_taps); coef = def; }
+  if (sdrfm_truepeak_check_coef(coef, n_phases, n_taps) != SDRFM_OK || !limit_tp_window_ok(cfg->log2_window, n_taps)) return SDRFM_EINVAL;
+  return limit_create(cfg, coef, n_phases, n_taps, out);
+}
+
+int sdrfm_pcm_tplimit_get_detector(const sdrfm_pcm_limit_t* k, uint32_t* n_phases, uint32_t* n_taps, uint32_t* latency) {
+  if (!k) return SDRFM_EINVAL;
+  if (n_phases) *n_phases = k->P;
+  if (n_taps) *n_taps = k->nt;
+  if (latency) *latency = (1u << k->lw) - 1u + k->nt / 2u;
   return SDRFM_OK;
 }
 
@@ -155,7 +201,7 @@ int sdrfm_pcm_limit_reset(sdrfm_pcm_limit_t* k) {
   if (!k) return SDRFM_EINVAL;
   STRY(hipSetDevice(k->device), SDRFM_FAIL);
   STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  STRY(hipMemcpy(k->d_state, k->state0, sizeof(int32_t) * (size_t)limit_state_words(k->lw) * k->n_streams, hipMemcpyHostToDevice), SDRFM_FAIL);
+  STRY(hipMemcpy(k->d_state, k->state0, sizeof(int32_t) * (size_t)k->words * k->n_streams, hipMemcpyHostToDevice), SDRFM_FAIL);
   STRY(hipMemcpy(k->d_rec, k->rec0, sizeof(sdrfm_pcm_limit_rec) * (size_t)k->n_streams, hipMemcpyHostToDevice), SDRFM_FAIL);
   return SDRFM_OK;
 }
@@ -240,7 +286,7 @@ int sdrfm_pcm_limit_get_state(sdrfm_pcm_limit_t* k, int32_t* state) {
   if (!k || !state) return SDRFM_EINVAL;
   STRY(hipSetDevice(k->device), SDRFM_FAIL);
   STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  STRY(hipMemcpy(state, k->d_state, sizeof(int32_t) * (size_t)limit_state_words(k->lw) * k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
+  STRY(hipMemcpy(state, k->d_state, sizeof(int32_t) * (size_t)k->words * k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
   return SDRFM_OK;
 }
 
@@ -259,6 +305,6 @@ int sdrfm_pcm_limit_synchronize(sdrfm_pcm_limit_t* k) {
   return SDRFM_OK;
 }
 
-const char* sdrfm_pcm_limit_kernel_name(const sdrfm_pcm_limit_t* k) { return k ? "pcm-limit" : nullptr; }
+const char* sdrfm_pcm_limit_kernel_name(const sdrfm_pcm_limit_t* k) { return k ? (k->nt ? "pcm-limit-tp" : "pcm-limit") : nullptr; }
 
 }  // extern "C"

@@ -60,6 +60,8 @@ ABI_SYMBOLS = [
     "sdrfm_pcm_limit_set_stream", "sdrfm_pcm_limit_synchronize", "sdrfm_pcm_limit_kernel_name", "sdrfm_pcm_limit_s16",
     "sdrfm_pcm_limit_state_words", "sdrfm_pcm_limit_state_init", "sdrfm_pcm_limit_check_params", "sdrfm_pcm_limit_add",
     "sdrfm_pcm_limit_report", "sdrfm_pcm_limit_ceiling",
+    "sdrfm_pcm_tplimit_create", "sdrfm_pcm_tplimit_get_detector", "sdrfm_pcm_tplimit_s16", "sdrfm_pcm_tplimit_state_words",
+    "sdrfm_pcm_tplimit_state_init", "sdrfm_pcm_tplimit_latency",
 ]
 
 
@@ -600,6 +602,18 @@ def load_library(dev=False):
     lib.sdrfm_pcm_limit_report.restype = C.c_int
     lib.sdrfm_pcm_limit_ceiling.argtypes = [C.c_double]
     lib.sdrfm_pcm_limit_ceiling.restype = u32
+    lib.sdrfm_pcm_tplimit_create.argtypes = [C.POINTER(PcmLimitConfig), vp, u32, u32, C.POINTER(vp)]
+    lib.sdrfm_pcm_tplimit_create.restype = C.c_int
+    lib.sdrfm_pcm_tplimit_get_detector.argtypes = [vp, u32p, u32p, u32p]
+    lib.sdrfm_pcm_tplimit_get_detector.restype = C.c_int
+    lib.sdrfm_pcm_tplimit_s16.argtypes = [vp, u32, u32, u32, u32, vp, vp, u32, u32, vp, vp, vp]
+    lib.sdrfm_pcm_tplimit_s16.restype = C.c_int
+    lib.sdrfm_pcm_tplimit_state_words.argtypes = [u32, u32]
+    lib.sdrfm_pcm_tplimit_state_words.restype = u32
+    lib.sdrfm_pcm_tplimit_state_init.argtypes = [u32, u32, vp]
+    lib.sdrfm_pcm_tplimit_state_init.restype = C.c_int
+    lib.sdrfm_pcm_tplimit_latency.argtypes = [u32, u32]
+    lib.sdrfm_pcm_tplimit_latency.restype = u32
     lib.sdrfm_loudness_default_coef.argtypes = [vp]
     lib.sdrfm_loudness_default_coef.restype = C.c_int
     lib.sdrfm_loudness_check_coef.argtypes = [vp]

@@ -1,6 +1,7 @@
 """PcmLimiter — the Python mirror of the sdrfm_pcm_limit_* C entry points: the int16 stereo rows the PCM sinks leave, raised by
 a ramped make-up gain and held under a sample ceiling by a look-ahead limiter, per stream on the device; pcm_limit_host, the host routine that
-defines it; the records' join and report; and normalise_gain_q12, the policy that turns a LoudnessMonitor reading into the make-up gain."""
+defines it; the records' join and report; and normalise_gain_q12, the policy that turns a LoudnessMonitor reading into the make-up gain.
+detect="truepeak" and pcm_limit_tp_host are the true-peak form: the detector sees the oversampled waveform."""
 import ctypes as C
 
 import numpy as np
@@ -93,6 +94,68 @@ def pcm_limit_host(pcm, log2_window=6, gain_slew=1, J=0, params=None, state=None
     return (out[0] if np.ndim(pcm) == 1 else out), st, rec
 
 
+def _tp_table(coef):
+    """(coef int16 [P, NT] contiguous or None for the default table, P, NT)"""
+    if coef is None:
+        return None, 4, 12
+    c = np.ascontiguousarray(coef, dtype=np.int16)
+    if c.ndim != 2:
+        raise _l.SdrfmError(_l.EINVAL, "the true-peak limiter's table: int16 [n_phases, n_taps]")
+    return c, c.shape[0], c.shape[1]
+
+
+def limit_tp_state_init(log2_window, n_taps=12, n_streams=1):
+    """the true-peak form's state before the start: int32 [n_streams, 4 D + n_taps]"""
+    lib = _l.load_library()
+    if not all(0 <= int(v) <= 0xFFFFFFFF for v in (log2_window, n_taps)):
+        raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_tplimit_state_words")
+    words = int(lib.sdrfm_pcm_tplimit_state_words(int(log2_window), int(n_taps)))
+    if not words:
+        raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_tplimit_state_words")
+    st = np.zeros((int(n_streams), words), np.int32)
+    for k in range(st.shape[0]):
+        lib.sdrfm_pcm_tplimit_state_init(int(log2_window), int(n_taps), st[k].ctypes.data)
+    return st
+
+
+def pcm_limit_tp_host(pcm, log2_window=6, gain_slew=1, J=0, params=None, state=None, acc=None, coef=None):
+    """sdrfm_pcm_tplimit_s16 (the host-side C routine, the definition of the limiter's true-peak form): as pcm_limit_host, with the interpolator's
+    table coef int16 [P, NT] (None: the BS.1770 table) -> (out, state int32 [streams, 4 D + NT], records LIMIT_DTYPE [streams]); the output is
+    delayed by D + NT / 2 pairs"""
+    lib = _l.load_library()
+    rows = np.ascontiguousarray(np.atleast_2d(pcm), dtype=np.int16)
+    assert rows.ndim == 2 and rows.shape[1] % 2 == 0, rows.shape
+    ns, n = rows.shape[0], rows.shape[1] // 2
+    if params is None:
+        params = (CEILING_DEFAULT, RELEASE_DEFAULT, GAIN_UNITY, GAIN_UNITY)
+    par = np.asarray(params)
+    if par.dtype != LIMIT_PARAMS_DTYPE:
+        v = np.broadcast_to(np.asarray(params, dtype=object), (ns, 4))
+        if any(not 0 <= int(x) <= 0xFFFFFFFF for x in v.reshape(-1)):
+            raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_tplimit_s16: params")
+        par = np.array([tuple(int(x) for x in r) for r in v], dtype=LIMIT_PARAMS_DTYPE)
+    par = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(par), (ns,)))
+    if not all(0 <= int(x) <= 0xFFFFFFFF for x in (log2_window, gain_slew, J)) or n > 0xFFFFFFFF:
+        raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_tplimit_s16: log2_window, gain_slew, J or n")
+    c, P, NT = _tp_table(coef)
+    if c is not None and lib.sdrfm_truepeak_check_coef(c.ctypes.data, P, NT) != _l.OK:
+        raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_tplimit_s16: the table")
+    words = int(lib.sdrfm_pcm_tplimit_state_words(int(log2_window), NT))
+    if not words:
+        raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_tplimit_s16: log2_window against n_taps")
+    st = limit_tp_state_init(log2_window, NT, ns) if state is None else np.ascontiguousarray(np.atleast_2d(state), dtype=np.int32).copy()
+    rec = limit_identity(ns) if acc is None else np.ascontiguousarray(np.atleast_1d(acc), dtype=LIMIT_DTYPE).copy()
+    assert st.shape == (ns, words) and rec.shape == (ns,), (st.shape, rec.shape)
+    out = np.zeros_like(rows)
+    for k in range(ns):
+        rc = lib.sdrfm_pcm_tplimit_s16(rows[k].ctypes.data if n else None, n, int(log2_window), int(gain_slew), int(J), par.ctypes.data + 16 * k,
+                                       None if c is None else c.ctypes.data, P, NT, st[k].ctypes.data, out[k].ctypes.data if n else None,
+                                       rec.ctypes.data + 32 * k)
+        if rc != _l.OK:
+            raise _l.SdrfmError(rc, "sdrfm_pcm_tplimit_s16")
+    return (out[0] if np.ndim(pcm) == 1 else out), st, rec
+
+
 def limit_identity(n_streams=1):
     """the records of no pairs: the join's identity (0, 0, 32768, 0)"""
     r = np.zeros(int(n_streams), LIMIT_DTYPE)
@@ -130,21 +193,32 @@ def limit_report(records, fs_audio=48000.0):
 
 class PcmLimiter:
     """The device limiter behind the sinks (sdrfm_pcm_limit_*): per stream, the rows under a ramped make-up gain and a look-ahead limiter with a
-    window of 2^log2_window pairs, bit for bit pcm_limit_host.  After create: ceiling 29204, release 874, gain 4096."""
+    window of 2^log2_window pairs, bit for bit pcm_limit_host.  After create: ceiling 29204, release 874, gain 4096.
+    detect="truepeak" makes the true-peak form (sdrfm_pcm_tplimit_create), bit for bit pcm_limit_tp_host: the detector sees the waveform the
+    table coef (int16 [P, NT], None: the BS.1770 table) interpolates between the samples, and the ceiling reads as dBTP.
+    latency: pairs of delay; state_words: int32 words of state per stream; detector: (n_phases, n_taps), (0, 0) for the sample form."""
 
-    def __init__(self, n_streams, log2_window=6, gain_slew=1, device=0):
+    def __init__(self, n_streams, log2_window=6, gain_slew=1, device=0, detect="sample", coef=None):
+        if detect not in ("sample", "truepeak") or (detect == "sample" and coef is not None):
+            raise ValueError("PcmLimiter: detect is 'sample' or 'truepeak', and only the latter takes a table")
         self._lib = _l.load_library()
         self.n_streams, self.log2_window, self.gain_slew = int(n_streams), int(log2_window), int(gain_slew)
         if not all(0 <= v <= 0xFFFFFFFF for v in (self.n_streams, self.log2_window, self.gain_slew)):
             raise _l.SdrfmError(_l.EINVAL, "sdrfm_pcm_limit_create")
         cfg = _l.PcmLimitConfig(self.n_streams, self.log2_window, self.gain_slew, 0, device)
         self._h = C.c_void_p()
-        st = self._lib.sdrfm_pcm_limit_create(C.byref(cfg), C.byref(self._h))
+        if detect == "truepeak":
+            c, P, NT = _tp_table(coef)
+            st = self._lib.sdrfm_pcm_tplimit_create(C.byref(cfg), None if c is None else c.ctypes.data, P, NT, C.byref(self._h))
+        else:
+            st = self._lib.sdrfm_pcm_limit_create(C.byref(cfg), C.byref(self._h))
         if st != _l.OK:
             self._h = None
-            raise _l.SdrfmError(st, "sdrfm_pcm_limit_create")
-        self.latency = (1 << self.log2_window) - 1
-        self.state_words = 4 * self.latency
+            raise _l.SdrfmError(st, "sdrfm_pcm_tplimit_create" if detect == "truepeak" else "sdrfm_pcm_limit_create")
+        P, NT, lat = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._ck(self._lib.sdrfm_pcm_tplimit_get_detector(self._h, C.byref(P), C.byref(NT), C.byref(lat)), "sdrfm_pcm_tplimit_get_detector")
+        self.detect, self.detector, self.latency = detect, (int(P.value), int(NT.value)), int(lat.value)
+        self.state_words = 4 * ((1 << self.log2_window) - 1) + int(NT.value)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -207,7 +281,7 @@ class PcmLimiter:
         return par, int(J.value)
 
     def state(self):
-        """the DEVICE's state int32 [n_streams, 4 D]; synchronises the handle's stream"""
+        """the DEVICE's state int32 [n_streams, state_words]; synchronises the handle's stream"""
         st = np.zeros((self.n_streams, self.state_words), np.int32)
         self._ck(self._lib.sdrfm_pcm_limit_get_state(self._h, st.ctypes.data), "sdrfm_pcm_limit_get_state")
         return st
