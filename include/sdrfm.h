@@ -1428,6 +1428,98 @@ uint32_t sdrfm_pcm_tplimit_state_words(uint32_t log2_window, uint32_t n_taps);
 int  sdrfm_pcm_tplimit_state_init(uint32_t log2_window, uint32_t n_taps, int32_t* state /* 4 D + NT */);
 uint32_t sdrfm_pcm_tplimit_latency(uint32_t log2_window, uint32_t n_taps);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Raw-capture IQ meter: what the BYTES say, in front of every filter — ADC level, rail hits, DC and I/Q imbalance — so that a
+ * tuner's gain can be driven (rtlctl.c holds the control arithmetic) without copying the capture to the host.  A handle of its own beside the
+ * scan handle, with no stream state.  The rows are every handle's: iq[s * iq_stride + 2i] = I, [... + 2i + 1] = Q, bytes, i < n = nbytes / 2.
+ * With bI and bQ the raw bytes as unsigned integers (NO centring inside the sums), a call's record per stream is
+ *     n                        pairs
+ *     sum_i, sum_q             sum bI, sum bQ
+ *     sum_ii, sum_qq, sum_iq   sum bI^2, sum bQ^2, sum bI bQ
+ *     rail_i, rail_q           bytes equal to 0 or 255
+ * and its histogram row, SDRFM_IQ_HIST_BINS uint32: the counts of bI = 0 .. 255, then of bQ = 0 .. 255.  The row is tied to the record exactly:
+ * the sum of either half is n, sum b hist is sum_i or sum_q, sum b^2 hist is sum_ii or sum_qq, hist[0] + hist[255] is rail_i or rail_q; only
+ * sum_iq is not a function of the row.  EVERYTHING IS A SUM OF SMALL INTEGERS OVER THE BYTES: records and rows depend on nothing but the bytes,
+ * the device equals sdrfm_iq_meter_u8 integer for integer, and a capture cut at any even byte offset gives records (sdrfm_iq_meter_add) and
+ * rows (sdrfm_iq_hist_add, uint32 into uint64) that add up to the one call's.  No sum wraps: 64 MiB of 255 give sum_ii = 2^25 * 65025 < 2^42.
+ *
+ * sdrfm_iq_meter_process_batch's contract is sdrfm_scan_process_batch's, point by point and in its order.  NULL handle or NULL meters:
+ * SDRFM_EINVAL.  Host buffers: a synchronous staged call.  SDRFM_F_DEVICE_PTRS: iq, meters (8-byte aligned) and hist (4-byte aligned) are device
+ * memory on the handle's device and the call is only enqueued on the handle's stream; a misaligned meters or hist: SDRFM_EINVAL.
+ * SDRFM_F_OVERLAP and unknown flags: SDRFM_EINVAL.  Odd nbytes: SDRFM_EODD.  nbytes above the maximum, or iq_stride < nbytes with more than one
+ * stream: SDRFM_ECAPACITY.  meters (n_streams records) and hist (n_streams rows of SDRFM_IQ_HIST_BINS uint32, or NULL for the record alone) are
+ * OVERWRITTEN: zeroed on the handle's stream, then added to; nbytes == 0 gives zero records and rows.  Then iq NULL: SDRFM_EINVAL.  iq and
+ * iq_stride may be any byte value, odd ones included.
+ * sdrfm_iq_meter_create: NULL, a wrong struct_size, n_streams == 0 or above 65536, max_bytes_per_call above 64 MiB or flags != 0: SDRFM_EINVAL,
+ * all before any device is looked for.  Kernel name: that of the last call, "iq-meter" (also before any call) or "iq-meter-hist". */
+typedef struct sdrfm_iq_meter {   /* 64 bytes, all sums of the call's pairs */
+  uint64_t n;                      /* pairs */
+  uint64_t sum_i, sum_q;           /* sum bI, sum bQ */
+  uint64_t sum_ii, sum_qq, sum_iq; /* sum bI^2, sum bQ^2, sum bI bQ */
+  uint64_t rail_i, rail_q;         /* bytes equal to 0 or 255 */
+} sdrfm_iq_meter;
+#define SDRFM_IQ_HIST_BINS 512u    /* row: counts of bI = 0..255, then of bQ = 0..255; uint32 per call */
+#define SDRFM_IQ_MAX_BYTES (64u << 20)
+
+typedef struct sdrfm_iq_meter_config {
+  uint32_t struct_size;           /* = sizeof(sdrfm_iq_meter_config) */
+  uint32_t n_streams;
+  uint32_t max_bytes_per_call;    /* per stream; 0 = 1 MiB; at most 64 MiB */
+  int32_t  device;
+  uint32_t flags;                 /* 0 */
+} sdrfm_iq_meter_config;
+
+typedef struct sdrfm_iq_meter_handle sdrfm_iq_meter_t;
+
+int  sdrfm_iq_meter_create(const sdrfm_iq_meter_config* cfg, sdrfm_iq_meter_t** out);
+void sdrfm_iq_meter_destroy(sdrfm_iq_meter_t* h);
+int  sdrfm_iq_meter_process_batch(sdrfm_iq_meter_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, sdrfm_iq_meter* meters,
+                                  uint32_t* hist /* n_streams x SDRFM_IQ_HIST_BINS, or NULL */, uint32_t flags);
+int  sdrfm_iq_meter_set_stream(sdrfm_iq_meter_t* h, void* hip_stream);
+int  sdrfm_iq_meter_synchronize(sdrfm_iq_meter_t* h);
+const char* sdrfm_iq_meter_kernel_name(const sdrfm_iq_meter_t* h);
+
+/* Host-only (plain C99, no GPU).
+ *   sdrfm_iq_meter_u8   the definition as code: the record of nbytes / 2 pairs ADDED onto acc, and their counts onto hist512 (uint64, may be NULL).
+ *                       NULL acc, NULL iq with nbytes != 0: SDRFM_EINVAL; odd nbytes: SDRFM_EODD; nothing touched.
+ *   sdrfm_iq_meter_add  acc += m, field by field.  sdrfm_iq_hist_add: acc512[b] += row512[b].  NULL: SDRFM_EINVAL. */
+int  sdrfm_iq_meter_u8(const uint8_t* iq, size_t nbytes, sdrfm_iq_meter* acc, uint64_t* hist512);
+int  sdrfm_iq_meter_add(sdrfm_iq_meter* acc, const sdrfm_iq_meter* m);
+int  sdrfm_iq_hist_add(uint64_t* acc512, const uint32_t* row512);
+
+/* What a record says, in double.  The central moments are formed as integers first, in unsigned __int128 — n sum b^2 - (sum b)^2 and
+ * n sum bI bQ - sum bI sum bQ — and divided once by n^2, so a long quiet capture loses nothing to cancellation.  With var_i, var_q and cov those
+ * moments in LSB^2:
+ *     dc_i, dc_q            mean - 127.5, in LSB
+ *     rms_dbfs              10 log10((var_i + var_q) / 127.5^2): 0 for a complex tone that just touches the rails
+ *     total_dbfs            the same with the DC power dc_i^2 + dc_q^2 included
+ *     rail_share_i, _q      rail_i / n, rail_q / n
+ *     gain_db               10 log10(var_q / var_i)
+ *     skew_rad              asin(cov / sqrt(var_i var_q)), the ratio clamped to +-1
+ *     image_rejection_db    10 log10((1 + 2 g cos(skew) + g^2) / (1 - 2 g cos(skew) + g^2)), g = sqrt(var_q / var_i); +inf for g = 1 and no skew
+ * THE LAST THREE ASSUME a capture whose content is circular — stations off centre, noise, or FM through many turns of the phase — for which I and Q
+ * have equal power and no correlation before the front end's imbalance.  A carrier at centre, or a short capture of slow content, breaks the
+ * assumption; they are estimates, not bounds.  n == 0: every field is NaN (SDRFM_OK), as the other report routines answer.  Zero variance
+ * (var_i + var_q == 0): rms_dbfs is -inf; var_i == 0 or var_q == 0: the three imbalance fields are NaN.  NULL: SDRFM_EINVAL; so is a record no
+ * capture can give (a negative variance). */
+typedef struct sdrfm_iq_report_t {
+  double dc_i, dc_q, rms_dbfs, total_dbfs, rail_share_i, rail_share_q, gain_db, skew_rad, image_rejection_db;
+} sdrfm_iq_report_t;
+int  sdrfm_iq_meter_report(const sdrfm_iq_meter* m, sdrfm_iq_report_t* out);
+
+/* What an accumulated row says, per component c = I, Q, with the level of a code b its distance from mid-scale |2 b - 255| / 255 (1 at the rails):
+ *     n                     sum of the I half (the Q half's differs: SDRFM_EINVAL)
+ *     peak_c                the largest level among the codes used
+ *     level999_c            the smallest level L such that at least 99.9 % of the samples have a level <= L
+ *     codes_c               the number of codes used
+ *     headroom_db_c         -20 log10(level999_c): the 99.9 % level against the rail (a level is at least 1 / 255)
+ * n == 0: every field but n is NaN (SDRFM_OK).  NULL: SDRFM_EINVAL. */
+typedef struct sdrfm_iq_hist_report_t {
+  uint64_t n;
+  double peak_i, peak_q, level999_i, level999_q, codes_i, codes_q, headroom_db_i, headroom_db_q;
+} sdrfm_iq_hist_report_t;
+int  sdrfm_iq_hist_report(const uint64_t* hist512, sdrfm_iq_hist_report_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,8 @@ ABI_SYMBOLS = [
     "sdrfm_pcm_limit_report", "sdrfm_pcm_limit_ceiling",
     "sdrfm_pcm_tplimit_create", "sdrfm_pcm_tplimit_get_detector", "sdrfm_pcm_tplimit_s16", "sdrfm_pcm_tplimit_state_words",
     "sdrfm_pcm_tplimit_state_init", "sdrfm_pcm_tplimit_latency",
+    "sdrfm_iq_meter_create", "sdrfm_iq_meter_destroy", "sdrfm_iq_meter_process_batch", "sdrfm_iq_meter_set_stream", "sdrfm_iq_meter_synchronize",
+    "sdrfm_iq_meter_kernel_name", "sdrfm_iq_meter_u8", "sdrfm_iq_meter_add", "sdrfm_iq_hist_add", "sdrfm_iq_meter_report", "sdrfm_iq_hist_report",
 ]
 
 
@@ -247,6 +249,30 @@ class PcmLimitReport(C.Structure):
 LIMIT_DTYPE = np.dtype([(n, "<u8") for n, _ in PcmLimitRec._fields_])
 LIMIT_PARAMS_DTYPE = np.dtype([(n, "<u4") for n, _ in PcmLimitParams._fields_])
 assert LIMIT_DTYPE.itemsize == C.sizeof(PcmLimitRec) == 32 and LIMIT_PARAMS_DTYPE.itemsize == C.sizeof(PcmLimitParams) == 16
+
+
+class IqMeterConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_streams", C.c_uint32), ("max_bytes_per_call", C.c_uint32), ("device", C.c_int32), ("flags", C.c_uint32)]
+
+
+class IqMeter(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n", "sum_i", "sum_q", "sum_ii", "sum_qq", "sum_iq", "rail_i", "rail_q")]
+
+
+class IqReport(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("dc_i", "dc_q", "rms_dbfs", "total_dbfs", "rail_share_i", "rail_share_q", "gain_db", "skew_rad",
+                                          "image_rejection_db")]
+
+
+class IqHistReport(C.Structure):
+    _fields_ = [("n", C.c_uint64)] + [(n, C.c_double) for n in ("peak_i", "peak_q", "level999_i", "level999_q", "codes_i", "codes_q",
+                                                                  "headroom_db_i", "headroom_db_q")]
+
+
+# sdrfm_iq_meter as a structured dtype
+IQ_METER_DTYPE = np.dtype([(n, "<u8") for n, _ in IqMeter._fields_])
+assert IQ_METER_DTYPE.itemsize == C.sizeof(IqMeter) == 64
+IQ_HIST_BINS = 512      # SDRFM_IQ_HIST_BINS
 
 
 class RdsGroup(C.Structure):
@@ -614,6 +640,28 @@ def load_library(dev=False):
     lib.sdrfm_pcm_tplimit_state_init.restype = C.c_int
     lib.sdrfm_pcm_tplimit_latency.argtypes = [u32, u32]
     lib.sdrfm_pcm_tplimit_latency.restype = u32
+    lib.sdrfm_iq_meter_create.argtypes = [C.POINTER(IqMeterConfig), C.POINTER(vp)]
+    lib.sdrfm_iq_meter_create.restype = C.c_int
+    lib.sdrfm_iq_meter_destroy.argtypes = [vp]
+    lib.sdrfm_iq_meter_destroy.restype = None
+    lib.sdrfm_iq_meter_process_batch.argtypes = [vp, vp, C.c_size_t, u32, vp, vp, u32]
+    lib.sdrfm_iq_meter_process_batch.restype = C.c_int
+    lib.sdrfm_iq_meter_set_stream.argtypes = [vp, vp]
+    lib.sdrfm_iq_meter_set_stream.restype = C.c_int
+    lib.sdrfm_iq_meter_synchronize.argtypes = [vp]
+    lib.sdrfm_iq_meter_synchronize.restype = C.c_int
+    lib.sdrfm_iq_meter_kernel_name.argtypes = [vp]
+    lib.sdrfm_iq_meter_kernel_name.restype = C.c_char_p
+    lib.sdrfm_iq_meter_u8.argtypes = [vp, C.c_size_t, vp, vp]
+    lib.sdrfm_iq_meter_u8.restype = C.c_int
+    lib.sdrfm_iq_meter_add.argtypes = [vp, vp]
+    lib.sdrfm_iq_meter_add.restype = C.c_int
+    lib.sdrfm_iq_hist_add.argtypes = [vp, vp]
+    lib.sdrfm_iq_hist_add.restype = C.c_int
+    lib.sdrfm_iq_meter_report.argtypes = [vp, C.POINTER(IqReport)]
+    lib.sdrfm_iq_meter_report.restype = C.c_int
+    lib.sdrfm_iq_hist_report.argtypes = [vp, C.POINTER(IqHistReport)]
+    lib.sdrfm_iq_hist_report.restype = C.c_int
     lib.sdrfm_loudness_default_coef.argtypes = [vp]
     lib.sdrfm_loudness_default_coef.restype = C.c_int
     lib.sdrfm_loudness_check_coef.argtypes = [vp]

@@ -154,3 +154,17 @@ def make_iq_stations(n_samples, stations, fs=2.4e6, seed=0):
     out[0, 0::2] = np.clip(np.rint(127.5 + z.real + noise[0]), 0, 255)
     out[0, 1::2] = np.clip(np.rint(127.5 + z.imag + noise[1]), 0, 255)
     return out
+
+
+def impair_iq(iq_u8, dc_i=0.0, dc_q=0.0, gain_q=1.0, skew_rad=0.0, drive=1.0):
+    """A capture as a zero-IF front end with DC offsets and I/Q imbalance would have handed it over, in numpy: the bytes centred on 127.5,
+    I' = drive I + dc_i, Q' = drive gain_q (Q cos(skew_rad) + I sin(skew_rad)) + dc_q, put back on 127.5, rounded and clipped to 0 .. 255.
+    For circular content the components then differ by gain_q in amplitude and correlate with sin(skew_rad).  iq_u8: uint8 [..., 2n]; returns
+    uint8 of the same shape."""
+    x = np.asarray(iq_u8)
+    assert x.dtype == np.uint8 and x.shape[-1] % 2 == 0, (x.dtype, x.shape)
+    i, q = x[..., 0::2].astype(np.float64) - 127.5, x[..., 1::2].astype(np.float64) - 127.5
+    out = np.empty_like(x)
+    out[..., 0::2] = np.clip(np.rint(127.5 + float(drive) * i + float(dc_i)), 0, 255)
+    out[..., 1::2] = np.clip(np.rint(127.5 + float(drive) * float(gain_q) * (q * np.cos(float(skew_rad)) + i * np.sin(float(skew_rad))) + float(dc_q)), 0, 255)
+    return out
