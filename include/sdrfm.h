@@ -1520,6 +1520,101 @@ typedef struct sdrfm_iq_hist_report_t {
 } sdrfm_iq_hist_report_t;
 int  sdrfm_iq_hist_report(const uint64_t* hist512, sdrfm_iq_hist_report_t* out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * A PCM MIX BUS: n_bus output stereo rows formed from n_in input stereo rows on the device — station selection, crossfade and
+ * channel routing without a click.  A handle of its own beside the rate matcher and the limiter.  Rows are theirs: row[2i] = L, row[2i + 1] = R,
+ * int16, i < n.  All arithmetic is integer and exact: the device and the host routine agree bit for bit, and any cut of a run into calls gives
+ * the same PCM and the same joined records.
+ *
+ * Handle-wide, at create: n_in and n_bus in 1 .. 65536; n_slots K in 1 .. 8; slew in 1 .. 32768, Q15 units per pair; an optional curve of
+ * SDRFM_PCM_MIX_CURVE_LEN = 129 uint16 values t[0 .. 128] with t[0] = 0, t[128] = 32768 and no decrease (sdrfm_pcm_mix_check_curve).
+ * Every bus has K slots.  A slot (sdrfm_pcm_mix_slot, 16 bytes) names a source row src < n_in, or SDRFM_PCM_MIX_NONE, which contributes nothing;
+ * a channel mode; and a gain ramp (g0, gt), Q15 in [0, 32768].  With (L, R) the source pair the slot contributes (l, r):
+ *     0 STEREO (2L, 2R)    1 MONO (L + R, L + R)    2 LEFT (2L, 2L)    3 RIGHT (2R, 2R)    4 SWAP (2R, 2L)
+ * After create every slot is (NONE, STEREO, 0, 0).
+ *
+ * Pair i of a call; J the pairs since the last set_gains, saturating at 65536.  For a bus and each of its slots k:
+ *   1  g_k = ramp(g0_k, gt_k, slew, J + i + 1): towards gt by at most slew per pair (the closed form of the broadcast receiver's audio ramps)
+ *   2  c_k = g_k without a curve; with one c(32768) = t[128], else j = g >> 8, f = g & 255, c = t[j] + (((t[j + 1] - t[j]) f + 128) >> 8)
+ *   3  acc_c = sum over k of c_k (l_k or r_k) per channel, exactly (|acc| <= 8 * 2^15 * 2^16 = 2^34: a 64-bit sum)
+ *   4  v_c = (acc_c + 2^15) >> 16, arithmetic shift;  y_c = clamp(v_c, -32768, 32767)
+ *   Unity: one STEREO slot at 32768 beside slots at 0 gives y = x bit for bit.
+ *   Self-crossfade: without a curve (or with the linear one) two slots on one source and mode that ramp 32768 -> 0 and 0 -> 32768 from one
+ *   set_gains give y = x bit for bit at every pair and slew: both have moved by min(n slew, 32768).
+ *   MONO at 32768 is (L + R + 1) >> 1 and never clips.
+ *   A slot with src = NONE or g0 = gt = 0 contributes 0 (c(0) = 0) and its row is never read.
+ * Record per bus (sdrfm_pcm_mix_rec, 32 bytes, 8-byte aligned): n, the pairs covered; clipped_l and clipped_r, the outputs with v != y per channel;
+ * peak, the largest |v| of both channels before the clamp (<= 2^18).  The join (sdrfm_pcm_mix_add): the counts add, peak is the maximum —
+ * commutative, associative, identity (0, 0, 0, 0).
+ *
+ * Host side, plain C with no GPU behind it (csrc/pcm_mix.c):
+ *   sdrfm_pcm_mix_s16          ONE bus's call, the definition as code: in is the n_in input rows (in_stride int16 apart, not looked at for
+ *                              n_in == 1), slots the bus's n_slots slots, J as above; 2n int16 are written to out and the call's record is joined
+ *                              onto *acc.  SDRFM_EINVAL, with nothing touched: slots or acc NULL, in or out NULL with n > 0, n_in, n_slots or slew
+ *                              outside the ranges, n > 2^20, J > 65536, an odd in_stride, slots sdrfm_pcm_mix_check_slots refuses, a curve
+ *                              sdrfm_pcm_mix_check_curve refuses; SDRFM_ECAPACITY: n_in > 1 and in_stride < 2n.  out must not overlap in.
+ *   sdrfm_pcm_mix_check_slots  SDRFM_OK where every one of count slots has src < n_in or NONE, mode <= 4 and g0, gt <= 32768; else SDRFM_EINVAL
+ *                              (also for NULL).
+ *   sdrfm_pcm_mix_check_curve  SDRFM_OK for a table under the rules above; else SDRFM_EINVAL (also for NULL).
+ *   sdrfm_pcm_mix_add          the join; SDRFM_EINVAL for a NULL pointer.
+ *   sdrfm_pcm_mix_report       in double: peak_dbfs = 20 log10(peak / 32768) (-inf for 0), clipped_frac = (clipped_l + clipped_r) / (2n); every
+ *                              field NaN for n = 0.  SDRFM_EINVAL for a NULL pointer.
+ *
+ * The handle follows sdrfm_pcm_limit_*'s contract; every refusal is made before anything is enqueued and leaves the handle as it was:
+ *   create     config or out NULL, flags != 0, n_in, n_bus, n_slots or slew outside the ranges, a curve check_curve refuses: SDRFM_EINVAL before
+ *              any device is looked for; a missing or non-gfx950 device: SDRFM_NO_DEVICE.  curve NULL: c = g.
+ *   set_routes src and mode are n_bus x n_slots each; either may be NULL (those stay), not both; a src that is neither below n_in nor NONE, or a
+ *              mode above 4: SDRFM_EINVAL and nothing changes.  Gains and J are untouched; takes effect with the next call.  Waits for the
+ *              handle's stream.
+ *   set_gains  one target per slot, n_bus x n_slots; any above 32768 or a jump other than 0 and 1: SDRFM_EINVAL and every ramp stays.  Every
+ *              slot's ramp restarts at the value it has reached (jump = 0) or at its target (jump = 1), and J becomes 0.  Waits for the handle's
+ *              stream.
+ *   get_slots  the slots as the next call uses them (out, n_bus x n_slots, or NULL) and J (or NULL).
+ *   process_batch   flags outside SDRFM_F_DEVICE_PTRS, n > 2^20, an odd in_stride or out_stride (int16 elements): SDRFM_EINVAL; then n == 0 is a
+ *              no-op; then in or out NULL, or device rows that are not 4-byte aligned: SDRFM_EINVAL; n_in > 1 with in_stride < 2n, or n_bus > 1 with
+ *              out_stride < 2n: SDRFM_ECAPACITY; then the byte range of the output rows overlapping that of the input rows: SDRFM_EINVAL — bus b
+ *              writes while bus c reads, so there is no in-place form.  Exactly 2n int16 are written per bus row.  J advances by n, saturating,
+ *              on success only.  With SDRFM_F_DEVICE_PTRS the rows are device memory and the call only enqueues on the handle's stream; with
+ *              host buffers it stages, runs, copies back and is synchronous.
+ *   read       flags is a subset of SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET and out is 8-byte aligned and holds n_bus records: else
+ *              SDRFM_EINVAL.  Host out: synchronises, copies and, with SDRFM_AMETER_F_RESET, zeroes the records behind the copy; device out: the
+ *              same, enqueued on the handle's stream.
+ *   reset      the records to the identity; the slots, the ramps and J stay.
+ *   NULL handles answer SDRFM_EINVAL (destroy: nothing; kernel_name: NULL).
+ * The kernel (csrc/sdrfm_pcm_mix.hip, body and geometry in csrc/sdrfm_pcm_mix.h): n_bus x cdiv(n, SDRFM_PCM_MIX_SPAN) workgroups of 256 lanes, a
+ * bus's slots read once per workgroup and a dead slot skipped by a uniform branch, ramp and curve evaluated per pair from values, the curve in
+ * LDS, dword accesses throughout, the record by one 64-bit integer atomic per field and workgroup.  kernel name: "pcm-mix". */
+#define SDRFM_PCM_MIX_SPAN 2048u                   /* pairs of a workgroup of k_pcm_mix: the tests place their shapes around it */
+#define SDRFM_PCM_MIX_NONE 0xFFFFFFFFu             /* a slot's src: no source */
+#define SDRFM_PCM_MIX_CURVE_LEN 129u
+#define SDRFM_PCM_MIX_STEREO 0u
+#define SDRFM_PCM_MIX_MONO 1u
+#define SDRFM_PCM_MIX_LEFT 2u
+#define SDRFM_PCM_MIX_RIGHT 3u
+#define SDRFM_PCM_MIX_SWAP 4u
+typedef struct sdrfm_pcm_mix sdrfm_pcm_mix_t;
+typedef struct sdrfm_pcm_mix_config { uint32_t n_in, n_bus, n_slots, slew, flags; int32_t device; } sdrfm_pcm_mix_config;
+typedef struct sdrfm_pcm_mix_slot { uint32_t src, mode, g0, gt; } sdrfm_pcm_mix_slot;                            /* 16 bytes */
+typedef struct sdrfm_pcm_mix_rec { uint64_t n, clipped_l, clipped_r, peak; } sdrfm_pcm_mix_rec;                  /* 32 bytes, 8-byte aligned */
+typedef struct sdrfm_pcm_mix_report_t { double peak_dbfs, clipped_frac; } sdrfm_pcm_mix_report_t;
+int  sdrfm_pcm_mix_create(const sdrfm_pcm_mix_config* config, const uint16_t* curve /* 129, or NULL */, sdrfm_pcm_mix_t** out);
+void sdrfm_pcm_mix_destroy(sdrfm_pcm_mix_t* k);
+int  sdrfm_pcm_mix_reset(sdrfm_pcm_mix_t* k);
+int  sdrfm_pcm_mix_set_routes(sdrfm_pcm_mix_t* k, const uint32_t* src /* n_bus x n_slots, or NULL */, const uint32_t* mode /* likewise */);
+int  sdrfm_pcm_mix_set_gains(sdrfm_pcm_mix_t* k, const uint32_t* target /* n_bus x n_slots */, uint32_t jump /* 0 or 1 */);
+int  sdrfm_pcm_mix_get_slots(const sdrfm_pcm_mix_t* k, sdrfm_pcm_mix_slot* out /* n_bus x n_slots, or NULL */, uint32_t* J);
+int  sdrfm_pcm_mix_process_batch(sdrfm_pcm_mix_t* k, const int16_t* in, size_t in_stride, uint32_t n, int16_t* out, size_t out_stride, uint32_t flags);
+int  sdrfm_pcm_mix_read(sdrfm_pcm_mix_t* k, sdrfm_pcm_mix_rec* out /* n_bus records */, uint32_t flags);
+int  sdrfm_pcm_mix_set_stream(sdrfm_pcm_mix_t* k, void* hip_stream);
+int  sdrfm_pcm_mix_synchronize(sdrfm_pcm_mix_t* k);
+const char* sdrfm_pcm_mix_kernel_name(const sdrfm_pcm_mix_t* k);
+int  sdrfm_pcm_mix_s16(const int16_t* in, size_t in_stride, uint32_t n_in, uint32_t n, const sdrfm_pcm_mix_slot* slots, uint32_t n_slots, uint32_t slew,
+                       uint32_t J, const uint16_t* curve /* 129, or NULL */, int16_t* out, sdrfm_pcm_mix_rec* acc);
+int  sdrfm_pcm_mix_check_slots(const sdrfm_pcm_mix_slot* slots, uint32_t count, uint32_t n_in);
+int  sdrfm_pcm_mix_check_curve(const uint16_t* curve /* 129 */);
+int  sdrfm_pcm_mix_add(sdrfm_pcm_mix_rec* acc, const sdrfm_pcm_mix_rec* m);
+int  sdrfm_pcm_mix_report(const sdrfm_pcm_mix_rec* m, sdrfm_pcm_mix_report_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,14 +20,16 @@ from .rds import RdsDemod, RdsConfig, RdsSync, RdsGroup, rds_parse, rds_encode_g
 from .spectrum import SpectrumView, SpectrumConfig, power_db
 from .sink import PcmSink, StereoPcmSink, pcm_deemph_s16_host, pcm_deemph_stereo_s16_host, pcm_deemph_stereo_hicut_s16_host, hicut_slew, AUDIO_METER_DTYPE, pcm_audio_meter_host, audio_meter_add, audio_meter_report, audio_alarms, AudioMonitor
 from .rate import PcmRateMatcher, pcm_rate_host, step_for, ClockServo
-from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain, rds_gain, rds_lowpass_taps, tuned_channel_taps, tuned_rotation, retune_carry, pilot_gain, hicut_corner_hz, rate_coef, truepeak_coef
+from .taps import RTLSDR_FIR, rtlsdr_fir16, lowpass_taps, default_config, stereo_pilot_taps, stereo_diff_gain, rds_gain, rds_lowpass_taps, tuned_channel_taps, tuned_rotation, retune_carry, pilot_gain, hicut_corner_hz, rate_coef, truepeak_coef, mix_curve
 from .siggen import make_iq, make_iq_stereo, make_iq_rds, make_iq_stations, impair_iq, MODES
 from .frontend import ReplayFrontEnd, XferState
 from .loudness import LOUDNESS_STATE_DTYPE, loudness_default_coef, pcm_loudness_host, LoudnessGate, LoudnessMonitor, loudness_alarms
 from .truepeak import TRUEPEAK_DTYPE, truepeak_default_coef, truepeak_limit, pcm_truepeak_host, truepeak_add, truepeak_report, truepeak_alarms, headroom_gain_q15
 from .limit import PcmLimiter, LIMIT_DTYPE, pcm_limit_host, pcm_limit_tp_host, limit_add, limit_report, limit_ceiling, limit_release, normalise_gain_q12
 from .iqmeter import IqMeter, IQ_METER_DTYPE, IQ_HIST_BINS, iq_meter_host, iq_meter_add, iq_hist_add, iq_meter_report, iq_hist_report, gain_advice, nearest_gain
+from .mix import PcmMixer, MIX_DTYPE, MIX_SLOT_DTYPE, pcm_mix_host, mix_add, mix_report, slew_for, fade_pairs, dead_channel_modes
 from . import fanout
+from . import mix
 from . import rate
 from . import lib
 
@@ -47,4 +49,5 @@ __all__ = [
     "PcmLimiter", "LIMIT_DTYPE", "pcm_limit_host", "pcm_limit_tp_host", "limit_add", "limit_report", "limit_ceiling", "limit_release", "normalise_gain_q12",
     "IqMeter", "IQ_METER_DTYPE", "IQ_HIST_BINS", "iq_meter_host", "iq_meter_add", "iq_hist_add", "iq_meter_report", "iq_hist_report", "gain_advice", "nearest_gain",
     "impair_iq",
+    "PcmMixer", "MIX_DTYPE", "MIX_SLOT_DTYPE", "pcm_mix_host", "mix_add", "mix_report", "mix_curve", "slew_for", "fade_pairs", "dead_channel_modes", "mix",
 ]

@@ -64,6 +64,10 @@ ABI_SYMBOLS = [
     "sdrfm_pcm_tplimit_state_init", "sdrfm_pcm_tplimit_latency",
     "sdrfm_iq_meter_create", "sdrfm_iq_meter_destroy", "sdrfm_iq_meter_process_batch", "sdrfm_iq_meter_set_stream", "sdrfm_iq_meter_synchronize",
     "sdrfm_iq_meter_kernel_name", "sdrfm_iq_meter_u8", "sdrfm_iq_meter_add", "sdrfm_iq_hist_add", "sdrfm_iq_meter_report", "sdrfm_iq_hist_report",
+    "sdrfm_pcm_mix_create", "sdrfm_pcm_mix_destroy", "sdrfm_pcm_mix_reset", "sdrfm_pcm_mix_set_routes", "sdrfm_pcm_mix_set_gains",
+    "sdrfm_pcm_mix_get_slots", "sdrfm_pcm_mix_process_batch", "sdrfm_pcm_mix_read", "sdrfm_pcm_mix_set_stream", "sdrfm_pcm_mix_synchronize",
+    "sdrfm_pcm_mix_kernel_name", "sdrfm_pcm_mix_s16", "sdrfm_pcm_mix_check_slots", "sdrfm_pcm_mix_check_curve", "sdrfm_pcm_mix_add",
+    "sdrfm_pcm_mix_report",
 ]
 
 
@@ -273,6 +277,31 @@ class IqHistReport(C.Structure):
 IQ_METER_DTYPE = np.dtype([(n, "<u8") for n, _ in IqMeter._fields_])
 assert IQ_METER_DTYPE.itemsize == C.sizeof(IqMeter) == 64
 IQ_HIST_BINS = 512      # SDRFM_IQ_HIST_BINS
+
+
+class PcmMixConfig(C.Structure):
+    _fields_ = [("n_in", C.c_uint32), ("n_bus", C.c_uint32), ("n_slots", C.c_uint32), ("slew", C.c_uint32), ("flags", C.c_uint32), ("device", C.c_int32)]
+
+
+class PcmMixSlot(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("src", "mode", "g0", "gt")]
+
+
+class PcmMixRec(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n", "clipped_l", "clipped_r", "peak")]
+
+
+class PcmMixReport(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("peak_dbfs", "clipped_frac")]
+
+
+# sdrfm_pcm_mix_rec and sdrfm_pcm_mix_slot as structured dtypes
+MIX_DTYPE = np.dtype([(n, "<u8") for n, _ in PcmMixRec._fields_])
+MIX_SLOT_DTYPE = np.dtype([(n, "<u4") for n, _ in PcmMixSlot._fields_])
+assert MIX_DTYPE.itemsize == C.sizeof(PcmMixRec) == 32 and MIX_SLOT_DTYPE.itemsize == C.sizeof(PcmMixSlot) == 16
+MIX_SPAN = 2048               # SDRFM_PCM_MIX_SPAN
+MIX_NONE = 0xFFFFFFFF         # SDRFM_PCM_MIX_NONE
+MIX_CURVE_LEN = 129           # SDRFM_PCM_MIX_CURVE_LEN
 
 
 class RdsGroup(C.Structure):
@@ -662,6 +691,38 @@ def load_library(dev=False):
     lib.sdrfm_iq_meter_report.restype = C.c_int
     lib.sdrfm_iq_hist_report.argtypes = [vp, C.POINTER(IqHistReport)]
     lib.sdrfm_iq_hist_report.restype = C.c_int
+    lib.sdrfm_pcm_mix_create.argtypes = [C.POINTER(PcmMixConfig), vp, C.POINTER(vp)]
+    lib.sdrfm_pcm_mix_create.restype = C.c_int
+    lib.sdrfm_pcm_mix_destroy.argtypes = [vp]
+    lib.sdrfm_pcm_mix_destroy.restype = None
+    lib.sdrfm_pcm_mix_reset.argtypes = [vp]
+    lib.sdrfm_pcm_mix_reset.restype = C.c_int
+    lib.sdrfm_pcm_mix_set_routes.argtypes = [vp, vp, vp]
+    lib.sdrfm_pcm_mix_set_routes.restype = C.c_int
+    lib.sdrfm_pcm_mix_set_gains.argtypes = [vp, vp, u32]
+    lib.sdrfm_pcm_mix_set_gains.restype = C.c_int
+    lib.sdrfm_pcm_mix_get_slots.argtypes = [vp, vp, u32p]
+    lib.sdrfm_pcm_mix_get_slots.restype = C.c_int
+    lib.sdrfm_pcm_mix_process_batch.argtypes = [vp, vp, C.c_size_t, u32, vp, C.c_size_t, u32]
+    lib.sdrfm_pcm_mix_process_batch.restype = C.c_int
+    lib.sdrfm_pcm_mix_read.argtypes = [vp, vp, u32]
+    lib.sdrfm_pcm_mix_read.restype = C.c_int
+    lib.sdrfm_pcm_mix_set_stream.argtypes = [vp, vp]
+    lib.sdrfm_pcm_mix_set_stream.restype = C.c_int
+    lib.sdrfm_pcm_mix_synchronize.argtypes = [vp]
+    lib.sdrfm_pcm_mix_synchronize.restype = C.c_int
+    lib.sdrfm_pcm_mix_kernel_name.argtypes = [vp]
+    lib.sdrfm_pcm_mix_kernel_name.restype = C.c_char_p
+    lib.sdrfm_pcm_mix_s16.argtypes = [vp, C.c_size_t, u32, u32, vp, u32, u32, u32, vp, vp, vp]
+    lib.sdrfm_pcm_mix_s16.restype = C.c_int
+    lib.sdrfm_pcm_mix_check_slots.argtypes = [vp, u32, u32]
+    lib.sdrfm_pcm_mix_check_slots.restype = C.c_int
+    lib.sdrfm_pcm_mix_check_curve.argtypes = [vp]
+    lib.sdrfm_pcm_mix_check_curve.restype = C.c_int
+    lib.sdrfm_pcm_mix_add.argtypes = [vp, vp]
+    lib.sdrfm_pcm_mix_add.restype = C.c_int
+    lib.sdrfm_pcm_mix_report.argtypes = [vp, C.POINTER(PcmMixReport)]
+    lib.sdrfm_pcm_mix_report.restype = C.c_int
     lib.sdrfm_loudness_default_coef.argtypes = [vp]
     lib.sdrfm_loudness_default_coef.restype = C.c_int
     lib.sdrfm_loudness_check_coef.argtypes = [vp]

@@ -122,6 +122,21 @@ def rate_coef(NT=32, LOGPH=8, cutoff=None, beta=9.0, step=1 << 32):
     return q.astype(np.int16)
 
 
+def mix_curve(kind="equal_power"):
+    """a gain curve for the PCM mix bus: uint16 [129], the knots t[j] at gain 256 j in Q15.  "equal_power" is
+    round(32768 sin(pi j / 256)): two slots that crossfade pass 0.707 each at the middle, constant power for unrelated programmes.
+    "linear" is 256 j, under which the curve changes nothing.  Both start at 0, end at 32768 and do not decrease, as
+    sdrfm_pcm_mix_check_curve asks."""
+    j = np.arange(129, dtype=np.float64)
+    if kind == "equal_power":
+        t = np.rint(32768.0 * np.sin(np.pi * j / 256.0))
+    elif kind == "linear":
+        t = 256.0 * j
+    else:
+        raise ValueError("mix_curve: %r is neither 'equal_power' nor 'linear'" % (kind,))
+    return t.astype(np.uint16)
+
+
 def truepeak_coef(n_phases=4, n_taps=12, cutoff=0.9, beta=6.0):
     """a coefficient table for the true-peak meter: int16 [n_phases, n_taps] in Q15, a windowed-sinc interpolator laid out as
     the BS.1770-4 Annex 2 table is — coef[p][k] = Q15(h(k - (n_taps - 1) / 2 + (p - (n_phases - 1) / 2) / n_phases)) with h(t) = cutoff
