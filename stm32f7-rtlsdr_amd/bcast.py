@@ -35,7 +35,10 @@ class BroadcastConfig:
     force_generic: bool = False       # SDRFM_BCAST_CFG_FORCE_GENERIC (tests): never the fast kernel
 
 
-class BroadcastDemod:
+class BroadcastDemod(_l.StreamHandle):
+    _destroy = "sdrfm_bcast_destroy"
+    _prefix = "sdrfm_bcast"
+
     def __init__(self, cfg: BroadcastConfig):
         self._lib = _l.load_library()
         self.cfg = cfg
@@ -61,27 +64,6 @@ class BroadcastDemod:
         if st != _l.OK:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_bcast_create")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_bcast_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
 
     def reset(self):
         self._ck(self._lib.sdrfm_bcast_reset(self._h), "sdrfm_bcast_reset")
@@ -217,15 +199,9 @@ class BroadcastDemod:
         self._ck(self._lib.sdrfm_bcast_counts(self._h, int(nbytes), C.byref(na), C.byref(nr)), "sdrfm_bcast_counts")
         return na.value, nr.value
 
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_bcast_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_bcast_set_stream")
-
     @property
     def kernel_name(self):
         return self._lib.sdrfm_bcast_kernel_name(self._h).decode()
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_bcast_synchronize(self._h), "sdrfm_bcast_synchronize")
 
     def hist_kernel_name(self):
         """the kernel a hist call launches now: kernel_name and " + hist" (its step may be the generic one where the plain call's is fast)"""

@@ -32,6 +32,7 @@
 
 #include "../../include/sdrfm.h"
 #include "../../include/sdrfm_dev.h"
+#include "sdrfm_host.h"
 #include "sdrfm_math.h"
 #include "sdrfm_q.h"
 #include "sdrfm_fm_call.h"
@@ -1009,14 +1010,7 @@ static int route_create(sdrfm* h);
 static int route_reset(sdrfm* h);
 static int route_apply(sdrfm* h);
 
-#define HIP_TRY(expr, code)                                                                          \
-  do {                                                                                               \
-    hipError_t e__ = (expr);                                                                         \
-    if (e__ != hipSuccess) {                                                                         \
-      fprintf(stderr, "[sdrfm] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return (code);                                                                                 \
-    }                                                                                                \
-  } while (0)
+#define HIP_TRY STRY   // (csrc/sdrfm_host.h)
 
 // ---- per-stream routing between design Q and the bit-exact kernels (sdrfm_fm_route.h has the scheme) -----------------------------------
 static int route_create(sdrfm* h) {

@@ -17,16 +17,8 @@
 #include <new>
 
 #include "../../include/sdrfm.h"
+#include "sdrfm_host.h"
 #include "sdrfm_iq_meter.h"
-
-#define STRY(expr, code)                                                                                       \
-  do {                                                                                                         \
-    hipError_t e__ = (expr);                                                                                   \
-    if (e__ != hipSuccess) {                                                                                   \
-      fprintf(stderr, "[sdrfm] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__);  \
-      return (code);                                                                                           \
-    }                                                                                                          \
-  } while (0)
 
 static_assert(sizeof(sdrfm_iq_meter) == 64, "the record is 8 uint64");
 static_assert(IQM_MAX_BYTES == SDRFM_IQ_MAX_BYTES && 512u == SDRFM_IQ_HIST_BINS, "the header's limits");
@@ -44,30 +36,28 @@ __global__ void __launch_bounds__(IQM_NT) k_iq_meter(IqMeterParams p) {
 
 struct sdrfm_iq_meter_handle {
   uint32_t n_streams, max_bytes;
-  int device;
-  hipStream_t own_stream, stream;
+  HostStream hs;
   sdrfm_iq_meter* d_meters;        // host-buffer calls: the records [n_streams]
   uint32_t* d_hist;                // host-buffer hist calls: the rows [n_streams][512], allocated at the first such call
-  uint8_t* d_iq;                   // host-buffer calls: the rows staged, [n_streams][cap]
-  uint32_t cap;
+  RowStage stage;                  // host-buffer calls: the rows staged, bytes; nothing comes back through it
   bool last_hist;
 };
 
 static void iqm_free(sdrfm_iq_meter_handle* h) {
   if (!h) return;
-  (void)hipSetDevice(h->device);
+  (void)hipSetDevice(h->hs.device);
   if (h->d_meters) (void)hipFree(h->d_meters);
   if (h->d_hist) (void)hipFree(h->d_hist);
-  if (h->d_iq) (void)hipFree(h->d_iq);
-  if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+  row_stage_free(h->stage);
+  host_stream_close(h->hs);
   delete h;
 }
 
 // one call on device buffers, enqueued on the handle's stream: both outputs zeroed, then added to
 static int iqm_enqueue(sdrfm_iq_meter_handle* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, sdrfm_iq_meter* d_meters, uint32_t* d_hist) {
   const uint32_t ns = h->n_streams;
-  STRY(hipMemsetAsync(d_meters, 0, sizeof(sdrfm_iq_meter) * (size_t)ns, h->stream), SDRFM_FAIL);
-  if (d_hist) STRY(hipMemsetAsync(d_hist, 0, sizeof(uint32_t) * 512u * (size_t)ns, h->stream), SDRFM_FAIL);
+  STRY(hipMemsetAsync(d_meters, 0, sizeof(sdrfm_iq_meter) * (size_t)ns, h->hs.cur), SDRFM_FAIL);
+  if (d_hist) STRY(hipMemsetAsync(d_hist, 0, sizeof(uint32_t) * 512u * (size_t)ns, h->hs.cur), SDRFM_FAIL);
   h->last_hist = d_hist != nullptr;
   if (nbytes == 0) return SDRFM_OK;
   const IqmGrid g = iqm_grid(ns, nbytes);
@@ -75,19 +65,9 @@ static int iqm_enqueue(sdrfm_iq_meter_handle* h, const uint8_t* d_iq, size_t iq_
   p.iq = d_iq; p.iq_stride = ns > 1 ? iq_stride : 0; p.nbytes = nbytes; p.bps = g.bps; p.share = g.share;
   p.meters = reinterpret_cast<unsigned long long*>(d_meters); p.hist = d_hist;
   const dim3 grid(ns * g.bps), block(IQM_NT);
-  if (d_hist) hipLaunchKernelGGL(k_iq_meter<true>, grid, block, 0, h->stream, p);
-  else hipLaunchKernelGGL(k_iq_meter<false>, grid, block, 0, h->stream, p);
+  if (d_hist) hipLaunchKernelGGL(k_iq_meter<true>, grid, block, 0, h->hs.cur, p);
+  else hipLaunchKernelGGL(k_iq_meter<false>, grid, block, 0, h->hs.cur, p);
   STRY(hipGetLastError(), SDRFM_FAIL);
-  return SDRFM_OK;
-}
-
-static int iqm_reserve(sdrfm_iq_meter_handle* h, uint32_t nbytes) {
-  if (nbytes <= h->cap) return SDRFM_OK;
-  if (h->d_iq) (void)hipFree(h->d_iq);
-  h->d_iq = nullptr; h->cap = 0;
-  const uint32_t cap = (nbytes + IQM_CHUNK - 1u) & ~(IQM_CHUNK - 1u);
-  if (hipMalloc(&h->d_iq, (size_t)cap * h->n_streams) != hipSuccess) { h->d_iq = nullptr; return SDRFM_ENOMEM; }
-  h->cap = cap;
   return SDRFM_OK;
 }
 
@@ -98,29 +78,23 @@ int sdrfm_iq_meter_create(const sdrfm_iq_meter_config* cfg, sdrfm_iq_meter_t** o
   *out = nullptr;
   if (!cfg || cfg->struct_size != sizeof(sdrfm_iq_meter_config)) return SDRFM_EINVAL;
   if (!cfg->n_streams || cfg->n_streams > IQM_MAX_STREAMS || cfg->max_bytes_per_call > IQM_MAX_BYTES || cfg->flags) return SDRFM_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return SDRFM_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SDRFM_NO_DEVICE;
-  STRY(hipSetDevice(cfg->device), SDRFM_NO_DEVICE);
+  if (const int rc = host_open_device(cfg->device); rc != SDRFM_OK) return rc;
   sdrfm_iq_meter_handle* h = new (std::nothrow) sdrfm_iq_meter_handle();
   if (!h) return SDRFM_ENOMEM;
   memset(static_cast<void*>(h), 0, sizeof(*h));
-  h->n_streams = cfg->n_streams; h->max_bytes = cfg->max_bytes_per_call ? cfg->max_bytes_per_call : (1u << 20); h->device = cfg->device;
-  if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess ||
+  h->n_streams = cfg->n_streams; h->max_bytes = cfg->max_bytes_per_call ? cfg->max_bytes_per_call : (1u << 20); h->hs.device = cfg->device;
+  if (host_stream_open(h->hs, cfg->device) != SDRFM_OK ||
       hipMalloc(&h->d_meters, sizeof(sdrfm_iq_meter) * (size_t)h->n_streams) != hipSuccess) {
     iqm_free(h);
     return SDRFM_ENOMEM;
   }
-  h->stream = h->own_stream;
   *out = h;
   return SDRFM_OK;
 }
 
 void sdrfm_iq_meter_destroy(sdrfm_iq_meter_t* h) {
   if (!h) return;
-  (void)hipSetDevice(h->device);
-  (void)hipStreamSynchronize(h->stream);
+  (void)host_stream_wait(h->hs);
   iqm_free(h);
 }
 
@@ -141,39 +115,37 @@ int sdrfm_iq_meter_process_batch(sdrfm_iq_meter_t* h, const uint8_t* iq, size_t 
       h->last_hist = hist != nullptr;
       return SDRFM_OK;
     }
-    STRY(hipSetDevice(h->device), SDRFM_FAIL);
+    STRY(hipSetDevice(h->hs.device), SDRFM_FAIL);
     return iqm_enqueue(h, nullptr, 0, 0, meters, hist);
   }
   if (!iq) return SDRFM_EINVAL;
-  if (ns > 1 && iq_stride < nbytes) return SDRFM_ECAPACITY;
-  STRY(hipSetDevice(h->device), SDRFM_FAIL);
+  if (!pcm_rows_capacity(ns, iq_stride, nbytes)) return SDRFM_ECAPACITY;
+  STRY(hipSetDevice(h->hs.device), SDRFM_FAIL);
   if (dev) return iqm_enqueue(h, iq, iq_stride, nbytes, meters, hist);
   // host buffers: stage, meter, copy back, synchronous
-  int rc = iqm_reserve(h, nbytes);
+  RowStage& st = h->stage;
+  int rc = row_stage_reserve(st, RowShape{IQM_CHUNK, 1, ns, 0, 0, false}, nbytes, 0);
   if (rc != SDRFM_OK) return rc;
   if (hist && !h->d_hist && hipMalloc(&h->d_hist, sizeof(uint32_t) * 512u * (size_t)ns) != hipSuccess) { h->d_hist = nullptr; return SDRFM_ENOMEM; }
-  STRY(hipMemcpy2DAsync(h->d_iq, h->cap, iq, ns > 1 ? iq_stride : nbytes, nbytes, ns, hipMemcpyHostToDevice, h->stream), SDRFM_FAIL);
-  rc = iqm_enqueue(h, h->d_iq, h->cap, nbytes, h->d_meters, hist ? h->d_hist : nullptr);
+  rc = rows_to_device(st, 1, 0, iq, pcm_rows_pitch(ns, iq_stride, nbytes), nbytes, ns, h->hs.cur);
   if (rc != SDRFM_OK) return rc;
-  STRY(hipMemcpyAsync(meters, h->d_meters, sizeof(sdrfm_iq_meter) * (size_t)ns, hipMemcpyDeviceToHost, h->stream), SDRFM_FAIL);
-  if (hist) STRY(hipMemcpyAsync(hist, h->d_hist, sizeof(uint32_t) * 512u * (size_t)ns, hipMemcpyDeviceToHost, h->stream), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(h->stream), SDRFM_FAIL);
+  rc = iqm_enqueue(h, static_cast<const uint8_t*>(st.d_in), st.cap_in, nbytes, h->d_meters, hist ? h->d_hist : nullptr);
+  if (rc != SDRFM_OK) return rc;
+  STRY(hipMemcpyAsync(meters, h->d_meters, sizeof(sdrfm_iq_meter) * (size_t)ns, hipMemcpyDeviceToHost, h->hs.cur), SDRFM_FAIL);
+  if (hist) STRY(hipMemcpyAsync(hist, h->d_hist, sizeof(uint32_t) * 512u * (size_t)ns, hipMemcpyDeviceToHost, h->hs.cur), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(h->hs.cur), SDRFM_FAIL);
   return SDRFM_OK;
 }
 
 int sdrfm_iq_meter_set_stream(sdrfm_iq_meter_t* h, void* hip_stream) {
   if (!h) return SDRFM_EINVAL;
-  h->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->own_stream;
+  h->hs.cur = hip_stream ? static_cast<hipStream_t>(hip_stream) : h->hs.own;   // unlike the other handles: no hipSetDevice and no wait for the stream in use
   return SDRFM_OK;
 }
 
-int sdrfm_iq_meter_synchronize(sdrfm_iq_meter_t* h) {
-  if (!h) return SDRFM_EINVAL;
-  STRY(hipSetDevice(h->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(h->stream), SDRFM_FAIL);
-  return SDRFM_OK;
-}
+int sdrfm_iq_meter_synchronize(sdrfm_iq_meter_t* h) { return h ? host_stream_wait(h->hs) : SDRFM_EINVAL; }
 
+// unlike the other handles: "" for NULL, not NULL
 const char* sdrfm_iq_meter_kernel_name(const sdrfm_iq_meter_t* h) { return !h ? "" : h->last_hist ? "iq-meter-hist" : "iq-meter"; }
 
 }  // extern "C"

@@ -21,16 +21,8 @@
 #include <new>
 
 #include "../../include/sdrfm.h"
+#include "sdrfm_host.h"
 #include "sdrfm_limit.h"
-
-#define STRY(expr, code)                                                                                       \
-  do {                                                                                                         \
-    hipError_t e__ = (expr);                                                                                   \
-    if (e__ != hipSuccess) {                                                                                   \
-      fprintf(stderr, "[sdrfm] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__);  \
-      return (code);                                                                                           \
-    }                                                                                                          \
-  } while (0)
 
 namespace {
 
@@ -50,32 +42,28 @@ struct sdrfm_pcm_limit {
   uint32_t n_streams, lw, slew, J;
   uint32_t P, nt, words;           // the detector's table (0, 0 for the sample form) and the state's words per stream
   unsigned* d_table;               // the packed table, true-peak form only
-  int device;
-  hipStream_t own_stream, stream;
+  HostStream hs;
   sdrfm_pcm_limit_params* d_par;   // [n_streams]
   int32_t* d_state;                // [n_streams][4 D]
   sdrfm_pcm_limit_rec* d_rec;      // [n_streams]
   sdrfm_pcm_limit_params* par;     // host: the parameters as the device holds them
   int32_t* state0;                 // host: the state after reset, and the records' identity
   sdrfm_pcm_limit_rec* rec0;
-  int16_t* d_buf;                  // staging for host-pointer calls: limited in place
-  int16_t* h_buf;
-  uint32_t cap;                    // pairs per stream the staging holds
+  RowStage stage;                  // staging for host-pointer calls: pairs, limited in place
 };
 
 static void limit_free(sdrfm_pcm_limit* k) {
   if (!k) return;
-  (void)hipSetDevice(k->device);
+  (void)hipSetDevice(k->hs.device);
   if (k->d_par) (void)hipFree(k->d_par);
   if (k->d_state) (void)hipFree(k->d_state);
   if (k->d_rec) (void)hipFree(k->d_rec);
   if (k->d_table) (void)hipFree(k->d_table);
-  if (k->d_buf) (void)hipFree(k->d_buf);
-  free(k->h_buf);
+  row_stage_free(k->stage);
   free(k->par);
   free(k->state0);
   free(k->rec0);
-  if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
+  host_stream_close(k->hs);
   delete k;
 }
 
@@ -86,47 +74,30 @@ static int limit_launch(sdrfm_pcm_limit* k, const int16_t* in, size_t in_stride,
   p.par = k->d_par; p.state = k->d_state; p.rec = k->d_rec;
   p.n = n; p.lw = k->lw; p.slew = k->slew; p.J = k->J;
   p.table = k->d_table; p.nt = k->nt; p.P = k->P;
-  if (k->nt) hipLaunchKernelGGL(k_pcm_limit_tp, dim3(k->n_streams), dim3(SDRFM_LIMIT_NT), limit_tp_lds_bytes(), k->stream, p);
-  else hipLaunchKernelGGL(k_pcm_limit, dim3(k->n_streams), dim3(SDRFM_LIMIT_NT), limit_lds_bytes(), k->stream, static_cast<const LimitParams&>(p));
+  if (k->nt) hipLaunchKernelGGL(k_pcm_limit_tp, dim3(k->n_streams), dim3(SDRFM_LIMIT_NT), limit_tp_lds_bytes(), k->hs.cur, p);
+  else hipLaunchKernelGGL(k_pcm_limit, dim3(k->n_streams), dim3(SDRFM_LIMIT_NT), limit_lds_bytes(), k->hs.cur, static_cast<const LimitParams&>(p));
   STRY(hipGetLastError(), SDRFM_FAIL);
   k->J = audio_ctl_advance(k->J, n);
   return SDRFM_OK;
 }
 
-static int limit_reserve(sdrfm_pcm_limit* k, uint32_t n) {
-  if (n <= k->cap) return SDRFM_OK;
-  if (k->d_buf) (void)hipFree(k->d_buf);
-  free(k->h_buf);
-  k->d_buf = nullptr; k->h_buf = nullptr; k->cap = 0;
-  const uint32_t cap = (n + 1023u) & ~1023u;
-  k->h_buf = (int16_t*)malloc(sizeof(int16_t) * 2 * (size_t)cap * k->n_streams);
-  if (!k->h_buf || hipMalloc(&k->d_buf, sizeof(int16_t) * 2 * (size_t)cap * k->n_streams) != hipSuccess) return SDRFM_ENOMEM;
-  k->cap = cap;
-  return SDRFM_OK;
-}
-
 // the parameters to the device, behind whatever launch may still read them
 static int limit_upload(sdrfm_pcm_limit* k) {
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   STRY(hipMemcpy(k->d_par, k->par, sizeof(sdrfm_pcm_limit_params) * (size_t)k->n_streams, hipMemcpyHostToDevice), SDRFM_FAIL);
   return SDRFM_OK;
 }
 
 // the two constructors behind their refusals: coef NULL is the sample form, else a table sdrfm_truepeak_check_coef has taken
 static int limit_create(const sdrfm_pcm_limit_config* cfg, const int16_t* coef, uint32_t n_phases, uint32_t n_taps, sdrfm_pcm_limit_t** out) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return SDRFM_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SDRFM_NO_DEVICE;
-  STRY(hipSetDevice(cfg->device), SDRFM_NO_DEVICE);
+  if (const int rc = host_open_device(cfg->device); rc != SDRFM_OK) return rc;
   sdrfm_pcm_limit* k = new (std::nothrow) sdrfm_pcm_limit();
   if (!k) return SDRFM_ENOMEM;
   memset(static_cast<void*>(k), 0, sizeof(*k));
   const uint32_t ns = cfg->n_streams, words = coef ? limit_tp_state_words(cfg->log2_window, n_taps) : limit_state_words(cfg->log2_window);
   if (coef) { k->P = n_phases; k->nt = n_taps; }
   k->words = words;
-  k->n_streams = ns; k->lw = cfg->log2_window; k->slew = cfg->gain_slew; k->device = cfg->device;
+  k->n_streams = ns; k->lw = cfg->log2_window; k->slew = cfg->gain_slew; k->hs.device = cfg->device;
   k->par = (sdrfm_pcm_limit_params*)malloc(sizeof(sdrfm_pcm_limit_params) * ns);
   k->state0 = (int32_t*)malloc(sizeof(int32_t) * (size_t)words * ns);
   k->rec0 = (sdrfm_pcm_limit_rec*)malloc(sizeof(sdrfm_pcm_limit_rec) * ns);
@@ -138,12 +109,11 @@ static int limit_create(const sdrfm_pcm_limit_config* cfg, const int16_t* coef, 
     else (void)sdrfm_pcm_limit_state_init(k->lw, k->state0 + (size_t)s * words);
     k->rec0[s].n = 0; k->rec0[s].limited = 0; k->rec0[s].min_gain = SDRFM_LIMIT_ONE; k->rec0[s].at = 0;
   }
-  const bool ok = hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking) == hipSuccess &&
+  const bool ok = host_stream_open(k->hs, cfg->device) == SDRFM_OK &&
                   hipMalloc(&k->d_par, sizeof(sdrfm_pcm_limit_params) * ns) == hipSuccess &&
                   hipMalloc(&k->d_state, sizeof(int32_t) * (size_t)words * ns) == hipSuccess &&
                   hipMalloc(&k->d_rec, sizeof(sdrfm_pcm_limit_rec) * ns) == hipSuccess;
   if (!ok) { limit_free(k); return SDRFM_ENOMEM; }
-  k->stream = k->own_stream;
   if (coef) {
     unsigned packed[SDRFM_TP_TABLE_DWORDS];
     tp_pack_table(coef, n_phases, n_taps, packed);
@@ -192,15 +162,13 @@ int sdrfm_pcm_tplimit_get_detector(const sdrfm_pcm_limit_t* k, uint32_t* n_phase
 
 void sdrfm_pcm_limit_destroy(sdrfm_pcm_limit_t* k) {
   if (!k) return;
-  (void)hipSetDevice(k->device);
-  (void)hipStreamSynchronize(k->stream);
+  (void)host_stream_wait(k->hs);
   limit_free(k);
 }
 
 int sdrfm_pcm_limit_reset(sdrfm_pcm_limit_t* k) {
   if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   STRY(hipMemcpy(k->d_state, k->state0, sizeof(int32_t) * (size_t)k->words * k->n_streams, hipMemcpyHostToDevice), SDRFM_FAIL);
   STRY(hipMemcpy(k->d_rec, k->rec0, sizeof(sdrfm_pcm_limit_rec) * (size_t)k->n_streams, hipMemcpyHostToDevice), SDRFM_FAIL);
   return SDRFM_OK;
@@ -241,69 +209,43 @@ int sdrfm_pcm_limit_get_params(const sdrfm_pcm_limit_t* k, sdrfm_pcm_limit_param
 
 int sdrfm_pcm_limit_process_batch(sdrfm_pcm_limit_t* k, const int16_t* in, size_t in_stride, uint32_t n, int16_t* out, size_t out_stride, uint32_t flags) {
   if (!k) return SDRFM_EINVAL;
-  if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;
-  if (n > SDRFM_LIMIT_N_MAX) return SDRFM_EINVAL;
-  if ((in_stride | out_stride) & 1u) return SDRFM_EINVAL;           // rows are read and written as (L, R) dwords
-  if (n == 0) return SDRFM_OK;
-  if (!in || !out) return SDRFM_EINVAL;
-  const bool device_ptrs = (flags & SDRFM_F_DEVICE_PTRS) != 0;
-  if (device_ptrs && ((uintptr_t)in % 4 != 0 || (uintptr_t)out % 4 != 0)) return SDRFM_EINVAL;
-  if (k->n_streams > 1 && (in_stride < 2 * (size_t)n || out_stride < 2 * (size_t)n)) return SDRFM_ECAPACITY;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  if (device_ptrs) return limit_launch(k, in, in_stride, n, out, out_stride);
+  int rc = pcm_rows_refusal(flags, SDRFM_F_DEVICE_PTRS, n, SDRFM_LIMIT_N_MAX, in, in_stride, out, out_stride);
+  if (rc != SDRFM_OK) return rc == PCM_ROWS_EMPTY ? SDRFM_OK : rc;
+  const uint32_t ns = k->n_streams;
+  const size_t need = 2 * (size_t)n;
+  if (!pcm_rows_capacity(ns, in_stride, need) || !pcm_rows_capacity(ns, out_stride, need)) return SDRFM_ECAPACITY;
+  STRY(hipSetDevice(k->hs.device), SDRFM_FAIL);
+  if (flags & SDRFM_F_DEVICE_PTRS) return limit_launch(k, in, in_stride, n, out, out_stride);
   // host buffers: stage, limit in place, copy back, synchronous
-  int rc = limit_reserve(k, n);
+  RowStage& st = k->stage;
+  rc = row_stage_reserve(st, RowShape{1024u, PCM_PAIR_BYTES, ns, 0, 0, true}, n, 0);
   if (rc != SDRFM_OK) return rc;
-  const size_t is = (k->n_streams > 1) ? in_stride : 2 * (size_t)n, os = (k->n_streams > 1) ? out_stride : 2 * (size_t)n;
-  STRY(hipMemcpy2DAsync(k->d_buf, sizeof(int16_t) * 2 * k->cap, in, sizeof(int16_t) * is, sizeof(int16_t) * 2 * n, k->n_streams, hipMemcpyHostToDevice,
-                        k->stream), SDRFM_FAIL);
-  rc = limit_launch(k, k->d_buf, 2 * (size_t)k->cap, n, k->d_buf, 2 * (size_t)k->cap);
+  rc = rows_to_device(st, PCM_PAIR_BYTES, 0, in, sizeof(int16_t) * pcm_rows_pitch(ns, in_stride, need), PCM_PAIR_BYTES * n, ns, k->hs.cur);
   if (rc != SDRFM_OK) return rc;
-  STRY(hipMemcpy2DAsync(k->h_buf, sizeof(int16_t) * 2 * k->cap, k->d_buf, sizeof(int16_t) * 2 * k->cap, sizeof(int16_t) * 2 * n, k->n_streams,
-                        hipMemcpyDeviceToHost, k->stream), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  for (uint32_t s = 0; s < k->n_streams; ++s) memcpy(out + s * os, k->h_buf + (size_t)s * 2 * k->cap, sizeof(int16_t) * 2 * n);   // exactly 2n int16 per row
-  return SDRFM_OK;
+  int16_t* const d_buf = static_cast<int16_t*>(st.d_in);
+  rc = limit_launch(k, d_buf, 2 * (size_t)st.cap_in, n, d_buf, 2 * (size_t)st.cap_in);
+  if (rc != SDRFM_OK) return rc;
+  return rows_to_host(st, PCM_PAIR_BYTES, out, sizeof(int16_t) * pcm_rows_pitch(ns, out_stride, need), n, nullptr, ns, k->hs.cur);
 }
 
 int sdrfm_pcm_limit_read(sdrfm_pcm_limit_t* k, sdrfm_pcm_limit_rec* out, uint32_t flags) {
   if (!k || !out || (flags & ~(SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET)) || (uintptr_t)out % 8 != 0) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  const size_t bytes = sizeof(sdrfm_pcm_limit_rec) * (size_t)k->n_streams;
-  if (flags & SDRFM_F_DEVICE_PTRS) {                            // enqueued on the handle's stream, and nowhere else
-    STRY(hipMemcpyAsync(out, k->d_rec, bytes, hipMemcpyDeviceToDevice, k->stream), SDRFM_FAIL);
-    if (flags & SDRFM_AMETER_F_RESET) STRY(hipMemcpyAsync(k->d_rec, k->rec0, bytes, hipMemcpyHostToDevice, k->stream), SDRFM_FAIL);
-    return SDRFM_OK;
-  }
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  STRY(hipMemcpy(out, k->d_rec, bytes, hipMemcpyDeviceToHost), SDRFM_FAIL);
-  if (flags & SDRFM_AMETER_F_RESET)                             // the records only: the state stays and the stream continues
-    STRY(hipMemcpy(k->d_rec, k->rec0, bytes, hipMemcpyHostToDevice), SDRFM_FAIL);
-  return SDRFM_OK;
+  // a reset takes the records only, back to rec0: the state stays and the stream continues
+  return records_read(k->hs, out, k->d_rec, sizeof(sdrfm_pcm_limit_rec) * (size_t)k->n_streams, k->rec0, flags);
 }
 
 int sdrfm_pcm_limit_get_state(sdrfm_pcm_limit_t* k, int32_t* state) {
   if (!k || !state) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   STRY(hipMemcpy(state, k->d_state, sizeof(int32_t) * (size_t)k->words * k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
   return SDRFM_OK;
 }
 
 int sdrfm_pcm_limit_set_stream(sdrfm_pcm_limit_t* k, void* hip_stream) {
-  if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  k->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : k->own_stream;
-  return SDRFM_OK;
+  return k ? host_stream_use(k->hs, hip_stream) : SDRFM_EINVAL;
 }
 
-int sdrfm_pcm_limit_synchronize(sdrfm_pcm_limit_t* k) {
-  if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  return SDRFM_OK;
-}
+int sdrfm_pcm_limit_synchronize(sdrfm_pcm_limit_t* k) { return k ? host_stream_wait(k->hs) : SDRFM_EINVAL; }
 
 const char* sdrfm_pcm_limit_kernel_name(const sdrfm_pcm_limit_t* k) { return k ? (k->nt ? "pcm-limit-tp" : "pcm-limit") : nullptr; }
 

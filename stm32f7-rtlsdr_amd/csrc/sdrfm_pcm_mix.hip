@@ -18,16 +18,8 @@
 #include <new>
 
 #include "../../include/sdrfm.h"
+#include "sdrfm_host.h"
 #include "sdrfm_pcm_mix.h"
-
-#define STRY(expr, code)                                                                                       \
-  do {                                                                                                         \
-    hipError_t e__ = (expr);                                                                                   \
-    if (e__ != hipSuccess) {                                                                                   \
-      fprintf(stderr, "[sdrfm] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__);  \
-      return (code);                                                                                           \
-    }                                                                                                          \
-  } while (0)
 
 static_assert(sizeof(sdrfm_pcm_mix_slot) == 16 && sizeof(PmixSlot) == 16, "a slot is four uint32");
 static_assert(sizeof(sdrfm_pcm_mix_rec) == 32, "the record is four uint64");
@@ -46,29 +38,23 @@ __global__ void __launch_bounds__(PMIX_NT) k_pcm_mix(PmixParams p) {
 
 struct sdrfm_pcm_mix {
   uint32_t n_in, n_bus, n_slots, slew, J;
-  int device;
-  hipStream_t own_stream, stream;
+  HostStream hs;
   sdrfm_pcm_mix_slot* slots;       // host: [n_bus][n_slots], as the device holds them
   sdrfm_pcm_mix_slot* d_slots;
   uint16_t* d_curve;               // 129 values, or nullptr
   sdrfm_pcm_mix_rec* d_rec;        // [n_bus]
-  int16_t* d_in;                   // staging for host-pointer calls: [n_in][2 cap] and [n_bus][2 cap]
-  int16_t* d_out;
-  int16_t* h_out;
-  uint32_t cap;                    // pairs per row the staging holds
+  RowStage stage;                  // staging for host-pointer calls: pairs, [n_in] rows in and [n_bus] rows out
 };
 
 static void mix_free(sdrfm_pcm_mix* k) {
   if (!k) return;
-  (void)hipSetDevice(k->device);
+  (void)hipSetDevice(k->hs.device);
   if (k->d_slots) (void)hipFree(k->d_slots);
   if (k->d_curve) (void)hipFree(k->d_curve);
   if (k->d_rec) (void)hipFree(k->d_rec);
-  if (k->d_in) (void)hipFree(k->d_in);
-  if (k->d_out) (void)hipFree(k->d_out);
-  free(k->h_out);
+  row_stage_free(k->stage);
   free(k->slots);
-  if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
+  host_stream_close(k->hs);
   delete k;
 }
 
@@ -81,31 +67,15 @@ static int mix_launch(sdrfm_pcm_mix* k, const int16_t* in, size_t in_stride, uin
   p.slots = reinterpret_cast<const PmixSlot*>(k->d_slots); p.curve = k->d_curve;
   p.rec = reinterpret_cast<unsigned long long*>(k->d_rec);
   p.n = n; p.n_slots = k->n_slots; p.slew = k->slew; p.J = k->J;
-  hipLaunchKernelGGL(k_pcm_mix, dim3(k->n_bus, pmix_spans(n)), dim3(PMIX_NT), 0, k->stream, p);
+  hipLaunchKernelGGL(k_pcm_mix, dim3(k->n_bus, pmix_spans(n)), dim3(PMIX_NT), 0, k->hs.cur, p);
   STRY(hipGetLastError(), SDRFM_FAIL);
   k->J = audio_ctl_advance(k->J, n);
   return SDRFM_OK;
 }
 
-static int mix_reserve(sdrfm_pcm_mix* k, uint32_t n) {
-  if (n <= k->cap) return SDRFM_OK;
-  if (k->d_in) (void)hipFree(k->d_in);
-  if (k->d_out) (void)hipFree(k->d_out);
-  free(k->h_out);
-  k->d_in = nullptr; k->d_out = nullptr; k->h_out = nullptr; k->cap = 0;
-  const uint32_t cap = (n + 1023u) & ~1023u;
-  k->h_out = (int16_t*)malloc(sizeof(int16_t) * 2 * (size_t)cap * k->n_bus);
-  if (!k->h_out || hipMalloc(&k->d_in, sizeof(int16_t) * 2 * (size_t)cap * k->n_in) != hipSuccess ||
-      hipMalloc(&k->d_out, sizeof(int16_t) * 2 * (size_t)cap * k->n_bus) != hipSuccess)
-    return SDRFM_ENOMEM;
-  k->cap = cap;
-  return SDRFM_OK;
-}
-
 // the slots to the device, behind whatever launch may still read them
 static int mix_upload(sdrfm_pcm_mix* k) {
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   STRY(hipMemcpy(k->d_slots, k->slots, sizeof(sdrfm_pcm_mix_slot) * mix_slot_count(k), hipMemcpyHostToDevice), SDRFM_FAIL);
   return SDRFM_OK;
 }
@@ -119,28 +89,23 @@ int sdrfm_pcm_mix_create(const sdrfm_pcm_mix_config* cfg, const uint16_t* curve,
       cfg->n_slots > PMIX_SLOTS_MAX || cfg->slew < 1u || cfg->slew > PMIX_ONE)
     return SDRFM_EINVAL;
   if (curve && !pmix_curve_ok(curve)) return SDRFM_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return SDRFM_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SDRFM_NO_DEVICE;
-  STRY(hipSetDevice(cfg->device), SDRFM_NO_DEVICE);
+  if (const int rc = host_open_device(cfg->device); rc != SDRFM_OK) return rc;
   sdrfm_pcm_mix* k = new (std::nothrow) sdrfm_pcm_mix();
   if (!k) return SDRFM_ENOMEM;
   memset(static_cast<void*>(k), 0, sizeof(*k));
-  k->n_in = cfg->n_in; k->n_bus = cfg->n_bus; k->n_slots = cfg->n_slots; k->slew = cfg->slew; k->device = cfg->device;
+  k->n_in = cfg->n_in; k->n_bus = cfg->n_bus; k->n_slots = cfg->n_slots; k->slew = cfg->slew; k->hs.device = cfg->device;
   const size_t ns = mix_slot_count(k);
   k->slots = (sdrfm_pcm_mix_slot*)malloc(sizeof(sdrfm_pcm_mix_slot) * ns);
   if (!k->slots) { mix_free(k); return SDRFM_ENOMEM; }
   for (size_t s = 0; s < ns; ++s) { k->slots[s].src = SDRFM_PCM_MIX_NONE; k->slots[s].mode = SDRFM_PCM_MIX_STEREO; k->slots[s].g0 = k->slots[s].gt = 0; }
-  const bool ok = hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking) == hipSuccess &&
+  const bool ok = host_stream_open(k->hs, cfg->device) == SDRFM_OK &&
                   hipMalloc(&k->d_slots, sizeof(sdrfm_pcm_mix_slot) * ns) == hipSuccess &&
                   hipMalloc(&k->d_rec, sizeof(sdrfm_pcm_mix_rec) * k->n_bus) == hipSuccess &&
                   (!curve || hipMalloc(&k->d_curve, sizeof(uint16_t) * PMIX_CURVE_LEN) == hipSuccess);
   if (!ok) { mix_free(k); return SDRFM_ENOMEM; }
-  k->stream = k->own_stream;
   if (hipMemcpy(k->d_slots, k->slots, sizeof(sdrfm_pcm_mix_slot) * ns, hipMemcpyHostToDevice) != hipSuccess ||
       (curve && hipMemcpy(k->d_curve, curve, sizeof(uint16_t) * PMIX_CURVE_LEN, hipMemcpyHostToDevice) != hipSuccess) ||
-      hipMemsetAsync(k->d_rec, 0, sizeof(sdrfm_pcm_mix_rec) * k->n_bus, k->stream) != hipSuccess || hipStreamSynchronize(k->stream) != hipSuccess) {
+      hipMemsetAsync(k->d_rec, 0, sizeof(sdrfm_pcm_mix_rec) * k->n_bus, k->hs.cur) != hipSuccess || hipStreamSynchronize(k->hs.cur) != hipSuccess) {
     mix_free(k);
     return SDRFM_FAIL;
   }
@@ -150,17 +115,15 @@ int sdrfm_pcm_mix_create(const sdrfm_pcm_mix_config* cfg, const uint16_t* curve,
 
 void sdrfm_pcm_mix_destroy(sdrfm_pcm_mix_t* k) {
   if (!k) return;
-  (void)hipSetDevice(k->device);
-  (void)hipStreamSynchronize(k->stream);
+  (void)host_stream_wait(k->hs);
   mix_free(k);
 }
 
 int sdrfm_pcm_mix_reset(sdrfm_pcm_mix_t* k) {
   if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  STRY(hipMemsetAsync(k->d_rec, 0, sizeof(sdrfm_pcm_mix_rec) * (size_t)k->n_bus, k->stream), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
+  STRY(hipMemsetAsync(k->d_rec, 0, sizeof(sdrfm_pcm_mix_rec) * (size_t)k->n_bus, k->hs.cur), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->hs.cur), SDRFM_FAIL);
   return SDRFM_OK;
 }
 
@@ -201,67 +164,35 @@ int sdrfm_pcm_mix_get_slots(const sdrfm_pcm_mix_t* k, sdrfm_pcm_mix_slot* out, u
 
 int sdrfm_pcm_mix_process_batch(sdrfm_pcm_mix_t* k, const int16_t* in, size_t in_stride, uint32_t n, int16_t* out, size_t out_stride, uint32_t flags) {
   if (!k) return SDRFM_EINVAL;
-  if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;
-  if (n > PMIX_N_MAX) return SDRFM_EINVAL;
-  if ((in_stride | out_stride) & 1u) return SDRFM_EINVAL;           // rows are read and written as (L, R) dwords
-  if (n == 0) return SDRFM_OK;
-  if (!in || !out) return SDRFM_EINVAL;
-  const bool device_ptrs = (flags & SDRFM_F_DEVICE_PTRS) != 0;
-  if (device_ptrs && ((uintptr_t)in % 4 != 0 || (uintptr_t)out % 4 != 0)) return SDRFM_EINVAL;
-  if ((k->n_in > 1 && in_stride < 2 * (size_t)n) || (k->n_bus > 1 && out_stride < 2 * (size_t)n)) return SDRFM_ECAPACITY;
-  // bus b writes while bus c reads: the rows' byte ranges must be apart
-  const size_t is = k->n_in > 1 ? in_stride : 2 * (size_t)n, os = k->n_bus > 1 ? out_stride : 2 * (size_t)n;
-  const uintptr_t in0 = (uintptr_t)in, in1 = in0 + sizeof(int16_t) * ((k->n_in - 1u) * is + 2 * (size_t)n);
-  const uintptr_t out0 = (uintptr_t)out, out1 = out0 + sizeof(int16_t) * ((k->n_bus - 1u) * os + 2 * (size_t)n);
-  if (in0 < out1 && out0 < in1) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  if (device_ptrs) return mix_launch(k, in, in_stride, n, out, out_stride);
+  int rc = pcm_rows_refusal(flags, SDRFM_F_DEVICE_PTRS, n, PMIX_N_MAX, in, in_stride, out, out_stride);
+  if (rc != SDRFM_OK) return rc == PCM_ROWS_EMPTY ? SDRFM_OK : rc;
+  const size_t need = 2 * (size_t)n;
+  if (!pcm_rows_capacity(k->n_in, in_stride, need) || !pcm_rows_capacity(k->n_bus, out_stride, need)) return SDRFM_ECAPACITY;
+  const size_t is = pcm_rows_pitch(k->n_in, in_stride, need), os = pcm_rows_pitch(k->n_bus, out_stride, need);
+  if (!pcm_rows_apart(in, k->n_in, is, out, k->n_bus, os, n)) return SDRFM_EINVAL;   // bus b writes while bus c reads
+  STRY(hipSetDevice(k->hs.device), SDRFM_FAIL);
+  if (flags & SDRFM_F_DEVICE_PTRS) return mix_launch(k, in, in_stride, n, out, out_stride);
   // host buffers: stage, mix, copy back, synchronous
-  int rc = mix_reserve(k, n);
+  RowStage& st = k->stage;
+  rc = row_stage_reserve(st, RowShape{1024u, PCM_PAIR_BYTES, k->n_in, PCM_PAIR_BYTES, k->n_bus, true}, n, n);
   if (rc != SDRFM_OK) return rc;
-  STRY(hipMemcpy2DAsync(k->d_in, sizeof(int16_t) * 2 * k->cap, in, sizeof(int16_t) * is, sizeof(int16_t) * 2 * n, k->n_in, hipMemcpyHostToDevice,
-                        k->stream), SDRFM_FAIL);
-  rc = mix_launch(k, k->d_in, 2 * (size_t)k->cap, n, k->d_out, 2 * (size_t)k->cap);
+  rc = rows_to_device(st, PCM_PAIR_BYTES, 0, in, sizeof(int16_t) * is, PCM_PAIR_BYTES * n, k->n_in, k->hs.cur);
   if (rc != SDRFM_OK) return rc;
-  STRY(hipMemcpy2DAsync(k->h_out, sizeof(int16_t) * 2 * k->cap, k->d_out, sizeof(int16_t) * 2 * k->cap, sizeof(int16_t) * 2 * n, k->n_bus,
-                        hipMemcpyDeviceToHost, k->stream), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  for (uint32_t b = 0; b < k->n_bus; ++b) memcpy(out + b * os, k->h_out + (size_t)b * 2 * k->cap, sizeof(int16_t) * 2 * n);   // exactly 2n int16 per row
-  return SDRFM_OK;
+  rc = mix_launch(k, static_cast<int16_t*>(st.d_in), 2 * (size_t)st.cap_in, n, static_cast<int16_t*>(st.d_out), 2 * (size_t)st.cap_out);
+  if (rc != SDRFM_OK) return rc;
+  return rows_to_host(st, PCM_PAIR_BYTES, out, sizeof(int16_t) * os, n, nullptr, k->n_bus, k->hs.cur);
 }
 
 int sdrfm_pcm_mix_read(sdrfm_pcm_mix_t* k, sdrfm_pcm_mix_rec* out, uint32_t flags) {
   if (!k || !out || (flags & ~(SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET)) || (uintptr_t)out % 8 != 0) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  const size_t bytes = sizeof(sdrfm_pcm_mix_rec) * (size_t)k->n_bus;
-  if (flags & SDRFM_F_DEVICE_PTRS) {                              // enqueued on the handle's stream, and nowhere else
-    STRY(hipMemcpyAsync(out, k->d_rec, bytes, hipMemcpyDeviceToDevice, k->stream), SDRFM_FAIL);
-    if (flags & SDRFM_AMETER_F_RESET) STRY(hipMemsetAsync(k->d_rec, 0, bytes, k->stream), SDRFM_FAIL);
-    return SDRFM_OK;
-  }
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  STRY(hipMemcpy(out, k->d_rec, bytes, hipMemcpyDeviceToHost), SDRFM_FAIL);
-  if (flags & SDRFM_AMETER_F_RESET) {
-    STRY(hipMemsetAsync(k->d_rec, 0, bytes, k->stream), SDRFM_FAIL);
-    STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  }
-  return SDRFM_OK;
+  return records_read(k->hs, out, k->d_rec, sizeof(sdrfm_pcm_mix_rec) * (size_t)k->n_bus, nullptr, flags);
 }
 
 int sdrfm_pcm_mix_set_stream(sdrfm_pcm_mix_t* k, void* hip_stream) {
-  if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  k->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : k->own_stream;
-  return SDRFM_OK;
+  return k ? host_stream_use(k->hs, hip_stream) : SDRFM_EINVAL;
 }
 
-int sdrfm_pcm_mix_synchronize(sdrfm_pcm_mix_t* k) {
-  if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  return SDRFM_OK;
-}
+int sdrfm_pcm_mix_synchronize(sdrfm_pcm_mix_t* k) { return k ? host_stream_wait(k->hs) : SDRFM_EINVAL; }
 
 const char* sdrfm_pcm_mix_kernel_name(const sdrfm_pcm_mix_t* k) { return k ? "pcm-mix" : nullptr; }
 

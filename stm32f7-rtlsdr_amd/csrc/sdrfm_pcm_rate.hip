@@ -22,16 +22,8 @@
 #include <new>
 
 #include "../../include/sdrfm.h"
+#include "sdrfm_host.h"
 #include "sdrfm_pcm_rate.h"
-
-#define STRY(expr, code)                                                                                       \
-  do {                                                                                                         \
-    hipError_t e__ = (expr);                                                                                   \
-    if (e__ != hipSuccess) {                                                                                   \
-      fprintf(stderr, "[sdrfm] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__);  \
-      return (code);                                                                                           \
-    }                                                                                                          \
-  } while (0)
 
 namespace {
 
@@ -44,8 +36,7 @@ __global__ void __launch_bounds__(SDRFM_RATE_NT) k_pcm_rate(RateParams p) {
 
 struct sdrfm_pcm_rate {
   uint32_t n_streams, nt, logph;
-  int device;
-  hipStream_t own_stream, stream;
+  HostStream hs;
   unsigned* d_table;    // [(NPH + 1)][nt / 2 + 1]
   uint64_t* d_step;     // [n_streams]
   uint64_t* d_pos;      // [2][n_streams]
@@ -54,26 +45,21 @@ struct sdrfm_pcm_rate {
   uint64_t* step;       // host: the steps, and the mirror of the device's pos
   uint64_t* pos;
   uint32_t* cnt;        // scratch: the counts of the call being made
-  int16_t* d_in;        // staging for host-pointer calls
-  int16_t* d_out;
-  int16_t* h_out;
-  uint32_t cap_in, cap_out;   // pairs per stream the staging holds
+  RowStage stage;       // staging for host-pointer calls: pairs, the two sides grown apart (n in, the largest count out)
 };
 
 static void rate_free(sdrfm_pcm_rate* k) {
   if (!k) return;
-  (void)hipSetDevice(k->device);
+  (void)hipSetDevice(k->hs.device);
   if (k->d_table) (void)hipFree(k->d_table);
   if (k->d_step) (void)hipFree(k->d_step);
   if (k->d_pos) (void)hipFree(k->d_pos);
   if (k->d_hist) (void)hipFree(k->d_hist);
-  if (k->d_in) (void)hipFree(k->d_in);
-  if (k->d_out) (void)hipFree(k->d_out);
-  free(k->h_out);
+  row_stage_free(k->stage);
   free(k->step);
   free(k->pos);
   free(k->cnt);
-  if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
+  host_stream_close(k->hs);
   delete k;
 }
 
@@ -104,30 +90,10 @@ static int rate_launch(sdrfm_pcm_rate* k, const int16_t* in, size_t in_stride, u
   p.span = rate_span_len(max_step, k->nt, k->logph);
   p.plane_dw = rate_plane_dwords(p.span, max_step, k->nt);
   const uint32_t spans = max_cnt ? (max_cnt + p.span - 1u) / p.span : 1u;   // span 0 carries the state even when nothing comes out
-  hipLaunchKernelGGL(k_pcm_rate, dim3(spans, k->n_streams), dim3(SDRFM_RATE_NT), rate_lds_bytes(p.span, max_step, k->nt, k->logph), k->stream, p);
+  hipLaunchKernelGGL(k_pcm_rate, dim3(spans, k->n_streams), dim3(SDRFM_RATE_NT), rate_lds_bytes(p.span, max_step, k->nt, k->logph), k->hs.cur, p);
   STRY(hipGetLastError(), SDRFM_FAIL);
   for (uint32_t s = 0; s < k->n_streams; ++s) k->pos[s] = rate_advance(k->pos[s], k->step[s], n, k->cnt[s]);
   k->cur ^= 1u;
-  return SDRFM_OK;
-}
-
-static int rate_reserve(sdrfm_pcm_rate* k, uint32_t n, uint32_t max_cnt) {
-  if (n > k->cap_in) {
-    if (k->d_in) (void)hipFree(k->d_in);
-    k->d_in = nullptr; k->cap_in = 0;
-    const uint32_t cap = (n + 1023u) & ~1023u;
-    if (hipMalloc(&k->d_in, sizeof(int16_t) * 2 * (size_t)cap * k->n_streams) != hipSuccess) return SDRFM_ENOMEM;
-    k->cap_in = cap;
-  }
-  if (max_cnt > k->cap_out) {
-    if (k->d_out) (void)hipFree(k->d_out);
-    free(k->h_out);
-    k->d_out = nullptr; k->h_out = nullptr; k->cap_out = 0;
-    const uint32_t cap = (max_cnt + 1023u) & ~1023u;
-    k->h_out = (int16_t*)malloc(sizeof(int16_t) * 2 * (size_t)cap * k->n_streams);
-    if (!k->h_out || hipMalloc(&k->d_out, sizeof(int16_t) * 2 * (size_t)cap * k->n_streams) != hipSuccess) return SDRFM_ENOMEM;
-    k->cap_out = cap;
-  }
   return SDRFM_OK;
 }
 
@@ -138,16 +104,12 @@ int sdrfm_pcm_rate_create(const sdrfm_pcm_rate_config* cfg, sdrfm_pcm_rate_t** o
   *out = nullptr;
   if (!cfg || !cfg->n_streams || cfg->flags || !cfg->coef) return SDRFM_EINVAL;
   if (sdrfm_pcm_rate_check_coef(cfg->coef, cfg->n_taps, cfg->log2_phases) != SDRFM_OK) return SDRFM_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return SDRFM_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SDRFM_NO_DEVICE;
-  STRY(hipSetDevice(cfg->device), SDRFM_NO_DEVICE);
+  if (const int rc = host_open_device(cfg->device); rc != SDRFM_OK) return rc;
   sdrfm_pcm_rate* k = new (std::nothrow) sdrfm_pcm_rate();
   if (!k) return SDRFM_ENOMEM;
   memset(static_cast<void*>(k), 0, sizeof(*k));
   const uint32_t ns = cfg->n_streams, nt = cfg->n_taps;
-  k->n_streams = ns; k->nt = nt; k->logph = cfg->log2_phases; k->device = cfg->device;
+  k->n_streams = ns; k->nt = nt; k->logph = cfg->log2_phases; k->hs.device = cfg->device;
   k->step = (uint64_t*)malloc(sizeof(uint64_t) * ns);
   k->pos = (uint64_t*)malloc(sizeof(uint64_t) * ns);
   k->cnt = (uint32_t*)malloc(sizeof(uint32_t) * ns);
@@ -158,12 +120,11 @@ int sdrfm_pcm_rate_create(const sdrfm_pcm_rate_config* cfg, sdrfm_pcm_rate_t** o
     for (uint32_t m = 0; m < nt / 2u; ++m)
       tab[(size_t)p * rowdw + m] = (uint16_t)cfg->coef[(size_t)p * nt + 2 * m] | ((unsigned)(uint16_t)cfg->coef[(size_t)p * nt + 2 * m + 1] << 16);
   for (uint32_t s = 0; s < ns; ++s) { k->step[s] = (uint64_t)1 << 32; k->pos[s] = 0; }
-  const bool ok = hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking) == hipSuccess &&
+  const bool ok = host_stream_open(k->hs, cfg->device) == SDRFM_OK &&
                   hipMalloc(&k->d_table, sizeof(unsigned) * tabdw) == hipSuccess && hipMalloc(&k->d_step, sizeof(uint64_t) * ns) == hipSuccess &&
                   hipMalloc(&k->d_pos, sizeof(uint64_t) * 2 * ns) == hipSuccess &&
                   hipMalloc(&k->d_hist, sizeof(unsigned) * 2 * (size_t)ns * (nt - 1u)) == hipSuccess;
   if (!ok) { free(tab); rate_free(k); return SDRFM_ENOMEM; }
-  k->stream = k->own_stream;
   const bool up = hipMemcpy(k->d_table, tab, sizeof(unsigned) * tabdw, hipMemcpyHostToDevice) == hipSuccess &&
                   hipMemcpy(k->d_step, k->step, sizeof(uint64_t) * ns, hipMemcpyHostToDevice) == hipSuccess;
   free(tab);
@@ -176,17 +137,16 @@ int sdrfm_pcm_rate_create(const sdrfm_pcm_rate_config* cfg, sdrfm_pcm_rate_t** o
 
 void sdrfm_pcm_rate_destroy(sdrfm_pcm_rate_t* k) {
   if (!k) return;
-  (void)hipSetDevice(k->device);
-  (void)hipStreamSynchronize(k->stream);
+  (void)host_stream_wait(k->hs);
   rate_free(k);
 }
 
 int sdrfm_pcm_rate_reset(sdrfm_pcm_rate_t* k) {
   if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipMemsetAsync(k->d_pos, 0, sizeof(uint64_t) * 2 * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
-  STRY(hipMemsetAsync(k->d_hist, 0, sizeof(unsigned) * 2 * (size_t)k->n_streams * (k->nt - 1u), k->stream), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipSetDevice(k->hs.device), SDRFM_FAIL);                   // unlike the limiter and the mix bus: no wait for the stream before the state is cleared
+  STRY(hipMemsetAsync(k->d_pos, 0, sizeof(uint64_t) * 2 * (size_t)k->n_streams, k->hs.cur), SDRFM_FAIL);
+  STRY(hipMemsetAsync(k->d_hist, 0, sizeof(unsigned) * 2 * (size_t)k->n_streams * (k->nt - 1u), k->hs.cur), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->hs.cur), SDRFM_FAIL);
   for (uint32_t s = 0; s < k->n_streams; ++s) k->pos[s] = 0;
   k->cur = 0;
   return SDRFM_OK;
@@ -197,8 +157,7 @@ int sdrfm_pcm_rate_set_step(sdrfm_pcm_rate_t* k, const uint64_t* step) {
   if (!k || !step) return SDRFM_EINVAL;
   for (uint32_t s = 0; s < k->n_streams; ++s)
     if (step[s] < SDRFM_RATE_STEP_MIN || step[s] > SDRFM_RATE_STEP_MAX) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   STRY(hipMemcpy(k->d_step, step, sizeof(uint64_t) * (size_t)k->n_streams, hipMemcpyHostToDevice), SDRFM_FAIL);
   memcpy(k->step, step, sizeof(uint64_t) * (size_t)k->n_streams);
   return SDRFM_OK;
@@ -214,48 +173,39 @@ int sdrfm_pcm_rate_count(const sdrfm_pcm_rate_t* k, uint32_t n, uint32_t* n_out,
 int sdrfm_pcm_rate_process_batch(sdrfm_pcm_rate_t* k, const int16_t* in, size_t in_stride, uint32_t n, int16_t* out, size_t out_stride,
                                  uint32_t* n_out, uint32_t flags) {
   if (!k) return SDRFM_EINVAL;
-  if (flags & ~SDRFM_F_DEVICE_PTRS) return SDRFM_EINVAL;
-  if (n > SDRFM_RATE_N_MAX) return SDRFM_EINVAL;
-  if ((in_stride | out_stride) & 1u) return SDRFM_EINVAL;           // rows are read and written as (L, R) dwords
-  if (n == 0) {
-    for (uint32_t s = 0; n_out && s < k->n_streams; ++s) n_out[s] = 0;
+  const uint32_t ns = k->n_streams;
+  int rc = pcm_rows_refusal(flags, SDRFM_F_DEVICE_PTRS, n, SDRFM_RATE_N_MAX, in, in_stride, out, out_stride);
+  if (rc == PCM_ROWS_EMPTY) {
+    for (uint32_t s = 0; n_out && s < ns; ++s) n_out[s] = 0;
     return SDRFM_OK;
   }
-  if (!in || !out) return SDRFM_EINVAL;
-  const bool device_ptrs = (flags & SDRFM_F_DEVICE_PTRS) != 0;
-  if (device_ptrs && ((uintptr_t)in % 4 != 0 || (uintptr_t)out % 4 != 0)) return SDRFM_EINVAL;
+  if (rc != SDRFM_OK) return rc;
   uint64_t max_step = 0;
   const uint32_t max_cnt = rate_counts(k, n, k->cnt, &max_step);
-  if (k->n_streams > 1 && (in_stride < 2 * (size_t)n || out_stride < 2 * (size_t)max_cnt)) return SDRFM_ECAPACITY;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  if (device_ptrs) {
-    const int rc = rate_launch(k, in, in_stride, n, out, out_stride, max_cnt, max_step);
-    for (uint32_t s = 0; rc == SDRFM_OK && n_out && s < k->n_streams; ++s) n_out[s] = k->cnt[s];
+  const size_t need_in = 2 * (size_t)n, need_out = 2 * (size_t)max_cnt;
+  if (!pcm_rows_capacity(ns, in_stride, need_in) || !pcm_rows_capacity(ns, out_stride, need_out)) return SDRFM_ECAPACITY;
+  STRY(hipSetDevice(k->hs.device), SDRFM_FAIL);
+  if (flags & SDRFM_F_DEVICE_PTRS) {
+    rc = rate_launch(k, in, in_stride, n, out, out_stride, max_cnt, max_step);
+    for (uint32_t s = 0; rc == SDRFM_OK && n_out && s < ns; ++s) n_out[s] = k->cnt[s];
     return rc;
   }
-  // host buffers: stage, run, copy back, synchronous
-  int rc = rate_reserve(k, n, max_cnt);
+  // host buffers: stage, run, copy back exactly 2 cnt[s] int16 per row, synchronous
+  RowStage& st = k->stage;
+  rc = row_stage_reserve(st, RowShape{1024u, PCM_PAIR_BYTES, ns, PCM_PAIR_BYTES, ns, true}, n, max_cnt);
   if (rc != SDRFM_OK) return rc;
-  const size_t is = (k->n_streams > 1) ? in_stride : 2 * (size_t)n, os = (k->n_streams > 1) ? out_stride : 2 * (size_t)max_cnt;
-  STRY(hipMemcpy2DAsync(k->d_in, sizeof(int16_t) * 2 * k->cap_in, in, sizeof(int16_t) * is, sizeof(int16_t) * 2 * n, k->n_streams, hipMemcpyHostToDevice,
-                        k->stream), SDRFM_FAIL);
-  rc = rate_launch(k, k->d_in, 2 * (size_t)k->cap_in, n, k->d_out, 2 * (size_t)k->cap_out, max_cnt, max_step);
+  rc = rows_to_device(st, PCM_PAIR_BYTES, 0, in, sizeof(int16_t) * pcm_rows_pitch(ns, in_stride, need_in), PCM_PAIR_BYTES * n, ns, k->hs.cur);
   if (rc != SDRFM_OK) return rc;
-  if (max_cnt)
-    STRY(hipMemcpy2DAsync(k->h_out, sizeof(int16_t) * 2 * k->cap_out, k->d_out, sizeof(int16_t) * 2 * k->cap_out, sizeof(int16_t) * 2 * max_cnt, k->n_streams,
-                          hipMemcpyDeviceToHost, k->stream), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  for (uint32_t s = 0; s < k->n_streams; ++s) {                   // exactly 2 cnt[s] int16 per row
-    if (k->cnt[s]) memcpy(out + s * os, k->h_out + (size_t)s * 2 * k->cap_out, sizeof(int16_t) * 2 * k->cnt[s]);
-    if (n_out) n_out[s] = k->cnt[s];
-  }
-  return SDRFM_OK;
+  rc = rate_launch(k, static_cast<int16_t*>(st.d_in), 2 * (size_t)st.cap_in, n, static_cast<int16_t*>(st.d_out), 2 * (size_t)st.cap_out, max_cnt, max_step);
+  if (rc != SDRFM_OK) return rc;
+  rc = rows_to_host(st, PCM_PAIR_BYTES, out, sizeof(int16_t) * pcm_rows_pitch(ns, out_stride, need_out), max_cnt, k->cnt, ns, k->hs.cur);
+  for (uint32_t s = 0; rc == SDRFM_OK && n_out && s < ns; ++s) n_out[s] = k->cnt[s];
+  return rc;
 }
 
 int sdrfm_pcm_rate_get_state(sdrfm_pcm_rate_t* k, uint64_t* step, uint64_t* pos) {
   if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   uint64_t* dev = (uint64_t*)malloc(sizeof(uint64_t) * (size_t)k->n_streams);
   if (!dev) return SDRFM_ENOMEM;
   if (hipMemcpy(dev, k->d_pos + (size_t)k->cur * k->n_streams, sizeof(uint64_t) * (size_t)k->n_streams, hipMemcpyDeviceToHost) != hipSuccess) {
@@ -270,19 +220,10 @@ int sdrfm_pcm_rate_get_state(sdrfm_pcm_rate_t* k, uint64_t* step, uint64_t* pos)
 }
 
 int sdrfm_pcm_rate_set_stream(sdrfm_pcm_rate_t* k, void* hip_stream) {
-  if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  k->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : k->own_stream;
-  return SDRFM_OK;
+  return k ? host_stream_use(k->hs, hip_stream) : SDRFM_EINVAL;
 }
 
-int sdrfm_pcm_rate_synchronize(sdrfm_pcm_rate_t* k) {
-  if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  return SDRFM_OK;
-}
+int sdrfm_pcm_rate_synchronize(sdrfm_pcm_rate_t* k) { return k ? host_stream_wait(k->hs) : SDRFM_EINVAL; }
 
 const char* sdrfm_pcm_rate_kernel_name(const sdrfm_pcm_rate_t* k) { return k ? "pcm-rate" : nullptr; }
 

@@ -114,24 +114,20 @@ __global__ void __launch_bounds__(256) k_pcm_sink_scan(SinkParams p, float pc, c
 struct sdrfm_pcm_sink {
   uint32_t n_streams;
   float alpha, gain;
-  int device;
-  hipStream_t own_stream, stream;
+  HostStream hs;
   unsigned long long* d_sg;   // [SDRFM_CHAIN_SG_SLOTS][n_streams] {tag << 32 | bits of y[n-1]}, tag t in slot t % 8 (sdrfm_sink_chain.h)
   float* d_dpow;       // [SDRFM_CHAIN_FIX] (1 - alpha)^(k + 1)
   uint32_t calls;      // calls issued so far (mod 2^32): the tag d_sg holds when every one of them is through
-  float* d_audio;      // staging for host-pointer calls
-  int16_t* d_pcm;
-  uint32_t cap;        // samples per stream the staging holds
+  RowStage stage;      // staging for host-pointer calls: floats in, (L, R) pairs out, straight into the caller's rows
 };
 
 static void sink_free(sdrfm_pcm_sink* k) {
   if (!k) return;
-  (void)hipSetDevice(k->device);
+  (void)hipSetDevice(k->hs.device);
   if (k->d_sg) (void)hipFree(k->d_sg);
   if (k->d_dpow) (void)hipFree(k->d_dpow);
-  if (k->d_audio) (void)hipFree(k->d_audio);
-  if (k->d_pcm) (void)hipFree(k->d_pcm);
-  if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
+  row_stage_free(k->stage);
+  host_stream_close(k->hs);
   delete k;
 }
 
@@ -146,7 +142,7 @@ extern "C" int sdrfm_sink_chain_tables(float alpha, float* pc, float* w, float* 
 }
 
 int sdrfm_sink_chain_params(sdrfm_pcm_sink* k, int device, uint32_t n_streams, SdrfmSinkChain* out) {
-  if (!k || !out || k->device != device || k->n_streams != n_streams) return 0;
+  if (!k || !out || k->hs.device != device || k->n_streams != n_streams) return 0;
   out->pcm = nullptr; out->pcm_stride = 0; out->runstate = nullptr; out->run_call = 0;
   out->sg = k->d_sg; out->n_streams = n_streams; out->dpow = k->d_dpow; out->err = reinterpret_cast<uint32_t*>(k->d_dpow + SDRFM_CHAIN_FIX);
   out->call = k->calls;
@@ -192,35 +188,18 @@ int sdrfm_sink_launch_list_on(sdrfm_pcm_sink* k, const SdrfmSinkChain& c, const 
   return SDRFM_OK;
 }
 
-// staging rows for a host-pointer call of n samples per stream
-static int sink_reserve(sdrfm_pcm_sink* k, uint32_t n) {
-  if (n <= k->cap) return SDRFM_OK;
-  if (k->d_audio) (void)hipFree(k->d_audio);
-  if (k->d_pcm) (void)hipFree(k->d_pcm);
-  k->d_audio = nullptr; k->d_pcm = nullptr; k->cap = 0;
-  const uint32_t cap = (n + 1023u) & ~1023u;
-  if (hipMalloc(&k->d_audio, sizeof(float) * (size_t)cap * k->n_streams) != hipSuccess ||
-      hipMalloc(&k->d_pcm, sizeof(int16_t) * 2 * (size_t)cap * k->n_streams) != hipSuccess) return SDRFM_ENOMEM;
-  k->cap = cap;
-  return SDRFM_OK;
-}
-
 extern "C" {
 
 int sdrfm_pcm_sink_create(uint32_t n_streams, float alpha, float gain, int32_t device, sdrfm_pcm_sink_t** out) {
   if (!out) return SDRFM_EINVAL;
   *out = nullptr;
   if (!n_streams || !(alpha > 0.0f) || alpha > 1.0f || !(gain == gain)) return SDRFM_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return SDRFM_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SDRFM_NO_DEVICE;
-  STRY(hipSetDevice(device), SDRFM_NO_DEVICE);
+  if (const int rc = host_open_device(device); rc != SDRFM_OK) return rc;
   sdrfm_pcm_sink* k = new (std::nothrow) sdrfm_pcm_sink();
   if (!k) return SDRFM_ENOMEM;
   memset(static_cast<void*>(k), 0, sizeof(*k));
-  k->n_streams = n_streams; k->alpha = alpha; k->gain = gain; k->device = device;
-  if (hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking) != hipSuccess ||
+  k->n_streams = n_streams; k->alpha = alpha; k->gain = gain; k->hs.device = device;
+  if (host_stream_open(k->hs, device) != SDRFM_OK ||
       hipMalloc(&k->d_sg, sizeof(unsigned long long) * SDRFM_CHAIN_SG_SLOTS * n_streams) != hipSuccess ||
       hipMalloc(&k->d_dpow, sizeof(float) * (SDRFM_CHAIN_FIX + 1)) != hipSuccess) { sink_free(k); return SDRFM_ENOMEM; }   // (+ the error word)
   {
@@ -229,7 +208,6 @@ int sdrfm_pcm_sink_create(uint32_t n_streams, float alpha, float gain, int32_t d
     dp[SDRFM_CHAIN_FIX] = 0.0f;
     if (hipMemcpy(k->d_dpow, dp, sizeof(dp), hipMemcpyHostToDevice) != hipSuccess) { sink_free(k); return SDRFM_FAIL; }
   }
-  k->stream = k->own_stream;
   const int rc = sdrfm_pcm_sink_reset(k);
   if (rc != SDRFM_OK) { sink_free(k); return rc; }
   *out = k;
@@ -238,27 +216,22 @@ int sdrfm_pcm_sink_create(uint32_t n_streams, float alpha, float gain, int32_t d
 
 void sdrfm_pcm_sink_destroy(sdrfm_pcm_sink_t* k) {
   if (!k) return;
-  (void)hipSetDevice(k->device);
-  (void)hipStreamSynchronize(k->stream);
+  (void)host_stream_wait(k->hs);
   sink_free(k);
 }
 
 int sdrfm_pcm_sink_reset(sdrfm_pcm_sink_t* k) {
   if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipMemsetAsync(k->d_sg, 0, sizeof(unsigned long long) * SDRFM_CHAIN_SG_SLOTS * k->n_streams, k->stream), SDRFM_FAIL);
-  STRY(hipMemsetAsync(k->d_dpow + SDRFM_CHAIN_FIX, 0, sizeof(uint32_t), k->stream), SDRFM_FAIL);   // (the chain's error word)
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipSetDevice(k->hs.device), SDRFM_FAIL);                   // unlike the limiter and the mix bus: no wait for the stream before the state is cleared
+  STRY(hipMemsetAsync(k->d_sg, 0, sizeof(unsigned long long) * SDRFM_CHAIN_SG_SLOTS * k->n_streams, k->hs.cur), SDRFM_FAIL);
+  STRY(hipMemsetAsync(k->d_dpow + SDRFM_CHAIN_FIX, 0, sizeof(uint32_t), k->hs.cur), SDRFM_FAIL);   // (the chain's error word)
+  STRY(hipStreamSynchronize(k->hs.cur), SDRFM_FAIL);
   k->calls = 0;
   return SDRFM_OK;
 }
 
 int sdrfm_pcm_sink_set_stream(sdrfm_pcm_sink_t* k, void* hip_stream) {
-  if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  k->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : k->own_stream;
-  return SDRFM_OK;
+  return k ? host_stream_use(k->hs, hip_stream) : SDRFM_EINVAL;
 }
 
 // a run of a demodulator launch gave up waiting for its predecessor's word (sdrfm_sink_chain.h): the PCM since then is not to be trusted
@@ -271,8 +244,7 @@ static int sink_chain_error(sdrfm_pcm_sink* k) {
 
 int sdrfm_pcm_sink_synchronize(sdrfm_pcm_sink_t* k) {
   if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   return sink_chain_error(k);
 }
 
@@ -282,33 +254,31 @@ int sdrfm_pcm_sink_process_batch(sdrfm_pcm_sink_t* k, const float* audio, size_t
   if (flags & ~(SDRFM_F_DEVICE_PTRS | SDRFM_PCM_F_EXACT)) return SDRFM_EINVAL;
   if (n == 0) return SDRFM_OK;
   if (!audio || !pcm) return SDRFM_EINVAL;
-  if (k->n_streams > 1 && (audio_stride < n || pcm_stride < 2 * (size_t)n)) return SDRFM_ECAPACITY;
+  const uint32_t ns = k->n_streams;
+  // unlike the three newer handles: the capacity before the odd stride
+  if (!pcm_rows_capacity(ns, audio_stride, n) || !pcm_rows_capacity(ns, pcm_stride, 2 * (size_t)n)) return SDRFM_ECAPACITY;
   if (pcm_stride & 1u) return SDRFM_EINVAL;                          // rows are written as (L,R) dwords
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipSetDevice(k->hs.device), SDRFM_FAIL);
   const bool exact = (flags & SDRFM_PCM_F_EXACT) != 0;
   if (flags & SDRFM_F_DEVICE_PTRS) {
     if ((uintptr_t)pcm % 4 != 0) return SDRFM_EINVAL;
-    return sink_launch(k, audio, audio_stride, n, pcm, pcm_stride, k->stream, exact);
+    return sink_launch(k, audio, audio_stride, n, pcm, pcm_stride, k->hs.cur, exact);
   }
   // host buffers: stage, run, copy back, synchronous
-  int rc = sink_reserve(k, n);
+  RowStage& st = k->stage;
+  int rc = row_stage_reserve(st, RowShape{1024u, sizeof(float), ns, PCM_PAIR_BYTES, ns, false}, n, n);
   if (rc != SDRFM_OK) return rc;
-  const size_t as = (k->n_streams > 1) ? audio_stride : n, ps = (k->n_streams > 1) ? pcm_stride : 2 * (size_t)n;
-  STRY(hipMemcpy2DAsync(k->d_audio, sizeof(float) * k->cap, audio, sizeof(float) * as, sizeof(float) * n, k->n_streams,
-                        hipMemcpyHostToDevice, k->stream), SDRFM_FAIL);
-  rc = sink_launch(k, k->d_audio, k->cap, n, k->d_pcm, 2 * (size_t)k->cap, k->stream, exact);
+  rc = rows_to_device(st, sizeof(float), 0, audio, sizeof(float) * pcm_rows_pitch(ns, audio_stride, n), sizeof(float) * n, ns, k->hs.cur);
   if (rc != SDRFM_OK) return rc;
-  STRY(hipMemcpy2DAsync(pcm, sizeof(int16_t) * ps, k->d_pcm, sizeof(int16_t) * 2 * k->cap, sizeof(int16_t) * 2 * n, k->n_streams,
-                        hipMemcpyDeviceToHost, k->stream), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  return SDRFM_OK;
+  rc = sink_launch(k, static_cast<float*>(st.d_in), st.cap_in, n, static_cast<int16_t*>(st.d_out), 2 * (size_t)st.cap_out, k->hs.cur, exact);
+  if (rc != SDRFM_OK) return rc;
+  return rows_to_host(st, PCM_PAIR_BYTES, pcm, sizeof(int16_t) * pcm_rows_pitch(ns, pcm_stride, 2 * (size_t)n), n, nullptr, ns, k->hs.cur);
 }
 
 /* Host copy of the carried de-emphasis state y[n-1] of every stream (tests, and switching between this sink and the host one). */
 int sdrfm_pcm_sink_get_state(sdrfm_pcm_sink_t* k, float* state_out) {
   if (!k || !state_out) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   unsigned long long* tmp = new (std::nothrow) unsigned long long[k->n_streams];
   if (!tmp) return SDRFM_ENOMEM;
   const hipError_t e = hipMemcpy(tmp, k->d_sg + (size_t)(k->calls % SDRFM_CHAIN_SG_SLOTS) * k->n_streams, sizeof(unsigned long long) * k->n_streams, hipMemcpyDeviceToHost);

@@ -20,16 +20,8 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdio>
 
-#define STRY(expr, code)                                                                                       \
-  do {                                                                                                         \
-    hipError_t e__ = (expr);                                                                                   \
-    if (e__ != hipSuccess) {                                                                                   \
-      fprintf(stderr, "[sdrfm] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__);  \
-      return (code);                                                                                           \
-    }                                                                                                          \
-  } while (0)
+#include "sdrfm_host.h"
 
 namespace {
 

@@ -146,13 +146,9 @@ __global__ void __launch_bounds__(SDRFM_TP_NT) k_pcm_truepeak(TruePeakParams p) 
 struct sdrfm_pcm_stereo_sink {
   uint32_t n_streams;
   float alpha, gain;
-  int device;
-  hipStream_t own_stream, stream;
+  HostStream hs;
   float* d_state;      // [n_streams][2]
-  float* d_left;       // staging for host-pointer calls
-  float* d_right;
-  int16_t* d_pcm;
-  uint32_t cap;        // samples per stream the staging holds
+  RowStage stage;      // staging for host-pointer calls: floats in, the streams' left rows then their right rows; (L, R) pairs out
   // the high-cut (sdrfm_pcm_stereo_sink_set_hicut): the streams' ramps on the host and, from the first set on, on the device; the sink's slew and the
   // samples taken since the last set (saturated).  hicut: the sink is conditioned and launches the conditioned kernels
   HicutRec* hc_host;   // [n_streams]
@@ -186,11 +182,9 @@ static const HicutRec HICUT_FLAT = {(uint16_t)SDRFM_ACTL_ONE, (uint16_t)SDRFM_AC
 
 static void stereo_sink_free(sdrfm_pcm_stereo_sink* k) {
   if (!k) return;
-  (void)hipSetDevice(k->device);
+  (void)hipSetDevice(k->hs.device);
   if (k->d_state) (void)hipFree(k->d_state);
-  if (k->d_left) (void)hipFree(k->d_left);
-  if (k->d_right) (void)hipFree(k->d_right);
-  if (k->d_pcm) (void)hipFree(k->d_pcm);
+  row_stage_free(k->stage);
   if (k->d_hc) (void)hipFree(k->d_hc);
   if (k->d_meter) (void)hipFree(k->d_meter);
   if (k->d_lstate) (void)hipFree(k->d_lstate);
@@ -200,7 +194,7 @@ static void stereo_sink_free(sdrfm_pcm_stereo_sink* k) {
   if (k->d_tphist) (void)hipFree(k->d_tphist);
   if (k->d_tptab) (void)hipFree(k->d_tptab);
   free(k->hc_host);
-  if (k->own_stream) (void)hipStreamDestroy(k->own_stream);
+  host_stream_close(k->hs);
   delete k;
 }
 
@@ -215,7 +209,7 @@ static StereoSinkParams stereo_sink_params(const sdrfm_pcm_stereo_sink* k, const
 // the checks every call makes of its PCM rows against n > 0 outputs
 static int stereo_sink_pcm_ok(uint32_t n_streams, uint32_t n, const int16_t* pcm, size_t pcm_stride, bool device_ptrs) {
   if (!pcm) return SDRFM_EINVAL;
-  if (n_streams > 1 && pcm_stride < 2 * (size_t)n) return SDRFM_ECAPACITY;
+  if (!pcm_rows_capacity(n_streams, pcm_stride, 2 * (size_t)n)) return SDRFM_ECAPACITY;   // unlike the three newer handles: before the odd stride
   if (pcm_stride & 1u) return SDRFM_EINVAL;                        // rows are written as (L, R) dwords
   if (device_ptrs && (uintptr_t)pcm % 4 != 0) return SDRFM_EINVAL;
   return SDRFM_OK;
@@ -224,25 +218,16 @@ static int stereo_sink_pcm_ok(uint32_t n_streams, uint32_t n, const int16_t* pcm
 // ---- the sink behind a stereo or a broadcast launch (sdrfm_sink_stereo.h) ----------------------------------------------------------------------------
 int sdrfm_stereo_sink_check(const sdrfm_pcm_stereo_sink* k, int device, uint32_t n_streams, uint32_t n, const int16_t* pcm, size_t pcm_stride,
                             bool device_ptrs) {
-  if (!k || k->device != device || k->n_streams != n_streams) return SDRFM_EINVAL;
+  if (!k || k->hs.device != device || k->n_streams != n_streams) return SDRFM_EINVAL;
   return n ? stereo_sink_pcm_ok(n_streams, n, pcm, pcm_stride, device_ptrs) : SDRFM_OK;
 }
 
 int sdrfm_stereo_sink_reserve(sdrfm_pcm_stereo_sink* k, uint32_t n, int16_t** d_pcm, size_t* d_pcm_stride) {
   if (!k) return SDRFM_EINVAL;
-  if (n > k->cap) {
-    if (k->d_left) (void)hipFree(k->d_left);
-    if (k->d_right) (void)hipFree(k->d_right);
-    if (k->d_pcm) (void)hipFree(k->d_pcm);
-    k->d_left = nullptr; k->d_right = nullptr; k->d_pcm = nullptr; k->cap = 0;
-    const uint32_t cap = (n + 1023u) & ~1023u;
-    if (hipMalloc(&k->d_left, sizeof(float) * (size_t)cap * k->n_streams) != hipSuccess ||
-        hipMalloc(&k->d_right, sizeof(float) * (size_t)cap * k->n_streams) != hipSuccess ||
-        hipMalloc(&k->d_pcm, sizeof(int16_t) * 2 * (size_t)cap * k->n_streams) != hipSuccess) return SDRFM_ENOMEM;
-    k->cap = cap;
-  }
-  if (d_pcm) *d_pcm = k->d_pcm;
-  if (d_pcm_stride) *d_pcm_stride = 2 * (size_t)k->cap;
+  const int rc = row_stage_reserve(k->stage, RowShape{1024u, sizeof(float), 2 * (size_t)k->n_streams, PCM_PAIR_BYTES, k->n_streams, false}, n, n);
+  if (rc != SDRFM_OK) return rc;
+  if (d_pcm) *d_pcm = static_cast<int16_t*>(k->stage.d_out);
+  if (d_pcm_stride) *d_pcm_stride = 2 * (size_t)k->stage.cap_out;
   return SDRFM_OK;
 }
 
@@ -291,9 +276,9 @@ int sdrfm_stereo_sink_launch_on(sdrfm_pcm_stereo_sink* k, const float* left, con
 int sdrfm_stereo_sink_copy_back(const sdrfm_pcm_stereo_sink* k, int16_t* pcm, size_t pcm_stride, uint32_t n, hipStream_t stream) {
   if (!k) return SDRFM_EINVAL;
   if (n == 0) return SDRFM_OK;
-  const size_t ps = (k->n_streams > 1) ? pcm_stride : 2 * (size_t)n;
-  STRY(hipMemcpy2DAsync(pcm, sizeof(int16_t) * ps, k->d_pcm, sizeof(int16_t) * 2 * k->cap, sizeof(int16_t) * 2 * n, k->n_streams, hipMemcpyDeviceToHost,
-                        stream), SDRFM_FAIL);
+  const size_t ps = pcm_rows_pitch(k->n_streams, pcm_stride, 2 * (size_t)n);
+  STRY(hipMemcpy2DAsync(pcm, sizeof(int16_t) * ps, k->stage.d_out, PCM_PAIR_BYTES * k->stage.cap_out, PCM_PAIR_BYTES * n, k->n_streams,
+                        hipMemcpyDeviceToHost, stream), SDRFM_FAIL);
   return SDRFM_OK;
 }
 
@@ -303,22 +288,17 @@ int sdrfm_pcm_stereo_sink_create(uint32_t n_streams, float alpha, float gain, in
   if (!out) return SDRFM_EINVAL;
   *out = nullptr;
   if (!n_streams || !(alpha > 0.0f) || alpha > 1.0f || !(gain == gain)) return SDRFM_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return SDRFM_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SDRFM_NO_DEVICE;
-  STRY(hipSetDevice(device), SDRFM_NO_DEVICE);
+  if (const int rc = host_open_device(device); rc != SDRFM_OK) return rc;
   sdrfm_pcm_stereo_sink* k = new (std::nothrow) sdrfm_pcm_stereo_sink();
   if (!k) return SDRFM_ENOMEM;
   memset(static_cast<void*>(k), 0, sizeof(*k));
-  k->n_streams = n_streams; k->alpha = alpha; k->gain = gain; k->device = device;
+  k->n_streams = n_streams; k->alpha = alpha; k->gain = gain; k->hs.device = device;
   k->slew = SDRFM_ACTL_ONE; k->J = SDRFM_ACTL_J_MAX;
   k->hc_host = (HicutRec*)malloc(sizeof(HicutRec) * (size_t)n_streams);
   if (!k->hc_host) { stereo_sink_free(k); return SDRFM_ENOMEM; }
   for (size_t s = 0; s < n_streams; ++s) k->hc_host[s] = HICUT_FLAT;
-  if (hipStreamCreateWithFlags(&k->own_stream, hipStreamNonBlocking) != hipSuccess ||
+  if (host_stream_open(k->hs, device) != SDRFM_OK ||
       hipMalloc(&k->d_state, sizeof(float) * 2 * (size_t)n_streams) != hipSuccess) { stereo_sink_free(k); return SDRFM_ENOMEM; }
-  k->stream = k->own_stream;
   const int rc = sdrfm_pcm_stereo_sink_reset(k);
   if (rc != SDRFM_OK) { stereo_sink_free(k); return rc; }
   *out = k;
@@ -327,44 +307,34 @@ int sdrfm_pcm_stereo_sink_create(uint32_t n_streams, float alpha, float gain, in
 
 void sdrfm_pcm_stereo_sink_destroy(sdrfm_pcm_stereo_sink_t* k) {
   if (!k) return;
-  (void)hipSetDevice(k->device);
-  (void)hipStreamSynchronize(k->stream);
+  (void)host_stream_wait(k->hs);
   stereo_sink_free(k);
 }
 
 int sdrfm_pcm_stereo_sink_reset(sdrfm_pcm_stereo_sink_t* k) {
   if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipMemsetAsync(k->d_state, 0, sizeof(float) * 2 * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
-  if (k->meter) STRY(hipMemsetAsync(k->d_meter, 0, sizeof(sdrfm_audio_meter) * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
+  STRY(hipSetDevice(k->hs.device), SDRFM_FAIL);                      // unlike the limiter and the mix bus: no wait for the stream before the state is cleared
+  STRY(hipMemsetAsync(k->d_state, 0, sizeof(float) * 2 * (size_t)k->n_streams, k->hs.cur), SDRFM_FAIL);
+  if (k->meter) STRY(hipMemsetAsync(k->d_meter, 0, sizeof(sdrfm_audio_meter) * (size_t)k->n_streams, k->hs.cur), SDRFM_FAIL);
   if (k->loud) {
-    STRY(hipMemsetAsync(k->d_lstate, 0, sizeof(sdrfm_loudness_state) * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
-    STRY(hipMemsetAsync(k->d_lring, 0, sizeof(sdrfm_loudness_block) * (size_t)k->n_streams * k->lcap, k->stream), SDRFM_FAIL);
+    STRY(hipMemsetAsync(k->d_lstate, 0, sizeof(sdrfm_loudness_state) * (size_t)k->n_streams, k->hs.cur), SDRFM_FAIL);
+    STRY(hipMemsetAsync(k->d_lring, 0, sizeof(sdrfm_loudness_block) * (size_t)k->n_streams * k->lcap, k->hs.cur), SDRFM_FAIL);
     k->lpos = k->lread = 0;
   }
   if (k->tpeak) {
-    STRY(hipMemsetAsync(k->d_tprec, 0, sizeof(sdrfm_truepeak) * (size_t)k->n_streams, k->stream), SDRFM_FAIL);
-    STRY(hipMemsetAsync(k->d_tphist, 0, sizeof(unsigned) * (size_t)k->n_streams * (k->tp_nt - 1u), k->stream), SDRFM_FAIL);
+    STRY(hipMemsetAsync(k->d_tprec, 0, sizeof(sdrfm_truepeak) * (size_t)k->n_streams, k->hs.cur), SDRFM_FAIL);
+    STRY(hipMemsetAsync(k->d_tphist, 0, sizeof(unsigned) * (size_t)k->n_streams * (k->tp_nt - 1u), k->hs.cur), SDRFM_FAIL);
   }
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->hs.cur), SDRFM_FAIL);
   k->J = SDRFM_ACTL_J_MAX;                                      // the high-cut's settings stay, its ramps are complete
   return SDRFM_OK;
 }
 
 int sdrfm_pcm_stereo_sink_set_stream(sdrfm_pcm_stereo_sink_t* k, void* hip_stream) {
-  if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  k->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : k->own_stream;
-  return SDRFM_OK;
+  return k ? host_stream_use(k->hs, hip_stream) : SDRFM_EINVAL;
 }
 
-int sdrfm_pcm_stereo_sink_synchronize(sdrfm_pcm_stereo_sink_t* k) {
-  if (!k) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  return SDRFM_OK;
-}
+int sdrfm_pcm_stereo_sink_synchronize(sdrfm_pcm_stereo_sink_t* k) { return k ? host_stream_wait(k->hs) : SDRFM_EINVAL; }
 
 int sdrfm_pcm_stereo_sink_process_batch(sdrfm_pcm_stereo_sink_t* k, const float* left, const float* right, size_t audio_stride, uint32_t n,
                                         int16_t* pcm, size_t pcm_stride, uint32_t flags) {
@@ -373,34 +343,35 @@ int sdrfm_pcm_stereo_sink_process_batch(sdrfm_pcm_stereo_sink_t* k, const float*
   if (n == 0) return SDRFM_OK;
   if (!left || !right) return SDRFM_EINVAL;
   if (!pcm) return SDRFM_EINVAL;
-  if (k->n_streams > 1 && audio_stride < n) return SDRFM_ECAPACITY;
+  if (!pcm_rows_capacity(k->n_streams, audio_stride, n)) return SDRFM_ECAPACITY;
   const bool device_ptrs = (flags & SDRFM_F_DEVICE_PTRS) != 0;
   const int ok = stereo_sink_pcm_ok(k->n_streams, n, pcm, pcm_stride, device_ptrs);
   if (ok != SDRFM_OK) return ok;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
+  STRY(hipSetDevice(k->hs.device), SDRFM_FAIL);
   const bool exact = (flags & SDRFM_PCM_F_EXACT) != 0;
-  if (device_ptrs) return stereo_sink_launch(k, left, right, audio_stride, n, pcm, pcm_stride, k->stream, exact);
+  if (device_ptrs) return stereo_sink_launch(k, left, right, audio_stride, n, pcm, pcm_stride, k->hs.cur, exact);
   // host buffers: stage, run, copy back, synchronous
   int rc = sdrfm_stereo_sink_reserve(k, n, nullptr, nullptr);
   if (rc != SDRFM_OK) return rc;
-  const size_t as = (k->n_streams > 1) ? audio_stride : n;
-  STRY(hipMemcpy2DAsync(k->d_left, sizeof(float) * k->cap, left, sizeof(float) * as, sizeof(float) * n, k->n_streams, hipMemcpyHostToDevice, k->stream),
-       SDRFM_FAIL);
-  STRY(hipMemcpy2DAsync(k->d_right, sizeof(float) * k->cap, right, sizeof(float) * as, sizeof(float) * n, k->n_streams, hipMemcpyHostToDevice, k->stream),
-       SDRFM_FAIL);
-  rc = stereo_sink_launch(k, k->d_left, k->d_right, k->cap, n, k->d_pcm, 2 * (size_t)k->cap, k->stream, exact);
+  const RowStage& st = k->stage;
+  const size_t ns = k->n_streams, as = sizeof(float) * pcm_rows_pitch(ns, audio_stride, n);
+  rc = rows_to_device(st, sizeof(float), 0, left, as, sizeof(float) * n, ns, k->hs.cur);
   if (rc != SDRFM_OK) return rc;
-  const int cb = sdrfm_stereo_sink_copy_back(k, pcm, pcm_stride, n, k->stream);
+  rc = rows_to_device(st, sizeof(float), ns, right, as, sizeof(float) * n, ns, k->hs.cur);
+  if (rc != SDRFM_OK) return rc;
+  float* const d_left = static_cast<float*>(st.d_in);
+  rc = stereo_sink_launch(k, d_left, d_left + ns * st.cap_in, st.cap_in, n, static_cast<int16_t*>(st.d_out), 2 * (size_t)st.cap_out, k->hs.cur, exact);
+  if (rc != SDRFM_OK) return rc;
+  const int cb = sdrfm_stereo_sink_copy_back(k, pcm, pcm_stride, n, k->hs.cur);
   if (cb != SDRFM_OK) return cb;
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->hs.cur), SDRFM_FAIL);
   return SDRFM_OK;
 }
 
 /* Host copy of the carried de-emphasis states of every stream: state_out[2s] = L, state_out[2s + 1] = R. */
 int sdrfm_pcm_stereo_sink_get_state(sdrfm_pcm_stereo_sink_t* k, float* state_out) {
   if (!k || !state_out) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   STRY(hipMemcpy(state_out, k->d_state, sizeof(float) * 2 * (size_t)k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
   return SDRFM_OK;
 }
@@ -415,9 +386,9 @@ int sdrfm_pcm_stereo_sink_set_hicut(sdrfm_pcm_stereo_sink_t* k, const uint16_t* 
   for (uint32_t s = 0; hicut_q15 && s < ns; ++s)
     if (hicut_q15[s] < SDRFM_HICUT_MIN || hicut_q15[s] > SDRFM_ACTL_ONE) return SDRFM_EINVAL;
   if (slew_q15 && k->alpha * 0.03125f < 0.001f) return SDRFM_EINVAL;   // the smallest effective coefficient, alpha SDRFM_HICUT_MIN / 32768, stays >= 0.001
-  if (hipSetDevice(k->device) != hipSuccess) return SDRFM_FAIL;
+  if (hipSetDevice(k->hs.device) != hipSuccess) return SDRFM_FAIL;
   if (!slew_q15) {                                               // back to the plain kernels: h = 1, nothing to ramp
-    if (hipStreamSynchronize(k->stream) != hipSuccess) return SDRFM_FAIL;
+    if (hipStreamSynchronize(k->hs.cur) != hipSuccess) return SDRFM_FAIL;
     for (uint32_t s = 0; s < ns; ++s) k->hc_host[s] = HICUT_FLAT;
     k->hicut = false;
     k->slew = SDRFM_ACTL_ONE;
@@ -425,7 +396,7 @@ int sdrfm_pcm_stereo_sink_set_hicut(sdrfm_pcm_stereo_sink_t* k, const uint16_t* 
     return SDRFM_OK;
   }
   if (!k->d_hc && hipMalloc(&k->d_hc, sizeof(HicutRec) * ns) != hipSuccess) return SDRFM_ENOMEM;
-  if (hipStreamSynchronize(k->stream) != hipSuccess) return SDRFM_FAIL;   // no launch still reads the records about to be replaced
+  if (hipStreamSynchronize(k->hs.cur) != hipSuccess) return SDRFM_FAIL;   // no launch still reads the records about to be replaced
   for (uint32_t s = 0; s < ns; ++s) {
     HicutRec& r = k->hc_host[s];
     r.h0 = (uint16_t)audio_ctl_ramp(r.h0, r.ht, k->slew, k->J);
@@ -454,12 +425,12 @@ int sdrfm_pcm_stereo_sink_get_hicut(const sdrfm_pcm_stereo_sink_t* k, uint16_t* 
 // what a launch may still use
 int sdrfm_pcm_stereo_sink_meter_enable(sdrfm_pcm_stereo_sink_t* k, uint32_t quiet_lsb) {
   if (!k || quiet_lsb > SDRFM_AM_QUIET_MAX) return SDRFM_EINVAL;
-  if (hipSetDevice(k->device) != hipSuccess) return SDRFM_FAIL;
+  if (hipSetDevice(k->hs.device) != hipSuccess) return SDRFM_FAIL;
   const size_t bytes = sizeof(sdrfm_audio_meter) * (size_t)k->n_streams;
   if (!k->d_meter && hipMalloc(&k->d_meter, bytes) != hipSuccess) { k->d_meter = nullptr; return SDRFM_ENOMEM; }
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  STRY(hipMemsetAsync(k->d_meter, 0, bytes, k->stream), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->hs.cur), SDRFM_FAIL);
+  STRY(hipMemsetAsync(k->d_meter, 0, bytes, k->hs.cur), SDRFM_FAIL);
+  STRY(hipStreamSynchronize(k->hs.cur), SDRFM_FAIL);
   k->quiet_lsb = quiet_lsb;
   k->meter = true;
   return SDRFM_OK;
@@ -468,28 +439,14 @@ int sdrfm_pcm_stereo_sink_meter_enable(sdrfm_pcm_stereo_sink_t* k, uint32_t quie
 int sdrfm_pcm_stereo_sink_meter_disable(sdrfm_pcm_stereo_sink_t* k) {
   if (!k) return SDRFM_EINVAL;
   if (!k->meter) return SDRFM_OK;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   k->meter = false;
   return SDRFM_OK;
 }
 
 int sdrfm_pcm_stereo_sink_meter_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_audio_meter* out, uint32_t flags) {
   if (!k || !out || (flags & ~(SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET)) || (uintptr_t)out % 8 != 0 || !k->meter) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  const size_t bytes = sizeof(sdrfm_audio_meter) * (size_t)k->n_streams;
-  if (flags & SDRFM_F_DEVICE_PTRS) {                            // enqueued on the sink's stream, and nowhere else
-    STRY(hipMemcpyAsync(out, k->d_meter, bytes, hipMemcpyDeviceToDevice, k->stream), SDRFM_FAIL);
-    if (flags & SDRFM_AMETER_F_RESET) STRY(hipMemsetAsync(k->d_meter, 0, bytes, k->stream), SDRFM_FAIL);
-    return SDRFM_OK;
-  }
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  STRY(hipMemcpy(out, k->d_meter, bytes, hipMemcpyDeviceToHost), SDRFM_FAIL);
-  if (flags & SDRFM_AMETER_F_RESET) {
-    STRY(hipMemsetAsync(k->d_meter, 0, bytes, k->stream), SDRFM_FAIL);
-    STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  }
-  return SDRFM_OK;
+  return records_read(k->hs, out, k->d_meter, sizeof(sdrfm_audio_meter) * (size_t)k->n_streams, nullptr, flags);
 }
 
 // the loudness meter.  Every check comes before any device work; enable and disable wait for the sink's stream before they
@@ -515,16 +472,16 @@ int sdrfm_pcm_stereo_sink_loudness_enable(sdrfm_pcm_stereo_sink_t* k, const sdrf
   if (coef && sdrfm_loudness_check_domain(&c, nullptr, nullptr) != SDRFM_OK) return SDRFM_EINVAL;
   double pw[SDRFM_LD_TABLE];
   ld_matrix_powers(c.c, pw);                                    // on the host, here: the scan's A^(L 2^i) in its balanced coordinates
-  if (hipSetDevice(k->device) != hipSuccess) return SDRFM_FAIL;
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (hipSetDevice(k->hs.device) != hipSuccess) return SDRFM_FAIL;
+  STRY(hipStreamSynchronize(k->hs.cur), SDRFM_FAIL);
   loudness_release(k);                                          // an enabled sink starts over
   const size_t sb = sizeof(sdrfm_loudness_state) * (size_t)k->n_streams, rb = sizeof(sdrfm_loudness_block) * (size_t)k->n_streams * cap_blocks;
   if (hipMalloc(&k->d_lstate, sb) != hipSuccess || hipMalloc(&k->d_lring, rb) != hipSuccess || hipMalloc(&k->d_lpw, sizeof(pw)) != hipSuccess) {
     loudness_release(k);
     return SDRFM_ENOMEM;
   }
-  if (hipMemsetAsync(k->d_lstate, 0, sb, k->stream) != hipSuccess || hipMemsetAsync(k->d_lring, 0, rb, k->stream) != hipSuccess ||
-      hipMemcpyAsync(k->d_lpw, pw, sizeof(pw), hipMemcpyHostToDevice, k->stream) != hipSuccess || hipStreamSynchronize(k->stream) != hipSuccess) {
+  if (hipMemsetAsync(k->d_lstate, 0, sb, k->hs.cur) != hipSuccess || hipMemsetAsync(k->d_lring, 0, rb, k->hs.cur) != hipSuccess ||
+      hipMemcpyAsync(k->d_lpw, pw, sizeof(pw), hipMemcpyHostToDevice, k->hs.cur) != hipSuccess || hipStreamSynchronize(k->hs.cur) != hipSuccess) {
     loudness_release(k);
     return SDRFM_FAIL;
   }
@@ -536,8 +493,7 @@ int sdrfm_pcm_stereo_sink_loudness_enable(sdrfm_pcm_stereo_sink_t* k, const sdrf
 int sdrfm_pcm_stereo_sink_loudness_disable(sdrfm_pcm_stereo_sink_t* k) {
   if (!k) return SDRFM_EINVAL;
   if (!k->loud) return SDRFM_OK;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   loudness_release(k);
   return SDRFM_OK;
 }
@@ -550,8 +506,7 @@ int sdrfm_pcm_stereo_sink_loudness_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_loudne
   const uint32_t nb = (uint32_t)(done - first);                 // <= lcap
   if (nb > out_cap_blocks) return SDRFM_ECAPACITY;
   if (nb && !out) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   if (nb) {                                                     // the ring wraps at most once inside [first, done)
     const uint32_t s0 = ld_ring_slot(first, k->lcap);
     const uint32_t a = nb < k->lcap - s0 ? nb : k->lcap - s0, b = nb - a;
@@ -567,8 +522,7 @@ int sdrfm_pcm_stereo_sink_loudness_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_loudne
 
 int sdrfm_pcm_stereo_sink_loudness_get_state(sdrfm_pcm_stereo_sink_t* k, sdrfm_loudness_state* out) {
   if (!k || !out || !k->loud) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   STRY(hipMemcpy(out, k->d_lstate, sizeof(sdrfm_loudness_state) * (size_t)k->n_streams, hipMemcpyDeviceToHost), SDRFM_FAIL);
   return SDRFM_OK;
 }
@@ -593,8 +547,8 @@ int sdrfm_pcm_stereo_sink_truepeak_enable(sdrfm_pcm_stereo_sink_t* k, const int1
   if (sdrfm_truepeak_check_coef(coef, n_phases, n_taps) != SDRFM_OK) return SDRFM_EINVAL;
   uint32_t tab[SDRFM_TP_TABLE_DWORDS];
   tp_pack_table(coef, n_phases, n_taps, tab);
-  if (hipSetDevice(k->device) != hipSuccess) return SDRFM_FAIL;
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (hipSetDevice(k->hs.device) != hipSuccess) return SDRFM_FAIL;
+  STRY(hipStreamSynchronize(k->hs.cur), SDRFM_FAIL);
   truepeak_release(k);                                          // an enabled sink starts over
   const size_t rb = sizeof(sdrfm_truepeak) * (size_t)k->n_streams, hb = sizeof(unsigned) * (size_t)k->n_streams * (n_taps - 1u);
   const size_t tb = sizeof(uint32_t) * n_phases * (n_taps / 2u);
@@ -602,8 +556,8 @@ int sdrfm_pcm_stereo_sink_truepeak_enable(sdrfm_pcm_stereo_sink_t* k, const int1
     truepeak_release(k);
     return SDRFM_ENOMEM;
   }
-  if (hipMemsetAsync(k->d_tprec, 0, rb, k->stream) != hipSuccess || hipMemsetAsync(k->d_tphist, 0, hb, k->stream) != hipSuccess ||
-      hipMemcpyAsync(k->d_tptab, tab, tb, hipMemcpyHostToDevice, k->stream) != hipSuccess || hipStreamSynchronize(k->stream) != hipSuccess) {
+  if (hipMemsetAsync(k->d_tprec, 0, rb, k->hs.cur) != hipSuccess || hipMemsetAsync(k->d_tphist, 0, hb, k->hs.cur) != hipSuccess ||
+      hipMemcpyAsync(k->d_tptab, tab, tb, hipMemcpyHostToDevice, k->hs.cur) != hipSuccess || hipStreamSynchronize(k->hs.cur) != hipSuccess) {
     truepeak_release(k);
     return SDRFM_FAIL;
   }
@@ -615,28 +569,15 @@ int sdrfm_pcm_stereo_sink_truepeak_enable(sdrfm_pcm_stereo_sink_t* k, const int1
 int sdrfm_pcm_stereo_sink_truepeak_disable(sdrfm_pcm_stereo_sink_t* k) {
   if (!k) return SDRFM_EINVAL;
   if (!k->tpeak) return SDRFM_OK;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
+  if (const int rc = host_stream_wait(k->hs); rc != SDRFM_OK) return rc;
   truepeak_release(k);
   return SDRFM_OK;
 }
 
 int sdrfm_pcm_stereo_sink_truepeak_read(sdrfm_pcm_stereo_sink_t* k, sdrfm_truepeak* out, uint32_t flags) {
   if (!k || !out || (flags & ~(SDRFM_F_DEVICE_PTRS | SDRFM_AMETER_F_RESET)) || (uintptr_t)out % 8 != 0 || !k->tpeak) return SDRFM_EINVAL;
-  STRY(hipSetDevice(k->device), SDRFM_FAIL);
-  const size_t bytes = sizeof(sdrfm_truepeak) * (size_t)k->n_streams;
-  if (flags & SDRFM_F_DEVICE_PTRS) {                            // enqueued on the sink's stream, and nowhere else
-    STRY(hipMemcpyAsync(out, k->d_tprec, bytes, hipMemcpyDeviceToDevice, k->stream), SDRFM_FAIL);
-    if (flags & SDRFM_AMETER_F_RESET) STRY(hipMemsetAsync(k->d_tprec, 0, bytes, k->stream), SDRFM_FAIL);
-    return SDRFM_OK;
-  }
-  STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  STRY(hipMemcpy(out, k->d_tprec, bytes, hipMemcpyDeviceToHost), SDRFM_FAIL);
-  if (flags & SDRFM_AMETER_F_RESET) {                           // the records only: the history stays and the stream continues
-    STRY(hipMemsetAsync(k->d_tprec, 0, bytes, k->stream), SDRFM_FAIL);
-    STRY(hipStreamSynchronize(k->stream), SDRFM_FAIL);
-  }
-  return SDRFM_OK;
+  // a reset takes the records only: the history stays and the stream continues
+  return records_read(k->hs, out, k->d_tprec, sizeof(sdrfm_truepeak) * (size_t)k->n_streams, nullptr, flags);
 }
 
 }  // extern "C"

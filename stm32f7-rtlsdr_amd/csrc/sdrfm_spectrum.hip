@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "../../include/sdrfm.h"
+#include "sdrfm_host.h"
 
 typedef float sf2_t __attribute__((ext_vector_type(2)));
 typedef int si4_t __attribute__((ext_vector_type(4)));
@@ -635,15 +636,6 @@ struct sdrfm_spectrum {
 #endif
 };
 
-#define STRY(expr, code)                                                                                     \
-  do {                                                                                                       \
-    hipError_t e__ = (expr);                                                                                 \
-    if (e__ != hipSuccess) {                                                                                 \
-      fprintf(stderr, "[sdrfm_spectrum] %s failed: %s (%s:%d)\n", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-      return (code);                                                                                         \
-    }                                                                                                        \
-  } while (0)
-
 static void sfree(sdrfm_spectrum* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
@@ -681,10 +673,7 @@ int sdrfm_spectrum_create(const sdrfm_spectrum_config* cfg, sdrfm_spectrum_t** o
   while ((1u << logn) < cfg->nfft) ++logn;
   if ((1u << logn) != cfg->nfft || logn < 6 || logn > 12) return SDRFM_EINVAL;
   if (cfg->window) for (uint32_t n = 0; n < cfg->nfft; ++n) if (!std::isfinite(cfg->window[n])) return SDRFM_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return SDRFM_NO_DEVICE;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SDRFM_NO_DEVICE;
+  if (const int rc = host_open_device(cfg->device); rc != SDRFM_OK) return rc;
   sdrfm_spectrum* h = new sdrfm_spectrum();
   memset(h, 0, sizeof(*h));
   h->cfg = *cfg; h->cfg.window = nullptr;

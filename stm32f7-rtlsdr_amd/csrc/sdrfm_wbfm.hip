@@ -23,6 +23,7 @@
 #include <new>
 
 #include "../../include/sdrfm.h"
+#include "sdrfm_host.h"
 #include "sdrfm_math.h"
 
 #include <type_traits>
@@ -1084,11 +1085,8 @@ int sdrfm_wbfm_create(const sdrfm_wbfm_config* cfg, sdrfm_wbfm_t** out) {
       cfg->resamp_down > 256) return SDRFM_EINVAL;
   for (uint32_t k = 0; k < cfg->proto_taps; ++k) if (!std::isfinite(cfg->proto_coeffs[k])) return SDRFM_EINVAL;
   for (uint32_t k = 0; k < cfg->resamp_taps; ++k) if (!std::isfinite(cfg->resamp_coeffs[k])) return SDRFM_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->device < 0 || cfg->device >= ndev) return SDRFM_NO_DEVICE;
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, cfg->device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SDRFM_NO_DEVICE;
-  WTRY(hipSetDevice(cfg->device), SDRFM_NO_DEVICE);
+  if (const int rc = host_open_device(cfg->device, &prop); rc != SDRFM_OK) return rc;
   sdrfm_wbfm* h = new (std::nothrow) sdrfm_wbfm();
   if (!h) return SDRFM_ENOMEM;
   memset(static_cast<void*>(h), 0, sizeof(*h));

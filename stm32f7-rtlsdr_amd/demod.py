@@ -27,8 +27,9 @@ class FmConfig:
     dev_library: bool = False       # load csrc/libsdrfm_dev.so (instrumented / ablation kernels, SDRFM_* environment knobs)
 
 
-class FmDemod:
+class FmDemod(_l.Handle):
     """One sdrfm_t handle. Not thread-safe (same model as the reference's single superloop, src/main.c:72-80)."""
+    _destroy = "sdrfm_destroy"
 
     def __init__(self, cfg: FmConfig):
         self._lib = _l.load_library(dev=cfg.dev_library)
@@ -50,28 +51,6 @@ class FmDemod:
         if st != _l.OK:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_create")
-
-    # -- lifecycle --------------------------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
 
     def reset(self):
         self._ck(self._lib.sdrfm_reset(self._h), "sdrfm_reset")

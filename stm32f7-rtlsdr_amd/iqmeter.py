@@ -128,9 +128,11 @@ def nearest_gain(gains_tenth_db, current, step_db):
     return min(gains, key=lambda g: (abs(g - want), g))
 
 
-class IqMeter:
+class IqMeter(_l.StreamHandle):
     """The device meter over raw capture rows (sdrfm_iq_meter_*): per stream the record, and where asked for the 2 x 256 counts of the byte values,
     integer for integer iq_meter_host's.  No stream state: every call stands alone, and calls add up through iq_meter_add / iq_hist_add."""
+    _destroy = "sdrfm_iq_meter_destroy"
+    _prefix = "sdrfm_iq_meter"
 
     def __init__(self, n_streams, max_bytes_per_call=0, device=0):
         self._lib = _l.load_library()
@@ -144,36 +146,9 @@ class IqMeter:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_iq_meter_create")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_iq_meter_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
     @property
     def kernel_name(self):
         return self._lib.sdrfm_iq_meter_kernel_name(self._h).decode()
-
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_iq_meter_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_iq_meter_set_stream")
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_iq_meter_synchronize(self._h), "sdrfm_iq_meter_synchronize")
 
     def process_batch(self, iq, hist=False):
         """host memory: iq uint8 [n_streams, nbytes] (or [nbytes] for one stream) -> records IQ_METER_DTYPE [n_streams], and with hist=True also

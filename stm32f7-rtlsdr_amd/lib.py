@@ -88,6 +88,46 @@ class SdrfmError(RuntimeError):
         super().__init__("%s%s (%s)" % (where + ": " if where else "", name, msg))
 
 
+class Handle:
+    """The lifecycle the handle classes share: the C handle in _h, destroyed once by close, on deletion or at the end of a with block; _ck turns a
+    status into an SdrfmError.  A class names its C destroy function in _destroy, as a literal."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def _ck(self, st, where):
+        if st != OK:
+            raise SdrfmError(st, where)
+
+
+class StreamHandle(Handle):
+    """A Handle whose C handle has <prefix>_set_stream and <prefix>_synchronize; the class names the prefix in _prefix, as a literal."""
+    _prefix = None
+
+    def set_stream(self, ptr):
+        where = self._prefix + "_set_stream"
+        self._ck(getattr(self._lib, where)(self._h, C.c_void_p(int(ptr) if ptr else None)), where)
+
+    def synchronize(self):
+        where = self._prefix + "_synchronize"
+        self._ck(getattr(self._lib, where)(self._h), where)
+
+
 class Config(C.Structure):
     _fields_ = [
         ("struct_size", C.c_uint32), ("n_streams", C.c_uint32), ("fir_taps", C.c_uint32), ("fir_decim", C.c_uint32),

@@ -191,12 +191,14 @@ def limit_report(records, fs_audio=48000.0):
     return out
 
 
-class PcmLimiter:
+class PcmLimiter(_l.StreamHandle):
     """The device limiter behind the sinks (sdrfm_pcm_limit_*): per stream, the rows under a ramped make-up gain and a look-ahead limiter with a
     window of 2^log2_window pairs, bit for bit pcm_limit_host.  After create: ceiling 29204, release 874, gain 4096.
     detect="truepeak" makes the true-peak form (sdrfm_pcm_tplimit_create), bit for bit pcm_limit_tp_host: the detector sees the waveform the
     table coef (int16 [P, NT], None: the BS.1770 table) interpolates between the samples, and the ceiling reads as dBTP.
     latency: pairs of delay; state_words: int32 words of state per stream; detector: (n_phases, n_taps), (0, 0) for the sample form."""
+    _destroy = "sdrfm_pcm_limit_destroy"
+    _prefix = "sdrfm_pcm_limit"
 
     def __init__(self, n_streams, log2_window=6, gain_slew=1, device=0, detect="sample", coef=None):
         if detect not in ("sample", "truepeak") or (detect == "sample" and coef is not None):
@@ -220,27 +222,6 @@ class PcmLimiter:
         self.detect, self.detector, self.latency = detect, (int(P.value), int(NT.value)), int(lat.value)
         self.state_words = 4 * ((1 << self.log2_window) - 1) + int(NT.value)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_pcm_limit_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
     def _u32(self, v, where):
         x = [int(e) for e in np.broadcast_to(np.asarray(v, dtype=object), (self.n_streams,))]
         if min(x) < 0 or max(x) > 0xFFFFFFFF:
@@ -253,12 +234,6 @@ class PcmLimiter:
 
     def reset(self):
         self._ck(self._lib.sdrfm_pcm_limit_reset(self._h), "sdrfm_pcm_limit_reset")
-
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_pcm_limit_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_pcm_limit_set_stream")
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_pcm_limit_synchronize(self._h), "sdrfm_pcm_limit_synchronize")
 
     def set_params(self, ceiling=None, release=None):
         """one ceiling (LSB, 1 .. 32767) and one release (Q23 per pair, 1 .. 2^23) for every stream or one per stream; None keeps what is set.

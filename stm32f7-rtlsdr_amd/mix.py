@@ -171,9 +171,11 @@ def crossfade_plan(slots, J, slew, bus, src, mode="stereo"):
     return free, srcs, modes, target
 
 
-class PcmMixer:
+class PcmMixer(_l.StreamHandle):
     """The device mix bus (sdrfm_pcm_mix_*): n_bus rows from n_in rows, bit for bit pcm_mix_host.  After create every slot is
     (NONE, stereo, 0, 0): the buses are silent until routed.  curve: None (c = g), "equal_power", "linear" or 129 uint16 values."""
+    _destroy = "sdrfm_pcm_mix_destroy"
+    _prefix = "sdrfm_pcm_mix"
 
     def __init__(self, n_in, n_bus, n_slots=2, slew=32, curve=None, device=0):
         self._lib = _l.load_library()
@@ -188,27 +190,6 @@ class PcmMixer:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_pcm_mix_create")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_pcm_mix_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
     def _u32(self, v, where):
         x = [int(e) for e in np.broadcast_to(np.asarray(v, dtype=object), (self.n_bus, self.n_slots)).reshape(-1)]
         if min(x) < 0 or max(x) > 0xFFFFFFFF:
@@ -221,12 +202,6 @@ class PcmMixer:
     def reset(self):
         """the records to the identity; the slots, the ramps and J stay"""
         self._ck(self._lib.sdrfm_pcm_mix_reset(self._h), "sdrfm_pcm_mix_reset")
-
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_pcm_mix_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_pcm_mix_set_stream")
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_pcm_mix_synchronize(self._h), "sdrfm_pcm_mix_synchronize")
 
     def set_routes(self, src=None, mode=None):
         """src (a row below n_in, or NONE) and mode (0 .. 4 or a name) per slot, [n_bus, n_slots] or one value for all; None keeps what is set.

@@ -56,9 +56,11 @@ def pcm_rate_host(pcm, coef, step, pos=0, hist=None):
     return out[:2 * cnt.value].copy(), int(p.value), h
 
 
-class PcmRateMatcher:
+class PcmRateMatcher(_l.StreamHandle):
     """The device rate matcher behind the sinks (sdrfm_pcm_rate_*): per stream, out = the rows resampled by step / 2^32 input pairs per output
     pair through coef (taps.rate_coef), bit for bit pcm_rate_host.  Every step starts at 2^32."""
+    _destroy = "sdrfm_pcm_rate_destroy"
+    _prefix = "sdrfm_pcm_rate"
 
     def __init__(self, n_streams, coef, device=0):
         self._lib = _l.load_library()
@@ -71,39 +73,12 @@ class PcmRateMatcher:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_pcm_rate_create")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_pcm_rate_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
     @property
     def kernel_name(self):
         return self._lib.sdrfm_pcm_rate_kernel_name(self._h).decode()
 
     def reset(self):
         self._ck(self._lib.sdrfm_pcm_rate_reset(self._h), "sdrfm_pcm_rate_reset")
-
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_pcm_rate_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_pcm_rate_set_stream")
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_pcm_rate_synchronize(self._h), "sdrfm_pcm_rate_synchronize")
 
     def set_step(self, step):
         """one step (32.32, in [2^30, 2^34]) for every stream or one per stream; it takes effect at the next call's first output"""

@@ -31,7 +31,10 @@ class RdsConfig:
     force_generic: bool = False       # SDRFM_RDS_CFG_FORCE_GENERIC (tests): never the fast kernel
 
 
-class RdsDemod:
+class RdsDemod(_l.StreamHandle):
+    _destroy = "sdrfm_rds_destroy"
+    _prefix = "sdrfm_rds"
+
     def __init__(self, cfg: RdsConfig):
         self._lib = _l.load_library()
         self.cfg = cfg
@@ -54,27 +57,6 @@ class RdsDemod:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_rds_create")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_rds_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
     def reset(self):
         self._ck(self._lib.sdrfm_rds_reset(self._h), "sdrfm_rds_reset")
 
@@ -84,15 +66,9 @@ class RdsDemod:
         self._ck(self._lib.sdrfm_rds_count(self._h, int(nbytes), C.byref(n)), "sdrfm_rds_count")
         return n.value
 
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_rds_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_rds_set_stream")
-
     @property
     def kernel_name(self):
         return self._lib.sdrfm_rds_kernel_name(self._h).decode()
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_rds_synchronize(self._h), "sdrfm_rds_synchronize")
 
     def process_batch(self, iq: np.ndarray):
         """host memory: iq [n_streams, nbytes] uint8 -> (bb [n_streams, n_out] complex64, pilot_count [n_streams] uint32)"""

@@ -49,7 +49,10 @@ def _tuning(offsets_hz, h, fs, D):
     return ctaps, rot
 
 
-class ScanDemod:
+class ScanDemod(_l.StreamHandle):
+    _destroy = "sdrfm_scan_destroy"
+    _prefix = "sdrfm_scan"
+
     def __init__(self, cfg: ScanConfig):
         self._lib = _l.load_library()
         self.cfg = cfg
@@ -80,27 +83,6 @@ class ScanDemod:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_scan_create")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_scan_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
     def reset(self):
         self._ck(self._lib.sdrfm_scan_reset(self._h), "sdrfm_scan_reset")
 
@@ -116,15 +98,9 @@ class ScanDemod:
         assert ctaps.size == self.n_streams * 2 * self._T and rot.size == self.n_streams, (ctaps.shape, rot.shape)
         self._ck(self._lib.sdrfm_scan_tune(self._h, ctaps.ctypes.data, rot.ctypes.data), "sdrfm_scan_tune")
 
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_scan_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_scan_set_stream")
-
     @property
     def kernel_name(self):
         return self._lib.sdrfm_scan_kernel_name(self._h).decode()
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_scan_synchronize(self._h), "sdrfm_scan_synchronize")
 
     def process_batch(self, iq: np.ndarray):
         """host memory: iq [n_streams, nbytes] uint8 (one row with shared_input) -> records, a METER_DTYPE array [n_streams]"""

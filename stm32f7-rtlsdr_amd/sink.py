@@ -22,9 +22,11 @@ def pcm_deemph_s16_host(audio, alpha, gain, state=0.0):
 PCM_F_EXACT = 4   # SDRFM_PCM_F_EXACT (include/sdrfm.h)
 
 
-class PcmSink:
+class PcmSink(_l.StreamHandle):
     """exact=False (default): the blocked-scan kernel (PCM within 1 LSB of the exact form); exact=True: SDRFM_PCM_F_EXACT, one lane per stream,
     bit-identical to the host routine sdrfm_pcm_deemph_s16."""
+    _destroy = "sdrfm_pcm_sink_destroy"
+    _prefix = "sdrfm_pcm_sink"
 
     def __init__(self, n_streams, alpha, gain, device=0, exact=False):
         self._lib = _l.load_library()
@@ -36,35 +38,8 @@ class PcmSink:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_pcm_sink_create")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_pcm_sink_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
     def reset(self):
         self._ck(self._lib.sdrfm_pcm_sink_reset(self._h), "sdrfm_pcm_sink_reset")
-
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_pcm_sink_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_pcm_sink_set_stream")
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_pcm_sink_synchronize(self._h), "sdrfm_pcm_sink_synchronize")
 
     def synchronize_status(self):
         """sdrfm_pcm_sink_synchronize's status as it is (0 = fine; SDRFM_FAIL when a run of a demodulator launch waited in vain for its predecessor's state)."""
@@ -143,10 +118,12 @@ def hicut_slew(ramp_ms, rate_hz=48000.0):
     return 32768 if n <= 1.0 else max(1, int(np.ceil(32768.0 / n)))
 
 
-class StereoPcmSink:
+class StereoPcmSink(_l.StreamHandle):
     """The device sink for L and R rows (sdrfm_pcm_stereo_sink_*): pcm[2i] = L, pcm[2i + 1] = R, each channel de-emphasised on its own.
     exact=False (default): the blocked scan, per channel the mono PcmSink's default form bit for bit (PCM within 1 LSB of the exact form);
     exact=True: SDRFM_PCM_F_EXACT, one lane per stream, bit-identical to the host routine sdrfm_pcm_deemph_stereo_s16."""
+    _destroy = "sdrfm_pcm_stereo_sink_destroy"
+    _prefix = "sdrfm_pcm_stereo_sink"
 
     def __init__(self, n_streams, alpha, gain, device=0, exact=False):
         self._lib = _l.load_library()
@@ -158,35 +135,8 @@ class StereoPcmSink:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_pcm_stereo_sink_create")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_pcm_stereo_sink_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
     def reset(self):
         self._ck(self._lib.sdrfm_pcm_stereo_sink_reset(self._h), "sdrfm_pcm_stereo_sink_reset")
-
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_pcm_stereo_sink_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_pcm_stereo_sink_set_stream")
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_pcm_stereo_sink_synchronize(self._h), "sdrfm_pcm_stereo_sink_synchronize")
 
     def state(self):
         """[n_streams, 2] float32: the carried de-emphasis states (L, R) of every stream"""

@@ -19,7 +19,10 @@ class SpectrumConfig:
     dev_library: bool = False         # tools only: csrc/libsdrfm_dev.so (phase stamps, SDRFM_SPEC_VARIANT)
 
 
-class SpectrumView:
+class SpectrumView(_l.StreamHandle):
+    _destroy = "sdrfm_spectrum_destroy"
+    _prefix = "sdrfm_spectrum"
+
     def __init__(self, cfg: SpectrumConfig):
         self._lib = _l.load_library(dev=cfg.dev_library)
         self.cfg = cfg
@@ -36,27 +39,6 @@ class SpectrumView:
         if st != _l.OK:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_spectrum_create")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_spectrum_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_spectrum_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_spectrum_set_stream")
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_spectrum_synchronize(self._h), "sdrfm_spectrum_synchronize")
 
     @property
     def kernel_name(self):

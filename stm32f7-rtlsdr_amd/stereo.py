@@ -33,7 +33,10 @@ def _pilot_floats(b):
     return np.ascontiguousarray(b, dtype=np.float32).reshape(-1)
 
 
-class StereoDemod:
+class StereoDemod(_l.StreamHandle):
+    _destroy = "sdrfm_stereo_destroy"
+    _prefix = "sdrfm_stereo"
+
     def __init__(self, cfg: StereoConfig):
         self._lib = _l.load_library()
         self.cfg = cfg
@@ -56,27 +59,6 @@ class StereoDemod:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_stereo_create")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_stereo_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
     def reset(self):
         self._ck(self._lib.sdrfm_stereo_reset(self._h), "sdrfm_stereo_reset")
 
@@ -85,15 +67,9 @@ class StereoDemod:
         self._ck(self._lib.sdrfm_stereo_audio_count(self._h, int(nbytes), C.byref(n)), "sdrfm_stereo_audio_count")
         return n.value
 
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_stereo_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_stereo_set_stream")
-
     @property
     def kernel_name(self):
         return self._lib.sdrfm_stereo_kernel_name(self._h).decode()
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_stereo_synchronize(self._h), "sdrfm_stereo_synchronize")
 
     def process_batch(self, iq: np.ndarray):
         """host memory: iq [n_streams, nbytes] uint8 -> (L, R) [n_streams, n_audio] float32 and pilot_count [n_streams] uint32"""

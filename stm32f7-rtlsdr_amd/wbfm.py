@@ -24,7 +24,10 @@ class WbfmConfig:
     dev_library: bool = False         # load csrc/libsdrfm_dev.so (instrumented build; tools only)
 
 
-class WbfmDemod:
+class WbfmDemod(_l.StreamHandle):
+    _destroy = "sdrfm_wbfm_destroy"
+    _prefix = "sdrfm_wbfm"
+
     def __init__(self, cfg: WbfmConfig):
         self._lib = _l.load_library(dev=cfg.dev_library)
         self.cfg = cfg
@@ -44,21 +47,6 @@ class WbfmDemod:
             self._h = None
             raise _l.SdrfmError(st, "sdrfm_wbfm_create")
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.sdrfm_wbfm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, st, where):
-        if st != _l.OK:
-            raise _l.SdrfmError(st, where)
-
     def reset(self):
         self._ck(self._lib.sdrfm_wbfm_reset(self._h), "sdrfm_wbfm_reset")
 
@@ -67,15 +55,9 @@ class WbfmDemod:
         self._ck(self._lib.sdrfm_wbfm_audio_count(self._h, int(nbytes), C.byref(n)), "sdrfm_wbfm_audio_count")
         return n.value
 
-    def set_stream(self, ptr):
-        self._ck(self._lib.sdrfm_wbfm_set_stream(self._h, C.c_void_p(int(ptr) if ptr else None)), "sdrfm_wbfm_set_stream")
-
     @property
     def kernel_name(self):
         return self._lib.sdrfm_wbfm_kernel_name(self._h).decode()
-
-    def synchronize(self):
-        self._ck(self._lib.sdrfm_wbfm_synchronize(self._h), "sdrfm_wbfm_synchronize")
 
     def process_batch(self, iq: np.ndarray) -> np.ndarray:
         """host memory: iq [n_streams, nbytes] uint8 -> audio [n_streams, 16, n_audio] float32"""

@@ -244,6 +244,19 @@ def test_host_buffers_against_device_buffers(pkg, torch, hist):
 
 
 @pytest.mark.parametrize("hist", FORMS)
+def test_host_staging_grows_and_is_reused_below_capacity(pkg, torch, hist):
+    """host-buffer calls of 1000, 1025 and 3 byte-pairs in that order on one handle of 3 streams, then 2049 byte-pairs, the first length past the
+    4096 bytes the staging is rounded up to, and 3 again: the staging is made, reused, outgrown, and used far below its capacity with the last
+    call's bytes still behind the valid ones.  Every call's records and rows are the host routine's"""
+    x = cases.random_rows(67, 3, 2 * 2049 + 8)
+    with pkg.IqMeter(3) as m:
+        for k, pairs in enumerate((1000, 1025, 3, 2049, 3)):
+            rows = np.ascontiguousarray(x[:, k:k + 2 * pairs])
+            got = m.process_batch(rows, hist=hist)
+            assert _same(pkg, got if hist else (got, None), rows, hist), pairs
+
+
+@pytest.mark.parametrize("hist", FORMS)
 def test_one_stream_fills_the_machine_like_sixteen(pkg, torch, geometry, hist):
     """the shared-capture case: one row of 1 MiB on a 1-stream handle (256 workgroups) against a 16-stream handle given that row sixteen times"""
     row = cases.random_rows(67, 1, 1 << 20)

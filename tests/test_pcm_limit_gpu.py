@@ -248,6 +248,21 @@ def test_device_rows_in_place_padding_and_the_callers_stream(pkg, rows, T):
             assert np.array_equal(a.state(), b.state()) and ref_lim[1].holds(a) and ref_lim[1].holds(b)
 
 
+def test_host_staging_grows_and_is_reused_below_capacity(pkg, rows):
+    """host-buffer calls of 1000, 1025 and 3 pairs in that order on one handle of 3 streams, the stream going on from call to call: the staging is
+    made, outgrown, and then used far below its capacity with the last call's pairs still behind the valid ones.  PCM, state and records after
+    every call are the host routine's"""
+    lim, host = _pair(pkg, 3, 6)
+    with lim:
+        a = 0
+        for n in (1000, 1025, 3):
+            x = _input(rows, 3, a, a + n)
+            a += n
+            got, want = lim.process_batch(x), host.call(x)
+            assert got.shape == (3, 2 * n) and np.array_equal(got, want), n
+            assert host.holds(lim), n
+
+
 def test_read_with_and_without_reset_and_reset(pkg, rows, T):
     import torch
     lw, ns, n = 6, 3, 1500

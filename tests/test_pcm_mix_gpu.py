@@ -278,6 +278,22 @@ def test_call_forms(pkg):
         assert np.array_equal(_device_call(b, x3, n_bus), a.process_batch(x3))
 
 
+def test_host_staging_grows_and_is_reused_below_capacity(pkg):
+    """host-buffer calls of 1000, 1025 and 3 pairs in that order on one handle of 3 rows in and 3 buses: the staging is made, outgrown, and
+    then used far below its capacity with the last call's pairs still behind the valid ones.  Every call's PCM and the records are the host
+    routine's, J going on from call to call"""
+    dev, host = _pair(pkg, 3, 3, 2, cases.SLEWS[1], "equal_power")
+    with dev:
+        table = cases.slot_table(77, 3, 3, 2)
+        cases.load(dev, table)
+        host.load(table)
+        for call, n in enumerate((1000, 1025, 3)):
+            x = cases.rows(7700 + call, 3, n)
+            got = dev.process_batch(x)
+            assert got.shape == (3, 2 * n) and np.array_equal(got, host.process_batch(x)), n
+            assert host.holds(dev) and dev.read().tobytes() == host.rec.tobytes(), n
+
+
 def test_every_refusal_leaves_the_handle_as_it_was(pkg):
     import torch
     lib = pkg.load_library()

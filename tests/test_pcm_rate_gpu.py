@@ -218,6 +218,25 @@ def test_device_rows_strides_padding_and_the_callers_stream(pkg, rows, tables):
         assert n_out.value == want.size // 2 and np.array_equal(got[:want.size], want) and (got[want.size:] == -32768).all()
 
 
+def test_host_staging_grows_and_is_reused_below_capacity(pkg, rows, tables):
+    """host-buffer calls of 1000, 1025 and 3 pairs in that order on one handle of 3 streams at three steps (2^30, 2^32 and 2^32 (1 + 1e-4), so the
+    counts differ from stream to stream and the first stream's are four times the input's): both sides of the staging are made, outgrown, and then used far below their
+    capacity with the last call's pairs still behind the valid ones.  Every call's outputs, counts and pos are the reference's"""
+    coef, steps, cuts = tables[32, 8], _steps(3), (1000, 1025, 3)
+    with pkg.PcmRateMatcher(3, coef) as rm:
+        rm.set_step(steps)
+        a = 0
+        for c, n in enumerate(cuts):
+            cnt, _ = rm.count(n)
+            got = rm.process_batch(_input(rows, 3, a, a + n))
+            a += n
+            _, pos = rm.state()
+            for s in range(3):
+                outs, poss = _ref_calls(rows, coef, (32, 8), s % ROWS, steps[s], cuts)
+                assert int(cnt[s]) == outs[c].size // 2 == got[s].size // 2, (n, s)
+                assert np.array_equal(got[s], outs[c]) and int(pos[s]) == poss[c], (n, s, steps[s])
+
+
 def test_reset_and_reuse(pkg, rows, tables):
     coef = tables[64, 8]
     steps = _steps(3)
