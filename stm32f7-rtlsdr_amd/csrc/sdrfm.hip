@@ -37,6 +37,7 @@
 #include "sdrfm_q.h"
 #include "sdrfm_fm_call.h"
 #include "sdrfm_fm_route.h"
+#include "sdrfm_fm_carry.h"
 #include "sdrfm_fm_plan.h"
 
 #include "sdrfm_b.h"
@@ -927,9 +928,7 @@ struct sdrfm {
   float2* d_yprev[2];
   float* d_hist_d[2];
   uint8_t* d_hist_b[2];   // raw-byte twin of hist_x (design B reads its halo from it)
-  uint64_t n_seen;        // IQ samples consumed since reset (history is all-real once >= T-1)
-  int cur;  // index of the state set holding the current state
-  uint32_t phase_x, phase_d;
+  FmCarry carry;          // what a call leaves for the next one, and the overlap's joins (sdrfm_fm_carry.h): only its functions read or write it
   // staging for host-pointer calls
   uint8_t* d_iq;
   size_t d_iq_stride;
@@ -964,14 +963,11 @@ struct sdrfm {
   uint32_t q_c0, q_nslot;
   char fast_q_name[64];
   // design Q's conditioning guard: thresholds, the zero-padded taps of the repair path's chain, the last 64 raw samples of
-  // every stream (kept like the other state sets), statistics; and what the current state set holds: y[-1] as the definition has it
-  // (reset, or a bit-exact kernel served the previous call) or design Q's own value; hist_q written by design Q or not
+  // every stream (kept like the other state sets), statistics (what the current state set holds: carry)
   float q_guard_r, q_guard_a;
   float* d_hpad;
   uint8_t* d_hist_q[2];
   unsigned int* d_qstat;
-  bool yprev_exact, hist_q_valid;
-  bool prev_by_q;         // design Q served (some streams of) the previous call: the state it left is what an overlapped call's warm-up reproduces (route_apply leaves this alone)
   // Per-stream routing between design Q and the bit-exact kernels (sdrfm_fm_route.h has the scheme and the host's bookkeeping: route); here its device resources
   FmRoute route;
   uint32_t* rt_pass_dev[SDRFM_Q_ADAPT_SETS]; uint32_t* rt_pass_host[SDRFM_Q_ADAPT_SETS]; uint32_t* rt_pass_host_dev[SDRFM_Q_ADAPT_SETS];   // repair passes per stream: the set the open window adds into / pinned read-back
@@ -991,16 +987,9 @@ struct sdrfm {
   // sdrfm_process_batch_pcm: the sink whose chain the call's design-Q launch ends with (sdrfm_sink_chain.h); pcm_fused: that launch took it
   sdrfm_pcm_sink* pcm_sink; int16_t* pcm_out; size_t pcm_out_stride; bool pcm_fused;
   bool pcm_no_audio; float* d_pcm_audio; size_t pcm_audio_stride; uint32_t pcm_audio_cap, pcm_audio_flip;   // a call without an audio buffer: the library's own, for the calls that need one
-  const int16_t* prev_ovl_pcm; size_t prev_ovl_pcm_stride;       // the PCM rows the previous overlapped call may still be writing
   int16_t* d_pcm_stage;                                          // sdrfm_process_batch_pcm with host buffers: the PCM rows before they are copied back
   unsigned long long* d_runstate; uint32_t runstate_cap;        // the runs' hand-off words (sdrfm_sink_chain.h), allocated at the first such call
   uint32_t chain_calls;                                          // launches that held a sink's chain so far: their set and tag of d_runstate (never rewound)
-  bool ovl_pending[2], ovl_bound[2], ovl_join_style;   // (bound: the latest kernel of stream k carries ovl_done[k] as its stop event; join_style: the caller joins after every call)
-  uint32_t ovl_next;
-  // the previous call's device buffer (valid after a SDRFM_F_DEVICE_PTRS call): what an overlapped call warms its streams up from
-  const uint8_t* prev_iq; size_t prev_stride; uint32_t prev_nbytes;
-  // the audio buffer the most recent overlapped call writes (it may still be running when the next call is made)
-  const float* prev_ovl_audio; size_t prev_ovl_audio_stride; uint32_t prev_ovl_audio_n;
 };
 
 static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nbytes, float* d_audio, size_t audio_stride,
@@ -1374,7 +1363,7 @@ int sdrfm_reset(sdrfm_t* h) {
   const size_t ns = h->cfg.n_streams, T = h->cfg.fir_taps, Ta = h->cfg.audio_taps;
   const size_t hx = (T > 1 ? T - 1 : 1), hd = (Ta > 1 ? Ta - 1 : 1);
   { const int jrc = join_overlap(h); if (jrc != SDRFM_OK) return jrc; }
-  h->prev_iq = nullptr;
+  fm_carry_reset(h->carry);                                       // (what a reset keeps of the overlap's state: marked there)
   for (int i = 0; i < 2; ++i) {
     HIP_TRY(hipMemsetAsync(h->d_hist_x[i], 0, sizeof(float2) * ns * hx, h->stream), SDRFM_FAIL);
     HIP_TRY(hipMemsetAsync(h->d_yprev[i], 0, sizeof(float2) * ns, h->stream), SDRFM_FAIL);
@@ -1382,34 +1371,30 @@ int sdrfm_reset(sdrfm_t* h) {
     HIP_TRY(hipMemsetAsync(h->d_hist_b[i], 0, 2 * ns * hx, h->stream), SDRFM_FAIL);
     if (h->d_hist_q[i]) HIP_TRY(hipMemsetAsync(h->d_hist_q[i], 0, 2 * SDRFM_Q_TP * ns, h->stream), SDRFM_FAIL);
   }
-  h->yprev_exact = true;                                          // y[-1] = 0, as the definition has it
-  h->hist_q_valid = false;
-  h->prev_by_q = false;
   HIP_TRY(hipStreamSynchronize(h->stream), SDRFM_FAIL);
   { const int rrc = route_reset(h); if (rrc != SDRFM_OK) return rrc; }   // (behind the synchronisation: no kernel is left that could add to the statistics)
-  h->cur = 0;
-  h->phase_x = h->phase_d = 0;
-  h->n_seen = 0;                                                  // (chain_calls goes on: d_runstate keeps the words its launches left)
-  return SDRFM_OK;
+  return SDRFM_OK;                                                // (chain_calls goes on: d_runstate keeps the words its launches left)
 }
 
 int sdrfm_audio_count(const sdrfm_t* h, uint32_t nbytes, uint32_t* n_audio) {
   if (!h || !n_audio) return SDRFM_EINVAL;
   if (nbytes & 1u) return SDRFM_EODD;
-  *n_audio = fm_counts(h->phase_x, h->phase_d, nbytes, h->cfg.fir_decim, h->cfg.audio_decim).A;
+  *n_audio = fm_carry_counts(h->carry, nbytes, h->cfg.fir_decim, h->cfg.audio_decim).A;
   return SDRFM_OK;
 }
 
-// Everything issued with SDRFM_F_OVERLAP so far is ordered before whatever the handle's stream is given next.
-static int join_overlap(sdrfm* h) {
-  for (int k = 0; k < 2; ++k)
-    if (h->ovl_pending[k]) {
-      if (!h->ovl_bound[k]) HIP_TRY(hipEventRecord(h->ovl_done[k], h->ovl_stream[k]), SDRFM_FAIL);   // (else: the stream's latest kernel carries the event — enqueue())
-      HIP_TRY(hipStreamWaitEvent(h->stream, h->ovl_done[k], 0), SDRFM_FAIL);
-      h->ovl_pending[k] = false;
-    }
+// One of the three joins (sdrfm_fm_carry.h: fm_carry_join says which internal streams it covers): `waiter` is ordered behind ovl_done[k], recorded here where the
+// stream's latest kernel does not carry it (enqueue()).
+static int join(sdrfm* h, FmJoinKind kind, hipStream_t waiter) {
+  const FmJoin j = fm_carry_join(h->carry, kind);
+  for (uint32_t k = 0; k < 2; ++k) {
+    if (j.record[k]) HIP_TRY(hipEventRecord(h->ovl_done[k], h->ovl_stream[k]), SDRFM_FAIL);
+    if (j.wait[k]) { HIP_TRY(hipStreamWaitEvent(waiter, h->ovl_done[k], 0), SDRFM_FAIL); fm_carry_joined(h->carry, kind, k); }
+  }
   return SDRFM_OK;
 }
+// Everything issued with SDRFM_F_OVERLAP so far is ordered before whatever the handle's stream is given next.
+static int join_overlap(sdrfm* h) { return join(h, FM_JOIN_ALL, h->stream); }
 
 // A new assignment of streams to kernels: the list [clean streams | noisy streams] goes to the other version's buffers, and the state
 // every stream carries is made the same for both kinds of kernel first (y[-1] of the streams design Q served last becomes the
@@ -1425,13 +1410,14 @@ static int route_apply(sdrfm* h) {
   if (l.wait) HIP_TRY(hipEventSynchronize(h->rt_applied[v]), SDRFM_FAIL);   // (this version's host buffer feeds a copy enqueued two assignments ago)
   uint32_t* L = h->rt_list_host[v];
   const uint32_t nn = fm_route_list_fill(r, L).n_noisy;
-  if (!h->yprev_exact && h->hist_q_valid)                        // (design Q served ns - r.n_noisy streams at the previous call: the clean part of the list in use)
-    HIP_TRY(sdrfm_q_fix_yprev(h->d_hist_q[h->cur], h->d_hpad, h->d_yprev[h->cur], ns - r.n_noisy, r.n_noisy ? h->rt_list_dev[r.list_cur] : nullptr,
+  const int cur = fm_carry_set(h->carry);
+  if (fm_carry_fix_yprev(h->carry))                              // (design Q served ns - r.n_noisy streams at the previous call: the clean part of the list in use)
+    HIP_TRY(sdrfm_q_fix_yprev(h->d_hist_q[cur], h->d_hpad, h->d_yprev[cur], ns - r.n_noisy, r.n_noisy ? h->rt_list_dev[r.list_cur] : nullptr,
                               h->stream), SDRFM_FAIL);
   if (c.fir_taps > 1)
-    HIP_TRY(hipMemcpy2DAsync(h->d_hist_q[h->cur] + 2 * (SDRFM_Q_TP - (c.fir_taps - 1)), 2 * SDRFM_Q_TP, h->d_hist_b[h->cur], 2 * (size_t)(c.fir_taps - 1),
+    HIP_TRY(hipMemcpy2DAsync(h->d_hist_q[cur] + 2 * (SDRFM_Q_TP - (c.fir_taps - 1)), 2 * SDRFM_Q_TP, h->d_hist_b[cur], 2 * (size_t)(c.fir_taps - 1),
                              2 * (size_t)(c.fir_taps - 1), ns, hipMemcpyDeviceToDevice, h->stream), SDRFM_FAIL);
-  h->yprev_exact = true; h->hist_q_valid = true;
+  fm_carry_assigned(h->carry);
   HIP_TRY(hipMemcpyAsync(h->rt_list_dev[v], L, (size_t)ns * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream), SDRFM_FAIL);
   HIP_TRY(hipEventRecord(h->rt_applied[v], h->stream), SDRFM_FAIL);
   for (int k = 0; k < 2; ++k)
@@ -1450,27 +1436,14 @@ int sdrfm_flush(sdrfm_t* h) {
 int sdrfm_flush_previous(sdrfm_t* h) {
   if (!h) return SDRFM_EINVAL;
   HIP_TRY(hipSetDevice(h->device), SDRFM_FAIL);
-  const uint32_t k = h->ovl_next;                                // the stream the NEXT call takes = the one the call before the last took
-  h->ovl_join_style = true;                                     // (a join after every call: from now on the kernels carry their stream's completion event)
-  if (h->ovl_pending[k]) {
-    if (!h->ovl_bound[k]) HIP_TRY(hipEventRecord(h->ovl_done[k], h->ovl_stream[k]), SDRFM_FAIL);
-    HIP_TRY(hipStreamWaitEvent(h->stream, h->ovl_done[k], 0), SDRFM_FAIL);
-    h->ovl_pending[k] = false;
-  }
-  return SDRFM_OK;
+  return join(h, FM_JOIN_PREVIOUS, h->stream);                  // (that internal stream is pending no more: fm_carry_joined has the difference to sdrfm_wait_previous)
 }
 
 // A stream of the caller's behind all overlapped calls but the most recent one; the handle's own stream is not touched (it keeps its pending joins).
 int sdrfm_wait_previous(sdrfm_t* h, void* hip_stream) {
   if (!h || !hip_stream) return SDRFM_EINVAL;
   HIP_TRY(hipSetDevice(h->device), SDRFM_FAIL);
-  const uint32_t k = h->ovl_next;                                // the stream the NEXT call takes = the one the call before the last took
-  h->ovl_join_style = true;                                     // (a join after every call: from now on the kernels carry their stream's completion event)
-  if (h->ovl_pending[k]) {
-    if (!h->ovl_bound[k]) { HIP_TRY(hipEventRecord(h->ovl_done[k], h->ovl_stream[k]), SDRFM_FAIL); h->ovl_bound[k] = true; }   // (recorded once: it covers the stream's latest call)
-    HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ovl_done[k], 0), SDRFM_FAIL);
-  }
-  return SDRFM_OK;
+  return join(h, FM_JOIN_PREVIOUS_ON_CALLER, static_cast<hipStream_t>(hip_stream));   // (it stays pending for the handle's stream; the event is recorded once: fm_carry_joined)
 }
 
 int sdrfm_set_stream(sdrfm_t* h, void* hip_stream) {
@@ -1574,7 +1547,7 @@ static const char* launch_bx(sdrfm* h, const FmCall& cl, CallParams p, uint32_t 
 static int route_window_close(sdrfm* h) {
   const uint32_t ns_all = h->cfg.n_streams;
   hipStream_t wst[3] = {h->ovl_stream[0], h->ovl_stream[1], h->stream};
-  const FmRouteClose cw = fm_route_close(h->route, h->ovl_bound[0], h->ovl_bound[1]);
+  const FmRouteClose cw = fm_route_close(h->route, h->carry.ovl_bound[0], h->carry.ovl_bound[1]);
   const uint32_t i = cw.set;
   for (int kk = 0; kk < 3; ++kk) {
     if (cw.wait[kk] == FM_ROUTE_NO_EVENT) continue;
@@ -1593,28 +1566,30 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
                    uint32_t* n_audio, uint32_t call_flags) {
   const sdrfm_config& c = h->cfg;
   const FmGeom& g = h->geo;
-  const FmCounts n = fm_counts(h->phase_x, h->phase_d, nbytes, c.fir_decim, c.audio_decim);
+  FmCarry& cy = h->carry;
+  const FmCounts n = fm_carry_counts(cy, nbytes, c.fir_decim, c.audio_decim);
   const uint32_t N = n.N, M = n.M, A = n.A;
   if (n_audio) *n_audio = A;
   if (N == 0) return SDRFM_OK;
   if (A > audio_stride && c.n_streams > 1) return SDRFM_ECAPACITY;
-  const FmCall cl = {N, M, A, h->phase_x, h->phase_d, h->n_seen, ((uintptr_t)d_iq % 4 == 0) && (iq_stride % 4 == 0),
-                     ((uintptr_t)d_iq % 16 == 0) && (iq_stride % 16 == 0)};
+  const FmCall cl = fm_carry_call(cy, n, d_iq, iq_stride);
+  const FmRows rows = {d_iq, iq_stride, nbytes, d_audio, audio_stride, h->pcm_out, h->pcm_out_stride};
+  const int cur = fm_carry_set(cy);
 
   CallParams p;                                                   // every stream, no tiling yet: each launch fills its own copy
   p.iq = d_iq; p.iq_stride = iq_stride; p.audio = d_audio; p.audio_stride = audio_stride;
-  p.hist_x_in = h->d_hist_x[h->cur]; p.hist_x_out = h->d_hist_x[h->cur ^ 1];
-  p.yprev_in = h->d_yprev[h->cur]; p.yprev_out = h->d_yprev[h->cur ^ 1];
-  p.hist_d_in = h->d_hist_d[h->cur]; p.hist_d_out = h->d_hist_d[h->cur ^ 1];
-  p.hist_b_in = h->d_hist_b[h->cur]; p.hist_b_out = h->d_hist_b[h->cur ^ 1];
+  p.hist_x_in = h->d_hist_x[cur]; p.hist_x_out = h->d_hist_x[cur ^ 1];
+  p.yprev_in = h->d_yprev[cur]; p.yprev_out = h->d_yprev[cur ^ 1];
+  p.hist_d_in = h->d_hist_d[cur]; p.hist_d_out = h->d_hist_d[cur ^ 1];
+  p.hist_b_in = h->d_hist_b[cur]; p.hist_b_out = h->d_hist_b[cur ^ 1];
   p.h = h->d_h; p.g = h->d_g;
   p.T = c.fir_taps; p.D = c.fir_decim; p.Ta = c.audio_taps; p.Da = c.audio_decim;
   p.N = N; p.M = M; p.A = A;
-  p.e0 = (int32_t)(c.fir_decim - 1 - h->phase_x);
-  p.f0 = (int32_t)(c.audio_decim - 1 - h->phase_d);
+  p.e0 = (int32_t)(c.fir_decim - 1 - cl.phase_x);
+  p.f0 = (int32_t)(c.audio_decim - 1 - cl.phase_d);
   p.NA = 0; p.tiles_per_stream = 0; p.fold_state = 0;
   p.n_streams = c.n_streams;
-  p.phase_x = h->phase_x;
+  p.phase_x = cl.phase_x;
   p.AB = h->AB;
   p.dbg = h->d_dbg;
   p.prio_balance = h->prio_balance;
@@ -1648,23 +1623,9 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
   // SDRFM_F_OVERLAP: the call goes to one of two internal streams and warms every stream up from the previous call's buffer instead
   // of reading the carried state, so that it depends on nothing the previous call computes (the state sets are still written, for
   // whatever call comes next without the flag).  Any other call first orders the handle's stream behind the overlapped ones.
-  // What the flag asks of the caller is checked where that is cheap: a call whose rows overlap the previous call's rows (one buffer used
-  // for every call) or whose audio buffer is the one the previous overlapped call may still be writing runs as if the flag were absent.
-  // So does a call right behind one design Q did not serve (prev_by_q; NOT hist_q_valid, which route_apply also sets when it refills hist_q from the
-  // bit-exact kernels' samples): the warm-up would recompute y[-1] and the last Ta - 1 discriminator outputs with design Q's arithmetic where the same
-  // call without the flag takes over the definition's from the bit-exact kernels' state — the first audio outputs then differ in their last bits, and
-  // the flag promises the same audio bit for bit (tests/test_fm_shapes_gpu.py: "prev-served-by-b", "prev-served-by-b-then-routed").
-  const bool ovl = q_ok && (call_flags & SDRFM_F_OVERLAP) && h->prev_iq && h->prev_by_q &&
-                   fm_ovl_geometry_ok(g, cl, h->prev_nbytes, ((uintptr_t)h->prev_iq % 16 == 0) && (h->prev_stride % 16 == 0)) &&
-                   !fm_rows_overlap(h->prev_iq, h->prev_stride, h->prev_nbytes, d_iq, iq_stride, nbytes, c.n_streams) &&
-                   // (a call that writes no audio — no buffer given, the chain inside the launch — has no audio rows to collide)
-                   !(!(with_chain && h->pcm_no_audio) && h->prev_ovl_audio &&
-                     fm_rows_overlap(reinterpret_cast<const uint8_t*>(h->prev_ovl_audio), h->prev_ovl_audio_stride * sizeof(float),
-                                     h->prev_ovl_audio_n * sizeof(float), reinterpret_cast<const uint8_t*>(d_audio),
-                                     audio_stride * sizeof(float), (size_t)A * sizeof(float), c.n_streams)) &&
-                   !(with_chain && h->prev_ovl_pcm && fm_rows_overlap(reinterpret_cast<const uint8_t*>(h->prev_ovl_pcm), h->prev_ovl_pcm_stride * sizeof(int16_t),
-                                                                      h->prev_ovl_audio_n * 2 * sizeof(int16_t), reinterpret_cast<const uint8_t*>(h->pcm_out),
-                                                                      h->pcm_out_stride * sizeof(int16_t), (size_t)A * 2 * sizeof(int16_t), c.n_streams));
+  // What the flag asks of the caller is checked where that is cheap, and a call right behind one design Q did not serve runs as if the flag were
+  // absent: fm_carry_overlap (sdrfm_fm_carry.h) has the terms and the reason for each.
+  const bool ovl = fm_carry_overlap(cy, g, cl, rows, q_ok, (call_flags & SDRFM_F_OVERLAP) != 0, with_chain, h->pcm_no_audio, c.n_streams) == FM_OVL_YES;
   if (!ovl) { const int jrc = join_overlap(h); if (jrc != SDRFM_OK) return jrc; }
   if (bx_all) {
     // A bit-exact kernel takes over from design Q: the y[-1] it is handed must be the definition's (design Q's own is within 1e-4 of it,
@@ -1672,13 +1633,12 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     // Only the streams design Q served at the previous call (the clean part of the list in use, as in route_apply): a routed stream's y[-1] IS
     // the definition's — its bit-exact kernel wrote it — and design Q left no raw samples for it (a call design Q cannot take behind
     // a mixed call overwrote it from stale rows; tests/test_route_gpu.py::test_a_call_design_q_cannot_take_behind_mixed_calls).
-    if (!h->yprev_exact && h->hist_q_valid) {
+    if (fm_carry_fix_yprev(cy)) {
       const uint32_t nn = rt.noisy ? rt.n_noisy : 0u;
-      HIP_TRY(sdrfm_q_fix_yprev(h->d_hist_q[h->cur], h->d_hpad, h->d_yprev[h->cur], c.n_streams - nn, nn ? h->rt_list_dev[rt.list_cur] : nullptr, h->stream),
+      HIP_TRY(sdrfm_q_fix_yprev(h->d_hist_q[cur], h->d_hpad, h->d_yprev[cur], c.n_streams - nn, nn ? h->rt_list_dev[rt.list_cur] : nullptr, h->stream),
               SDRFM_FAIL);
     }
-    h->yprev_exact = true; h->hist_q_valid = false; h->prev_by_q = false;
-    h->prev_ovl_audio = nullptr;
+    fm_carry_to_bx(cy);
   }
   const uint32_t* list_dev = (rt.noisy && n_noisy) ? h->rt_list_dev[rt.list_cur] : nullptr;   // [clean streams][noisy streams]
   bool behind_in = false;                                        // overlapped call: the handle's stream holds work the launches have to be ordered behind
@@ -1693,9 +1653,11 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     }
   }
   // the stream this call's launches go to: one of the two internal streams in turn (overlapped calls), or the handle's stream
-  hipStream_t qs = h->stream;
-  uint32_t k = 2;                                                 // its slot: internal stream 0 / 1, or 2 = the handle's stream
-  if (ovl) { k = h->ovl_next; h->ovl_next ^= 1u; qs = h->ovl_stream[k]; if (behind_in) HIP_TRY(hipStreamWaitEvent(qs, h->ovl_in, 0), SDRFM_FAIL); }
+  const FmSlot slot = fm_carry_slot(cy, ovl, behind_in);
+  const uint32_t k = slot.k;                                      // its slot: internal stream 0 / 1, or 2 = the handle's stream
+  const hipStream_t qs = ovl ? h->ovl_stream[k] : h->stream;
+  if (slot.wait_in) HIP_TRY(hipStreamWaitEvent(qs, h->ovl_in, 0), SDRFM_FAIL);
+  const FmPrev prev = fm_carry_prev(cy, ovl);                     // an overlapped call reads what lies before the call from the previous call's buffer
 
   // ---- the bit-exact launch: every stream (on the handle's stream), or the noisy streams of a mixed call — inside design Q's launch where k_mix has an
   // instance (fuse: only its parameters are prepared here), else a launch of their own ahead of design Q's on the call's stream
@@ -1710,7 +1672,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     // no state of the previous call — which may still be running on the other internal stream — is read
     const FmTiles t = fm_b_tiles(g, cl, n_noisy, split.bx_waves, true);
     pb.NA = t.NA; pb.tiles_per_stream = t.tiles_per_stream; pb.fold_state = t.fold_state; pb_blocks = t.grid;
-    if (ovl) { pb.iq_prev = h->prev_iq; pb.iq_prev_stride = h->prev_stride; pb.N_prev = h->prev_nbytes / 2; }
+    pb.iq_prev = prev.iq; pb.iq_prev_stride = prev.stride; pb.N_prev = prev.N;
     bx_name = h->fast_name;
   } else if (mixed) {
     // The noisy streams' launch goes ahead of design Q's on the call's own stream: no third stream (streams of one priority share a small pool of
@@ -1731,8 +1693,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
   if (q_ok) {
     const uint32_t q_steps = fm_q_steps(M);
     SdrfmQParams q;
-    q.iq_prev = nullptr; q.iq_prev_stride = 0; q.N_prev = 0;
-    if (ovl) { q.iq_prev = h->prev_iq; q.iq_prev_stride = h->prev_stride; q.N_prev = h->prev_nbytes / 2; }
+    q.iq_prev = prev.iq; q.iq_prev_stride = prev.stride; q.N_prev = prev.N;
     q.iq = d_iq; q.iq_stride = iq_stride; q.audio = d_audio; q.audio_stride = audio_stride;
     q.yprev_in = p.yprev_in; q.yprev_out = p.yprev_out; q.hist_d_in = p.hist_d_in; q.hist_d_out = p.hist_d_out;
     q.hist_b_in = p.hist_b_in; q.hist_b_out = p.hist_b_out; q.hist_x_out = p.hist_x_out;
@@ -1741,11 +1702,12 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     q.slist = list_dev;                                           // (its first n_clean entries)
     // the guard's repair path reads the last 64 raw samples before the call: left by the previous design-Q call, or taken now from the
     // T - 1 the other kernels keep (the 64th, which only y[-1] needs, is then not there — nor needed: their y[-1] is the definition's)
-    if (!h->hist_q_valid && !ovl && c.fir_taps > 1)
-      HIP_TRY(hipMemcpy2DAsync(h->d_hist_q[h->cur] + 2 * (SDRFM_Q_TP - (c.fir_taps - 1)), 2 * SDRFM_Q_TP, p.hist_b_in, 2 * (size_t)(c.fir_taps - 1),
+    const FmQPre pre = fm_carry_q_pre(cy, ovl, c.fir_taps);
+    if (pre.refill_hist_q)
+      HIP_TRY(hipMemcpy2DAsync(h->d_hist_q[cur] + 2 * (SDRFM_Q_TP - (c.fir_taps - 1)), 2 * SDRFM_Q_TP, p.hist_b_in, 2 * (size_t)(c.fir_taps - 1),
                                2 * (size_t)(c.fir_taps - 1), c.n_streams, hipMemcpyDeviceToDevice, h->stream), SDRFM_FAIL);
-    q.hpad = h->d_hpad; q.hist_q_in = h->d_hist_q[h->cur]; q.hist_q_out = h->d_hist_q[h->cur ^ 1];
-    q.guard_r = h->q_guard_r; q.guard_a = h->q_guard_a; q.seed = h->q_seed; q.guard_rq = h->q_guard_r / h->q_scale; q.yprev_exact = h->yprev_exact ? 1u : 0u; q.n_repaired = h->d_qstat;
+    q.hpad = h->d_hpad; q.hist_q_in = h->d_hist_q[cur]; q.hist_q_out = h->d_hist_q[cur ^ 1];
+    q.guard_r = h->q_guard_r; q.guard_a = h->q_guard_a; q.seed = h->q_seed; q.guard_rq = h->q_guard_r / h->q_scale; q.yprev_exact = pre.yprev_exact ? 1u : 0u; q.n_repaired = h->d_qstat;
     const FmRuns r = fm_q_runs(cl, split.q_total, n_clean, with_chain, h->runstate_cap, fm_chain_run_quads(g.Da));
     q.runs = r.runs;
     // The counter set of the routing window this call adds to, and the stop event its kernel carries (fm_route_stop): one of the window's, or the overlap's.
@@ -1755,8 +1717,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     // event also stands for the window's kernels on it.  A caller that joins once in a while (sdrfm_flush at the end of a burst: bench.py) keeps kernels without a
     // stop event and pays one marker per join: under the kernel tracer a stop event on every kernel shortens the time two kernels are resident (0.96 -> 0.75 of a
     // 100-call burst, +3 % per call; un-profiled within the noise): profiles/r05_q_experiments.txt item 15.
-    const bool carry = ovl && h->ovl_join_style;
-    const FmRouteStop stop = fm_route_stop(rt, counting, k, carry);
+    const FmRouteStop stop = fm_route_stop(rt, counting, k, pre.carry);
     q.stream_pass = counting ? h->rt_pass_dev[stop.set] : nullptr;
     const hipEvent_t done = stop.evt == FM_ROUTE_OVL_DONE ? h->ovl_done[k] : stop.evt == FM_ROUTE_WINDOW_EVENT ? h->rt_win_evt[stop.set][k] : nullptr;
     with_chain = r.with_chain;
@@ -1777,10 +1738,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     else if (with_chain) HIP_TRY(sdrfm_q_launch_pcm(q, chain, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, qs, done), SDRFM_FAIL);
     else HIP_TRY(sdrfm_q_launch(q, h->q_c0, h->q_nslot, c.fir_decim, c.audio_decim, qs, done), SDRFM_FAIL);
     if (with_chain) { sdrfm_sink_chain_issued(h->pcm_sink); h->pcm_fused = true; }
-    if (ovl) { h->ovl_pending[k] = true; h->ovl_bound[k] = carry; }
-    h->prev_ovl_audio = (ovl && !(with_chain && h->pcm_no_audio)) ? d_audio : nullptr; h->prev_ovl_audio_stride = audio_stride; h->prev_ovl_audio_n = A;
-    h->prev_ovl_pcm = (ovl && with_chain) ? h->pcm_out : nullptr; h->prev_ovl_pcm_stride = h->pcm_out_stride;
-    h->yprev_exact = false; h->hist_q_valid = true; h->prev_by_q = true;
+    fm_carry_q_launched(cy, ovl, k, pre.carry, rows, A, with_chain, h->pcm_no_audio);
     // ---- the window close ----------------------------------------------------------------------------------------------------------------------
     if (counting && fm_route_count(rt, fm_win_stages(r.runs, q_steps, c.audio_decim))) { const int wrc = route_window_close(h); if (wrc != SDRFM_OK) return wrc; }
     snprintf(q_name, sizeof(q_name), "%s%s%s", h->fast_q_name, ovl ? " overlapped" : "", h->pcm_fused ? " + pcm" : "");
@@ -1793,7 +1751,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
     snprintf(h->kernel_name, sizeof(h->kernel_name), "%s", bx_all ? bx_name : q_name);
   }
   // ---- the first-call fix-up -------------------------------------------------------------------------------------------------------------------
-  if (halo_bytes && h->n_seen + 1 < c.fir_taps) {
+  if (halo_bytes && cl.n_seen + 1 < c.fir_taps) {
     // Designs Q, B and S read their halo as bytes, which cannot express the zero history at the start of a stream: the few audio
     // outputs that depend on inputs before the first real sample are recomputed by the generic kernel (tile 0..k only), for every stream
     // (a call this early is never overlapped, so the handle's stream is behind every launch above).
@@ -1804,12 +1762,7 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
   }
   HIP_TRY(hipGetLastError(), SDRFM_FAIL);
 
-  h->cur ^= 1;
-  h->n_seen += N;
-  if (call_flags & SDRFM_F_DEVICE_PTRS) { h->prev_iq = d_iq; h->prev_stride = iq_stride; h->prev_nbytes = nbytes; }
-  else h->prev_iq = nullptr;
-  h->phase_x = n.phase_x;
-  h->phase_d = n.phase_d;
+  fm_carry_advance(cy, n, rows, (call_flags & SDRFM_F_DEVICE_PTRS) != 0);
   return SDRFM_OK;
 }
 

@@ -3,7 +3,7 @@
  * "Which kernel serves a stream at which call is a function of the bytes and the call sequence alone" is a property of the header's integers; the GPU tests
  * need 1 200 calls to see one back-off expire and cannot place a reset, a mask or a late read-back where they hurt.  Here the header is driven the way
  * csrc/sdrfm.hip drives it (Sim: intake, who serves, the kernel's stop event, the count, the close — with fm_serve of csrc/sdrfm_fm_call.h deciding who
- * serves, on the geometry the library plans: fm_geom.h) against an emulated device: streams as kernel counts, events as positions in them, counter sets,
+ * serves, on the geometry the library plans: fm_geom.h; csrc/sdrfm_fm_carry.h deciding which calls overlap, their slots and the joins) against an emulated device: streams as kernel counts, events as positions in them, counter sets,
  * and a queue of read-backs of which the TEST decides when each one arrives.
  *   known answers   from the constants and from what tests/test_route_gpu.py holds on hardware (calls 64, 1088, 1152; window 68 closes at call 1103), the
  *                   list's order, the strict threshold, the call patterns that need no event record — literals here, not the header's macros
@@ -17,7 +17,7 @@
 #include <deque>
 #include <vector>
 
-#include "../../stm32f7-rtlsdr_amd/csrc/sdrfm_fm_call.h"
+#include "../../stm32f7-rtlsdr_amd/csrc/sdrfm_fm_carry.h"
 #include "../../stm32f7-rtlsdr_amd/csrc/sdrfm_fm_route.h"
 #include "fm_geom.h"
 
@@ -63,7 +63,7 @@ struct Sim {
   Arrival arrival; Rng arrive_rng;
   uint64_t pos[3];                                               // kernels on internal stream 0, 1, the handle's stream
   Event win_evt[4][3], ovl_done[2];
-  bool ovl_pending[2], ovl_bound[2], join_style, prev_q; uint32_t ovl_next;
+  FmCarry cy;                                                    // the handle's carried state: the header's functions keep it, as in sdrfm.hip
   // the test's own account
   uint64_t epoch, window, call, taken;                           // resets so far; windows closed / calls made / read-backs taken in since the last one
   uint32_t my_win_calls;
@@ -84,7 +84,7 @@ struct Sim {
     for (int i = 0; i < 4; ++i) { pass_dev[i].assign(ns, 0); pass_host[i].assign(ns, 0xdeadbeef); }
     for (int v = 0; v < 2; ++v) { list[v].assign(ns, ~0u); list_clean[v] = 0; }
     memset(pos, 0, sizeof(pos)); memset(win_evt, 0, sizeof(win_evt)); memset(ovl_done, 0, sizeof(ovl_done)); memset(win_last, 0, sizeof(win_last));
-    ovl_pending[0] = ovl_pending[1] = ovl_bound[0] = ovl_bound[1] = join_style = prev_q = false; ovl_next = 0;
+    memset(&cy, 0, sizeof(cy));
     epoch = window = call = taken = 0; my_win_calls = 0; have_mask = false; records = forced = 0;
     reset();
   }
@@ -106,15 +106,16 @@ struct Sim {
       if (!rb.arrived) { if (arrival == AT_ONCE || (arrival == AT_RANDOM && arrive_rng.one_in(24))) deliver(rb); else break; }
   }
   void record(Event& e, int slot) { e = Event{slot, pos[slot], false, window}; }
-  void join_overlap() {
-    for (int k = 0; k < 2; ++k)
-      if (ovl_pending[k]) { if (!ovl_bound[k]) record(ovl_done[k], k); ovl_pending[k] = false; }
+  void join(FmJoinKind kind) {                                   // sdrfm.hip's join(): the waits move no event
+    const FmJoin j = fm_carry_join(cy, kind);
+    for (uint32_t k = 0; k < 2; ++k) { if (j.record[k]) record(ovl_done[k], (int)k); if (j.wait[k]) fm_carry_joined(cy, kind, k); }
   }
-  void flush_previous() { const uint32_t k = ovl_next; join_style = true; if (ovl_pending[k]) { if (!ovl_bound[k]) record(ovl_done[k], k); ovl_pending[k] = false; } }
-  void wait_previous() { const uint32_t k = ovl_next; join_style = true; if (ovl_pending[k] && !ovl_bound[k]) { record(ovl_done[k], k); ovl_bound[k] = true; } }
+  void join_overlap() { join(FM_JOIN_ALL); }
+  void flush_previous() { join(FM_JOIN_PREVIOUS); }
+  void wait_previous() { join(FM_JOIN_PREVIOUS_ON_CALLER); }
 
   void reset() {                                                 // sdrfm_reset: joins and synchronises, then route_reset
-    join_overlap(); prev_q = false;
+    join_overlap(); fm_carry_reset(cy);
     fm_route_reset(r);
     for (int i = 0; i < 4; ++i) pass_dev[i].assign(ns, 0);
     queue.clear();
@@ -122,7 +123,7 @@ struct Sim {
     close_call.clear();
   }
   void apply() {                                                 // route_apply
-    join_overlap();
+    join_overlap(); fm_carry_assigned(cy);
     const int cur = r.list_cur; const uint32_t nn = r.n_noisy;
     const FmRouteList l = fm_route_list_begin(r);
     CHECK(l.v == (cur ^ 1), "the list in use is rewritten");
@@ -162,7 +163,7 @@ struct Sim {
   }
 
   void close() {                                                 // route_window_close
-    const FmRouteClose cw = fm_route_close(r, ovl_bound[0], ovl_bound[1]);
+    const FmRouteClose cw = fm_route_close(r, cy.ovl_bound[0], cy.ovl_bound[1]);
     CHECK(cw.set == window % kSets, "window %" PRIu64 " closes set %u", window, cw.set);
     uint64_t what = cw.set;
     for (int k = 0; k < 3; ++k) {
@@ -204,15 +205,16 @@ struct Sim {
     fm_route_count_call(r);
     uint64_t what = mix64(sv.q_ok * 8 + sv.mixed * 4 + sv.fuse * 2 + 1);
     for (uint32_t s = 0; s < ns; ++s) what = mix64(what ^ r.noisy[s]);
-    const bool ovl = sv.q_ok && want_ovl && prev_q;
+    // (three input buffers in turn, no audio rows: only who served the previous call can refuse the flag; c carries the position, the carry only the rest)
+    const FmRows rows = {reinterpret_cast<const uint8_t*>((uintptr_t)(call % 3 + 1) << 28), 2 * (size_t)c.N, 2 * c.N, nullptr, 0, nullptr, 0};
+    const bool ovl = fm_carry_overlap(cy, g, c, rows, sv.q_ok, want_ovl, false, false, ns) == FM_OVL_YES;
     if (!ovl) join_overlap();
-    if (sv.bx_all) prev_q = false;
-    uint32_t k = 2;
-    if (ovl) { k = ovl_next; ovl_next ^= 1u; }
+    if (sv.bx_all) fm_carry_to_bx(cy);
+    const uint32_t k = fm_carry_slot(cy, ovl, false).k;
     if (sv.mixed && !sv.fuse) (void)fm_route_bx_take(r);
     if (sv.q_ok) {
       const uint64_t at = ++pos[k];                              // the design-Q kernel
-      const bool carry = ovl && join_style;
+      const bool carry = fm_carry_q_pre(cy, ovl, g.T).carry;
       const FmRouteStop stop = fm_route_stop(r, true, k, carry);
       what = mix64(what ^ (stop.evt * 4 + stop.set));
       // (b) no set is counted into while its read-back is under way
@@ -231,13 +233,13 @@ struct Sim {
       if (stop.evt == FM_ROUTE_OVL_DONE) { CHECK(carry && k < 2, "slot %u", k); ovl_done[k < 2 ? k : 0] = Event{(int)k, at, true, window}; }
       CHECK(stop.evt != FM_ROUTE_NO_EVENT || (!carry && my_win_calls + 2 < kWindow), "call %u of its window carries no event", my_win_calls);
       win_last[k] = at;
-      if (ovl) { ovl_pending[k] = true; ovl_bound[k] = carry; }
-      prev_q = true;
+      fm_carry_q_launched(cy, ovl, k, carry, rows, c.A, false, false);
       const bool closes = fm_route_count(r, stages);
       ++my_win_calls;
       CHECK(closes == (my_win_calls == kWindow), "call %u of its window %s", my_win_calls, closes ? "closes it" : "does not close it");
       if (closes) close();
     }
+    fm_carry_advance(cy, FmCounts{c.N, c.M, c.A, 0, 0}, rows, true);
     trace.push_back(what);
     ++call;
     return sv.q_ok;
@@ -308,7 +310,7 @@ static void play(Sim& sim, const std::vector<Action>& acts, size_t from, size_t*
     else if (a.kind == 2) sim.wait_previous();
     else if (a.kind == 3) {
       sim.reset();
-      if (reset_at) { *reset_at = i; *at_reset = OvlState{{sim.ovl_bound[0], sim.ovl_bound[1]}, sim.join_style, sim.ovl_next}; *trace_at_reset = sim.trace.size(); }
+      if (reset_at) { *reset_at = i; *at_reset = OvlState{{sim.cy.ovl_bound[0], sim.cy.ovl_bound[1]}, sim.cy.ovl_join_style, sim.cy.ovl_next}; *trace_at_reset = sim.trace.size(); }
     } else {
       Rng m{a.seed};
       std::vector<uint8_t> mask(sim.ns);
@@ -349,7 +351,7 @@ static void one_case(uint64_t seed, bool long_run) {
   // state, which a reset keeps, given to it)
   if (had_reset) {
     Sim sim(ns, AT_RANDOM, seed, 0);
-    sim.ovl_bound[0] = ovl_at_reset.bound[0]; sim.ovl_bound[1] = ovl_at_reset.bound[1]; sim.join_style = ovl_at_reset.join_style; sim.ovl_next = ovl_at_reset.next;
+    sim.cy.ovl_bound[0] = ovl_at_reset.bound[0]; sim.cy.ovl_bound[1] = ovl_at_reset.bound[1]; sim.cy.ovl_join_style = ovl_at_reset.join_style; sim.cy.ovl_next = ovl_at_reset.next;
     for (size_t i = 0; i <= reset_at; ++i) sim.epoch += acts[i].kind == 3;   // (the noise of the windows after THAT reset)
     play(sim, acts, reset_at + 1, nullptr, nullptr, nullptr);
     CHECK(sim.trace.size() + trace_at_reset == first.size() && std::equal(sim.trace.begin(), sim.trace.end(), first.begin() + (long)trace_at_reset),

@@ -185,3 +185,74 @@ def test_broken_promises_fall_back_to_serial_calls(pkg, oracle_mod, tol):
     for s in (0, 100, 255):
         want = oracle_mod.Oracle(h, g).process(np.concatenate([x[s] for x in host]))
         assert scaled_err(got[s], want) <= tol
+
+
+# ---- the joins a caller sees: sdrfm_flush, sdrfm_flush_previous, sdrfm_wait_previous, sdrfm_reset ----------------------------------------------------
+JOIN_NS, JOIN_NSAMP, JOIN_CALLS = 264, 1600, 6                      # the smallest shape design Q takes on 256 CUs (tests/fm_shape_cases.py), 32 audio outputs a call
+
+
+@pytest.fixture(scope="module")
+def join_burst(pkg):
+    """Six calls' input on the device and what the same calls give made one after the other: straight through, and with a reset behind the third."""
+    import torch
+    iqs = [torch.from_numpy(pkg.make_iq(JOIN_NS, JOIN_NSAMP, mode=("fm", "random")[b & 1], first_id=1300 + 7 * b)).cuda() for b in range(JOIN_CALLS)]
+    torch.cuda.synchronize()
+    want = {}
+    for reset_at in (None, 3):
+        out = [torch.full((JOIN_NS, JOIN_NSAMP // 50), float("nan"), dtype=torch.float32, device="cuda") for _ in range(JOIN_CALLS)]
+        with _handles(pkg, JOIN_NS) as ref:
+            for b in range(JOIN_CALLS):
+                if b == reset_at:
+                    ref.reset()
+                assert ref.process_batch_device(iqs[b], out[b]) == JOIN_NSAMP // 50
+                assert ref.kernel_name.startswith("fast-q") and "overlapped" not in ref.kernel_name
+            ref.synchronize()
+        want[reset_at] = [o.cpu().numpy() for o in out]
+        assert all(np.isfinite(w).all() for w in want[reset_at])
+    return iqs, want
+
+
+@pytest.mark.parametrize("join", ["flush", "flush_previous", "wait_previous", "reset"])
+def test_six_overlapped_calls_equal_serial_calls_under_every_join(pkg, join_burst, join):
+    """What a caller sees of the three joins and of a reset in the middle of a burst: every call's audio, read by a consumer that is ordered behind the call
+    by that join alone (a copy on the handle's stream, or on a stream of the consumer's own for sdrfm_wait_previous), is bit for bit the serial calls'."""
+    import torch
+    iqs, want_all = join_burst
+    want = want_all[3 if join == "reset" else None]
+    A, nb = JOIN_NSAMP // 50, JOIN_CALLS
+    two = join in ("flush_previous", "wait_previous")              # a join after every call: two audio buffers in turn; else one per call
+    audio = [torch.full((JOIN_NS, A), float("nan"), dtype=torch.float32, device="cuda") for _ in range(2 if two else nb)]
+    res = [torch.full((JOIN_NS, A), float("nan"), dtype=torch.float32, device="cuda") for _ in range(nb)]
+    torch.cuda.synchronize()
+    st, consumer = torch.cuda.Stream(), torch.cuda.Stream()
+    names = []
+    with _handles(pkg, JOIN_NS) as dm:
+        dm.set_stream(st.cuda_stream)
+
+        def take(b, on):                                               # the consumer of call b's audio
+            with torch.cuda.stream(on):
+                res[b].copy_(audio[b & 1 if two else b], non_blocking=True)
+
+        for b in range(nb):
+            if join == "reset" and b == 3:
+                dm.reset()
+            if join == "wait_previous" and b >= 2:
+                st.wait_stream(consumer)                               # (call b rewrites the rows call b - 2's consumer reads: it is ordered behind the handle's stream)
+            assert dm.process_batch_device(iqs[b], audio[b & 1 if two else b], overlap=True) == A
+            names.append(dm.kernel_name)
+            if join == "flush_previous" and b:
+                dm.flush(keep_last=True)
+                take(b - 1, st)
+            if join == "wait_previous" and b:
+                dm.wait_previous(consumer.cuda_stream)
+                take(b - 1, consumer)
+        dm.flush()
+        for b in (range(nb) if not two else [nb - 1]):
+            take(b, st)
+        st.synchronize(); consumer.synchronize()
+    first = (0, 3) if join == "reset" else (0,)                     # nothing to warm up from: served as an ordinary call (fm_shape_cases: canary-q-overlapped)
+    for b, n in enumerate(names):
+        assert n.startswith("fast-q") and ("overlapped" in n) == (b not in first), (b, names)
+    for b in range(nb):
+        a = res[b].cpu().numpy()
+        assert np.array_equal(a.view(np.uint32), want[b].view(np.uint32)), (join, b, int(np.argmax((a != want[b]).any(axis=0))))
