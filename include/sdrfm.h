@@ -303,6 +303,10 @@ int  sdrfm_stereo_audio_count(const sdrfm_stereo_t* h, uint32_t nbytes, uint32_t
 /* left / right for stream s at left + s*audio_stride, right + s*audio_stride (floats) */
 int  sdrfm_stereo_process_batch(sdrfm_stereo_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left, float* right,
                                 size_t audio_stride, uint32_t* pilot_count, uint32_t* n_audio, uint32_t flags);
+/* sdrfm_stereo_set_stream, and sdrfm_rds_set_stream, sdrfm_bcast_set_stream and sdrfm_scan_set_stream likewise: run on a caller-owned HIP stream
+ * (NULL: the handle's own again).  The call WAITS for the stream in use before it switches, as the PCM-side handles' set_stream does: a launch on the
+ * old stream may still read the taps and write the carried state that a tune, a reset or a call behind the switch replaces.  _reset zeroes the
+ * carried state in stream order and waits for the stream; _synchronize waits for it. */
 int  sdrfm_stereo_set_stream(sdrfm_stereo_t* h, void* hip_stream);
 int  sdrfm_stereo_synchronize(sdrfm_stereo_t* h);
 const char* sdrfm_stereo_kernel_name(const sdrfm_stereo_t* h);
@@ -360,7 +364,7 @@ int  sdrfm_rds_count(const sdrfm_rds_t* h, uint32_t nbytes, uint32_t* n_out);
 /* bb for stream s at bb + s*bb_stride (floats; 2 per output: bb_stride >= 2 * n_out) */
 int  sdrfm_rds_process_batch(sdrfm_rds_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* bb, size_t bb_stride,
                              uint32_t* pilot_count, uint32_t* n_out, uint32_t flags);
-int  sdrfm_rds_set_stream(sdrfm_rds_t* h, void* hip_stream);
+int  sdrfm_rds_set_stream(sdrfm_rds_t* h, void* hip_stream);   /* waits for the stream in use, then switches: see sdrfm_stereo_set_stream */
 int  sdrfm_rds_synchronize(sdrfm_rds_t* h);
 const char* sdrfm_rds_kernel_name(const sdrfm_rds_t* h);
 
@@ -451,7 +455,7 @@ int  sdrfm_bcast_counts(const sdrfm_bcast_t* h, uint32_t nbytes, uint32_t* n_aud
 int  sdrfm_bcast_process_batch(sdrfm_bcast_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, float* left, float* right,
                                size_t audio_stride, float* bb, size_t bb_stride, uint32_t* pilot_count, uint32_t* n_audio,
                                uint32_t* n_rds, uint32_t flags);
-int  sdrfm_bcast_set_stream(sdrfm_bcast_t* h, void* hip_stream);
+int  sdrfm_bcast_set_stream(sdrfm_bcast_t* h, void* hip_stream);   /* waits for the stream in use, then switches: see sdrfm_stereo_set_stream */
 int  sdrfm_bcast_synchronize(sdrfm_bcast_t* h);
 const char* sdrfm_bcast_kernel_name(const sdrfm_bcast_t* h);
 
@@ -545,7 +549,7 @@ void sdrfm_scan_destroy(sdrfm_scan_t* h);
 int  sdrfm_scan_reset(sdrfm_scan_t* h);
 int  sdrfm_scan_tune(sdrfm_scan_t* h, const float* ctaps, const float* rot);
 int  sdrfm_scan_process_batch(sdrfm_scan_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, sdrfm_scan_meter* meters, uint32_t flags);
-int  sdrfm_scan_set_stream(sdrfm_scan_t* h, void* hip_stream);
+int  sdrfm_scan_set_stream(sdrfm_scan_t* h, void* hip_stream);   /* waits for the stream in use, then switches: see sdrfm_stereo_set_stream */
 int  sdrfm_scan_synchronize(sdrfm_scan_t* h);
 const char* sdrfm_scan_kernel_name(const sdrfm_scan_t* h);
 
@@ -766,8 +770,21 @@ int  sdrfm_pcm_stereo_sink_get_state(sdrfm_pcm_stereo_sink_t* k, float* state_ou
  * sdrfm_pcm_stereo_sink_process_batch against this call's n_audio (NULL only when that is 0); every other argument as by the handle's own call.  With
  * SDRFM_F_DEVICE_PTRS every buffer is device memory and the call only enqueues; with host buffers the PCM is copied back beside the rest and the call is
  * synchronous.  Every check is made before anything is enqueued: a refused call leaves the handle and the sink as they were.
- * These calls launch the sink on the HANDLE's stream and ignore sdrfm_pcm_stereo_sink_set_stream: do not mix the two on one sink without giving both the same
- * stream or synchronising between them, and call sdrfm_pcm_stereo_sink_get_state, _reset and _destroy only after the handle's _synchronize. */
+ * These calls launch the sink — and behind it the audio, loudness and true-peak meter kernels of a sink that has them enabled — on the HANDLE's stream
+ * and ignore sdrfm_pcm_stereo_sink_set_stream, while every control call of the sink waits for, and enqueues on, the SINK's stream.  Two arrangements
+ * are in order.  Either both are given the SAME caller's stream (sdrfm_*_set_stream on the handle and sdrfm_pcm_stereo_sink_set_stream on the sink):
+ * the sink's stream is then the one the launches are on, and every control call waits or enqueues as its own paragraph says, with calls pending.
+ * Or the sink's control calls are made only after the handle's _synchronize.  That holds for EVERY control call of the sink, by what it does:
+ *   read      _get_state, _meter_read, _truepeak_read (host or device out), _loudness_read, _loudness_get_state: else the copy is made before the
+ *             launch has run;
+ *   replace   _set_hicut, _meter_enable (the threshold), sdrfm_pcm_stereo_sink_process_batch on the same sink: else records and states that a
+ *             pending launch still reads are replaced under it;
+ *   zero      _reset, _meter_enable on an enabled sink, a _meter_read or _truepeak_read with SDRFM_AMETER_F_RESET: else the zeroes land in front
+ *             of the launch and the launch's sums stay in the records;
+ *   free      _meter_disable, _loudness_enable on an enabled sink, _loudness_disable, _truepeak_enable on an enabled sink, _truepeak_disable,
+ *             _destroy: else memory a pending launch uses is freed.
+ * _get_hicut and the sink's other answers from host memory touch no device and may be called at any time.  tests/test_stream_order_front_gpu.py
+ * holds the first arrangement with a call pending. */
 int  sdrfm_stereo_process_batch_pcm(sdrfm_stereo_t* h, sdrfm_pcm_stereo_sink_t* sink, const uint8_t* iq, size_t iq_stride, uint32_t nbytes,
                                     float* left, float* right, size_t audio_stride, int16_t* pcm, size_t pcm_stride,
                                     uint32_t* pilot_count, uint32_t* n_audio, uint32_t flags);
@@ -951,7 +968,7 @@ int  sdrfm_bcast_get_audio(const sdrfm_bcast_t* h, uint16_t* blend_q15, uint16_t
  * sdrfm_pcm_stereo_sink_get_hicut gives, per stream, the value the next sample starts from and the target; *slew_q15 is 0 on a sink that is not
  * conditioned.  Any pointer may be NULL.  It touches no device.
  * Around the one-call forms, which launch on the HANDLE's stream, call set and get only after the handle's _synchronize — the rule of
- * sdrfm_pcm_stereo_sink_get_state. */
+ * the one-call forms at sdrfm_stereo_process_batch_pcm, which also allows them with both on one caller's stream. */
 #define SDRFM_HICUT_MIN 1024u
 int  sdrfm_pcm_deemph_stereo_hicut_s16(const float* left, const float* right, uint32_t n, float alpha, float gain, uint16_t h0, uint16_t ht,
                                        uint32_t slew, uint32_t J, float* state, int16_t* pcm_stereo);
@@ -1004,7 +1021,7 @@ int  sdrfm_pcm_stereo_sink_get_hicut(const sdrfm_pcm_stereo_sink_t* k, uint16_t*
  * the PCM rows just written and joins the call's record onto each stream's.  The sink kernels are the same kernels with the same arguments:
  * PCM, states and high-cut ramps keep their bits.  What lies in a row behind 2n is the caller's: it is neither read nor written.
  * Around the one-call forms, which launch on the HANDLE's stream, call enable, disable and read only after the handle's _synchronize — the
- * rule of sdrfm_pcm_stereo_sink_get_state. */
+ * rule of the one-call forms at sdrfm_stereo_process_batch_pcm, which also allows them with both on one caller's stream. */
 typedef struct sdrfm_audio_runs { uint64_t count, lead, trail, longest; } sdrfm_audio_runs;   /* 32 bytes */
 typedef struct sdrfm_audio_meter {                 /* 192 bytes, 8-byte aligned */
   uint64_t n;                                       /* sample pairs */
@@ -1178,7 +1195,7 @@ int  sdrfm_pcm_rate_check_coef(const int16_t* coef, uint32_t n_taps, uint32_t lo
  * own figures; for other sets of the domain the predicate's margin is the only statement.  pos and the block bookkeeping
  * are exact.
  * Around the one-call forms, which launch on the HANDLE's stream, call enable, disable, read and get_state only after the handle's _synchronize
- * — the rule of sdrfm_pcm_stereo_sink_get_state. */
+ * — the rule of the one-call forms at sdrfm_stereo_process_batch_pcm, which also allows them with both on one caller's stream. */
 typedef struct sdrfm_loudness_coef { double c[10]; } sdrfm_loudness_coef;                              /* shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2 */
 typedef struct sdrfm_loudness_state { uint64_t pos; double z[2][4]; double e[2]; } sdrfm_loudness_state;   /* 88 bytes */
 typedef struct sdrfm_loudness_block { double e_l, e_r; } sdrfm_loudness_block;                         /* 16 bytes */
@@ -1255,7 +1272,7 @@ int  sdrfm_pcm_stereo_sink_loudness_get_state(sdrfm_pcm_stereo_sink_t* k, sdrfm_
  * lane takes a pair's P phases of both channels as packed 16-bit dot products, each half-row into an int32 and the two halves summed in 64
  * bits; per channel one 64-bit key (peak << 32 | ~index) reduced by max over lanes, waves and the workgroup — no atomics.
  * Around the one-call forms, which launch on the HANDLE's stream, call enable, disable and read only after the handle's _synchronize — the rule
- * of sdrfm_pcm_stereo_sink_get_state. */
+ * of the one-call forms at sdrfm_stereo_process_batch_pcm, which also allows them with both on one caller's stream. */
 typedef struct sdrfm_truepeak {                    /* 64 bytes, 8-byte aligned */
   uint64_t n;
   uint64_t peak_l, peak_r;
@@ -1475,7 +1492,7 @@ int  sdrfm_iq_meter_create(const sdrfm_iq_meter_config* cfg, sdrfm_iq_meter_t** 
 void sdrfm_iq_meter_destroy(sdrfm_iq_meter_t* h);
 int  sdrfm_iq_meter_process_batch(sdrfm_iq_meter_t* h, const uint8_t* iq, size_t iq_stride, uint32_t nbytes, sdrfm_iq_meter* meters,
                                   uint32_t* hist /* n_streams x SDRFM_IQ_HIST_BINS, or NULL */, uint32_t flags);
-int  sdrfm_iq_meter_set_stream(sdrfm_iq_meter_t* h, void* hip_stream);
+int  sdrfm_iq_meter_set_stream(sdrfm_iq_meter_t* h, void* hip_stream);   /* does NOT wait for the stream in use (every call stands alone): synchronise first */
 int  sdrfm_iq_meter_synchronize(sdrfm_iq_meter_t* h);
 const char* sdrfm_iq_meter_kernel_name(const sdrfm_iq_meter_t* h);
 

@@ -643,8 +643,7 @@ int sdrfm_bcast_process_batch_metered_hist(sdrfm_bcast_t* h, sdrfm_pcm_stereo_si
 
 int sdrfm_bcast_set_stream(sdrfm_bcast_t* h, void* hip_stream) {
   if (!h) return SDRFM_EINVAL;
-  h->f.stream = hip_stream ? (hipStream_t)hip_stream : h->f.own_stream;
-  return SDRFM_OK;
+  return front_use_stream(h->f, hip_stream);
 }
 
 int sdrfm_bcast_synchronize(sdrfm_bcast_t* h) {

@@ -438,6 +438,14 @@ int front_reset(PilotFront& f) {
   return SDRFM_OK;
 }
 
+// waits for the stream in use, then switches: hip_stream, or NULL for the handle's own (as host_stream_use does for the PCM-side handles).  A
+// launch on the old stream may still read the taps and write the state that a tune, a reset or a call behind the switch replaces
+int front_use_stream(PilotFront& f, void* hip_stream) {
+  if (hipSetDevice(f.device) != hipSuccess || hipStreamSynchronize(f.stream) != hipSuccess) return SDRFM_FAIL;
+  f.stream = hip_stream ? (hipStream_t)hip_stream : f.own_stream;
+  return SDRFM_OK;
+}
+
 // a step geometry and its LDS bytes
 struct FrontStep {
   uint32_t NY, NDT, region_words;

@@ -244,8 +244,7 @@ int sdrfm_rds_process_batch(sdrfm_rds_t* h, const uint8_t* iq, size_t iq_stride,
 
 int sdrfm_rds_set_stream(sdrfm_rds_t* h, void* hip_stream) {
   if (!h) return SDRFM_EINVAL;
-  h->f.stream = hip_stream ? (hipStream_t)hip_stream : h->f.own_stream;
-  return SDRFM_OK;
+  return front_use_stream(h->f, hip_stream);
 }
 
 int sdrfm_rds_synchronize(sdrfm_rds_t* h) {

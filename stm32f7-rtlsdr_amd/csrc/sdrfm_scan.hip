@@ -336,8 +336,7 @@ int sdrfm_scan_process_batch_hist(sdrfm_scan_t* h, const uint8_t* iq, size_t iq_
 
 int sdrfm_scan_set_stream(sdrfm_scan_t* h, void* hip_stream) {
   if (!h) return SDRFM_EINVAL;
-  h->f.stream = hip_stream ? (hipStream_t)hip_stream : h->f.own_stream;
-  return SDRFM_OK;
+  return front_use_stream(h->f, hip_stream);
 }
 
 int sdrfm_scan_synchronize(sdrfm_scan_t* h) {

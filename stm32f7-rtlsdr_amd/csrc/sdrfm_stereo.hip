@@ -279,8 +279,7 @@ int sdrfm_stereo_process_batch_pcm(sdrfm_stereo_t* h, sdrfm_pcm_stereo_sink_t* s
 
 int sdrfm_stereo_set_stream(sdrfm_stereo_t* h, void* hip_stream) {
   if (!h) return SDRFM_EINVAL;
-  h->f.stream = hip_stream ? (hipStream_t)hip_stream : h->f.own_stream;
-  return SDRFM_OK;
+  return front_use_stream(h->f, hip_stream);
 }
 
 int sdrfm_stereo_synchronize(sdrfm_stereo_t* h) {
