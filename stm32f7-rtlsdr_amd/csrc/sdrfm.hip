@@ -1708,7 +1708,11 @@ static int enqueue(sdrfm* h, const uint8_t* d_iq, size_t iq_stride, uint32_t nby
                                2 * (size_t)(c.fir_taps - 1), c.n_streams, hipMemcpyDeviceToDevice, h->stream), SDRFM_FAIL);
     q.hpad = h->d_hpad; q.hist_q_in = h->d_hist_q[cur]; q.hist_q_out = h->d_hist_q[cur ^ 1];
     q.guard_r = h->q_guard_r; q.guard_a = h->q_guard_a; q.seed = h->q_seed; q.guard_rq = h->q_guard_r / h->q_scale; q.yprev_exact = pre.yprev_exact ? 1u : 0u; q.n_repaired = h->d_qstat;
-    const FmRuns r = fm_q_runs(cl, split.q_total, n_clean, with_chain, h->runstate_cap, fm_chain_run_quads(g.Da));
+    // Overlapped plain calls are cut for whole audio stages (fewer, longer runs: two calls are resident together); serial calls, the PCM chain's and mixed
+    // launches keep the count that fills the machine once.  Whatever depends on the count follows it: the window's stages below, the chain's slots, q.runs.
+    const bool staged = prev.iq != nullptr && !with_chain && !mixed;
+    const FmRuns r = fm_q_runs(cl, split.q_total, n_clean, with_chain, h->runstate_cap, fm_chain_run_quads(g.Da), staged, g.Da, SDRFM_Q_PARK_STAGES,
+                               (uint64_t)g.q_lds_waves_per_cu * g.n_cu);
     q.runs = r.runs;
     // The counter set of the routing window this call adds to, and the stop event its kernel carries (fm_route_stop): one of the window's, or the overlap's.
     // For a caller that joins after every call (sdrfm_flush_previous: the consumer loop of INTEGRATION.md) an overlapped call's kernel carries its internal

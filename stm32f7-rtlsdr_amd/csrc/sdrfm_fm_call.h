@@ -30,6 +30,7 @@ struct FmGeom {
   // design Q
   uint32_t q_waves_per_cu;
   size_t q_lds;                      // LDS bytes of one of its waves
+  uint32_t q_lds_waves_per_cu;       // ... and how many of them a CU's LDS holds (15 at D = 10; q_waves_per_cu is what a launch is cut for)
   // design B
   uint32_t fast_R;                   // outputs per lane and sub-tile of the handle's tile
   size_t fast_lds;
@@ -268,9 +269,40 @@ struct FmRuns { uint32_t runs; bool with_chain; };
 static inline uint32_t fm_q_min_steps(uint32_t n_clean, uint32_t q_steps, uint32_t q_total) {
   return ((uint64_t)n_clean * (q_steps / 4) >= (uint64_t)q_total / 2) ? 4u : 2u;
 }
+// What a run costs, in vector instructions per lane, counted once in the gfx950 assembly of k_mfir<0,5,10,5> as the library's Makefile builds it (static counts
+// along the path of a warmed-up run that meets no repair; not fitted to any timing — they only rank run counts):
+//   a run, whatever its length: 140 before the first matrix issue + 29 the peeled last step has over a loop step + 21 for the two flush set-ups behind it
+//                               + 10 on the way out = 200
+//   an audio stage:             76 for its 128 outputs + 10 for the flush's trip that stores them = 86
+//   a step, whole or partly filled: 105 vector instructions and 9 matrix issues = 114 (the audio stage apart)
+#define SDRFM_FM_Q_RUN_VALU 200u
+#define SDRFM_FM_Q_STAGE_VALU 86u
+#define SDRFM_FM_Q_STEP_VALU 114u
+// a stream's Gq = Qt + (warm-up quads) grid quads dealt out to `runs` runs as the kernel does it (sdrfm_q.hip: e0, e1): the longest run's quads, the steps it walks
+// and the audio stages it executes
+struct FmRunShape { uint32_t quads, steps, stages; };
+static inline FmRunShape fm_q_run_shape(uint32_t M, uint32_t runs, bool overlapped, uint32_t Da) {
+  const uint32_t Gq = fm_q_quads(M) + runs - 1u + (overlapped ? 1u : 0u);
+  FmRunShape s;
+  s.quads = (Gq + runs - 1u) / runs; s.steps = (s.quads + 3u) / 4u; s.stages = (s.steps + Da - 1u) / Da;
+  return s;
+}
+static inline uint64_t fm_q_runs_cost(uint32_t runs, const FmRunShape& s) {
+  return (uint64_t)runs * (SDRFM_FM_Q_RUN_VALU + (uint64_t)SDRFM_FM_Q_STAGE_VALU * s.stages + (uint64_t)SDRFM_FM_Q_STEP_VALU * s.steps);
+}
 // chain_run_quads: fm_chain_run_quads(Da) of the handle (the default is the BASELINE front end's, Da = 5: the least any rate needs)
+// staged (an overlapped plain call; Da, park_stages = SDRFM_Q_PARK_STAGES, lds_waves = the waves the device holds by LDS: FmGeom::q_lds_waves_per_cu x n_cu): the
+// count is chosen for whole audio stages.  Filling the machine once (`fill`, the rule below) leaves a run of the headline call 16 steps: four audio stages, the last
+// of them computed for one step's d's, and every run pays its fixed cost.  Two overlapped calls are resident together, so fewer, longer runs still occupy every
+// wave slot.  Among the counts from `fill` down to the least that does (2 n_clean runs >= lds_waves), those whose runs execute NO MORE STAGES than fill's (the longer
+// run only fills the last stage up: nothing this rule picks adds a stage to a run, let alone a flush inside the step loop) are ranked by
+// runs x (SDRFM_FM_Q_RUN_VALU + SDRFM_FM_Q_STAGE_VALU x stages + SDRFM_FM_Q_STEP_VALU x steps); ties go to the larger count.  The step term keeps counts out
+// that leave every run's last step mostly empty: 11 runs of the headline call walk 11 x 18 = 198 steps against 192 and 190, and measure slower than 12
+// (profiles/q_runs_ab.txt).  Every constraint of the rule below is an upper bound on the count, so it holds for the choice as well.  Calls that do not
+// fill the machine (min_steps = 2, a single stream) keep `fill`.
 static inline FmRuns fm_q_runs(const FmCall& c, uint32_t q_total, uint32_t n_clean, bool with_chain, uint32_t runstate_cap,
-                               uint32_t chain_run_quads = fm_chain_run_quads(5u)) {
+                               uint32_t chain_run_quads = fm_chain_run_quads(5u), bool staged = false, uint32_t Da = 0u, uint32_t park_stages = 0u,
+                               uint64_t lds_waves = 0u) {
   const uint32_t q_steps = fm_q_steps(c.M), q_quads = fm_q_quads(c.M);
   uint32_t runs = q_total / n_clean;
   const uint32_t min_steps = fm_q_min_steps(n_clean, q_steps, q_total);
@@ -279,6 +311,20 @@ static inline FmRuns fm_q_runs(const FmCall& c, uint32_t q_total, uint32_t n_cle
   // into fewer runs for it)
   if (with_chain && runs > q_quads / chain_run_quads) runs = q_quads / chain_run_quads;
   if (runs < 1) runs = 1;
+  if (staged && Da && min_steps == 4u && n_clean > 1u && runs > 1u) {
+    uint32_t least = (uint32_t)((lds_waves + 2ull * n_clean - 1u) / (2ull * n_clean));
+    if (least < 1u) least = 1u;
+    const uint32_t fill_stages = fm_q_run_shape(c.M, runs, true, Da).stages;
+    uint32_t best = runs;
+    uint64_t best_cost = ~0ull;
+    for (uint32_t r = runs; r >= least; --r) {
+      const FmRunShape s = fm_q_run_shape(c.M, r, true, Da);
+      if (s.stages > fill_stages || s.stages > park_stages) break;   // (fewer runs are longer still)
+      const uint64_t cost = fm_q_runs_cost(r, s);
+      if (cost < best_cost) { best_cost = cost; best = r; }
+    }
+    runs = best;
+  }
   // (the runs' hand-off words were allocated for the largest grid: a launch they cannot hold goes without the chain)
   if (with_chain && (uint64_t)n_clean * runs > runstate_cap) with_chain = false;
   return FmRuns{runs, with_chain};

@@ -153,6 +153,7 @@ static inline FmPlan fm_plan(const FmPlanIn& in, const FmKnobs& k, const FmRefus
     if (SDRFM_FM_LDS_PER_CU / in.q_default_lds < geo.q_waves_per_cu) geo.q_waves_per_cu = SDRFM_FM_LDS_PER_CU / in.q_default_lds;   // (D = 16: 11 one-wave workgroups fit a CU's LDS)
     if (k.q_waves_per_cu) geo.q_waves_per_cu = k.q_waves_per_cu;
     geo.q_lds = in.q_lds;
+    geo.q_lds_waves_per_cu = in.q_lds ? (uint32_t)(SDRFM_FM_LDS_PER_CU / in.q_lds) : 0u;
     snprintf(p.fast_q_name, sizeof(p.fast_q_name), "fast-q T%u D%u Ta%u Da%u %s", in.T, in.D, in.Ta, in.Da, in.q_symbol ? in.q_symbol : "");
   }
 

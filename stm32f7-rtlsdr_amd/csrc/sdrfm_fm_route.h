@@ -68,6 +68,10 @@ static inline void fm_route_reset(FmRoute& r) {
 // the window that last counted into its set left — SETS windows ago, (SETS - 1) windows of calls after the read-back was enqueued.
 static inline int fm_route_due(const FmRoute& r) { return (r.win_calls == 0 && r.rb_pending[r.set]) ? (int)r.set : -1; }
 // pass[s]: repair passes of stream s in that window.  More than a quarter of its audio stages: the stream leaves design Q for a while.
+// (rb_stages adds fm_win_stages of every call with the run count that call was launched with.  fm_win_stages leaves the warm-up quads out — runs x ceil(floor(q_steps
+// / runs) / Da) —, so at configs[2] it counts 3 stages for each of a serial call's 12 runs, which execute 4 (and take a pass at each), and 4 for each of an overlapped
+// call's 10 runs, which execute 4: the threshold is more than 9 passes out of 48 executed stages in a window of serial calls and more than 10 out of 40 in a window of
+// overlapped ones — 19 % against 25 %.  A noise-only stream repairs at almost every stage and a carrier at none, so both sit far from either figure.)
 static inline void fm_route_take(FmRoute& r, uint32_t set, const uint32_t* pass) {
   r.rb_pending[set] = false;
   for (uint32_t s = 0; s < r.ns; ++s)

@@ -62,7 +62,7 @@ namespace {
 
 constexpr int QTA = (int)SDRFM_Q_TA;            // audio taps (every instance)
 constexpr int DB0 = 128;                        // d buffer: word DB0 + sigma = first d of the current audio stage
-constexpr int ABS = 4;                          // audio stages (128 outputs each) parked in LDS before they are stored (2, which lets 16 waves fit a CU: no faster, r06_q_experiments.txt item 5)
+constexpr int ABS = (int)SDRFM_Q_PARK_STAGES;   // audio stages (128 outputs each) parked in LDS before they are stored (2, which lets 16 waves fit a CU: no faster, r06_q_experiments.txt item 5)
 constexpr int ABW = 128 * ABS;                  // words, after the d buffer
 constexpr int FLW = 64 + 2;                     // words, after the parked audio: up to 128 two-byte entries of lanes waiting for the repair path, two counters
 #ifndef SDRFM_Q_GTAB
@@ -1094,7 +1094,7 @@ __device__ __forceinline__ void mfir_body(const SdrfmQParams& p, const uint32_t 
         osm = 0;
         mbase += 128 * QDA;
       }
-      if (npend == ABS) flush_audio();                          // (long runs only: configs[2]'s runs hold 3.4 stages)
+      if (npend == ABS) flush_audio();                          // (long runs only: configs[2]'s runs hold four stages at most, 3.2 of d's in a serial call's 16 steps, 3.8 in an overlapped call's 19)
       Q_PHASE(6);                                               // audio stage
     }
 #if SDRFM_Q_PEEL

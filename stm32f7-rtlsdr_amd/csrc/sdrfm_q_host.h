@@ -18,6 +18,8 @@ extern "C" {
 
 #define SDRFM_Q_TA 32u                      /* audio taps (every instance) */
 #define SDRFM_Q_TP 64u                      /* the repair path's chain length: channel taps padded with zeros to this many (design Q serves T <= 64) */
+#define SDRFM_Q_PARK_STAGES 4u               /* audio stages (128 outputs each) a run parks in LDS before it stores them: a run of more stages flushes inside its step loop.
+                                               The kernel's LDS layout (sdrfm_q.hip: ABS, q_lds) and the host's run plan (sdrfm_fm_call.h: fm_q_runs) both take it from here */
 #define SDRFM_Q_SPARSE_CHUNKS(D) (((D) + 3u) / 4u)   /* K-chunks of 128 window bytes (v_smfmac_i32_16x16x128_i8) per digit */
 
 /* h[0..T) -> A[ceil(D/4)][3][64][16] (sparse chunk, digit, lane, kept slot), the fp32 scale q (y = q * (S0 + 256 S1 + 65536 S2) + cst),
